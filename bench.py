@@ -198,6 +198,37 @@ def run_steps(env, actions, first, count):
         env.step(actions[i % n_rows])
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs stays under 64 MB whatever the batch
+
+
+def dump_outputs(env, out_dir):
+    """--dump-outputs: what the last step handed its caller — step()'s obs, reward, terminated,
+    truncated and every `info` column — as <out_dir>/<name>.npy (obs and returns f32, flags as
+    0/1 f32, info columns f64).  A batch too large for DUMP_BYTES is written for a fixed, seeded
+    sample of envs, the same rows in every array; env_ids.npy names them."""
+    import torch
+    from gym_trading_env_amd.batched import LazyInfo
+    obs, reward, term, trunc = env._results()  # the buffers step() returned, last step's values
+    info = LazyInfo(env)
+    N, keys = env.num_envs, list(env.info_keys)
+    per_env = 4 * obs[0].numel() + 3 * 4 + 8 * (len(keys) + 1)
+    n = min(N, DUMP_BYTES // per_env)
+    ids = np.arange(N) if n == N else np.sort(np.random.default_rng(0).choice(N, n, replace=False))
+    sel = torch.from_numpy(ids).to(obs.device)
+    arrays = {"env_ids": ids.astype(np.float64),
+              "obs": obs[sel].cpu().numpy(),
+              "reward": reward[sel].cpu().numpy(),
+              "terminated": term[sel].float().cpu().numpy(),
+              "truncated": trunc[sel].float().cpu().numpy()}
+    for k in keys:
+        arrays["info_" + k] = np.asarray(info[k], dtype=np.float64)[ids]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step ({n} of {N} envs) written to {out_dir}",
+          file=sys.stderr)
+
+
 def pmc_traffic(args, N, timeout_s=150):
     """Bytes per step-kernel launch from the hardware counters, collected NOW: one
     `rocprofv3 --pmc <counter>` child pass per counter (FETCH_SIZE and WRITE_SIZE need
@@ -390,6 +421,10 @@ def main():
                     help="single GPU: capture G (even) consecutive steps into ONE HIP graph "
                          "(BatchedTradingEnv.capture_steps) and time replays of it — one host call "
                          "per G steps — instead of G launches; for launch-bound batches (c2)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0's envs) "
+                         "as DIR/<name>.npy: obs, reward, terminated, truncated and info_<column>, "
+                         "under 64 MB (a fixed, seeded sample of envs when the batch is larger)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-python-loop", type=float, default=0.0, metavar="SECONDS",
                     help="cpu_baseline calibration only, no GPU: time the interpreter-bound per-env loop "
@@ -592,6 +627,8 @@ def main():
     episodes0 = int(env.state("episode").sum())
     el, ev_ms = timed(modes[0] if modes else None, 0)
     episodes = int(env.state("episode").sum()) - episodes0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs)
     mode = modes[0] if modes else None
     other_modes = {}
     for k, m in enumerate(modes[1:]):
