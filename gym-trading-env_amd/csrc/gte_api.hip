@@ -12,8 +12,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gte_device.h"
@@ -162,7 +164,87 @@ struct gte_env {
   bool view_reads = false; // gte_read_envs_view has been used: the buffer is kept at full size
   void* h_logpack = nullptr;  // pinned host memory for gte_read_log_envs
   size_t h_logpack_bytes = 0;
+  // sparse flag stores (flag ledger below): the next step may store only the flags that change
+  bool flags_sparse_ok = false;
+  const uint8_t* flags_term = nullptr;   // ... into these two buffers, which this env's last step
+  const uint8_t* flags_trunc = nullptr;  //     wrote and nothing has written since
 };
+
+// Flag ledger.  A step stores an env's terminated / truncated bytes only where they change
+// (store_flags, gte_kernels.hip) when the two buffers hold exactly what this env's previous step
+// stored there.  That is true only while nothing else writes them, and the host keeps the proof
+// here, process-wide (several envs may share or rotate buffers):
+//   * an env's eager step records the ranges it wrote: its next step may be sparse if it writes the
+//     same two buffers again;
+//   * every launch that writes flag bytes (any env's step, reset or rollout) withdraws that right
+//     from every OTHER env whose recorded ranges it overlaps; a reset, a rollout and any rebinding
+//     of outputs or returns withdraw it from the env itself;
+//   * a range written by a step inside a graph capture is never sparse again: a replay writes it at
+//     times the host does not see.  Captured steps themselves store densely, so a replay is correct
+//     whatever ran before it.
+// A dense step stores every flag and brings each record's flags_out up to date, so one dense step
+// restores the invariant whatever happened before.
+namespace {
+struct FlagRange { gte_env* env; uintptr_t lo, hi; };
+std::mutex g_flag_mu;
+std::vector<FlagRange> g_flag_last;                         // ranges each env's last eager step wrote
+std::vector<std::pair<uintptr_t, uintptr_t>> g_flag_captured;  // ranges written inside a capture
+
+bool ranges_overlap(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) {
+  return a_lo < b_hi && b_lo < a_hi;
+}
+// (g_flag_mu held) env E's launch writes [ptr, ptr + n): other envs that rely on those bytes lose the right
+void flags_clobber_locked(const gte_env* E, const void* ptr, size_t n) {
+  if (!ptr || !n) return;
+  const uintptr_t lo = (uintptr_t)ptr, hi = lo + n;
+  for (const FlagRange& r : g_flag_last)
+    if (r.env != E && ranges_overlap(lo, hi, r.lo, r.hi)) r.env->flags_sparse_ok = false;
+}
+void flags_forget_locked(const gte_env* E) {
+  size_t k = 0;
+  for (size_t i = 0; i < g_flag_last.size(); ++i)
+    if (g_flag_last[i].env != E) g_flag_last[k++] = g_flag_last[i];
+  g_flag_last.resize(k);
+}
+}  // namespace
+
+// A launch that is not a plain eager step writes (or may write) flag bytes: [ptr, ptr + n) for each
+// pair given; the env's own next step stores densely.
+static void flags_unsure(gte_env* E, std::initializer_list<std::pair<const void*, size_t>> written) {
+  std::lock_guard<std::mutex> lock(g_flag_mu);
+  E->flags_sparse_ok = false;
+  for (const auto& w : written) flags_clobber_locked(E, w.first, w.second);
+}
+
+// May this step of E store its flags sparsely into p's buffers?
+static bool flags_may_skip(gte_env* E, const Params& p, bool capturing) {
+  if (capturing || (E->cfg.kernel_variant & 16384)) return false;  // (16384: A/B, always dense)
+  std::lock_guard<std::mutex> lock(g_flag_mu);
+  return E->flags_sparse_ok && E->flags_term == p.terminated && E->flags_trunc == p.truncated;
+}
+
+// E's step wrote every env's flags (densely or sparsely) into p's buffers
+static void flags_stepped(gte_env* E, const Params& p, bool capturing) {
+  const size_t N = (size_t)p.N;
+  const uintptr_t t = (uintptr_t)p.terminated, u = (uintptr_t)p.truncated;
+  std::lock_guard<std::mutex> lock(g_flag_mu);
+  flags_clobber_locked(E, p.terminated, N);
+  flags_clobber_locked(E, p.truncated, N);
+  flags_forget_locked(E);
+  E->flags_sparse_ok = false;
+  if (capturing) {
+    g_flag_captured.emplace_back(t, t + N);
+    g_flag_captured.emplace_back(u, u + N);
+    return;
+  }
+  for (const auto& c : g_flag_captured)
+    if (ranges_overlap(t, t + N, c.first, c.second) || ranges_overlap(u, u + N, c.first, c.second)) return;
+  g_flag_last.push_back({E, t, t + N});
+  g_flag_last.push_back({E, u, u + N});
+  E->flags_term = p.terminated;
+  E->flags_trunc = p.truncated;
+  E->flags_sparse_ok = true;
+}
 
 template <typename T>
 static int dev_alloc(gte_env* E, T** out, size_t count, bool zero = true) {
@@ -670,6 +752,23 @@ static int ensure_owned_obs(gte_env* E) {
   return GTE_OK;
 }
 
+// Re-sort the processing order (gte_kernels.hip, "L2-affinity permutation").  The histogram is
+// zero between re-sorts only because the scan kernel clears it: if a launch fails part-way it may be
+// left counting, and a later scatter would hand out ranks past N.  So a failure turns the re-sort off
+// for good and the env goes on in identity order (results do not depend on the order).
+static int resort(gte_env* E) {
+  E->steps_since_rebuild = 0;
+  const hipError_t e = gte::launch_affinity_rebuild(E->p, E->d_bins, E->n_bins_per_ds, E->d_slot_of_rank,
+                                                    E->d_perm, E->stream);
+  if (e != hipSuccess) {
+    E->affinity_period = 0;
+    E->p.perm = nullptr;
+    return fail(GTE_ERR_HIP, "re-sort of the processing order: %s", hipGetErrorString(e));
+  }
+  E->p.perm = E->d_perm;
+  return GTE_OK;
+}
+
 int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
               const int32_t* inj_pos_index, const int32_t* inj_dataset) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
@@ -688,15 +787,11 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   E->term_slot = 0;
   p.term_count = E->term_base;
   p.term_count_next = E->term_base + 1;
+  flags_unsure(E, {{p.terminated, N}, {p.truncated, N}});  // (masked envs get zero flags, flags_out untouched)
   HIPCHK(gte::launch_reset(p, E->vec, E->cfg.nontemporal_obs, E->coop, E->stage, E->blocks,
                            E->threads, E->stream));
   TRY(append_log(E));
-  if (E->affinity_period > 0) {  // new start rows: re-sort the processing order
-    HIPCHK(gte::launch_affinity_rebuild(E->p, E->d_bins, E->n_bins_per_ds, E->d_slot_of_rank,
-                                        E->d_perm, E->stream));
-    E->p.perm = E->d_perm;
-    E->steps_since_rebuild = 0;
-  }
+  if (E->affinity_period > 0) TRY(resort(E));  // new start rows: re-sort the processing order
   // host staging buffers may be reused by the caller right away: pageable copies above
   // are complete on return, but keep the contract simple and explicit
   HIPCHK(hipStreamSynchronize(E->stream));
@@ -742,8 +837,8 @@ int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
   if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_step before gte_reset");
   if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
   // Stream capture (hipStreamBeginCapture by whoever owns the stream — e.g. torch.cuda.graph around
-  // policy + step): everything a step enqueues is capturable — kernels and one memset of the
-  // re-sort — provided nothing comes from pageable host memory, and the host-side bookkeeping a
+  // policy + step): everything a step enqueues is capturable — the step kernel and the re-sort's
+  // three kernels, no memset — provided nothing comes from pageable host memory, and the host-side bookkeeping a
   // replay cannot repeat stays consistent: the two-slot terminal counter alternates per launch, so
   // a graph must hold an EVEN number of steps and be replayed from the slot it was captured at
   // (gte_get_outputs().term_slot; StepGraph in step_graph.py checks both); the trajectory log's
@@ -761,9 +856,7 @@ int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
   if (E->affinity_period > 0 && ++E->steps_since_rebuild >= E->affinity_period) {
     // envs drift one row per step and ~1/duration of them jump at a reset: re-sort now and
     // then (3 tiny launches, stream-ordered between two steps)
-    HIPCHK(gte::launch_affinity_rebuild(E->p, E->d_bins, E->n_bins_per_ds, E->d_slot_of_rank,
-                                        E->d_perm, E->stream));
-    E->steps_since_rebuild = 0;
+    TRY(resort(E));
   }
   Params p = E->p;
   if (actions_on_device) {
@@ -789,6 +882,10 @@ int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
     p.log = E->log;
     p.log_row_base = (E->log_rows % E->cfg.log_steps) * (int64_t)p.N;
   }
+  // terminated / truncated: only the changed ones, where the flag ledger proves the buffers hold the
+  // previous step's flags (dense inside a capture: a replay cannot rely on what ran before it)
+  const bool capturing = capture == hipStreamCaptureStatusActive;
+  p.flags_sparse = flags_may_skip(E, p, capturing) ? 1 : 0;
   // (hot_tu_covers: the isolated instantiations have no terminal records and no trajectory row)
   const bool hot = E->vec == 4 && E->coop && E->stage == 1 && !(E->cfg.kernel_variant & 64) &&
                    gte::hot_tu_covers(p);
@@ -799,6 +896,7 @@ int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
   else
     HIPCHK(gte::launch_step(p, E->vec, E->cfg.nontemporal_obs, E->coop, E->stage, E->blocks,
                             E->threads, E->stream));
+  flags_stepped(E, p, capturing);
   if (fused_log) E->log_rows += 1;
   else TRY(append_log(E));
   return GTE_OK;
@@ -817,6 +915,17 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
   const size_t V = (size_t)E->p.W * (size_t)E->p.Fobs;
   if (b->obs && ((uintptr_t)b->obs & 15)) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
   HIPCHK(hipSetDevice(E->cfg.device));
+  // the fused kernels write flags into the env's buffers or the per-step rows (flag ledger)
+  struct FlagsAfterRollout {
+    gte_env* E;
+    const gte_rollout_bufs* b;
+    size_t rows;
+    ~FlagsAfterRollout() {
+      const size_t N = (size_t)E->p.N;
+      flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}, {b->terminated, rows * N},
+                       {b->truncated, rows * N}});
+    }
+  } flags_after_rollout{E, b, (size_t)n_steps};
   // kernel_variant 128 = never fused (A/B and tests of the per-launch path)
   const bool fused = E->vec == 4 && E->coop && E->stage == 1 && !E->cfg.final_obs && !E->p.persist &&
                      E->cfg.log_steps == 0 && !(E->cfg.kernel_variant & 128);
@@ -852,9 +961,7 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
     if (E->affinity_period > 0) {
       E->steps_since_rebuild += n;
       if (E->steps_since_rebuild >= E->affinity_period) {
-        HIPCHK(gte::launch_affinity_rebuild(E->p, E->d_bins, E->n_bins_per_ds, E->d_slot_of_rank,
-                                            E->d_perm, E->stream));
-        E->steps_since_rebuild = 0;
+        TRY(resort(E));
       }
     }
     return GTE_OK;
@@ -1186,6 +1293,7 @@ int gte_bind_outputs(gte_env* E, const gte_outputs* b) {
   HIPCHK(hipStreamSynchronize(E->stream));
   Params& p = E->p;
   if (b->obs && ((uintptr_t)b->obs & 15)) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
+  flags_unsure(E, {});
   p.obs = b->obs;  // NULL: back to the library's own buffers (allocated on first need)
   if (E->cfg.final_obs) p.final_obs = b->final_obs;
   if (E->was_reset) TRY(ensure_owned_obs(E));
@@ -1258,6 +1366,7 @@ int gte_bind_returns(gte_env* E, float* reward, uint8_t* terminated, uint8_t* tr
   if (!E || !reward || !terminated || !truncated) return fail(GTE_ERR_INVALID, "NULL argument");
   // Params travel by value with every launch: later launches see the new pointers,
   // launches already enqueued keep the old ones.
+  flags_unsure(E, {});  // (rotated buffers hold an older step's flags: the next step stores densely)
   E->p.reward = reward;
   E->p.terminated = terminated;
   E->p.truncated = truncated;
@@ -1527,6 +1636,10 @@ void gte_destroy(gte_env* E) {
   if (E->ev0) (void)hipEventDestroy(E->ev0);
   if (E->ev1) (void)hipEventDestroy(E->ev1);
   if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
+  {
+    std::lock_guard<std::mutex> lock(g_flag_mu);
+    flags_forget_locked(E);
+  }
   delete E;
 }
 

@@ -43,7 +43,8 @@ struct alignas(128) EnvRec {
   double asset, fiat, ia, ifi, pv, realpos;  // 48 B
   // cold half: written where it changes (a reset, a limit-order fill, an episode end)
   int32_t start, episode, needs_reset, eps_on_ds;
-  int32_t n_picks, q_head, lo_n, pad0;
+  int32_t n_picks, q_head, lo_n;
+  int32_t flags_out;  // terminated | truncated << 1 as the env's last step stored them (store_flags)
   int32_t pad1[8];                           // -> 128 B
 };
 static_assert(offsetof(EnvRec, start) == 64, "EnvRec: the hot half is the first 64 bytes");
@@ -111,6 +112,8 @@ struct Params {
   int32_t debug;       // gte_config.debug_flags (timing ablations)
   int32_t lean_rows;   // != 0: full waves of 16-byte-vector windows take the lean copy loop (gte_kernels.hip)
   int32_t hot_lds;     // != 0: a step's record stores go through LDS, one 64-byte request per env (gte_kernel)
+  int32_t flags_sparse;  // != 0: terminated / truncated hold what each env's previous step stored there
+                         // (EnvRec.flags_out), so a step stores only the flags that change (gte_step decides)
   // --- trajectory row written by THIS launch's phase A (a gte_step with log_steps > 0; the
   // shared-TU step kernel only).  log.idx == null: none (the host appends it with gte_log_kernel)
   LogArrays log;

@@ -69,7 +69,7 @@ enum { MODE_STEP = 0, MODE_RESET = 1 };
 // the rare reset branches: carried through the fp64 state machine they cost the step kernel
 // four more VGPRs, i.e. an occupancy step.
 struct EnvRegs {
-  int32_t idx, step, pos, dsi, start, needs_reset, lo_n;
+  int32_t idx, step, pos, dsi, start, needs_reset, lo_n, flags_out;
   Portfolio q;
   double pv, realpos;
 };
@@ -81,9 +81,9 @@ __device__ inline void load_state(const Params& p, int e, EnvRegs& s) {
   const double2* rd = reinterpret_cast<const double2*>(&r->asset);  // offset 16
   const double2 d0 = rd[0], d1 = rd[1], d2 = rd[2];
   const int4 b = ri[4];  // start, (episode), needs_reset, (eps_on_ds)
-  const int4 c = ri[5];  // (n_picks), (q_head), lo_n, pad
+  const int4 c = ri[5];  // (n_picks), (q_head), lo_n, flags_out
   s.idx = a.x; s.step = a.y; s.pos = a.z; s.dsi = a.w;
-  s.start = b.x; s.needs_reset = b.z; s.lo_n = c.z;
+  s.start = b.x; s.needs_reset = b.z; s.lo_n = c.z; s.flags_out = c.w;
   s.q.asset = d0.x; s.q.fiat = d0.y; s.q.ia = d1.x; s.q.ifi = d1.y;
   s.pv = d2.x; s.realpos = d2.y;
 }
@@ -114,6 +114,20 @@ __device__ inline void store_state_lds(lds_byte_ptr h, const EnvRegs& s) {
   *(ld2)(h + 48) = d2;
 }
 __device__ inline void store_state(const Params& p, int e, const EnvRegs& s) { store_state_at(&p.rec[e], s); }
+
+// A step's terminated / truncated bytes (f: bit0 terminated, bit1 truncated).  About N/500 envs end
+// per step, so the flags of all but a few envs repeat the previous step's; each of the two scattered
+// byte stores costs wave 0 a request per env.  With p.flags_sparse the host has established that the
+// two buffers hold exactly what each env's previous step stored there (EnvRec.flags_out; gte_step):
+// only a change is stored.  A dense launch stores every env's flags and brings flags_out up to date,
+// so one dense step makes any buffer and record consistent again.
+__device__ inline void store_flags(const Params& p, int e, EnvRegs& s, int32_t f) {
+  if (!p.flags_sparse || f != s.flags_out) {
+    p.terminated[e] = (uint8_t)(f & 1);
+    p.truncated[e] = (uint8_t)(f >> 1);
+  }
+  if (f != s.flags_out) { s.flags_out = f; p.rec[e].flags_out = f; }
+}
 
 // MultiDatasetTradingEnv.next_dataset, environments.py:380-391
 __device__ inline void next_dataset(const Params& p, int e, int32_t inj_ds, EnvRegs& s,
@@ -344,18 +358,17 @@ __device__ inline void phase_a(const Params& p, int e, bool active, int lane, Ob
         do_reset(p, e, qi, qp, qd, s, fresh);
         if (pc) pc->idx = -1;
         p.reward[e] = 0.0f; p.reward64[e] = 0.0;
-        p.terminated[e] = 0; p.truncated[e] = 0;
+        store_flags(p, e, s, 0);
         if (so) { so->reward = 0.0; so->flags = 0; }
         stepped = false;
       } else if (s.idx >= (int32_t)p.ds[s.dsi].T - 1) {
         // no auto-reset and no row left: the reference raises IndexError (:239);
         // the batch leaves such an env frozen, flags still raised
         p.reward[e] = 0.0f; p.reward64[e] = 0.0;
-        // its flags stay raised (rewritten, not relied upon: a rollout writes every step's
+        // its flags stay raised (stored again by a dense step: a rollout writes every step's
         // flags to a fresh row): the valuation has not moved since the 0.7 test (:246), and
         // being on the last row is the truncation rule itself (:248)
-        p.terminated[e] = (s.pv / p.V0) <= 0.7 ? 1 : 0;
-        p.truncated[e] = 1;
+        store_flags(p, e, s, ((s.pv / p.V0) <= 0.7 ? 1 : 0) | 2);
         if (so) { so->reward = 0.0; so->flags = ((s.pv / p.V0) <= 0.7 ? 1 : 0) | 2; }
         stepped = false;
         ended = true;  // so it stays in the terminal list
@@ -398,8 +411,7 @@ __device__ inline void phase_a(const Params& p, int e, bool active, int lane, Ob
       s.pv = pv;
       p.reward64[e] = rew;
       p.reward[e] = (float)rew;
-      p.terminated[e] = done ? 1 : 0;
-      p.truncated[e] = trunc ? 1 : 0;
+      store_flags(p, e, s, (done ? 1 : 0) | (trunc ? 2 : 0));
       if (so) { so->reward = rew; so->flags = (done ? 1 : 0) | (trunc ? 2 : 0); }
       ended = done || trunc;
       if (ended) { s.needs_reset = 1; p.rec[e].needs_reset = 1; }
