@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-GTE_ABI_VERSION = 2
+GTE_ABI_VERSION = 3
 GTE_MAX_POSITIONS = 32
 GTE_MAX_DYN = 4
 GTE_COMM_ID_BYTES = 128
@@ -151,7 +151,14 @@ class GteLogView(C.Structure):
                 ("real_position", C.c_void_p), ("reward", C.c_void_p), ("flags", C.c_void_p),
                 ("rows", C.c_int64), ("L", C.c_int32), ("N", C.c_int32),
                 ("asset", C.c_void_p), ("fiat", C.c_void_p), ("interest_asset", C.c_void_p),
-                ("interest_fiat", C.c_void_p), ("env_stride", C.c_int64), ("row_stride", C.c_int64)]
+                ("interest_fiat", C.c_void_p), ("env_stride", C.c_int64), ("row_stride", C.c_int64),
+                ("cursor", C.c_void_p), ("cursor_slot", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class GteSchedule(C.Structure):
+    """struct gte_schedule: the host-side schedule a stream capture advances (StepGraph)."""
+
+    _fields_ = [("log_rows", C.c_int64), ("term_slot", C.c_int32), ("steps_since_rebuild", C.c_int32)]
 
 
 class GteLogBatch(C.Structure):
@@ -191,6 +198,9 @@ SYMBOLS = {
     "gte_set_autoreset_injection": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
     "gte_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "gte_get_schedule": (C.c_int, [C.c_void_p, _P(GteSchedule)]),
+    "gte_set_schedule": (C.c_int, [C.c_void_p, _P(GteSchedule)]),
+    "gte_advance_log": (C.c_int, [C.c_void_p, C.c_int64]),
     "gte_add_limit_orders": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_get_log": (C.c_int, [C.c_void_p, _P(GteLogView)]),
     "gte_read_log_portfolio": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4

@@ -227,6 +227,8 @@ class BatchedTradingEnv(_VectorEnvBase):
 
         self._final_view, self._final_epoch, self._final_tensors = _abi.GteStateView(), -1, {}
         self._logv, self._log_tensors, self._pos_table = _abi.GteLogView(), {}, None
+        self._log_cursor = None  # torch view of gte_log_view.cursor (i64 [2]), made on first need
+        self._log_back = None    # arange(-L, 0) on the device, made before a capture (StepGraph)
         self._state = _abi.GteStateView()
         self._epoch, self._state_epoch = 0, -1  # state snapshots are taken lazily
         self._snap_epoch, self._snap, self._snap_obs = -1, None, None  # numpy mode, per step
@@ -432,6 +434,16 @@ class BatchedTradingEnv(_VectorEnvBase):
             self._host_columns[name] = col
         return col
 
+    def _require_device_column(self, name):
+        """Inside a graph capture: info column `name` must already be on the device (a host
+        column cannot be read there, and its first upload is a copy a capture cannot hold)."""
+        if self._dataset_host_column(name).dtype.kind not in "fiub":
+            raise ValueError(f"History column {name!r} holds host values: it cannot be read inside a "
+                             "graph capture")
+        if name not in self._dev_columns:
+            raise ValueError(f"History column {name!r} is uploaded to the device on first use, which "
+                             "a graph capture cannot hold: read it once before capturing")
+
     def _dataset_column(self, name, ds, idx):
         """Values of info column `name` at (dataset, row) pairs; on the device for numeric
         columns in torch mode, else host arrays."""
@@ -556,6 +568,36 @@ class BatchedTradingEnv(_VectorEnvBase):
         _abi.check(self._lib, self._lib.gte_get_log(self._h, C.byref(self._logv)))
         return self._logv
 
+    def _capturing(self) -> bool:
+        """Is torch's current stream capturing a graph (StepGraph)?"""
+        return self._torch is not None and self._torch.cuda.is_current_stream_capturing()
+
+    def _log_order_on_device(self, view):
+        """The physical log rows of the last L steps, oldest first, as a device tensor [L], computed
+        from the log's row count on the device (gte_log_view.cursor) — in a graph, each replay's
+        own rows.  Needs a full log."""
+        torch = self._torch
+        if self._log_cursor is None:
+            class _Raw:
+                __cuda_array_interface__ = {"shape": (2,), "typestr": "<i8", "version": 2,
+                                            "strides": None, "data": (int(view.cursor), False)}
+            self._log_cursor = torch.as_tensor(_Raw(), device=self._t["obs"].device)
+        slot, L = int(view.cursor_slot), int(view.L)
+        count = self._log_cursor[slot:slot + 1]
+        back = self._log_back if self._log_back is not None else torch.arange(-L, 0, device=count.device)
+        return torch.remainder(back + count, L)
+
+    def _device_result(self, x, what):
+        """Inside a graph capture a callable's value must already be a device tensor."""
+        if self._capturing():
+            from .device_array import DeviceArray
+            t = x.t if isinstance(x, DeviceArray) else x
+            if not (isinstance(t, self._torch.Tensor) and t.is_cuda):
+                raise ValueError(f"{what} returned {type(x).__name__} inside a graph capture: only "
+                                 "device values (History columns and what is computed from them) "
+                                 "can be captured")
+        return x
+
     def _log_tensor(self, name):
         """torch view [L, N] of one log array (no copy)."""
         t = self._log_tensors.get(name)
@@ -631,6 +673,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         """`historical_info["reward", -1] = reward` (environments.py:267) for the batch."""
         if self._torch is not None:
             from .device_array import to_tensor
+            value = self._device_result(value, "the value assigned to h['reward', -1]")
             r = to_tensor(value, self._t["obs"].device, self._torch.float64).contiguous()
             self._keep_reward = r
             _abi.check(self._lib, self._lib.gte_set_log_reward(self._h, C.c_void_p(r.data_ptr())))
@@ -650,7 +693,9 @@ class BatchedTradingEnv(_VectorEnvBase):
         BatchedHistory, where the reference calls them per env: reward after `History.add`
         (environments.py:265-267: skipped — reward 0 — when done; rows a reset wrote have reward
         0, :196), then the dynamic features inside `_get_obs` (:153-154), which therefore see the
-        reward."""
+        reward.  Inside a graph capture nothing here waits for the device: the callables must
+        return device values, and in same-step mode the fresh History is evaluated every step
+        and merged with torch.where."""
         if self._reward_callable is None and not self._dyn_callables:
             return
         torch = self._torch
@@ -665,9 +710,9 @@ class BatchedTradingEnv(_VectorEnvBase):
         # step's h[..., -2] must be)
         h = self.batched_history(terminal=same_step)
         ended = (self._t["terminated"] | self._t["truncated"]) if same_step else None
-        newest = (h._rows - 1) % h._L
+        capturing = self._capturing()
         if self._reward_callable is not None and not after_reset:
-            r = to_tensor(self._reward_callable(h), dev, torch.float64)
+            r = to_tensor(self._device_result(self._reward_callable(h), "reward_function"), dev, torch.float64)
             if r.shape != (N,):
                 raise ValueError(f"reward_function must return one value per env, got shape {tuple(r.shape)}")
             # one kernel applies the reference's rules (0 where terminated, :265, and on reset rows,
@@ -681,9 +726,10 @@ class BatchedTradingEnv(_VectorEnvBase):
             cols = (C.c_void_p * self.cfg.n_dyn)()
             is_f64 = (C.c_int32 * self.cfg.n_dyn)()
             keep = []
-            fresh = self.batched_history() if (same_step and bool(ended.any())) else None
+            # (a capture cannot ask the device whether an env ended: it evaluates `fresh` every step)
+            fresh = self.batched_history() if (same_step and (capturing or bool(ended.any()))) else None
             for i, fn in self._dyn_callables:
-                v = to_tensor(fn(h), dev, None)
+                v = to_tensor(self._device_result(fn(h), "a dynamic feature function"), dev, None)
                 if v.dtype not in (torch.float32, torch.float64):
                     v = v.to(torch.float64)
                 if v.shape != (N,):
@@ -693,11 +739,15 @@ class BatchedTradingEnv(_VectorEnvBase):
                     # observation the one of the reset row (reset() evaluates it on a 1-row History)
                     col = self.datasets[0].n_static + i
                     fo = self._t["final_obs"]
-                    if fo.dim() == 3:
+                    if capturing:  # (a boolean-mask write waits for the device)
+                        last = fo[:, -1, col] if fo.dim() == 3 else fo[:, col]
+                        last.copy_(torch.where(ended, v.to(fo.dtype), last))
+                    elif fo.dim() == 3:
                         fo[ended, -1, col] = v[ended].to(fo.dtype)
                     else:  # windows=None: the observation is one row
                         fo[ended, col] = v[ended].to(fo.dtype)
-                    v = torch.where(ended, to_tensor(fn(fresh), dev, v.dtype), v)
+                    v_fresh = self._device_result(fn(fresh), "a dynamic feature function")
+                    v = torch.where(ended, to_tensor(v_fresh, dev, v.dtype), v)
                 v = v.contiguous()
                 keep.append(v)
                 cols[i] = v.data_ptr()
@@ -952,7 +1002,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         host->device copy."""
         self._launch_step(actions)
         self._apply_callables(after_reset=False)
-        if self.verbose > 0 and self._user_log:
+        if self.verbose > 0 and self._user_log and not self._capturing():  # (a report synchronises)
             import time
             now = time.monotonic()
             if now - self._last_report >= self.verbose_interval:
@@ -1017,7 +1067,13 @@ class BatchedTradingEnv(_VectorEnvBase):
         """Record `body(i)` for i in range(n_steps) — each call taking ONE `step()` with a CUDA
         int32 action tensor, plus any torch code around it (the policy) — into a HIP graph
         (`torch.cuda.graph`); `.replay()` on the returned `StepGraph` runs them again with one
-        host call.  For launch-bound batches (config 2: 4 096 envs).  n_steps must be even."""
+        host call.  For launch-bound batches (config 2: 4 096 envs).  n_steps must be even.
+
+        Logged envs and Python callables are captured too, once the log is full (``log_steps``
+        eager steps, the reset included): the History reads of the callables pick their rows on
+        the device, the callables must return device values, and same-step terminal observations
+        are merged with torch.where.  Inside the capture `verbose` reports are skipped (a report
+        synchronises); `return_slots` > 1 is refused.  See step_graph.py."""
         from .step_graph import StepGraph
         return StepGraph(self, body, n_steps)
 

@@ -22,8 +22,18 @@ Differences from one env's History, inherent to a batch: `h[col]` is a sliding w
 last `log_steps` steps of every env (episodes of different envs start at different rows;
 `h.episode_mask()` marks the rows of each env's current episode), and non-numeric columns
 (`date`, object-valued `data_*`) are host arrays.
+
+Inside a graph capture (`capture_steps`, torch.cuda.is_current_stream_capturing()) the rows are
+picked on the device from the log's row count there (gte_log_view.cursor), so that every replay
+reads the rows of its own step: `h[col, -k]`, `h[col]`, `h[[cols]]`, `h[-1]` (entries computed
+when read), `episode_mask()` and `h["reward", -1] = x` give the values of the eager views.  The
+log must be full (`len(h)` is then `log_steps` in every replay).  What needs the host cannot be
+captured and is refused: `h[col, t >= 0]` (its bounds check reads the device), host-valued
+columns (`date`, object-valued `data_*`) and assigning a host value.
 """
 from __future__ import annotations
+
+from collections.abc import Mapping
 
 import numpy as np
 
@@ -58,6 +68,14 @@ class BatchedHistory:
         view = env._log_view()
         self._rows, self._L = int(view.rows), int(view.L)
         self._have = min(self._rows, self._L)
+        # in a capture: the physical rows of the window, oldest first, as a device tensor [L]
+        self._dev = None
+        if env._capturing():
+            if self._rows < self._L:
+                raise ValueError(f"a BatchedHistory inside a graph capture needs a full log: take "
+                                 f"log_steps = {self._L} eager steps (reset included) before capturing, "
+                                 f"{self._rows} rows are logged")
+            self._dev = env._log_order_on_device(view)
 
     def __len__(self):
         """Rows available per env: min(steps logged so far, log_steps)."""
@@ -66,11 +84,16 @@ class BatchedHistory:
     # -- row selection -------------------------------------------------------------------------
     def _phys(self, t):
         """Physical log row (scalar) of relative row t < 0, or per-env rows [N] of episode row
-        t >= 0 (row t of every env's current episode)."""
+        t >= 0 (row t of every env's current episode).  In a capture: a device tensor [1]."""
         if t < 0:
             if -t > self._have:
                 raise IndexError(f"index {t} is out of bounds: {self._have} rows are logged")
+            if self._dev is not None:
+                return self._dev[self._L + t:self._L + t + 1]
             return (self._rows + t) % self._L
+        if self._dev is not None:
+            raise ValueError(f"h[column, {t}] cannot be captured into a graph: its bounds check reads "
+                             "the device (use negative indices, or h[column] with episode_mask())")
         step = self._env._log_row("step", (self._rows - 1) % self._L, raw=True)
         if self._terminal:
             step = self._env._overlay(step, "step")
@@ -80,9 +103,10 @@ class BatchedHistory:
                              "of some env")
         return (self._rows - 1 - back) % self._L
 
-    def _column(self, name, phys):
+    def _column(self, name, phys, t=None):
         """Values of column `name` at physical row(s) `phys`: a scalar row, a per-env row vector
-        [N] or None for every logged row, oldest first ([R, N])."""
+        [N] or None for every logged row, oldest first ([R, N]).  t: the relative row `phys`
+        stands for (when it is one)."""
         v = self._log_column(name, phys)
         if not self._terminal:
             return v
@@ -91,30 +115,41 @@ class BatchedHistory:
             v = v.clone() if hasattr(v, "clone") else v.copy()
             v[-1] = e._overlay(v[-1], name)
             return v
+        if self._dev is not None:  # a full log: relative row -1 is the newest one
+            return e._overlay(v, name) if t == -1 else v
         if np.ndim(phys) == 0:
             return e._overlay(v, name) if int(phys) == newest else v
         return e._overlay(v, name, only=(phys == newest))
 
     def _log_column(self, name, phys):
+        if self._dev is not None and phys is not None:  # one row, picked on the device: [1, N] -> [N]
+            return self._log_column_rows(name, None, phys)[0]
+        return self._log_column_rows(name, phys, self._order())
+
+    def _log_column_rows(self, name, phys, order):
         e = self._env
         if name in _LOG_COLUMNS:
-            return e._log_rows(name, phys, self._order())
+            return e._log_rows(name, phys, order)
         if name == "position":
-            return e._take(e._positions_table(), e._log_rows("position_index", phys, self._order()))
+            return e._take(e._positions_table(), e._log_rows("position_index", phys, order))
         if name.startswith("portfolio_distribution_"):
             k = name[len("portfolio_distribution_"):]
             if k in ("interest_asset", "interest_fiat"):
-                return e._log_rows(k, phys, self._order())
+                return e._log_rows(k, phys, order)
             if k in _DIST:  # Portfolio.get_portfolio_distribution, portfolio.py:49-57
-                src = e._log_rows("asset" if k.endswith("asset") else "fiat", phys, self._order())
+                src = e._log_rows("asset" if k.endswith("asset") else "fiat", phys, order)
                 return e._relu(-src if k.startswith("borrowed") else src)
         if name == "date" or name.startswith("data_"):
-            return e._dataset_column(name, e._log_rows("dataset_index", phys, self._order()),
-                                     e._log_rows("idx", phys, self._order()))
+            if self._dev is not None:
+                e._require_device_column(name)
+            return e._dataset_column(name, e._log_rows("dataset_index", phys, order),
+                                     e._log_rows("idx", phys, order))
         raise ValueError(f"Feature {name} does not exist ... Check the available features : {self.columns}")
 
     def _order(self):
         """Physical rows of the logged window, oldest first."""
+        if self._dev is not None:
+            return self._dev
         return (np.arange(self._have) + self._rows - self._have) % self._L
 
     # -- the History protocol --------------------------------------------------------------------
@@ -124,9 +159,11 @@ class BatchedHistory:
             column, t = arg
             if isinstance(t, slice):
                 return self[column][t]
-            return e._wrap(self._column(column, self._phys(int(t))))
+            return e._wrap(self._column(column, self._phys(int(t)), int(t)))
         if isinstance(arg, (int, np.integer)):
             phys = self._phys(int(arg))
+            if self._dev is not None:  # host-valued columns cannot be captured: read when asked for
+                return _CapturedRow(self, phys, int(arg))
             return {c: e._wrap(self._column(c, phys)) for c in self.columns}
         if isinstance(arg, str):
             return e._wrap(self._column(arg, None))
@@ -143,6 +180,27 @@ class BatchedHistory:
     def episode_mask(self):
         """bool [R, N]: True where the logged row belongs to the env's CURRENT episode."""
         e = self._env
-        step_now = e._log_rows("step", (self._rows - 1) % self._L, self._order())
+        if self._dev is not None:
+            step_now = e._log_rows("step", None, self._dev[-1:])[0]
+        else:
+            step_now = e._log_rows("step", (self._rows - 1) % self._L, self._order())
         age = e._arange_rows(self._have)  # 0 = oldest logged row
         return e._wrap((self._have - 1 - age)[:, None] <= step_now[None, :])
+
+
+class _CapturedRow(Mapping):
+    """h[t] inside a graph capture: the columns of relative row t, each computed when read."""
+
+    def __init__(self, h, phys, t):
+        self._h, self._phys, self._t = h, phys, t
+
+    def __getitem__(self, column):
+        if column not in self._h.columns:
+            raise KeyError(column)
+        return self._h._env._wrap(self._h._column(column, self._phys, self._t))
+
+    def __iter__(self):
+        return iter(self._h.columns)
+
+    def __len__(self):
+        return len(self._h.columns)

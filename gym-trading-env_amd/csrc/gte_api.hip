@@ -43,8 +43,10 @@ hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_ste
                                 hipStream_t stream);
 hipError_t launch_set_dynamic_columns(const Params& p, const void* const* cols, const int32_t* is_f64,
                                       hipStream_t stream);
-hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* newest, int terminal_view,
-                               hipStream_t stream);
+hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* rows, const int64_t* last,
+                               int terminal_view, hipStream_t stream);
+hipError_t launch_set_log_reward(LogRow* rows, const int64_t* last, int L, int n, const double* reward,
+                                 hipStream_t stream);
 hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, int threads,
                           hipStream_t stream);
 int rollout_blocks_per_cu(const Params& p, int nt);
@@ -55,7 +57,7 @@ struct StateSoA {
 hipError_t launch_extract_state(const EnvRec* rec, int n, const StateSoA& o, hipStream_t stream);
 hipError_t launch_rewind_queue(EnvRec* rec, int n, hipStream_t stream);
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                      const uint8_t* trunc, int n, int64_t row_base, const LogArrays& o,
+                      const uint8_t* trunc, int n, const int64_t* cursor, int L, const LogArrays& o,
                       hipStream_t stream);
 hipError_t launch_snapshot(const EnvRec* rec, const double* reward64, const uint8_t* term,
                            const uint8_t* trunc, const float* obs, int64_t obs_elems, int first,
@@ -142,6 +144,12 @@ struct gte_env {
   gte::StateSoA soa = {};  // host-facing struct-of-arrays mirrors (gte_get_state)
   gte::StateSoA fsoa = {}; // the same for the terminal records (gte_get_final_state)
   gte::LogArrays log = {}; // device trajectory log (cfg.log_steps rows per env)
+  // Log cursor: the row count on the device, i64 [2] (log_cursor_other, gte_device.h).  A launch
+  // that appends a row when the terminal counter's slot is s reads log_cursor[s ^ 1] and writes
+  // log_cursor[s]; so whenever the stream is idle log_cursor[term_slot] == log_rows, the host's
+  // mirror of it (gte_get_log().rows, the host-side reads), which every host-side change of
+  // term_slot keeps true (park_cursor).  Nothing enqueued depends on a row index computed here.
+  int64_t* log_cursor = nullptr;
   int64_t log_rows = 0;
   int rollout_epw = 0;     // envs per wavefront of the fused rollout kernel (0 = not chosen yet)
   int resident_slots[3] = {0, 0, 0};  // workgroups of that geometry the chip holds at once
@@ -419,6 +427,8 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   if (cfg->log_steps > 0) {
     const size_t LN = (size_t)cfg->log_steps * N;
     chk(dev_alloc(E, &E->log.rows, LN));  // 80 B per (row, env)
+    chk(dev_alloc(E, &E->log_cursor, 2));  // (hipMalloc: 256-byte aligned, as the slot pair needs)
+    p.log_L = cfg->log_steps;
   }
   double* d_pos = nullptr;
   chk(dev_alloc(E, &d_pos, GTE_MAX_POSITIONS));
@@ -719,13 +729,23 @@ static int check_injection(const gte_env* E, size_t count, const int32_t* idx, c
   return GTE_OK;
 }
 
-// append one trajectory row per env (after a reset or a step)
+// append one trajectory row per env (after a reset or a step; term_slot is the launch's slot)
 static int append_log(gte_env* E) {
   if (E->cfg.log_steps <= 0) return GTE_OK;
   const Params& p = E->p;
-  const int64_t row_base = (E->log_rows % E->cfg.log_steps) * (int64_t)p.N;
-  HIPCHK(gte::launch_log(p.rec, p.reward64, p.terminated, p.truncated, p.N, row_base, E->log, E->stream));
+  HIPCHK(gte::launch_log(p.rec, p.reward64, p.terminated, p.truncated, p.N, E->log_cursor + (E->term_slot ^ 1),
+                         E->cfg.log_steps, E->log, E->stream));
   E->log_rows += 1;
+  return GTE_OK;
+}
+
+// Before the host resets term_slot: log_cursor[slot] is the slot the next appending launch will
+// read, so copy the count there from the slot the last launch wrote (stream-ordered, device to
+// device: the count never passes through the host).
+static int park_cursor(gte_env* E, int slot) {
+  if (!E->log_cursor || E->term_slot == slot) return GTE_OK;
+  HIPCHK(hipMemcpyAsync(E->log_cursor + slot, E->log_cursor + E->term_slot, sizeof(int64_t),
+                        hipMemcpyDeviceToDevice, E->stream));
   return GTE_OK;
 }
 
@@ -784,6 +804,7 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   if (inj_pos_index) { TRY(stage(E, E->d_inj_pos, inj_pos_index, 4 * N)); p.inj_pos = E->d_inj_pos; }
   if (inj_dataset) { TRY(stage(E, E->d_inj_ds, inj_dataset, 4 * N)); p.inj_ds = E->d_inj_ds; }
   HIPCHK(hipMemsetAsync(E->term_base, 0, 2 * sizeof(int32_t), E->stream));
+  TRY(park_cursor(E, 1));  // the reset's log row (slot 0) reads the count from slot 1
   E->term_slot = 0;
   p.term_count = E->term_base;
   p.term_count_next = E->term_base + 1;
@@ -841,17 +862,17 @@ int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
   // three kernels, no memset — provided nothing comes from pageable host memory, and the host-side bookkeeping a
   // replay cannot repeat stays consistent: the two-slot terminal counter alternates per launch, so
   // a graph must hold an EVEN number of steps and be replayed from the slot it was captured at
-  // (gte_get_outputs().term_slot; StepGraph in step_graph.py checks both); the trajectory log's
-  // row index is host state, so logged envs cannot be captured.
+  // (gte_get_outputs().term_slot; StepGraph in step_graph.py checks both).  The trajectory log's
+  // row index comes from the device cursor (log_cursor above), so logged envs are capturable too;
+  // the host's mirror of it (log_rows) advances during a capture as if the steps ran: the owner of
+  // the capture restores it and advances it per replay (gte_get_schedule / gte_set_schedule /
+  // gte_advance_log).
   hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(E->stream, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
   if (capture == hipStreamCaptureStatusActive) {
     if (!actions_on_device)
       return fail(GTE_ERR_STATE, "gte_step on a capturing stream needs device-resident actions "
                                  "(a copy from pageable host memory cannot be captured)");
-    if (E->cfg.log_steps > 0)
-      return fail(GTE_ERR_STATE, "gte_step on a capturing stream: the trajectory log's row index is "
-                                 "host state a replay would not advance (log_steps must be 0)");
   }
   if (E->affinity_period > 0 && ++E->steps_since_rebuild >= E->affinity_period) {
     // envs drift one row per step and ~1/duration of them jump at a reset: re-sort now and
@@ -880,7 +901,7 @@ int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
   const bool fused_log = E->cfg.log_steps > 0 && !(E->cfg.kernel_variant & 1024);
   if (fused_log) {
     p.log = E->log;
-    p.log_row_base = (E->log_rows % E->cfg.log_steps) * (int64_t)p.N;
+    p.log_cursor = E->log_cursor + (E->term_slot ^ 1);
   }
   // terminated / truncated: only the changed ones, where the flag ledger proves the buffers hold the
   // previous step's flags (dense inside a capture: a replay cannot rely on what ran before it)
@@ -899,6 +920,35 @@ int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
   flags_stepped(E, p, capturing);
   if (fused_log) E->log_rows += 1;
   else TRY(append_log(E));
+  return GTE_OK;
+}
+
+// The host schedule a stream capture advances without running anything (term_slot, log_rows,
+// steps_since_rebuild): saved before a capture and put back after it, whether it succeeded or not.
+int gte_get_schedule(gte_env* E, gte_schedule* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  out->log_rows = E->log_rows;
+  out->term_slot = E->term_slot;
+  out->steps_since_rebuild = E->steps_since_rebuild;
+  return GTE_OK;
+}
+
+int gte_set_schedule(gte_env* E, const gte_schedule* s) {
+  if (!E || !s) return fail(GTE_ERR_INVALID, "NULL argument");
+  if ((s->term_slot != 0 && s->term_slot != 1) || s->log_rows < 0 || s->steps_since_rebuild < 0)
+    return fail(GTE_ERR_INVALID, "not a schedule gte_get_schedule returned");
+  E->log_rows = s->log_rows;
+  E->term_slot = s->term_slot;
+  E->steps_since_rebuild = s->steps_since_rebuild;
+  flags_unsure(E, {});  // the flag ledger may have recorded captured steps as run: the next step is dense
+  return GTE_OK;
+}
+
+int gte_advance_log(gte_env* E, int64_t rows) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
+  if (rows < 0) return fail(GTE_ERR_INVALID, "rows must be >= 0");
+  E->log_rows += rows;
   return GTE_OK;
 }
 
@@ -1140,6 +1190,7 @@ int gte_get_log(gte_env* E, gte_log_view* out) {
   out->interest_asset = &r->ia; out->interest_fiat = &r->ifi;
   out->env_stride = (int64_t)sizeof(gte::LogRow);
   out->row_stride = (int64_t)sizeof(gte::LogRow) * E->p.N;
+  out->cursor = E->log_cursor; out->cursor_slot = E->term_slot; out->reserved0 = 0;
   return GTE_OK;
 }
 
@@ -1256,9 +1307,9 @@ int gte_set_log_reward(gte_env* E, const double* reward_device) {
   if (!E || !reward_device) return fail(GTE_ERR_INVALID, "NULL argument");
   if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
   if (E->log_rows <= 0) return fail(GTE_ERR_STATE, "the log is empty");
-  const int64_t row = (E->log_rows - 1) % E->cfg.log_steps;
-  HIPCHK(hipMemcpy2DAsync(&E->log.rows[row * (int64_t)E->p.N].reward, sizeof(gte::LogRow), reward_device,
-                          sizeof(double), sizeof(double), (size_t)E->p.N, hipMemcpyDeviceToDevice, E->stream));
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(gte::launch_set_log_reward(E->log.rows, E->log_cursor + E->term_slot, E->cfg.log_steps, E->p.N,
+                                    reward_device, E->stream));
   return GTE_OK;
 }
 
@@ -1267,8 +1318,7 @@ int gte_apply_reward(gte_env* E, const double* reward_device, int32_t terminal_v
   if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
   if (E->log_rows <= 0) return fail(GTE_ERR_STATE, "the log is empty");
   HIPCHK(hipSetDevice(E->cfg.device));
-  const int64_t row = (E->log_rows - 1) % E->cfg.log_steps;
-  HIPCHK(gte::launch_apply_reward(E->p, reward_device, E->log.rows + row * (int64_t)E->p.N,
+  HIPCHK(gte::launch_apply_reward(E->p, reward_device, E->log.rows, E->log_cursor + E->term_slot,
                                   terminal_view ? 1 : 0, E->stream));
   return GTE_OK;
 }
@@ -1303,6 +1353,7 @@ int gte_bind_outputs(gte_env* E, const gte_outputs* b) {
   p.truncated = b->truncated ? b->truncated : E->owned.truncated;
   E->term_base = b->term_count ? b->term_count : E->owned.term_count;  // i32 [2]
   HIPCHK(hipMemset(E->term_base, 0, 2 * sizeof(int32_t)));
+  TRY(park_cursor(E, 0));  // the next step (slot 1) reads the log's count from slot 0
   HIPCHK(hipDeviceSynchronize());
   E->term_slot = 0;
   p.term_ids = b->term_ids ? b->term_ids : E->owned.term_ids;

@@ -9,8 +9,10 @@ namespace gte {
 // Trajectory log (LogArrays, gte_device.h): the row of a reset, of a step of the kernels that do
 // not write it themselves (the isolated hot instantiations, the unfused rollout loop).
 __global__ void gte_log_kernel(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                               const uint8_t* trunc, int n, int64_t row_base, LogArrays o) {
+                               const uint8_t* trunc, int n, const int64_t* cursor, int L, LogArrays o) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t count = *cursor;  // rows written before this one (log_cursor_other, gte_device.h)
+  if (blockIdx.x == 0 && threadIdx.x == 0) *log_cursor_other(cursor) = count + 1;
   if (e >= n) return;
   const EnvRec r = rec[e];
   LogRow w;
@@ -23,14 +25,30 @@ __global__ void gte_log_kernel(const EnvRec* rec, const double* reward64, const 
   w.flags = (uint8_t)((term[e] ? 1 : 0) | (trunc[e] ? 2 : 0));
 #pragma unroll
   for (int i = 0; i < 7; ++i) w.pad[i] = 0;
-  o.rows[row_base + e] = w;
+  o.rows[log_row(count, L) * (int64_t)n + e] = w;
 }
 
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                      const uint8_t* trunc, int n, int64_t row_base, const LogArrays& o,
+                      const uint8_t* trunc, int n, const int64_t* cursor, int L, const LogArrays& o,
                       hipStream_t stream) {
   hipLaunchKernelGGL(gte_log_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rec, reward64, term,
-                     trunc, n, row_base, o);
+                     trunc, n, cursor, L, o);
+  return hipGetLastError();
+}
+
+// The NEWEST log row's reward column <- f64 [N] (historical_info["reward", -1] = reward,
+// environments.py:267); the row comes from the device cursor (`last`: the slot the last append wrote).
+__global__ void gte_set_log_reward_kernel(LogRow* rows, const int64_t* last, int L, int n,
+                                          const double* reward) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  rows[log_row(*last - 1, L) * (int64_t)n + e].reward = reward[e];
+}
+
+hipError_t launch_set_log_reward(LogRow* rows, const int64_t* last, int L, int n, const double* reward,
+                                 hipStream_t stream) {
+  hipLaunchKernelGGL(gte_set_log_reward_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rows, last, L,
+                     n, reward);
   return hipGetLastError();
 }
 
@@ -102,10 +120,11 @@ hipError_t launch_set_dynamic_columns(const Params& p, const void* const* cols, 
 // terminal_view (same-step auto-reset): an env that ended shows its TERMINAL row to the callable,
 // so the reset row underneath does not zero the reward it RETURNS; the log row itself — the reset
 // row of the next episode — keeps the reference's 0.
-__global__ void gte_apply_reward_kernel(const Params p, const double* reward, LogRow* newest,
-                                        int terminal_view) {
+__global__ void gte_apply_reward_kernel(const Params p, const double* reward, LogRow* rows,
+                                        const int64_t* last, int terminal_view) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= p.N) return;
+  LogRow* newest = rows + log_row(*last - 1, p.log_L) * (int64_t)p.N;  // (the device cursor: gte_set_log_reward)
   const bool term = p.terminated[e] != 0;
   const bool ended = term || p.truncated[e] != 0;
   const bool log_reset_row = newest[e].step == 0;
@@ -117,10 +136,10 @@ __global__ void gte_apply_reward_kernel(const Params p, const double* reward, Lo
   newest[e].reward = log_reset_row ? 0.0 : r;  // the log row of a reset keeps reward 0 (:196)
 }
 
-hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* newest, int terminal_view,
-                               hipStream_t stream) {
+hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* rows, const int64_t* last,
+                               int terminal_view, hipStream_t stream) {
   hipLaunchKernelGGL(gte_apply_reward_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, reward,
-                     newest, terminal_view);
+                     rows, last, terminal_view);
   return hipGetLastError();
 }
 

@@ -114,11 +114,28 @@ struct Params {
   int32_t hot_lds;     // != 0: a step's record stores go through LDS, one 64-byte request per env (gte_kernel)
   int32_t flags_sparse;  // != 0: terminated / truncated hold what each env's previous step stored there
                          // (EnvRec.flags_out), so a step stores only the flags that change (gte_step decides)
+  int32_t log_L;         // rows of the trajectory log (gte_config.log_steps; fills what was padding)
   // --- trajectory row written by THIS launch's phase A (a gte_step with log_steps > 0; the
   // shared-TU step kernel only).  log.idx == null: none (the host appends it with gte_log_kernel)
   LogArrays log;
-  int64_t log_row_base;  // index of env 0 in the row being written: (row % L) * N
+  int64_t* log_cursor;   // the slot of the log cursor this launch reads (log_cursor_other below)
 };
+static_assert(offsetof(Params, log) == 384 && offsetof(Params, log_cursor) == 392 && sizeof(Params) == 400,
+              "Params keeps its layout (log_cursor replaced log_row_base in place)");
+
+// The trajectory log's row count lives on the device, so that a replayed graph appends where the
+// log really is: a 16-byte-aligned pair int64_t[2] (gte_env::log_cursor, gte_api.hip) used with the
+// parity of the two-slot terminal counter.  A launch that appends a row reads the count from one
+// slot and publishes count + 1 in the other one; it never writes the slot it reads, and the kernel
+// boundary makes the new count visible to the next launch.
+__device__ inline int64_t* log_cursor_other(const int64_t* slot) {
+  return (int64_t*)((uintptr_t)slot ^ sizeof(int64_t));
+}
+// physical row (in [0, L) whatever the count) of log row number `count`
+__device__ inline int64_t log_row(int64_t count, int L) {
+  const int64_t r = count % L;
+  return r < 0 ? r + L : r;
+}
 
 // What the ISOLATED hot instantiations of the step kernel (gte_hot.hip / gte_hot_nt.hip, compiled
 // with GTE_HOT_ONLY) leave OUT of phase A: the terminal records behind `final_info`

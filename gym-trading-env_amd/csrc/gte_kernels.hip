@@ -591,12 +591,13 @@ __device__ inline void flush_hot_records(const Params& p, const WgLds& L, int s_
 // (80 contiguous bytes, two requests per env where the twelve columns were twelve).
 __device__ inline void flush_log_rows(const Params& p, const WgLds& L, int s_first, int n_env, int lane) {
   typedef float __attribute__((ext_vector_type(4))) f4;
+  const int64_t row_base = log_row(*p.log_cursor, p.log_L) * (int64_t)p.N;  // env 0 of the row (uniform)
   for (int i = lane; i < n_env * 5; i += 64) {
     const int q = i / 5, part = i - q * 5;
     const int sl = s_first + q;
     const int env = L.job[sl].env;  // (>= 0 for the first n_env slots)
     const f4 v = *reinterpret_cast<const f4*>(L.logrow + sizeof(LogRow) * sl + 16 * part);
-    *(reinterpret_cast<f4*>(&p.log.rows[p.log_row_base + env]) + part) = v;
+    *(reinterpret_cast<f4*>(&p.log.rows[row_base + env]) + part) = v;
   }
 }
 
@@ -948,6 +949,11 @@ __global__ __launch_bounds__(256) void gte_kernel(const Params p, const uint64_t
   // the terminal counter has two slots used alternately, so no memset launch is
   // needed between steps: this launch clears the slot the NEXT launch will use
   if (MODE == MODE_STEP && blockIdx.x == 0 && threadIdx.x == 0) p.term_count_next[0] = 0;
+#ifndef GTE_HOT_ONLY  // p.log: hot_tu_covers() keeps such launches off the isolated TUs
+  // this launch appends one log row: the next launch finds the count in the other cursor slot
+  if (MODE == MODE_STEP && p.log.rows && blockIdx.x == 0 && threadIdx.x == 0)
+    *log_cursor_other(p.log_cursor) = *p.log_cursor + 1;
+#endif
   const int EPB = p.epw * GTE_WAVES;  // envs per workgroup
   const int wg_first = blockIdx.x * EPB;
   if (wg_first >= p.N) return;  // whole workgroup exits together (before any barrier)

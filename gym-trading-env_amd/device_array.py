@@ -43,7 +43,8 @@ def _scalar_tensor(x, like):
         dt = like.dtype if not isinstance(x, float) or like.is_floating_point() else torch.float64
     else:
         dt = torch.float64
-    return torch.as_tensor(x, dtype=dt, device=like.device)
+    # (a fill on the device, not a host->device copy: the value can be part of a captured graph)
+    return torch.full((), x, dtype=dt, device=like.device)
 
 
 def _first_tensor(args):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GTE_ABI_VERSION 2
+#define GTE_ABI_VERSION 3
 #define GTE_MAX_POSITIONS 32
 #define GTE_MAX_DYN 4
 
@@ -229,12 +229,31 @@ int gte_set_autoreset_injection(gte_env* env, int32_t n_episodes,
  * (:244-251) -> reward (:17-18,:265-267) -> _get_obs (:152-160).
  * actions: i32 [N] position indices, -1 = None (hold, :234); a host pointer,
  * or a device pointer when actions_on_device != 0.
- * Stream capture: with device-resident actions and log_steps == 0 everything the call enqueues
- * can be captured into a HIP graph by the owner of the env's stream (gte_set_stream).  The
- * terminal counter alternates between its two slots per launch: capture an EVEN number of steps
- * and replay the graph only when gte_get_outputs().term_slot equals its value at capture time
- * (it does after any number of replays and after an even number of eager steps). */
+ * Stream capture: with device-resident actions everything the call enqueues can be captured into
+ * a HIP graph by the owner of the env's stream (gte_set_stream).  The terminal counter alternates
+ * between its two slots per launch: capture an EVEN number of steps and replay the graph only when
+ * gte_get_outputs().term_slot equals its value at capture time (it does after any number of
+ * replays and after an even number of eager steps).  With log_steps > 0 the log's row index is
+ * device state (gte_log_view.cursor), so a replay appends its rows where the log is; the host's
+ * count of them (gte_log_view.rows) advances during the capture as if the steps had run: save the
+ * schedule before the capture, restore it afterwards (also after a failed capture) and advance
+ * the count by the captured steps after each replay (gte_get_schedule below).  A graph re-sorts
+ * the processing order (gte_config.affinity_period) where the capture did. */
 int gte_step(gte_env* env, const int32_t* actions, int32_t actions_on_device);
+
+/* The host-side schedule of an env, which a stream capture advances although it runs nothing.
+ * gte_get_schedule saves it; gte_set_schedule puts a saved one back (only to undo the bookkeeping
+ * of launches that never ran: a capture) and makes the next step store every flag; after each
+ * replay of a graph that appended k log rows, gte_advance_log(env, k) keeps gte_log_view.rows
+ * exact. */
+typedef struct gte_schedule {
+  int64_t log_rows;             /* gte_log_view.rows                                  */
+  int32_t term_slot;            /* gte_outputs.term_slot                              */
+  int32_t steps_since_rebuild;  /* steps since the processing order was last re-sorted */
+} gte_schedule;
+int gte_get_schedule(gte_env* env, gte_schedule* out);
+int gte_set_schedule(gte_env* env, const gte_schedule* schedule);
+int gte_advance_log(gte_env* env, int64_t rows);
 
 /* TradingEnv.add_limit_order (environments.py:227-231) for every env with
  * pos_index[i] >= 0 (HOST arrays of length N; persistent == NULL means all
@@ -265,7 +284,10 @@ int gte_set_dynamic_columns(gte_env* env, const void* const* columns_device, con
  * below address column c of row 0, env 0, and element (r, e) of a column lives `row_stride`
  * bytes per row and `env_stride` bytes per env further: p + (r % L) * row_stride + e *
  * env_stride.  `rows` counts the rows written so far (the newest is rows - 1).  An episode of
- * env e is the run of rows whose `step` goes 0, 1, 2, ... (step 0 = the reset row). */
+ * env e is the run of rows whose `step` goes 0, 1, 2, ... (step 0 = the reset row).  The same
+ * count lives on the device, where launches read it: cursor[cursor_slot] equals `rows` once
+ * everything enqueued so far has run (a launch that appends a row reads one slot and writes the
+ * count + 1 to the other). */
 typedef struct gte_log_view {
   int32_t* idx;             /* i32 [L, N] _idx  (strided, see above)               */
   int32_t* step;            /* i32 [L, N] _step                                   */
@@ -284,6 +306,9 @@ typedef struct gte_log_view {
   double*  interest_fiat;   /*   environments.py:262)                                */
   int64_t  env_stride;      /* bytes from env e to env e + 1 of the same row          */
   int64_t  row_stride;      /* bytes from row r to row r + 1 of the same env          */
+  int64_t* cursor;          /* i64 [2] DEVICE: the rows written, see above              */
+  int32_t  cursor_slot;     /* the slot of `cursor` the last enqueued append wrote      */
+  int32_t  reserved0;
 } gte_log_view;
 int gte_get_log(gte_env* env, gte_log_view* out);
 /* the last `n` (<= L) rows of ONE env, oldest first, into host arrays of length n (any may

@@ -1,0 +1,218 @@
+"""Logged envs and Python callables captured into a HIP graph (`capture_steps` with a trajectory
+log: the log's row count is device state, gte.h "Stream capture").  Every case runs a graphed env
+beside an eager twin built with the same seed, through auto-resets and several replays, and
+compares state, observations, returns, the terminal list, the whole log (all envs), the History
+of a few envs and the host's count of log rows.  Needs an MI355X."""
+import numpy as np
+import pandas as pd
+import pytest
+
+import custom_callables as cc
+
+pytestmark = pytest.mark.gpu
+
+N = 3000
+STATE = ("idx", "step", "position_index", "episode", "portfolio_valuation", "asset", "fiat",
+         "interest_asset", "interest_fiat", "real_position")
+
+
+def _data(seed=5, T=600, Fs=6):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(0, 1, (T, Fs)).astype(np.float32),
+            100 * np.exp(np.cumsum(rng.normal(-1e-3, 3e-2, T))))
+
+
+def _policy(obs):
+    """A deterministic 'policy': the action is a function of the newest observation row."""
+    import torch
+    row = obs[:, -1] if obs.dim() == 3 else obs
+    return ((row[:, 0] > 0).to(torch.int32) + (row[:, 1] > 0.5).to(torch.int32)).contiguous()
+
+
+def _twins(data=None, **kw):
+    from gym_trading_env_amd.batched import BatchedTradingEnv
+    args = dict(num_envs=N, positions=[-1, 0, 1], windows=8, trading_fees=1e-3,
+                borrow_interest_rate=1e-4, max_episode_duration=13, seed=17, verbose=0,
+                output="torch")
+    args.update(kw)
+    data = _data() if data is None else data
+    return BatchedTradingEnv(data, **args), BatchedTradingEnv(data, **args)
+
+
+def _step(env, n=1):
+    for _ in range(n):
+        env.step(_policy(env._t["obs"]))
+
+
+def _capture(env, K):
+    return env.capture_steps(lambda i: env.step(_policy(env._t["obs"])), K)
+
+
+def _same(eager, graphed, ids=(0, 1, 1234, N - 1)):
+    import torch
+    torch.cuda.synchronize()
+    for k in ("obs", "reward", "reward64", "terminated", "truncated"):
+        assert torch.equal(eager._t[k], graphed._t[k]), k
+    te, tg = eager.terminal_ids(), graphed.terminal_ids()
+    np.testing.assert_array_equal(te, tg)
+    if eager.cfg.final_obs:
+        assert torch.equal(eager._t["final_obs"][te], graphed._t["final_obs"][tg])
+        np.testing.assert_array_equal(eager.final_state("portfolio_valuation")[te],
+                                      graphed.final_state("portfolio_valuation")[tg])
+    for k in STATE:
+        np.testing.assert_array_equal(eager.state(k), graphed.state(k), err_msg=k)
+    assert eager._log_view().rows == graphed._log_view().rows
+    everyone = np.arange(N)
+    a = {k: v.copy() for k, v in eager.read_log_envs(everyone).items()}
+    b = graphed.read_log_envs(everyone)
+    for k, v in a.items():
+        np.testing.assert_array_equal(v, b[k], err_msg=f"log column {k}")
+    for e in ids:
+        he, hg = eager.history(e), graphed.history(e)
+        assert he.columns == hg.columns and len(he) == len(hg)
+        for c in he.columns:
+            if c != "date":
+                np.testing.assert_array_equal(np.asarray(he[c]), np.asarray(hg[c]), err_msg=c)
+
+
+def _run(eager, graphed, K, rounds=4, warm=None):
+    """reset both, fill the log eagerly, capture K steps, then alternate K eager steps with one
+    replay (and an even number of eager steps on both now and then)"""
+    eager.reset()
+    graphed.reset()
+    warm = int(eager.cfg.log_steps) if warm is None else warm
+    _step(eager, warm)
+    _step(graphed, warm)
+    g = _capture(graphed, K)
+    _same(eager, graphed)  # the capture executed nothing
+    ends = 0
+    for r in range(rounds):
+        for _ in range(K):
+            _step(eager)
+            ends += int((eager._t["terminated"] | eager._t["truncated"]).sum())
+        g.replay()
+        _same(eager, graphed)
+        if r == 1:
+            _step(eager, 2)
+            _step(graphed, 2)
+            _same(eager, graphed)
+    assert ends >= N  # every env went through an auto-reset inside a replayed stretch
+    return g
+
+
+@pytest.mark.parametrize("kernel_variant,mode", [(0, "next_step"), (1024, "next_step"), (0, "same_step")])
+def test_user_log_graph_equals_eager_steps(kernel_variant, mode):
+    """log_steps = 5 with K = 6: a replay starts at a different row of the log every time (K is no
+    multiple of L), so the row index can only come from the device.  1024: the separate log launch."""
+    eager, graphed = _twins(log_steps=5, kernel_variant=kernel_variant, autoreset=mode)
+    g = _run(eager, graphed, K=6)
+    # the odd-eager-step guard still fires, and one more step makes the graph usable again
+    _step(eager)
+    _step(graphed)
+    with pytest.raises(RuntimeError, match="odd number of eager steps"):
+        g.replay()
+    _step(eager)
+    _step(graphed)
+    g.replay()
+    _step(eager, 6)
+    _same(eager, graphed)
+    eager.close(); graphed.close()
+
+
+@pytest.mark.parametrize("mode", ["next_step", "same_step"])
+def test_python_reward_graph_equals_eager_steps(mode):
+    """The reference's vectorised example reward (np.log of two History rows) inside the graph."""
+    eager, graphed = _twins(reward_function=cc.reward_log_return_example, autoreset=mode,
+                            final_obs=(mode == "same_step"))
+    _run(eager, graphed, K=4, rounds=6)
+    eager.close(); graphed.close()
+
+
+def test_python_dynamic_features_graph_equals_eager_steps():
+    """Both DYNAMIC callables in same-step mode: the terminal observations carry the feature of the
+    terminal row, the returned ones that of the reset row (evaluated every step in a graph)."""
+    eager, graphed = _twins(dynamic_feature_functions=list(cc.DYNAMIC.values()), autoreset="same_step",
+                            final_obs=True)
+    _run(eager, graphed, K=4, rounds=6)
+    eager.close(); graphed.close()
+
+
+def _rolling_reward(h):
+    """A reward over the whole logged window [L, N] and its episode mask."""
+    pv = h["portfolio_valuation"]
+    ref = np.where(h.episode_mask(), pv, pv[-1]).mean(axis=0)
+    return np.log(pv[-1] / ref) - 1e-4 * abs(h["position", -1] - h["position", -2])
+
+
+def test_rolling_window_reward_graph_equals_eager_steps():
+    eager, graphed = _twins(reward_function=_rolling_reward, log_steps=8)
+    _run(eager, graphed, K=6)
+    eager.close(); graphed.close()
+
+
+def test_graph_after_rebinding_outputs():
+    """gte_bind_outputs resets the terminal counter's slot after logged steps: the log's count
+    moves to the slot the next launch reads, and captures go on from there."""
+    eager, graphed = _twins(log_steps=5, reward_function=cc.reward_simple_return_minus_turnover)
+    eager.reset()
+    graphed.reset()
+    _step(eager, 7)  # (an odd number: the slot the log's count sits in is not the one reset to)
+    _step(graphed, 7)
+    eager._bind_torch_outputs()
+    graphed._bind_torch_outputs()
+    _step(eager, 3)
+    _step(graphed, 3)
+    _same(eager, graphed)
+    g = _capture(graphed, 6)
+    for _ in range(3):
+        _step(eager, 6)
+        g.replay()
+        _same(eager, graphed)
+    eager.close(); graphed.close()
+
+
+def test_what_a_logged_capture_refuses():
+    import torch
+    T = 600
+    feat, close = _data(T=T)
+    df = pd.DataFrame({"close": close}, index=pd.date_range("2022-03-01", periods=T, freq="30min"))
+    for j in range(feat.shape[1]):
+        df[f"feature_{j}"] = feat[:, j]
+    eager, graphed = _twins(data=df, log_steps=5)
+    eager.reset()
+    graphed.reset()
+    # the log is not full yet
+    with pytest.raises(ValueError, match="full log"):
+        _capture(graphed, 2)
+    _step(eager, 4)
+    _step(graphed, 4)
+
+    def body_reading(index):
+        def body(i):
+            graphed.step(_policy(graphed._t["obs"]))
+            graphed.batched_history()[index]
+        return body
+    with pytest.raises(ValueError, match="bounds check"):  # h[col, t >= 0]
+        graphed.capture_steps(body_reading(("portfolio_valuation", 0)), 2)
+    with pytest.raises(ValueError, match="host values"):  # datetimes stay on the host
+        graphed.capture_steps(body_reading(("date", -1)), 2)
+    torch.cuda.synchronize()
+    _same(eager, graphed)
+
+    # a body that raises part-way leaves the env exactly like its twin
+    def failing(i):
+        graphed.step(_policy(graphed._t["obs"]))
+        if i == 3:
+            raise KeyError("the policy failed")
+    with pytest.raises(KeyError):
+        graphed.capture_steps(failing, 6)
+    torch.cuda.synchronize()
+    _step(eager, 3)
+    _step(graphed, 3)
+    _same(eager, graphed)
+    g = _capture(graphed, 4)
+    for _ in range(3):
+        _step(eager, 4)
+        g.replay()
+        _same(eager, graphed)
+    eager.close(); graphed.close()
