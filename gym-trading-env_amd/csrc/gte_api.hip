@@ -109,6 +109,29 @@ static int fail(int code, const char* fmt, ...) {
                   "%s failed: %s", #expr, hipGetErrorString(e_));                 \
   } while (0)
 
+// Which kernels an env launches, with what geometry: decided by plan_launches (gte_create) and changed
+// later only where noted.  p.epw, p.lean_rows and p.hot_lds are set there too.
+struct LaunchPlan {
+  int vec = 1, blocks = 0, threads = 256;
+  bool coop = false;       // wave 0 of a workgroup runs phase A for the whole workgroup
+  int stage = 0;           // dynamic columns: 0 global, 1 raw rings in LDS, 2 resolved in LDS
+  int hot_per_cu = 0;      // resident workgroups per CU the geometry was sized for (0 = n/a)
+  int store = 0;           // observation store policy (store_out): 0 plain, 1 nt, 2 sc1 (never 3)
+  bool hot_tu = false;     // the step may go to the isolated hot instantiations (hot_tu_covers permitting)
+  bool fused_log = false;  // the step kernel writes the trajectory row itself
+  bool always_dense = false;     // every step stores all flags (flag ledger below)
+  bool fused_rollout = false;    // gte_rollout may use the fused kernels ...
+  bool resident_rollout = false; // ... and among them the window-resident one
+  // L2-affinity processing order (gte_kernels.hip, "L2-affinity permutation")
+  int affinity_period = 0;       // 0 = off (also set by finalize and by a failed re-sort)
+  int n_bins_per_ds = 0;
+  // rollout geometries, chosen by the first rollout that needs them
+  int rollout_epw = 0;     // envs per wavefront of the fused rollout kernel (0 = not chosen yet)
+  int resident_slots[3] = {0, 0, 0};  // workgroups of that geometry the chip holds at once
+  int resident_epb[3] = {0, 0, 0};  // envs per workgroup of the window-resident rollout kernel per
+                                    // store policy (0 = not chosen yet, -1 = shape not covered)
+};
+
 struct gte_env {
   gte_config cfg;
   Params p;
@@ -129,15 +152,11 @@ struct gte_env {
   uint8_t* d_lo_persist_in = nullptr;
   bool finalized = false;
   bool was_reset = false;
-  int vec = 1, blocks = 0, threads = 256;
-  bool coop = false;       // wave 0 of a workgroup runs phase A for the whole workgroup
-  int stage = 0;           // dynamic columns: 0 global, 1 raw rings in LDS, 2 resolved in LDS
+  LaunchPlan plan;
   int32_t* term_base = nullptr;  // the two-slot terminal counter in use (owned or bound)
   int term_slot = 0;       // slot the last launch added to
-  // L2-affinity processing order (gte_kernels.hip, "L2-affinity permutation")
-  int affinity_period = 0;       // 0 = off
+  // L2-affinity processing order (plan.affinity_period)
   int steps_since_rebuild = 0;
-  int n_bins_per_ds = 0;
   int32_t* d_perm = nullptr;
   int32_t* d_slot_of_rank = nullptr;
   int32_t* d_bins = nullptr;
@@ -151,14 +170,8 @@ struct gte_env {
   // term_slot keeps true (park_cursor).  Nothing enqueued depends on a row index computed here.
   int64_t* log_cursor = nullptr;
   int64_t log_rows = 0;
-  int rollout_epw = 0;     // envs per wavefront of the fused rollout kernel (0 = not chosen yet)
-  int resident_slots[3] = {0, 0, 0};  // workgroups of that geometry the chip holds at once
   int32_t* d_group_counter = nullptr; // the resident kernel's work queue (next group of envs)
-  int resident_epb[3] = {0, 0, 0};  // envs per workgroup of the window-resident rollout kernel per
-                                    // store policy (0 = not chosen yet, -1 = shape not covered)
-  int hot_per_cu = 0;      // resident workgroups per CU the geometry was sized for (0 = n/a)
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
-  bool store_auto = false; // the observation store policy was chosen here (cfg said 3)
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 0;
@@ -226,7 +239,7 @@ static void flags_unsure(gte_env* E, std::initializer_list<std::pair<const void*
 
 // May this step of E store its flags sparsely into p's buffers?
 static bool flags_may_skip(gte_env* E, const Params& p, bool capturing) {
-  if (capturing || (E->cfg.kernel_variant & 16384)) return false;  // (16384: A/B, always dense)
+  if (capturing || E->plan.always_dense) return false;
   std::lock_guard<std::mutex> lock(g_flag_mu);
   return E->flags_sparse_ok && E->flags_term == p.terminated && E->flags_trunc == p.truncated;
 }
@@ -335,6 +348,201 @@ static int require_device(int device) {
   return GTE_OK;
 }
 
+static int alloc_soa(gte_env* E, gte::StateSoA* o, size_t N) {
+  for (int32_t** a : {&o->idx, &o->step, &o->pos, &o->dsi, &o->start, &o->episode, &o->needs_reset})
+    TRY(dev_alloc(E, a, N));
+  for (double** a : {&o->asset, &o->fiat, &o->ia, &o->ifi, &o->pv, &o->realpos}) TRY(dev_alloc(E, a, N));
+  return GTE_OK;
+}
+
+// gte_create's way out once the env exists: free it, keep the message of the failure
+static int create_failed(gte_env* E, int rc) {
+  const std::string keep = g_err;
+  gte_destroy(E);
+  g_err = keep;
+  return rc;
+}
+
+// Step launch geometry: EPW environments per wavefront, 4 wavefronts per workgroup.  hot_ok: the
+// config leaves the hot kernel's cooperative, LDS-staged shape on; lean_ok: the lean copy loop.
+static void step_geometry(gte_env* E, bool hot_ok, bool lean_ok) {
+  LaunchPlan& L = E->plan;
+  Params& p = E->p;
+  L.vec = (p.Fobs % 4 == 0) ? 4 : 1;
+  const int64_t vpe = (int64_t)p.W * p.Fobs / L.vec;  // vectors per env
+  int epw = E->cfg.envs_per_wave;
+  if (epw == 0) {
+    // windows of at least one wave instruction: 16 envs per wave (64 per workgroup, cooperative
+    // phase A) measured best at every size tried; tiny windows may pack up to 64 per wave
+    epw = (vpe >= 64) ? 16 : 64;
+    // enough wavefronts to fill 256 CUs x 16 waves ...
+    while (epw > 1 && ((int64_t)p.N + epw - 1) / epw < 4096) epw >>= 1;
+    // ... but at least one full wave instruction (64 vectors) of copy work per wavefront
+    // (small windows are latency-bound: 16 envs/wave with cooperative phase A measured
+    // 5.4 us vs 7.5 us at 64 envs/wave on config 2, profiles/r01_tune_c2.log)
+    while (epw < 64 && (int64_t)epw * vpe < 64) epw <<= 1;
+    // Windowed shapes on the hot kernel.  Two regimes, both measured (DESIGN.md §4):
+    //  * every workgroup resident at once, at least 16 waves on every CU: the launch ends when the
+    //    BUSIEST CU is done (workgroups are dealt evenly: ceil(wgs / CUs) per CU), so take the
+    //    envs-per-wave with the fewest envs on that CU; ties go to the bigger workgroup (fewer
+    //    phase-A waves).  Config 3, us per step by envs on the busiest CU: 256 (16 per wave) 39.5,
+    //    260 (13) 40.4, 264 (11) 40.5, 280 (14) 40.7, 288 (12) 42.0, 300 (15) 42.0; config 5:
+    //    128 (8 per wave, 4 workgroups per CU) 36.3, 16 per wave on 2 per CU 43.5
+    //    (profiles/r02_tune_epw.log, r02_waves_ab.log, r02_c5_sweep.log).
+    //  * more workgroups than the chip holds (the observations stream to HBM): small workgroups —
+    //    the phase A of those that start later hides behind the copies of those already running
+    //    and the tail is one small workgroup.  Config 3 (profiles/r02_tune_epw_repeat.log, 3 passes
+    //    each): 262 144 envs 16 per wave 156.4, 12: 154.7, 8: 149.2, 6: 143.8, 4: 142.6, 3: 145.5,
+    //    2: 169.0; 131 072 envs 16: 86.7, 11: 83.3, 8: 80.1, 6: 79.0, 4: 78.2, 3: 79.8; 100 003 envs
+    //    16: 74.5, 9: 62.1, 6: 60.0, 4: 61.6 -> about 640 vectors of copy work per wave (4 envs
+    //    of 20x32), 960 below 120 000 envs.
+    const bool hot_shape = L.vec == 4 && vpe >= 64 && p.nd > 0 && !p.persist && !E->cfg.final_obs &&
+                           (L.store == 1 || L.store == 2) && hot_ok;
+    if (hot_shape) {
+      hipDeviceProp_t prop;
+      if (hipGetDeviceProperties(&prop, E->cfg.device) == hipSuccess) {
+        const int64_t n_cu = prop.multiProcessorCount;
+        int some_per_cu = 0;  // (residency of any candidate: the occupancy queries work)
+        int64_t fewest = 0;
+        int one_round_epw = 0, one_round_per_cu = 0;
+        for (int e = 64 / GTE_WAVES; e >= 1; --e) {
+          if ((int64_t)e * vpe < 64) break;
+          Params q = p;
+          q.epw = e;  // registers AND the workgroup's LDS (which shrinks with e) bound residency
+          const size_t smem = gte::lds_bytes(q, 1);
+          const int per_cu = L.store == 1 ? gte::hot_blocks_per_cu_nt(smem) : gte::hot_blocks_per_cu(smem);
+          if (per_cu <= 0) break;
+          if (e <= 8 || !some_per_cu) some_per_cu = per_cu;
+          const int64_t wgs = ((int64_t)p.N + GTE_WAVES * e - 1) / (GTE_WAVES * e);
+          const int64_t busiest = (wgs + n_cu - 1) / n_cu;  // workgroups on the busiest CU
+          if (getenv("GTE_DEBUG_GEOMETRY"))
+            fprintf(stderr, "[gte] envs/wave %2d: LDS %5zu B, %d workgroups/CU resident, %lld workgroups, "
+                            "%lld on the busiest CU\n", e, smem, per_cu, (long long)wgs, (long long)busiest);
+          if (busiest <= per_cu && busiest * GTE_WAVES >= 16 && (fewest == 0 || busiest * e < fewest)) {
+            fewest = busiest * e;
+            one_round_epw = e;
+            one_round_per_cu = per_cu;
+          }
+        }
+        if (one_round_epw) {
+          epw = one_round_epw;
+          L.hot_per_cu = one_round_per_cu;
+        } else if (some_per_cu) {
+          L.hot_per_cu = some_per_cu;
+          const int64_t target = (int64_t)p.N >= 120000 ? 640 : 960;
+          int e = (int)((target + vpe / 2) / vpe);
+          e = e < 1 ? 1 : (e > 64 / GTE_WAVES ? 64 / GTE_WAVES : e);
+          while (e < 64 / GTE_WAVES && (int64_t)e * vpe < 64) ++e;
+          epw = e;
+          // Round 3: where the lean copy loop applies (whole passes of 4 wave instructions per wave,
+          // gte_kernels.hip) it beats the small workgroups above — 262 144 envs: 4 per wave 149 us,
+          // 8: 139.8, 16: 137.8; 131 072: 4: 80, 8: 74, 16: 71-78; 100 003: 6: 62, 8: 58.7, 16: 60-67
+          // (profiles/r03_epw_hbm.log) — so take the smallest envs-per-wave the lean loop accepts, twice
+          // that from 200 000 envs on.
+          if (lean_ok) {
+            int lean_e = 0;
+            for (int c = 1; c <= 64 / GTE_WAVES; ++c)
+              if (((int64_t)c * vpe) % 256 == 0 && (int64_t)c * p.W <= 512) { lean_e = c; break; }
+            if (lean_e) {
+              int c = lean_e;
+              while (c * 2 <= 64 / GTE_WAVES && (int64_t)c * vpe < 1280 && (int64_t)c * 2 * p.W <= 512) c *= 2;
+              if ((int64_t)p.N >= 200000 && c * 2 <= 64 / GTE_WAVES && (int64_t)c * 2 * p.W <= 512) c *= 2;
+              epw = c;
+            }
+          }
+        }
+      }
+    }
+  }
+  while (epw > 1 && (int64_t)epw * vpe > (1 << 20)) epw >>= 1;  // keeps the index math in range
+  // the LDS-staged dynamic columns must fit comfortably: shrink the workgroup's envs
+  while (epw > 1 && (int64_t)epw * GTE_WAVES * p.W * (p.nd ? p.nd : 1) * 4 > 32 * 1024) epw >>= 1;
+  p.epw = epw;
+  const int64_t waves = ((int64_t)p.N + epw - 1) / epw;
+  L.threads = 64 * GTE_WAVES;
+  L.blocks = (int)((waves + GTE_WAVES - 1) / GTE_WAVES);
+}
+
+// L2-affinity order: only worth it when every XCD gets several workgroups and the
+// windows are big enough to be bandwidth-bound
+static int setup_affinity(gte_env* E) {
+  LaunchPlan& L = E->plan;
+  const Params& p = E->p;
+  const size_t N = (size_t)p.N;
+  // Default re-sort period: the order decays as envs jump to new start rows, i.e. with the
+  // reset rate, about 1 / max_episode_duration of the envs per step once the episodes are out
+  // of phase.  Measured at duration 500, episodes staggered (profiles/r02_tune_affinity_period.log):
+  // every 128 steps 42.4 us per step, 64: 41.3, 32: 40.6, 16: 40.5, 8: 41.6 (a re-sort was four
+  // small launches then, ~25 us) -> re-sort after ~6 % of the envs have moved; 128 when episodes
+  // only end by the drawdown rule or at the end of the data.
+  int auto_period = 128;
+  if (p.max_dur > 0) {
+    auto_period = p.max_dur / 16;
+    auto_period = auto_period < 8 ? 8 : (auto_period > 128 ? 128 : auto_period);
+  }
+  const int period = E->cfg.affinity_period == 0 ? auto_period : E->cfg.affinity_period;
+  const int EPB = p.epw * GTE_WAVES;
+  const int n_wg = (p.N + EPB - 1) / EPB;
+  if (!(period > 0 && n_wg >= 64 && (int64_t)p.W * p.Fobs * 4 >= 512)) return GTE_OK;
+  // slots in XCD-major order: workgroup b runs on XCD b % 8 (round-robin dispatch)
+  std::vector<int32_t> slot_of_rank;
+  slot_of_rank.reserve(N);
+  for (int x = 0; x < 8; ++x)
+    for (int b = x; b < n_wg; b += 8)
+      for (int sl = b * EPB; sl < (b + 1) * EPB && sl < p.N; ++sl) slot_of_rank.push_back(sl);
+  int nb = 8192 / p.D;
+  if (const char* o = getenv("GTE_AFFINITY_BINS")) nb = atoi(o) / p.D;  // tuning: total bins of the counting sort
+  nb = nb < 1 ? 1 : (nb > 4096 ? 4096 : nb);
+  L.n_bins_per_ds = nb;
+  TRY(dev_alloc(E, &E->d_perm, N, false));
+  TRY(dev_alloc(E, &E->d_slot_of_rank, N, false));
+  TRY(dev_alloc(E, &E->d_bins, (size_t)2 * p.D * nb));  // histogram (zero-filled) + cursors
+  if (hipMemcpy(E->d_slot_of_rank, slot_of_rank.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice) !=
+      hipSuccess)
+    return fail(GTE_ERR_HIP, "copying slot_of_rank failed");
+  L.affinity_period = period;
+  return GTE_OK;
+}
+
+// Every launch choice of the env (LaunchPlan).  The only reader of cfg.kernel_variant, whose bits select
+// reference structures for A/B timing and the tests' twins (include/gte.h; 16384 = flags always dense).
+static int plan_launches(gte_env* E) {
+  LaunchPlan& L = E->plan;
+  Params& p = E->p;
+  const gte_config& cfg = E->cfg;
+  const int kv = cfg.kernel_variant;
+  // observation store policy (gte_kernels.hip, store_out): while the observation buffer fits
+  // the 256 MB Infinity Cache next to the feature table, sc1 stores keep it there (65 536 envs,
+  // 168 MB: 42.5 us vs 45.8 us with nt); beyond that the stores are a pure stream and
+  // non-temporal ones win (81 920 envs, 210 MB: 48 us vs 58 us; 262 144 envs: 162 us vs 261 us)
+  L.store = cfg.nontemporal_obs;
+  if (L.store == 3) L.store = ((size_t)p.N * p.W * p.Fobs * sizeof(float) > ((size_t)190 << 20)) ? 1 : 2;
+  step_geometry(E, !(kv & (1 | 2)), !(kv & 4096));
+  p.debug = cfg.debug_flags;
+  L.coop = (p.epw * GTE_WAVES <= 64) && !(kv & 1);
+  L.stage = (p.nd > 0 && gte::lds_bytes(p, 1) <= 48 * 1024 && !(kv & 2)) ? (p.persist ? 2 : 1) : 0;
+  // the lean copy loop (gte_kernels.hip): 16-byte vectors with the raw rings staged in LDS (stage 1;
+  // dyn_persist takes stage 2)
+  p.lean_rows = (L.vec == 4 && L.stage == 1 && !(kv & 4096)) ? 1 : 0;
+  p.hot_lds = (kv & 8192) ? 0 : 1;  // (8192: A/B, the stepping lane stores its record itself)
+  // the shape the isolated hot instantiations (gte_hot.hip) and the fused rollouts are written for
+  const bool hot_shape = L.vec == 4 && L.coop && L.stage == 1;
+  L.hot_tu = hot_shape && !(kv & 64);  // (64: A/B, the shared-TU instantiation instead)
+  // With a trajectory log the step kernel writes the row itself (shared-TU instantiation): the lane
+  // that stepped the env puts its 80-byte record into LDS and the copy waves write it out, five
+  // lanes per env.  At the config-3 shape, us per step: 38.5 against 43.2 with the separate
+  // gte_log_kernel launch (and 37.5 without a log; profiles/r03_log_ab.log).  (Rounds 1-2 kept the
+  // log as twelve [L, N] columns: twelve scattered stores per env from the stepping lane, which
+  // beyond 16 384 envs lost to the separate launch.)
+  // kernel_variant bit 1024 keeps the separate launch (A/B), 2048 = the default now.
+  L.fused_log = cfg.log_steps > 0 && !(kv & 1024);
+  L.always_dense = (kv & 16384) != 0;  // (A/B of the sparse flag stores)
+  // kernel_variant 128 = never fused (A/B and tests of the per-launch path)
+  L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & 128);
+  L.resident_rollout = p.W >= 2 && !(kv & 256);  // (256: the gather-per-step kernel instead)
+  return setup_affinity(E);
+}
+
 extern "C" {
 
 int gte_abi_version(void) { return GTE_ABI_VERSION; }
@@ -392,24 +600,12 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   chk(hipEventCreate(&E->ev0) == hipSuccess && hipEventCreate(&E->ev1) == hipSuccess
           ? GTE_OK : fail(GTE_ERR_HIP, "hipEventCreate failed"));
   chk(dev_alloc(E, &p.rec, N));  // zero-filled: every counter starts at 0
-  chk(dev_alloc(E, &E->soa.idx, N)); chk(dev_alloc(E, &E->soa.step, N));
-  chk(dev_alloc(E, &E->soa.pos, N)); chk(dev_alloc(E, &E->soa.dsi, N));
-  chk(dev_alloc(E, &E->soa.start, N)); chk(dev_alloc(E, &E->soa.episode, N));
-  chk(dev_alloc(E, &E->soa.needs_reset, N));
-  chk(dev_alloc(E, &E->soa.asset, N)); chk(dev_alloc(E, &E->soa.fiat, N));
-  chk(dev_alloc(E, &E->soa.ia, N)); chk(dev_alloc(E, &E->soa.ifi, N));
-  chk(dev_alloc(E, &E->soa.pv, N)); chk(dev_alloc(E, &E->soa.realpos, N));
+  chk(alloc_soa(E, &E->soa, N));
   // (the library's own observation buffers are allocated on first use, ensure_owned_obs: a caller
   // that binds its own — the torch path — never pays for a second copy of [N, W, F_obs])
   if (cfg->final_obs) {
     chk(dev_alloc(E, &p.final_rec, N));
-    chk(dev_alloc(E, &E->fsoa.idx, N)); chk(dev_alloc(E, &E->fsoa.step, N));
-    chk(dev_alloc(E, &E->fsoa.pos, N)); chk(dev_alloc(E, &E->fsoa.dsi, N));
-    chk(dev_alloc(E, &E->fsoa.start, N)); chk(dev_alloc(E, &E->fsoa.episode, N));
-    chk(dev_alloc(E, &E->fsoa.needs_reset, N));
-    chk(dev_alloc(E, &E->fsoa.asset, N)); chk(dev_alloc(E, &E->fsoa.fiat, N));
-    chk(dev_alloc(E, &E->fsoa.ia, N)); chk(dev_alloc(E, &E->fsoa.ifi, N));
-    chk(dev_alloc(E, &E->fsoa.pv, N)); chk(dev_alloc(E, &E->fsoa.realpos, N));
+    chk(alloc_soa(E, &E->fsoa, N));
   }
   {  // reward f32 [N] | terminated u8 [N] | truncated u8 [N] in ONE buffer of 6N bytes: the
      // layout a sharded run all-gathers as it is (gte_allgather_returns), no packing kernel
@@ -436,12 +632,7 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   if (rc == GTE_OK &&
       hipMemcpy(d_pos, cfg->positions, sizeof(double) * p.P, hipMemcpyHostToDevice) != hipSuccess)
     rc = fail(GTE_ERR_HIP, "copying positions failed");
-  if (rc != GTE_OK) {
-    std::string keep = g_err;
-    gte_destroy(E);
-    g_err = keep;
-    return rc;
-  }
+  if (rc != GTE_OK) return create_failed(E, rc);
   p.positions = d_pos;
   p.ds = E->d_ds;
   E->owned.obs_elems_per_env = (int64_t)p.W * p.Fobs;
@@ -455,164 +646,11 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   E->h_ds.assign((size_t)p.D, DatasetDesc{nullptr, nullptr, nullptr, nullptr, 0});
   for (auto& v : E->ds_allocs) v.assign((size_t)p.D, nullptr);
 
-  // observation store policy (gte_kernels.hip, store_out): while the observation buffer fits
-  // the 256 MB Infinity Cache next to the feature table, sc1 stores keep it there (65 536 envs,
-  // 168 MB: 42.5 us vs 45.8 us with nt); beyond that the stores are a pure stream and
-  // non-temporal ones win (81 920 envs, 210 MB: 48 us vs 58 us; 262 144 envs: 162 us vs 261 us)
-  E->store_auto = E->cfg.nontemporal_obs == 3;
-  if (E->store_auto)
-    E->cfg.nontemporal_obs = ((size_t)N * p.W * p.Fobs * sizeof(float) > ((size_t)190 << 20)) ? 1 : 2;
-
-  // launch geometry: EPW environments per wavefront, 4 wavefronts per workgroup
-  E->vec = (p.Fobs % 4 == 0) ? 4 : 1;
-  const int64_t vpe = (int64_t)p.W * p.Fobs / E->vec;  // vectors per env
-  int epw = cfg->envs_per_wave;
-  if (epw == 0) {
-    // windows of at least one wave instruction: 16 envs per wave (64 per workgroup, cooperative
-    // phase A) measured best at every size tried; tiny windows may pack up to 64 per wave
-    epw = (vpe >= 64) ? 16 : 64;
-    // enough wavefronts to fill 256 CUs x 16 waves ...
-    while (epw > 1 && ((int64_t)p.N + epw - 1) / epw < 4096) epw >>= 1;
-    // ... but at least one full wave instruction (64 vectors) of copy work per wavefront
-    // (small windows are latency-bound: 16 envs/wave with cooperative phase A measured
-    // 5.4 us vs 7.5 us at 64 envs/wave on config 2, profiles/r01_tune_c2.log)
-    while (epw < 64 && (int64_t)epw * vpe < 64) epw <<= 1;
-    // Windowed shapes on the hot kernel.  Two regimes, both measured (DESIGN.md §4):
-    //  * every workgroup resident at once, at least 16 waves on every CU: the launch ends when the
-    //    BUSIEST CU is done (workgroups are dealt evenly: ceil(wgs / CUs) per CU), so take the
-    //    envs-per-wave with the fewest envs on that CU; ties go to the bigger workgroup (fewer
-    //    phase-A waves).  Config 3, us per step by envs on the busiest CU: 256 (16 per wave) 39.5,
-    //    260 (13) 40.4, 264 (11) 40.5, 280 (14) 40.7, 288 (12) 42.0, 300 (15) 42.0; config 5:
-    //    128 (8 per wave, 4 workgroups per CU) 36.3, 16 per wave on 2 per CU 43.5
-    //    (profiles/r02_tune_epw.log, r02_waves_ab.log, r02_c5_sweep.log).
-    //  * more workgroups than the chip holds (the observations stream to HBM): small workgroups —
-    //    the phase A of those that start later hides behind the copies of those already running
-    //    and the tail is one small workgroup.  Config 3 (profiles/r02_tune_epw_repeat.log, 3 passes
-    //    each): 262 144 envs 16 per wave 156.4, 12: 154.7, 8: 149.2, 6: 143.8, 4: 142.6, 3: 145.5,
-    //    2: 169.0; 131 072 envs 16: 86.7, 11: 83.3, 8: 80.1, 6: 79.0, 4: 78.2, 3: 79.8; 100 003 envs
-    //    16: 74.5, 9: 62.1, 6: 60.0, 4: 61.6 -> about 640 vectors of copy work per wave (4 envs
-    //    of 20x32), 960 below 120 000 envs.
-    const bool hot_shape = E->vec == 4 && vpe >= 64 && p.nd > 0 && !p.persist && !cfg->final_obs &&
-                           (E->cfg.nontemporal_obs == 1 || E->cfg.nontemporal_obs == 2) &&
-                           !(cfg->kernel_variant & (1 | 2));
-    if (hot_shape) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) {
-        const int64_t n_cu = prop.multiProcessorCount;
-        int some_per_cu = 0;  // (residency of any candidate: the occupancy queries work)
-        int64_t fewest = 0;
-        int one_round_epw = 0, one_round_per_cu = 0;
-        for (int e = 64 / GTE_WAVES; e >= 1; --e) {
-          if ((int64_t)e * vpe < 64) break;
-          Params q = p;
-          q.epw = e;  // registers AND the workgroup's LDS (which shrinks with e) bound residency
-          const size_t smem = gte::lds_bytes(q, 1);
-          const int per_cu = E->cfg.nontemporal_obs == 1 ? gte::hot_blocks_per_cu_nt(smem)
-                                                          : gte::hot_blocks_per_cu(smem);
-          if (per_cu <= 0) break;
-          if (e <= 8 || !some_per_cu) some_per_cu = per_cu;
-          const int64_t wgs = ((int64_t)p.N + GTE_WAVES * e - 1) / (GTE_WAVES * e);
-          const int64_t busiest = (wgs + n_cu - 1) / n_cu;  // workgroups on the busiest CU
-          if (getenv("GTE_DEBUG_GEOMETRY"))
-            fprintf(stderr, "[gte] envs/wave %2d: LDS %5zu B, %d workgroups/CU resident, %lld workgroups, "
-                            "%lld on the busiest CU\n", e, smem, per_cu, (long long)wgs, (long long)busiest);
-          if (busiest <= per_cu && busiest * GTE_WAVES >= 16 && (fewest == 0 || busiest * e < fewest)) {
-            fewest = busiest * e;
-            one_round_epw = e;
-            one_round_per_cu = per_cu;
-          }
-        }
-        if (one_round_epw) {
-          epw = one_round_epw;
-          E->hot_per_cu = one_round_per_cu;
-        } else if (some_per_cu) {
-          E->hot_per_cu = some_per_cu;
-          const int64_t target = (int64_t)p.N >= 120000 ? 640 : 960;
-          int e = (int)((target + vpe / 2) / vpe);
-          e = e < 1 ? 1 : (e > 64 / GTE_WAVES ? 64 / GTE_WAVES : e);
-          while (e < 64 / GTE_WAVES && (int64_t)e * vpe < 64) ++e;
-          epw = e;
-          // Round 3: where the lean copy loop applies (whole passes of 4 wave instructions per wave,
-          // gte_kernels.hip) it beats the small workgroups above — 262 144 envs: 4 per wave 149 us,
-          // 8: 139.8, 16: 137.8; 131 072: 4: 80, 8: 74, 16: 71-78; 100 003: 6: 62, 8: 58.7, 16: 60-67
-          // (profiles/r03_epw_hbm.log) — so take the smallest envs-per-wave the lean loop accepts, twice
-          // that from 200 000 envs on.
-          if (!(cfg->kernel_variant & 4096)) {
-            int lean_e = 0;
-            for (int c = 1; c <= 64 / GTE_WAVES; ++c)
-              if (((int64_t)c * vpe) % 256 == 0 && (int64_t)c * p.W <= 512) { lean_e = c; break; }
-            if (lean_e) {
-              int c = lean_e;
-              while (c * 2 <= 64 / GTE_WAVES && (int64_t)c * vpe < 1280 && (int64_t)c * 2 * p.W <= 512) c *= 2;
-              if ((int64_t)p.N >= 200000 && c * 2 <= 64 / GTE_WAVES && (int64_t)c * 2 * p.W <= 512) c *= 2;
-              epw = c;
-            }
-          }
-        }
-      }
-    }
-  }
-  while (epw > 1 && (int64_t)epw * vpe > (1 << 20)) epw >>= 1;  // keeps the index math in range
-  // the LDS-staged dynamic columns must fit comfortably: shrink the workgroup's envs
-  while (epw > 1 && (int64_t)epw * GTE_WAVES * p.W * (p.nd ? p.nd : 1) * 4 > 32 * 1024) epw >>= 1;
-  p.epw = epw;
-  p.debug = cfg->debug_flags;
-  E->coop = (epw * GTE_WAVES <= 64) && !(cfg->kernel_variant & 1);
-  E->stage = (p.nd > 0 && gte::lds_bytes(p, 1) <= 48 * 1024 && !(cfg->kernel_variant & 2))
-                 ? (p.persist ? 2 : 1) : 0;
-  // the lean copy loop (gte_kernels.hip): 16-byte vectors with the raw rings staged in LDS
-  p.lean_rows = (E->vec == 4 && E->stage == 1 && !p.persist && !(cfg->kernel_variant & 4096)) ? 1 : 0;
-  p.hot_lds = (cfg->kernel_variant & 8192) ? 0 : 1;  // (8192: A/B, the stepping lane stores its record itself)
-  const int64_t waves = ((int64_t)p.N + epw - 1) / epw;
-  E->threads = 64 * GTE_WAVES;
-  E->blocks = (int)((waves + GTE_WAVES - 1) / GTE_WAVES);
-  // L2-affinity order: only worth it when every XCD gets several workgroups and the
-  // windows are big enough to be bandwidth-bound
-  {
-    // Default re-sort period: the order decays as envs jump to new start rows, i.e. with the
-    // reset rate, about 1 / max_episode_duration of the envs per step once the episodes are out
-    // of phase.  Measured at duration 500, episodes staggered (profiles/r02_tune_affinity_period.log):
-    // every 128 steps 42.4 us per step, 64: 41.3, 32: 40.6, 16: 40.5, 8: 41.6 (a re-sort was four
-    // small launches then, ~25 us) -> re-sort after ~6 % of the envs have moved; 128 when episodes
-    // only end by the drawdown rule or at the end of the data.
-    int auto_period = 128;
-    if (p.max_dur > 0) {
-      auto_period = p.max_dur / 16;
-      auto_period = auto_period < 8 ? 8 : (auto_period > 128 ? 128 : auto_period);
-    }
-    const int period = cfg->affinity_period == 0 ? auto_period : cfg->affinity_period;
-    const int EPB = epw * GTE_WAVES;
-    const int n_wg = (p.N + EPB - 1) / EPB;
-    if (period > 0 && n_wg >= 64 && vpe * E->vec * 4 >= 512) {
-      // slots in XCD-major order: workgroup b runs on XCD b % 8 (round-robin dispatch)
-      std::vector<int32_t> slot_of_rank;
-      slot_of_rank.reserve((size_t)p.N);
-      for (int x = 0; x < 8; ++x)
-        for (int b = x; b < n_wg; b += 8)
-          for (int sl = b * EPB; sl < (b + 1) * EPB && sl < p.N; ++sl) slot_of_rank.push_back(sl);
-      int nb = 8192 / p.D;
-      nb = nb < 1 ? 1 : (nb > 4096 ? 4096 : nb);
-      if (const char* o = getenv("GTE_AFFINITY_BINS")) {  // tuning: total bins of the counting sort
-        nb = atoi(o) / p.D;
-        nb = nb < 1 ? 1 : nb;
-      }
-      E->n_bins_per_ds = nb;
-      int rc2 = GTE_OK;
-      if (rc2 == GTE_OK) rc2 = dev_alloc(E, &E->d_perm, N, false);
-      if (rc2 == GTE_OK) rc2 = dev_alloc(E, &E->d_slot_of_rank, N, false);
-      if (rc2 == GTE_OK) rc2 = dev_alloc(E, &E->d_bins, (size_t)2 * p.D * nb);  // histogram (zero-filled) + cursors
-      if (rc2 == GTE_OK && hipMemcpy(E->d_slot_of_rank, slot_of_rank.data(), sizeof(int32_t) * N,
-                                     hipMemcpyHostToDevice) != hipSuccess)
-        rc2 = fail(GTE_ERR_HIP, "copying slot_of_rank failed");
-      if (rc2 != GTE_OK) { std::string keep = g_err; gte_destroy(E); g_err = keep; return rc2; }
-      E->affinity_period = period;
-    }
-  }
+  rc = plan_launches(E);
+  if (rc != GTE_OK) return create_failed(E, rc);
   // the zero-fills above ran on the null stream; the env's stream is non-blocking
-  if (hipDeviceSynchronize() != hipSuccess) {
-    gte_destroy(E);
-    return fail(GTE_ERR_HIP, "hipDeviceSynchronize failed after allocation");
-  }
+  if (hipDeviceSynchronize() != hipSuccess)
+    return create_failed(E, fail(GTE_ERR_HIP, "hipDeviceSynchronize failed after allocation"));
   p.final_obs = nullptr;  // (placeholder above)
   *out = E;
   return GTE_OK;
@@ -692,10 +730,10 @@ static int finalize(gte_env* E) {
   // per GPU, L2 hit rate 0.16 either way) only pay for the re-sorts and for scattered
   // observation stores: 39.4 us per step with the order, 36.8 without
   // (profiles/r02_c5_sweep.log).  Automatic (affinity_period = 0) turns it off there.
-  if (E->affinity_period > 0 && E->cfg.affinity_period == 0) {
+  if (E->plan.affinity_period > 0 && E->cfg.affinity_period == 0) {
     size_t table_bytes = 0;
     for (int d = 0; d < p.D; ++d) table_bytes += (size_t)E->h_ds[d].T * p.Fobs * sizeof(float);
-    if (table_bytes > ((size_t)64 << 20)) E->affinity_period = 0;
+    if (table_bytes > ((size_t)64 << 20)) E->plan.affinity_period = 0;
   }
   TRY(dev_alloc(E, &p.ring, (size_t)p.N * p.depth * (p.nd ? p.nd : 1)));
   HIPCHK(hipDeviceSynchronize());
@@ -729,10 +767,10 @@ static int check_injection(const gte_env* E, size_t count, const int32_t* idx, c
   return GTE_OK;
 }
 
-// append one trajectory row per env (after a reset or a step; term_slot is the launch's slot)
-static int append_log(gte_env* E) {
+// append one trajectory row per env (after a reset or a step, whose Params p were; term_slot is
+// the launch's slot)
+static int append_log(gte_env* E, const Params& p) {
   if (E->cfg.log_steps <= 0) return GTE_OK;
-  const Params& p = E->p;
   HIPCHK(gte::launch_log(p.rec, p.reward64, p.terminated, p.truncated, p.N, E->log_cursor + (E->term_slot ^ 1),
                          E->cfg.log_steps, E->log, E->stream));
   E->log_rows += 1;
@@ -778,10 +816,10 @@ static int ensure_owned_obs(gte_env* E) {
 // for good and the env goes on in identity order (results do not depend on the order).
 static int resort(gte_env* E) {
   E->steps_since_rebuild = 0;
-  const hipError_t e = gte::launch_affinity_rebuild(E->p, E->d_bins, E->n_bins_per_ds, E->d_slot_of_rank,
-                                                    E->d_perm, E->stream);
+  const hipError_t e = gte::launch_affinity_rebuild(E->p, E->d_bins, E->plan.n_bins_per_ds,
+                                                    E->d_slot_of_rank, E->d_perm, E->stream);
   if (e != hipSuccess) {
-    E->affinity_period = 0;
+    E->plan.affinity_period = 0;
     E->p.perm = nullptr;
     return fail(GTE_ERR_HIP, "re-sort of the processing order: %s", hipGetErrorString(e));
   }
@@ -809,10 +847,10 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   p.term_count = E->term_base;
   p.term_count_next = E->term_base + 1;
   flags_unsure(E, {{p.terminated, N}, {p.truncated, N}});  // (masked envs get zero flags, flags_out untouched)
-  HIPCHK(gte::launch_reset(p, E->vec, E->cfg.nontemporal_obs, E->coop, E->stage, E->blocks,
-                           E->threads, E->stream));
-  TRY(append_log(E));
-  if (E->affinity_period > 0) TRY(resort(E));  // new start rows: re-sort the processing order
+  const LaunchPlan& L = E->plan;
+  HIPCHK(gte::launch_reset(p, L.vec, L.store, L.coop, L.stage, L.blocks, L.threads, E->stream));
+  TRY(append_log(E, p));
+  if (L.affinity_period > 0) TRY(resort(E));  // new start rows: re-sort the processing order
   // host staging buffers may be reused by the caller right away: pageable copies above
   // are complete on return, but keep the contract simple and explicit
   HIPCHK(hipStreamSynchronize(E->stream));
@@ -853,74 +891,95 @@ int gte_set_autoreset_injection(gte_env* E, int32_t n, const int32_t* inj_idx,
   return GTE_OK;
 }
 
-int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_step before gte_reset");
-  if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
-  // Stream capture (hipStreamBeginCapture by whoever owns the stream — e.g. torch.cuda.graph around
-  // policy + step): everything a step enqueues is capturable — the step kernel and the re-sort's
-  // three kernels, no memset — provided nothing comes from pageable host memory, and the host-side bookkeeping a
-  // replay cannot repeat stays consistent: the two-slot terminal counter alternates per launch, so
-  // a graph must hold an EVEN number of steps and be replayed from the slot it was captured at
-  // (gte_get_outputs().term_slot; StepGraph in step_graph.py checks both).  The trajectory log's
-  // row index comes from the device cursor (log_cursor above), so logged envs are capturable too;
-  // the host's mirror of it (log_rows) advances during a capture as if the steps ran: the owner of
-  // the capture restores it and advances it per replay (gte_get_schedule / gte_set_schedule /
-  // gte_advance_log).
+// Stream capture (hipStreamBeginCapture by whoever owns the stream — e.g. torch.cuda.graph around
+// policy + step): everything a step enqueues is capturable — the step kernel and the re-sort's
+// three kernels, no memset — provided nothing comes from pageable host memory, and the host-side bookkeeping a
+// replay cannot repeat stays consistent: the two-slot terminal counter alternates per launch, so
+// a graph must hold an EVEN number of steps and be replayed from the slot it was captured at
+// (gte_get_outputs().term_slot; StepGraph in step_graph.py checks both).  The trajectory log's
+// row index comes from the device cursor (log_cursor above), so logged envs are capturable too;
+// the host's mirror of it (log_rows) advances during a capture as if the steps ran: the owner of
+// the capture restores it and advances it per replay (gte_get_schedule / gte_set_schedule /
+// gte_advance_log).
+static bool stream_capturing(gte_env* E) {
   hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(E->stream, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
-  if (capture == hipStreamCaptureStatusActive) {
-    if (!actions_on_device)
-      return fail(GTE_ERR_STATE, "gte_step on a capturing stream needs device-resident actions "
-                                 "(a copy from pageable host memory cannot be captured)");
-  }
-  if (E->affinity_period > 0 && ++E->steps_since_rebuild >= E->affinity_period) {
+  return capture == hipStreamCaptureStatusActive;
+}
+
+// two-slot terminal counter: this launch adds to one slot (cleared by the previous
+// launch or by gte_reset) and clears the other, so no memset sits between steps
+static void advance_term_slot(gte_env* E, Params& p) {
+  E->term_slot ^= 1;
+  p.term_count = E->term_base + E->term_slot;
+  p.term_count_next = E->term_base + (E->term_slot ^ 1);
+}
+
+// What one step launch reads and writes: the env's own buffers (gte_step) or one row of a
+// rollout's per-step buffers.  The actions are on the device.
+struct StepTargets {
+  const int32_t* actions;
+  float *obs, *reward;
+  double* reward64;
+  uint8_t *terminated, *truncated;
+};
+
+static StepTargets own_targets(const gte_env* E, const int32_t* actions) {
+  return {actions, E->p.obs, E->p.reward, E->p.reward64, E->p.terminated, E->p.truncated};
+}
+
+// The processing order ages with every step, fused or not: re-sort once it is due
+static int age_order(gte_env* E, int32_t steps) {
+  if (E->plan.affinity_period > 0 && (E->steps_since_rebuild += steps) >= E->plan.affinity_period) {
     // envs drift one row per step and ~1/duration of them jump at a reset: re-sort now and
     // then (3 tiny launches, stream-ordered between two steps)
     TRY(resort(E));
   }
-  Params p = E->p;
-  if (actions_on_device) {
-    p.actions = actions;
-  } else {
-    TRY(stage(E, E->d_actions, actions, sizeof(int32_t) * (size_t)p.N));
-    p.actions = E->d_actions;
-  }
-  // two-slot terminal counter: this launch adds to one slot (cleared by the previous
-  // launch or by gte_reset) and clears the other, so no memset sits between steps
-  E->term_slot ^= 1;
-  p.term_count = E->term_base + E->term_slot;
-  p.term_count_next = E->term_base + (E->term_slot ^ 1);
-  // With a trajectory log the step kernel writes the row itself (shared-TU instantiation): the lane
-  // that stepped the env puts its 80-byte record into LDS and the copy waves write it out, five
-  // lanes per env.  At the config-3 shape, us per step: 38.5 against 43.2 with the separate
-  // gte_log_kernel launch (and 37.5 without a log; profiles/r03_log_ab.log).  (Rounds 1-2 kept the
-  // log as twelve [L, N] columns: twelve scattered stores per env from the stepping lane, which
-  // beyond 16 384 envs lost to the separate launch.)
-  // kernel_variant bit 1024 keeps the separate launch (A/B), 2048 = the default now.
-  const bool fused_log = E->cfg.log_steps > 0 && !(E->cfg.kernel_variant & 1024);
-  if (fused_log) {
+  return GTE_OK;
+}
+
+// The one place a step is launched (gte_step; gte_rollout one launch per step), with store policy `store`
+static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool capturing) {
+  const LaunchPlan& L = E->plan;
+  TRY(age_order(E, 1));
+  Params p = E->p;  // (after the re-sort: it sets p.perm)
+  p.actions = t.actions; p.obs = t.obs; p.reward = t.reward; p.reward64 = t.reward64;
+  p.terminated = t.terminated; p.truncated = t.truncated;
+  advance_term_slot(E, p);
+  if (L.fused_log) {
     p.log = E->log;
     p.log_cursor = E->log_cursor + (E->term_slot ^ 1);
   }
   // terminated / truncated: only the changed ones, where the flag ledger proves the buffers hold the
   // previous step's flags (dense inside a capture: a replay cannot rely on what ran before it)
-  const bool capturing = capture == hipStreamCaptureStatusActive;
   p.flags_sparse = flags_may_skip(E, p, capturing) ? 1 : 0;
   // (hot_tu_covers: the isolated instantiations have no terminal records and no trajectory row)
-  const bool hot = E->vec == 4 && E->coop && E->stage == 1 && !(E->cfg.kernel_variant & 64) &&
-                   gte::hot_tu_covers(p);
-  if (hot && E->cfg.nontemporal_obs == 2)
-    HIPCHK(gte::launch_step_hot(p, E->blocks, E->threads, gte::lds_bytes(p, E->stage), E->stream));
-  else if (hot && E->cfg.nontemporal_obs == 1)
-    HIPCHK(gte::launch_step_hot_nt(p, E->blocks, E->threads, gte::lds_bytes(p, E->stage), E->stream));
+  const bool hot = L.hot_tu && gte::hot_tu_covers(p);
+  if (hot && store == 2)
+    HIPCHK(gte::launch_step_hot(p, L.blocks, L.threads, gte::lds_bytes(p, L.stage), E->stream));
+  else if (hot && store == 1)
+    HIPCHK(gte::launch_step_hot_nt(p, L.blocks, L.threads, gte::lds_bytes(p, L.stage), E->stream));
   else
-    HIPCHK(gte::launch_step(p, E->vec, E->cfg.nontemporal_obs, E->coop, E->stage, E->blocks,
-                            E->threads, E->stream));
+    HIPCHK(gte::launch_step(p, L.vec, store, L.coop, L.stage, L.blocks, L.threads, E->stream));
   flags_stepped(E, p, capturing);
-  if (fused_log) E->log_rows += 1;
-  else TRY(append_log(E));
+  if (L.fused_log) E->log_rows += 1;
+  else TRY(append_log(E, p));
   return GTE_OK;
+}
+
+int gte_step(gte_env* E, const int32_t* actions, int32_t actions_on_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_step before gte_reset");
+  if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
+  const bool capturing = stream_capturing(E);
+  if (capturing && !actions_on_device)
+    return fail(GTE_ERR_STATE, "gte_step on a capturing stream needs device-resident actions "
+                               "(a copy from pageable host memory cannot be captured)");
+  if (!actions_on_device) {
+    TRY(stage(E, E->d_actions, actions, sizeof(int32_t) * (size_t)E->p.N));
+    actions = E->d_actions;
+  }
+  return enqueue_step(E, own_targets(E, actions), E->plan.store, capturing);
 }
 
 // The host schedule a stream capture advances without running anything (term_slot, log_rows,
@@ -952,71 +1011,100 @@ int gte_advance_log(gte_env* E, int64_t rows) {
   return GTE_OK;
 }
 
-static bool cfg_is_auto_epw(const gte_env* E) { return E->cfg.envs_per_wave == 0; }
+// Window-resident kernel (gte_rollout.hip): each env's W-1 older rows stay in LDS for the
+// whole launch.  Geometry: E envs per workgroup such that (a) the newest rows fit the owner
+// threads, (b) as many envs as possible are resident per CU and (c) the workgroups fill a
+// whole number of rounds (each workgroup runs all K steps, so a part-filled last round costs
+// a full one): minimise rounds x max(phase A chain, the CU's observation bytes per step).
+static void choose_resident_epb(gte_env* E, const Params& p, int nt) {
+  LaunchPlan& L = E->plan;
+  L.resident_epb[nt] = -1;
+  hipDeviceProp_t prop;
+  const int64_t FV = p.Fobs / 4;
+  if (!L.resident_rollout || hipGetDeviceProperties(&prop, E->cfg.device) != hipSuccess) return;
+  double best = 0.0;
+  const char* force = getenv("GTE_RESIDENT_EPB");  // tuning: envs per group, no search
+  for (int e = 64; e >= 1; --e) {
+    if (force && atoi(force) != e) continue;
+    if ((int64_t)e * FV > 2 * 192) continue;  // RES_NEW * RES_OWNERS newest-row vectors
+    if (gte::resident_lds_bytes(p, e) > (size_t)160 * 1024) continue;
+    const int per_cu = gte::resident_blocks_per_cu(p, e, nt);
+    if (per_cu <= 0) continue;
+    const int64_t slots = (int64_t)per_cu * prop.multiProcessorCount;
+    const int64_t wgs = ((int64_t)p.N + e - 1) / e;
+    // the launch is a work queue over the groups: "rounds" is a real number, at least one
+    const double rounds = wgs > slots ? (double)wgs / (double)slots : 1.0;
+    const double live = (double)(wgs < slots ? (wgs + prop.multiProcessorCount - 1) / prop.multiProcessorCount
+                                             : per_cu);  // workgroups sharing a CU
+    const double us_bw = live * e * (double)p.W * p.Fobs * 4.0 / 22.0e3;  // ~5.6 TB/s over 256 CUs
+    // a workgroup's barriers and its state wave's latency are hidden by the OTHER workgroups
+    // of its CU: prefer four of them
+    // (measured at config 3, profiles/r02_resident_epb.log: 4 per CU 27.7 us per step, 3: 28.9,
+    // 2: 30.3, 1: 47.2)
+    static const double kAlone[5] = {1.7, 1.7, 1.10, 1.05, 1.0};
+    const double alone = kAlone[per_cu < 4 ? per_cu : 4];
+    const double cost = rounds * (us_bw > 3.0 ? us_bw : 3.0) * alone;
+    if (getenv("GTE_DEBUG_GEOMETRY"))
+      fprintf(stderr, "[gte] resident rollout, %2d envs/workgroup: LDS %6zu B, %d workgroups/CU, "
+                      "%lld groups, %.2f round(s), cost %.1f\n", e, gte::resident_lds_bytes(p, e),
+              per_cu, (long long)wgs, rounds, cost);
+    if (best == 0.0 || cost < best * 0.999) {
+      best = cost;
+      L.resident_epb[nt] = e;
+      L.resident_slots[nt] = (int)slots;
+    }
+  }
+}
 
-int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_rollout_bufs* b) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_rollout before gte_reset");
-  if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
-  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
-  static const gte_rollout_bufs none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (!b) b = &none;
+// The gather-per-step rollout kernel is a long-running loop: a workgroup that is not
+// resident from the start runs all K steps after the others have finished.  It needs more
+// registers than the step kernel, so it gets its own workgroup size, the smallest that
+// keeps every workgroup resident.
+static void choose_rollout_epw(gte_env* E, const Params& p, int nt) {
+  LaunchPlan& L = E->plan;
+  L.rollout_epw = p.epw;
+  hipDeviceProp_t prop;
+  if (E->cfg.envs_per_wave != 0 || hipGetDeviceProperties(&prop, E->cfg.device) != hipSuccess) return;
+  for (int e = 1; e <= 16; ++e) {
+    Params q = p;
+    q.epw = e;
+    if ((int64_t)e * p.W * p.Fobs / 4 < 64) continue;
+    const int per_cu = gte::rollout_blocks_per_cu(q, nt);
+    const int64_t wgs = ((int64_t)p.N + 4 * e - 1) / (4 * e);
+    if (per_cu > 0 && wgs <= (int64_t)per_cu * prop.multiProcessorCount) { L.rollout_epw = e; break; }
+    if (e == 16) L.rollout_epw = 16;  // more envs than one round holds: biggest workgroups
+  }
+}
+
+// gte_rollout's launches, after its checks
+static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_rollout_bufs* b) {
   const size_t N = (size_t)E->p.N;
   const size_t V = (size_t)E->p.W * (size_t)E->p.Fobs;
-  if (b->obs && ((uintptr_t)b->obs & 15)) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  // the fused kernels write flags into the env's buffers or the per-step rows (flag ledger)
-  struct FlagsAfterRollout {
-    gte_env* E;
-    const gte_rollout_bufs* b;
-    size_t rows;
-    ~FlagsAfterRollout() {
-      const size_t N = (size_t)E->p.N;
-      flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}, {b->terminated, rows * N},
-                       {b->truncated, rows * N}});
-    }
-  } flags_after_rollout{E, b, (size_t)n_steps};
-  // kernel_variant 128 = never fused (A/B and tests of the per-launch path)
-  const bool fused = E->vec == 4 && E->coop && E->stage == 1 && !E->cfg.final_obs && !E->p.persist &&
-                     E->cfg.log_steps == 0 && !(E->cfg.kernel_variant & 128);
+  const LaunchPlan& L = E->plan;
   // per-step observation rows are written once and not read back by the kernels: a stream
-  struct RestoreStorePolicy {  // whatever path leaves this function, the env's policy returns
-    int32_t& slot;
-    int32_t value;
-    ~RestoreStorePolicy() { slot = value; }
-  } restore_store_policy{E->cfg.nontemporal_obs, E->cfg.nontemporal_obs};
-  if (b->obs && E->store_auto) E->cfg.nontemporal_obs = 1;
+  // (non-temporal stores where the caller left the policy automatic)
+  const int nt = (b->obs && E->cfg.nontemporal_obs == 3) ? 1 : L.store;
+  const bool capturing = stream_capturing(E);
   // one step as its own launch, writing row k of every per-step buffer (what the unfused path
   // does for every step, and the backtest path for its last one)
-  const Params keep = E->p;
   auto step_row = [&](int32_t k) -> int {
-    if (b->obs) E->p.obs = b->obs + (size_t)k * N * V;
-    if (b->reward) E->p.reward = b->reward + (size_t)k * N;
-    if (b->reward64) E->p.reward64 = b->reward64 + (size_t)k * N;
-    if (b->terminated) E->p.terminated = b->terminated + (size_t)k * N;
-    if (b->truncated) E->p.truncated = b->truncated + (size_t)k * N;
-    int rc = gte_step(E, actions + (size_t)k * N, 1);
-    if (rc == GTE_OK && b->valuation) {
+    StepTargets t = own_targets(E, actions + (size_t)k * N);
+    if (b->obs) t.obs = b->obs + (size_t)k * N * V;
+    if (b->reward) t.reward = b->reward + (size_t)k * N;
+    if (b->reward64) t.reward64 = b->reward64 + (size_t)k * N;
+    if (b->terminated) t.terminated = b->terminated + (size_t)k * N;
+    if (b->truncated) t.truncated = b->truncated + (size_t)k * N;
+    TRY(enqueue_step(E, t, nt, capturing));
+    if (b->valuation) {
       hipError_t e = gte::launch_extract_state(E->p.rec, E->p.N, E->soa, E->stream);
       if (e == hipSuccess)
         e = hipMemcpyAsync(b->valuation + (size_t)k * N, E->soa.pv, 8 * N, hipMemcpyDeviceToDevice,
                            E->stream);
-      if (e != hipSuccess) rc = fail(GTE_ERR_HIP, "rollout: %s", hipGetErrorString(e));
-    }
-    E->p.obs = keep.obs; E->p.reward = keep.reward; E->p.reward64 = keep.reward64;
-    E->p.terminated = keep.terminated; E->p.truncated = keep.truncated;
-    return rc;
-  };
-  auto count_steps = [&](int32_t n) -> int {  // the processing order ages with every fused step too
-    if (E->affinity_period > 0) {
-      E->steps_since_rebuild += n;
-      if (E->steps_since_rebuild >= E->affinity_period) {
-        TRY(resort(E));
-      }
+      if (e != hipSuccess) return fail(GTE_ERR_HIP, "rollout: %s", hipGetErrorString(e));
     }
     return GTE_OK;
   };
-  if (!fused) {
+  if (!L.fused_rollout) {
     // same results, one launch per step
     for (int32_t k = 0; k < n_steps; ++k) TRY(step_row(k));
   } else if (!b->obs) {
@@ -1024,7 +1112,7 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
     // from registers (gte_rollout_state_kernel), then the last step as an ordinary launch, which
     // also produces the observation and the terminal list.
     if (n_steps > 1) {
-      TRY(count_steps(n_steps - 1));
+      TRY(age_order(E, n_steps - 1));
       gte::RolloutArgs r = {actions, n_steps - 1, nullptr, b->reward, b->reward64, b->terminated,
                             b->truncated, b->valuation, 0, 0, nullptr};
       // identity order: with no window to gather, the L2-affinity order would only scatter the
@@ -1041,58 +1129,11 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
     }
     TRY(step_row(n_steps - 1));
   } else {
-    TRY(count_steps(n_steps));
+    TRY(age_order(E, n_steps));
     Params p = E->p;
-    // Window-resident kernel (gte_rollout.hip): each env's W-1 older rows stay in LDS for the
-    // whole launch.  Geometry: E envs per workgroup such that (a) the newest rows fit the owner
-    // threads, (b) as many envs as possible are resident per CU and (c) the workgroups fill a
-    // whole number of rounds (each workgroup runs all K steps, so a part-filled last round costs
-    // a full one): minimise rounds x max(phase A chain, the CU's observation bytes per step).
-    const int nt = E->cfg.nontemporal_obs;
-    if (E->resident_epb[nt] == 0) {
-      E->resident_epb[nt] = -1;
-      hipDeviceProp_t prop;
-      const int64_t FV = p.Fobs / 4;
-      if (p.W >= 2 && !(E->cfg.kernel_variant & 256) &&
-          hipGetDeviceProperties(&prop, E->cfg.device) == hipSuccess) {
-        double best = 0.0;
-        const char* force = getenv("GTE_RESIDENT_EPB");  // tuning: envs per group, no search
-        for (int e = 64; e >= 1; --e) {
-          if (force && atoi(force) != e) continue;
-          if ((int64_t)e * FV > 2 * 192) continue;  // RES_NEW * RES_OWNERS newest-row vectors
-          if (gte::resident_lds_bytes(p, e) > (size_t)160 * 1024) continue;
-          const int per_cu = gte::resident_blocks_per_cu(p, e, nt);
-          if (per_cu <= 0) continue;
-          const int64_t slots = (int64_t)per_cu * prop.multiProcessorCount;
-          const int64_t wgs = ((int64_t)p.N + e - 1) / e;
-          // the launch is a work queue over the groups: "rounds" is a real number, at least one
-          const double rounds = wgs > slots ? (double)wgs / (double)slots : 1.0;
-          const double live = (double)(wgs < slots ? (wgs + prop.multiProcessorCount - 1) / prop.multiProcessorCount
-                                                   : per_cu);  // workgroups sharing a CU
-          const double us_bw = live * e * (double)p.W * p.Fobs * 4.0 / 22.0e3;  // ~5.6 TB/s over 256 CUs
-          // a workgroup's barriers and its state wave's latency are hidden by the OTHER workgroups
-          // of its CU: prefer four of them
-          // (measured at config 3, profiles/r02_resident_epb.log: 4 per CU 27.7 us per step, 3: 28.9,
-          // 2: 30.3, 1: 47.2)
-          static const double kAlone[5] = {1.7, 1.7, 1.10, 1.05, 1.0};
-          const double alone = kAlone[per_cu < 4 ? per_cu : 4];
-          const double cost = rounds * (us_bw > 3.0 ? us_bw : 3.0) * alone;
-          if (getenv("GTE_DEBUG_GEOMETRY"))
-            fprintf(stderr, "[gte] resident rollout, %2d envs/workgroup: LDS %6zu B, %d workgroups/CU, "
-                            "%lld groups, %.2f round(s), cost %.1f\n", e, gte::resident_lds_bytes(p, e),
-                    per_cu, (long long)wgs, rounds, cost);
-          if (best == 0.0 || cost < best * 0.999) {
-            best = cost;
-            E->resident_epb[nt] = e;
-            E->resident_slots[nt] = (int)slots;
-          }
-        }
-      }
-    }
-    E->term_slot ^= 1;
-    p.term_count = E->term_base + E->term_slot;
-    p.term_count_next = E->term_base + (E->term_slot ^ 1);
-    if (E->resident_epb[nt] > 0) {
+    if (L.resident_epb[nt] == 0) choose_resident_epb(E, p, nt);
+    advance_term_slot(E, p);
+    if (L.resident_epb[nt] > 0) {
       // identity processing order: the L2-affinity order exists for the table reads of the
       // per-step gather; here one row per env and step is read, and consecutive envs make each
       // workgroup's observation stores one contiguous run
@@ -1102,39 +1143,20 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
         HIPCHK(hipDeviceSynchronize());  // (the zero-fill ran on the null stream)
       }
       HIPCHK(hipMemsetAsync(E->d_group_counter, 0, sizeof(int32_t), E->stream));
-      const int epb = E->resident_epb[nt];
+      const int epb = L.resident_epb[nt];
       const int n_groups = (p.N + epb - 1) / epb;
       gte::RolloutArgs r = {actions, n_steps, b->obs, b->reward, b->reward64, b->terminated,
                             b->truncated, b->valuation, epb, n_groups, E->d_group_counter};
-      const int blocks = n_groups < E->resident_slots[nt] ? n_groups : E->resident_slots[nt];
+      const int blocks = n_groups < L.resident_slots[nt] ? n_groups : L.resident_slots[nt];
       const hipError_t le = gte::launch_rollout_resident(p, r, nt, blocks, E->stream);
       if (le != hipSuccess) return fail(GTE_ERR_HIP, "rollout launch: %s", hipGetErrorString(le));
     } else {
-      if (E->rollout_epw == 0) {
-        // The gather-per-step rollout kernel is a long-running loop: a workgroup that is not
-        // resident from the start runs all K steps after the others have finished.  It needs more
-        // registers than the step kernel, so it gets its own workgroup size, the smallest that
-        // keeps every workgroup resident.
-        E->rollout_epw = p.epw;
-        hipDeviceProp_t prop;
-        if (cfg_is_auto_epw(E) && hipGetDeviceProperties(&prop, E->cfg.device) == hipSuccess) {
-          for (int e = 1; e <= 16; ++e) {
-            Params q = p;
-            q.epw = e;
-            if ((int64_t)e * p.W * p.Fobs / 4 < 64) continue;
-            const int per_cu = gte::rollout_blocks_per_cu(q, E->cfg.nontemporal_obs);
-            const int64_t wgs = ((int64_t)p.N + 4 * e - 1) / (4 * e);
-            if (per_cu > 0 && wgs <= (int64_t)per_cu * prop.multiProcessorCount) { E->rollout_epw = e; break; }
-            if (e == 16) E->rollout_epw = 16;  // more envs than one round holds: biggest workgroups
-          }
-        }
-      }
-      p.epw = E->rollout_epw;
+      if (L.rollout_epw == 0) choose_rollout_epw(E, p, nt);
+      p.epw = L.rollout_epw;
       const int r_blocks = (int)((((int64_t)p.N + p.epw - 1) / p.epw + 3) / 4);
       gte::RolloutArgs r = {actions, n_steps, b->obs, b->reward, b->reward64, b->terminated,
                             b->truncated, b->valuation, 0, 0, nullptr};
-      const hipError_t le = gte::launch_rollout(p, r, E->cfg.nontemporal_obs, r_blocks, E->threads,
-                                                E->stream);
+      const hipError_t le = gte::launch_rollout(p, r, nt, r_blocks, L.threads, E->stream);
       if (le != hipSuccess) return fail(GTE_ERR_HIP, "rollout launch: %s", hipGetErrorString(le));
     }
   }
@@ -1145,6 +1167,22 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
   if (b->terminated) HIPCHK(hipMemcpyAsync(E->p.terminated, b->terminated + last, N, hipMemcpyDeviceToDevice, E->stream));
   if (b->truncated) HIPCHK(hipMemcpyAsync(E->p.truncated, b->truncated + last, N, hipMemcpyDeviceToDevice, E->stream));
   return GTE_OK;
+}
+
+int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_rollout_bufs* b) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_rollout before gte_reset");
+  if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
+  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
+  static const gte_rollout_bufs none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (!b) b = &none;
+  if (b->obs && ((uintptr_t)b->obs & 15)) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const int rc = rollout(E, actions, n_steps, b);
+  // the fused kernels write flags into the env's buffers or the per-step rows (flag ledger)
+  const size_t N = (size_t)E->p.N, rows = (size_t)n_steps * N;
+  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}, {b->terminated, rows}, {b->truncated, rows}});
+  return rc;
 }
 
 int gte_add_limit_orders(gte_env* E, const int32_t* pos_index, const double* limit,
@@ -1424,19 +1462,22 @@ int gte_bind_returns(gte_env* E, float* reward, uint8_t* terminated, uint8_t* tr
   return GTE_OK;
 }
 
-int gte_get_state(gte_env* E, gte_state_view* out) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  // the state lives in 128-byte records; snapshot it into struct-of-arrays mirrors
-  // (stream-ordered: the views reflect every launch enqueued before this call)
+// the state lives in 128-byte records; snapshot it into struct-of-arrays mirrors
+// (stream-ordered: the views reflect every launch enqueued before this call)
+static int state_view(gte_env* E, const EnvRec* rec, const gte::StateSoA& o, gte_state_view* out) {
   HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(gte::launch_extract_state(E->p.rec, E->p.N, E->soa, E->stream));
-  const gte::StateSoA& o = E->soa;
+  HIPCHK(gte::launch_extract_state(rec, E->p.N, o, E->stream));
   out->idx = o.idx; out->step = o.step; out->position_index = o.pos;
   out->dataset_index = o.dsi; out->start_idx = o.start; out->episode = o.episode;
   out->needs_reset = o.needs_reset; out->asset = o.asset; out->fiat = o.fiat;
   out->interest_asset = o.ia; out->interest_fiat = o.ifi;
   out->portfolio_valuation = o.pv; out->real_position = o.realpos;
   return GTE_OK;
+}
+
+int gte_get_state(gte_env* E, gte_state_view* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  return state_view(E, E->p.rec, E->soa, out);
 }
 
 int gte_set_dynamic_features(gte_env* E, const float* values_device, uint32_t mask) {
@@ -1461,15 +1502,7 @@ int gte_set_dynamic_columns(gte_env* E, const void* const* columns_device, const
 int gte_get_final_state(gte_env* E, gte_state_view* out) {
   if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
   if (!E->p.final_rec) return fail(GTE_ERR_STATE, "created without final_obs");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(gte::launch_extract_state(E->p.final_rec, E->p.N, E->fsoa, E->stream));
-  const gte::StateSoA& o = E->fsoa;
-  out->idx = o.idx; out->step = o.step; out->position_index = o.pos;
-  out->dataset_index = o.dsi; out->start_idx = o.start; out->episode = o.episode;
-  out->needs_reset = o.needs_reset; out->asset = o.asset; out->fiat = o.fiat;
-  out->interest_asset = o.ia; out->interest_fiat = o.ifi;
-  out->portfolio_valuation = o.pv; out->real_position = o.realpos;
-  return GTE_OK;
+  return state_view(E, E->p.final_rec, E->fsoa, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1653,11 +1686,11 @@ int gte_get_launch_info(gte_env* E, int32_t* envs_per_wave, int32_t* threads_per
                         int32_t* n_blocks, int32_t* vector_bytes) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   if (envs_per_wave) *envs_per_wave = E->p.epw;
-  if (threads_per_block) *threads_per_block = E->threads;
-  if (n_blocks) *n_blocks = E->blocks;
+  const LaunchPlan& L = E->plan;
+  if (threads_per_block) *threads_per_block = L.threads;
+  if (n_blocks) *n_blocks = L.blocks;
   if (vector_bytes)
-    *vector_bytes = E->vec * 4 + 1000 * ((E->coop ? 1 : 0) + 2 * E->stage +
-                                         16 * E->cfg.nontemporal_obs + 64 * (E->hot_per_cu & 15));
+    *vector_bytes = L.vec * 4 + 1000 * ((L.coop ? 1 : 0) + 2 * L.stage + 16 * L.store + 64 * (L.hot_per_cu & 15));
   return GTE_OK;
 }
 
