@@ -855,7 +855,10 @@ class BatchedTradingEnv(_VectorEnvBase):
         reference's columns (environments.py:186-197, 253-264: idx, step, date, position_index,
         position, real_position, data_*, portfolio_valuation, portfolio_distribution_*, reward),
         rebuilt from the device trajectory log.  Episodes longer than ``log_steps`` are
-        truncated at the front.
+        truncated at the front.  With auto-reset disabled, a frozen env (ended on its dataset's
+        last row) logs a copy of its last row every step until it is reset: the History leaves
+        the copies out, but they take log rows too, so the frozen time counts towards the
+        ``log_steps`` rows kept (once only copies are left, one row with reward 0 remains).
 
         finished=True (same-step auto-reset with ``final_obs``, right after the step in which the
         env ended): the episode that just FINISHED — its rows from the log plus the terminal row

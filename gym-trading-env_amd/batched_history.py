@@ -68,6 +68,9 @@ class BatchedHistory:
         view = env._log_view()
         self._rows, self._L = int(view.rows), int(view.L)
         self._have = min(self._rows, self._L)
+        # auto-reset disabled: a frozen env (ended on its dataset's last row) logs a copy of its last
+        # row every step until it is reset; those copies are no rows of its episode
+        self._frozen_runs = env.cfg.autoreset == _abi.AUTORESET_DISABLED
         # in a capture: the physical rows of the window, oldest first, as a device tensor [L]
         self._dev = None
         if env._capturing():
@@ -98,6 +101,8 @@ class BatchedHistory:
         if self._terminal:
             step = self._env._overlay(step, "step")
         back = step - t  # rows between the wanted row and the newest one
+        if self._frozen_runs:
+            back = back + self._frozen_copies(self._env._log_rows("step", None, self._order()))
         if bool((back < 0).any()) or bool((back >= self._have).any()):
             raise IndexError(f"index {t} is outside the current episode / the {self._L} logged rows "
                              "of some env")
@@ -177,15 +182,28 @@ class BatchedHistory:
             raise ValueError("only h['reward', -1] can be assigned (environments.py:267)")
         self._env._set_log_reward(value)
 
+    def _frozen_copies(self, steps):
+        """[N]: rows after the first of the run of equal `step` > 0 that ends each env's column of
+        `steps` [R, N] (oldest first) — the copies a frozen env logged, 0 for every other env."""
+        same = (steps == steps[-1:]) & (steps[-1:] > 0)
+        if self._env._torch is not None:
+            return (same.flip(0).to(self._env._torch.int32).cumprod(0).sum(0) - 1).clamp_min(0)
+        return np.maximum(np.cumprod(same[::-1], axis=0).sum(0) - 1, 0)
+
     def episode_mask(self):
-        """bool [R, N]: True where the logged row belongs to the env's CURRENT episode."""
+        """bool [R, N]: True where the logged row belongs to the env's CURRENT episode: its newest
+        `step + 1` rows (with auto-reset disabled, a frozen env's copies at the end count as one)."""
         e = self._env
         if self._dev is not None:
-            step_now = e._log_rows("step", None, self._dev[-1:])[0]
+            order = self._dev if self._frozen_runs else self._dev[-1:]
         else:
-            step_now = e._log_rows("step", (self._rows - 1) % self._L, self._order())
-        age = e._arange_rows(self._have)  # 0 = oldest logged row
-        return e._wrap((self._have - 1 - age)[:, None] <= step_now[None, :])
+            order = self._order() if self._frozen_runs else self._order()[-1:]
+        steps = e._log_rows("step", None, order)
+        step_now = steps[-1]
+        back = (self._have - 1 - e._arange_rows(self._have))[:, None]  # rows behind the newest one
+        if self._frozen_runs:
+            back = back - self._frozen_copies(steps)[None, :]
+        return e._wrap((back >= 0) & (back <= step_now[None, :]))
 
 
 class _CapturedRow(Mapping):

@@ -58,7 +58,7 @@ hipError_t launch_extract_state(const EnvRec* rec, int n, const StateSoA& o, hip
 hipError_t launch_rewind_queue(EnvRec* rec, int n, hipStream_t stream);
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term,
                       const uint8_t* trunc, int n, const int64_t* cursor, int L, const LogArrays& o,
-                      hipStream_t stream);
+                      const uint8_t* mask, hipStream_t stream);
 hipError_t launch_snapshot(const EnvRec* rec, const double* reward64, const uint8_t* term,
                            const uint8_t* trunc, const float* obs, int64_t obs_elems, int first,
                            int count, void* dst, float* dst_obs, hipStream_t stream);
@@ -69,7 +69,7 @@ struct LogPack {
   uint8_t* flags;
 };
 hipError_t launch_pack_log(const LogArrays& log, int N, int L, long long rows_written, const int32_t* ids,
-                           int n_ids, int max_rows, int finished, const EnvRec* final_rec,
+                           int n_ids, int max_rows, int finished, int frozen_runs, const EnvRec* final_rec,
                            const double* reward64, const LogPack& o, hipStream_t stream);
 const char* rccl_load();
 const char* rccl_error(int code);
@@ -768,12 +768,14 @@ static int check_injection(const gte_env* E, size_t count, const int32_t* idx, c
 }
 
 // append one trajectory row per env (after a reset or a step, whose Params p were; term_slot is
-// the launch's slot)
-static int append_log(gte_env* E, const Params& p) {
+// the launch's slot).  mask (a masked reset once the log has a row): no row is appended, the masked
+// envs' slot of the newest row is rewritten with their reset row, and the count stays.
+static int append_log(gte_env* E, const Params& p, const uint8_t* mask = nullptr) {
   if (E->cfg.log_steps <= 0) return GTE_OK;
+  if (E->log_rows == 0) mask = nullptr;
   HIPCHK(gte::launch_log(p.rec, p.reward64, p.terminated, p.truncated, p.N, E->log_cursor + (E->term_slot ^ 1),
-                         E->cfg.log_steps, E->log, E->stream));
-  E->log_rows += 1;
+                         E->cfg.log_steps, E->log, mask, E->stream));
+  if (!mask) E->log_rows += 1;
   return GTE_OK;
 }
 
@@ -849,7 +851,7 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   flags_unsure(E, {{p.terminated, N}, {p.truncated, N}});  // (masked envs get zero flags, flags_out untouched)
   const LaunchPlan& L = E->plan;
   HIPCHK(gte::launch_reset(p, L.vec, L.store, L.coop, L.stage, L.blocks, L.threads, E->stream));
-  TRY(append_log(E, p));
+  TRY(append_log(E, p, p.mask));
   if (L.affinity_period > 0) TRY(resort(E));  // new start rows: re-sort the processing order
   // host staging buffers may be reused by the caller right away: pageable copies above
   // are complete on return, but keep the contract simple and explicit
@@ -1331,6 +1333,7 @@ int gte_read_log_envs(gte_env* E, const int32_t* env_ids, int32_t n_ids, int32_t
   o.idx = w; o.step = w + cells; o.pos = w + 2 * cells; o.dsi = w + 3 * cells;
   o.flags = (uint8_t*)(w + 4 * cells);
   HIPCHK(gte::launch_pack_log(E->log, N, L, (long long)E->log_rows, ids, n_ids, max_rows, finished ? 1 : 0,
+                              E->cfg.autoreset == GTE_AUTORESET_DISABLED ? 1 : 0,
                               E->p.final_rec, E->p.reward64, o, E->stream));
   HIPCHK(hipStreamSynchronize(E->stream));
   out->n_rows = o.n_rows;

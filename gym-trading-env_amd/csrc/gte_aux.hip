@@ -8,12 +8,17 @@ namespace gte {
 // ---------------------------------------------------------------------------
 // Trajectory log (LogArrays, gte_device.h): the row of a reset, of a step of the kernels that do
 // not write it themselves (the isolated hot instantiations, the unfused rollout loop).
+// mask (a masked reset once the log has rows): the masked envs' slot of the NEWEST row is rewritten
+// in place and the row count stays — resetting some envs must not add a row to the episodes of
+// the others (the reference replaces one env's History, never another's).
 __global__ void gte_log_kernel(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                               const uint8_t* trunc, int n, const int64_t* cursor, int L, LogArrays o) {
+                               const uint8_t* trunc, int n, const int64_t* cursor, int L, LogArrays o,
+                               const uint8_t* mask) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t count = *cursor;  // rows written before this one (log_cursor_other, gte_device.h)
-  if (blockIdx.x == 0 && threadIdx.x == 0) *log_cursor_other(cursor) = count + 1;
-  if (e >= n) return;
+  const int64_t row = mask ? count - 1 : count;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *log_cursor_other(cursor) = row + 1;
+  if (e >= n || (mask && !mask[e])) return;
   const EnvRec r = rec[e];
   LogRow w;
   w.idx = r.idx; w.step = r.step; w.pos = r.pos; w.dsi = r.dsi;
@@ -25,14 +30,14 @@ __global__ void gte_log_kernel(const EnvRec* rec, const double* reward64, const 
   w.flags = (uint8_t)((term[e] ? 1 : 0) | (trunc[e] ? 2 : 0));
 #pragma unroll
   for (int i = 0; i < 7; ++i) w.pad[i] = 0;
-  o.rows[log_row(count, L) * (int64_t)n + e] = w;
+  o.rows[log_row(row, L) * (int64_t)n + e] = w;
 }
 
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term,
                       const uint8_t* trunc, int n, const int64_t* cursor, int L, const LogArrays& o,
-                      hipStream_t stream) {
+                      const uint8_t* mask, hipStream_t stream) {
   hipLaunchKernelGGL(gte_log_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rec, reward64, term,
-                     trunc, n, cursor, L, o);
+                     trunc, n, cursor, L, o, mask);
   return hipGetLastError();
 }
 
@@ -148,11 +153,14 @@ hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* ro
 // by one launch: what History holds for them (environments.py:253-264), without one strided copy
 // per column and env.  One workgroup per listed env.  The episode = the last run of logged rows
 // whose `step` counts ..., s-2, s-1, s (the newest row's step s says how far back it can reach;
-// the run is cut where the count breaks, e.g. at the repeated rows of a frozen env, and at the
-// front when it is longer than the log or than max_rows).  finished (same-step auto-reset with
-// final_obs, right after the step in which the env ended): the newest log row already describes
-// the next episode's reset row; the episode that just FINISHED is the rows before it plus the
-// terminal row from the env's terminal record, with that step's reward.
+// the run is cut where the count breaks and at the front when it is longer than the log or than
+// max_rows).  frozen_runs (auto-reset disabled): a run of rows with the same step s > 0 at the end
+// counts as its first row — the copies a frozen env (ended on its dataset's last row) logs while
+// it waits for a reset; they still take ring slots, so the frozen time pushes the episode out of
+// the log from the front.  finished (same-step auto-reset with final_obs, right after the step in
+// which the env ended): the newest log row already describes the next episode's reset row; the
+// episode that just FINISHED is the rows before it plus the terminal row from the env's terminal
+// record, with that step's reward.
 struct LogPack {
   int32_t* n_rows;                 // [n_ids]
   int32_t *idx, *step, *pos, *dsi; // [n_ids, max_rows], rows 0 .. n_rows-1 valid, oldest first
@@ -162,10 +170,10 @@ struct LogPack {
 
 __global__ __launch_bounds__(256) void gte_pack_log_kernel(const LogArrays log, int N, int L,
                                                            long long rows_written, const int32_t* ids,
-                                                           int max_rows, int finished,
+                                                           int max_rows, int finished, int frozen_runs,
                                                            const EnvRec* final_rec, const double* reward64,
                                                            LogPack o) {
-  __shared__ int s_start;
+  __shared__ int s_start, s_end;
   const int j = blockIdx.x, tid = threadIdx.x;
   const int e = ids[j];
   const int have = (int)(rows_written < (long long)L ? rows_written : (long long)L);
@@ -176,16 +184,25 @@ __global__ __launch_bounds__(256) void gte_pack_log_kernel(const LogArrays log, 
   const bool fin = finished != 0;
   auto step_at = [&](int r) -> int32_t { return (fin && r == have - 1) ? final_rec[e].step : log.rows[at(r)].step; };
   const int32_t s_new = step_at(have - 1);
-  int r0 = have - 1 - s_new;
+  if (tid == 0) s_end = 0;
+  __syncthreads();
+  int end = have - 1;  // the episode's newest row
+  if (frozen_runs && s_new > 0) {
+    for (int r = tid; r < have - 1; r += blockDim.x)
+      if (step_at(r) != s_new) atomicMax(&s_end, r + 1);
+    __syncthreads();
+    end = s_end;
+  }
+  int r0 = end - s_new;
   if (r0 < 0) r0 = 0;
   if (tid == 0) s_start = r0;
   __syncthreads();
-  for (int r = r0 + 1 + tid; r < have; r += blockDim.x)
+  for (int r = r0 + 1 + tid; r <= end; r += blockDim.x)
     if (step_at(r - 1) != step_at(r) - 1) atomicMax(&s_start, r);
   __syncthreads();
   int start = s_start;
-  int n = have - start;
-  if (n > max_rows) { start = have - max_rows; n = max_rows; }
+  int n = end + 1 - start;
+  if (n > max_rows) { start = end + 1 - max_rows; n = max_rows; }
   if (tid == 0) o.n_rows[j] = n;
   for (int r = tid; r < n; r += blockDim.x) {
     const int rr = start + r;
@@ -206,10 +223,10 @@ __global__ __launch_bounds__(256) void gte_pack_log_kernel(const LogArrays log, 
 }
 
 hipError_t launch_pack_log(const LogArrays& log, int N, int L, long long rows_written, const int32_t* ids,
-                           int n_ids, int max_rows, int finished, const EnvRec* final_rec,
+                           int n_ids, int max_rows, int finished, int frozen_runs, const EnvRec* final_rec,
                            const double* reward64, const LogPack& o, hipStream_t stream) {
   hipLaunchKernelGGL(gte_pack_log_kernel, dim3(n_ids), dim3(256), 0, stream, log, N, L, rows_written, ids,
-                     max_rows, finished, final_rec, reward64, o);
+                     max_rows, finished, frozen_runs, final_rec, reward64, o);
   return hipGetLastError();
 }
 

@@ -279,7 +279,8 @@ int gte_set_dynamic_features(gte_env* env, const float* values_device, uint32_t 
 int gte_set_dynamic_columns(gte_env* env, const void* const* columns_device, const int32_t* is_f64);
 
 /* Device trajectory log (gte_config.log_steps = L): after every gte_reset / gte_step one row per
- * env is appended (by the step kernel itself, or by a small launch).  The log is ONE array of
+ * env is appended (by the step kernel itself, or by a small launch) — except by a masked gte_reset
+ * once the log has a row, which rewrites the masked envs' slot of the newest row in place.  The log is ONE array of
  * 80-byte records [L, N] (the step kernel writes a row as two requests per env); the pointers
  * below address column c of row 0, env 0, and element (r, e) of a column lives `row_stride`
  * bytes per row and `env_stride` bytes per env further: p + (r % L) * row_stride + e *
@@ -324,7 +325,8 @@ int gte_read_log_portfolio(gte_env* env, int32_t env_id, int32_t n, double* asse
  * (environments.py:253-264; the reference's add_metric / get_metrics functions and save_for_render
  * read it, :274-307).  Episode of an env = the last run of its logged rows whose `step` counts up
  * by one to the newest row (cut at the front when longer than the log or than max_rows; max_rows
- * <= 0 means L).  finished != 0 (same-step auto-reset with final_obs, right after the step in
+ * <= 0 means L).  With auto-reset disabled, a run of equal `step` > 0 rows at the end (the copies
+ * a frozen env logs until it is reset) counts as its first row.  finished != 0 (same-step auto-reset with final_obs, right after the step in
  * which the envs ended): the episode that just FINISHED — the rows before the newest one (which
  * already is the next episode's reset row) plus the terminal row from the env's terminal record
  * with that step's reward.  The arrays are [n_ids, max_rows] row-major, rows 0 .. n_rows[j]-1 of

@@ -41,6 +41,10 @@ typedef struct gto_env {
   float* ring; /* [N, depth, nd] */
   /* outputs */
   float* final_obs; /* [N, W, Fobs] terminal observations (same-step mode, cfg.final_obs) */
+  /* the state of the terminal row of the env's last ended episode (same-step mode): what
+   * History logged at :253-264 before the wrapper's reset */
+  int32_t *f_idx, *f_step, *f_pos, *f_ds;
+  double *f_asset, *f_fiat, *f_ia, *f_ifi, *f_pv, *f_realpos;
   float* obs;
   float* reward;
   double* reward64;
@@ -380,6 +384,10 @@ static int step_one(gto_env* E, int32_t e, int32_t action) {
      * terminal row's dynamic features are written (matters for dyn_persist), and that
      * observation is what Gymnasium / SB3 report as the final one */
     get_obs(E, e);
+    E->f_idx[e] = E->idx[e]; E->f_step[e] = E->step[e]; E->f_pos[e] = E->pos[e];
+    E->f_ds[e] = E->ds[e]; E->f_asset[e] = E->asset[e]; E->f_fiat[e] = E->fiat[e];
+    E->f_ia[e] = E->ia[e]; E->f_ifi[e] = E->ifi[e]; E->f_pv[e] = E->pv[e];
+    E->f_realpos[e] = E->realpos[e];
     if (c->final_obs) {
       memcpy(E->final_obs + (int64_t)e * E->W * E->Fobs, E->obs + (int64_t)e * E->W * E->Fobs,
              sizeof(float) * E->W * E->Fobs);
@@ -425,6 +433,8 @@ gto_env* gto_create(const gte_config* cfg) {
   E->lo_limit = (double*)zalloc(sizeof(double) * N * cfg->n_positions);
   E->lo_persist = (uint8_t*)zalloc(N * cfg->n_positions);
   F64(asset); F64(fiat); F64(ia); F64(ifi); F64(pv); F64(realpos); F64(reward64);
+  I32(f_idx); I32(f_step); I32(f_pos); I32(f_ds);
+  F64(f_asset); F64(f_fiat); F64(f_ia); F64(f_ifi); F64(f_pv); F64(f_realpos);
 #undef I32
 #undef F64
   E->reward = (float*)zalloc(sizeof(float) * N);
@@ -563,6 +573,16 @@ GETTER(double, interest_asset, ia)
 GETTER(double, interest_fiat, ifi)
 GETTER(double, portfolio_valuation, pv)
 GETTER(double, real_position, realpos)
+GETTER(int32_t, final_idx, f_idx)
+GETTER(int32_t, final_step, f_step)
+GETTER(int32_t, final_position_index, f_pos)
+GETTER(int32_t, final_dataset_index, f_ds)
+GETTER(double, final_asset, f_asset)
+GETTER(double, final_fiat, f_fiat)
+GETTER(double, final_interest_asset, f_ia)
+GETTER(double, final_interest_fiat, f_ifi)
+GETTER(double, final_portfolio_valuation, f_pv)
+GETTER(double, final_real_position, f_realpos)
 int32_t gto_term_count(gto_env* E) { return E->term_count; }
 
 /* known-answer hook for the Portfolio arithmetic alone */
@@ -588,5 +608,7 @@ void gto_destroy(gto_env* E) {
   free(E->realpos); free(E->ring); free(E->obs); free(E->final_obs); free(E->reward);
   free(E->reward64); free(E->terminated); free(E->truncated); free(E->term_ids);
   free(E->q_idx); free(E->q_pos); free(E->q_ds); free(E->q_head);
+  free(E->f_idx); free(E->f_step); free(E->f_pos); free(E->f_ds); free(E->f_asset);
+  free(E->f_fiat); free(E->f_ia); free(E->f_ifi); free(E->f_pv); free(E->f_realpos);
   free(E);
 }

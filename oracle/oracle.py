@@ -22,6 +22,7 @@ _I32 = ("idx", "step", "position_index", "dataset_index", "start_idx", "episode"
         "needs_reset")
 _F64 = ("asset", "fiat", "interest_asset", "interest_fiat", "portfolio_valuation",
         "real_position")
+_FINAL = ("idx", "step", "position_index", "dataset_index") + _F64
 
 
 def build(force: bool = False) -> str:
@@ -51,7 +52,7 @@ def lib() -> C.CDLL:
         l.gto_destroy.argtypes = [C.c_void_p]
         l.gto_term_count.argtypes = [C.c_void_p]
         l.gto_term_count.restype = C.c_int32
-        for n in _I32 + _F64 + ("final_obs", "obs", "reward", "reward64", "terminated", "truncated", "term_ids"):
+        for n in _I32 + _F64 + tuple("final_" + x for x in _FINAL) + ("final_obs", "obs", "reward", "reward64", "terminated", "truncated", "term_ids"):
             f = getattr(l, "gto_get_" + n)
             f.restype = C.c_void_p
             f.argtypes = [C.c_void_p]
@@ -156,6 +157,13 @@ class OracleEnv:
     def state(self):
         out = {n: self._view(n, np.int32, (self.N,)) for n in _I32}
         out.update({n: self._view(n, np.float64, (self.N,)) for n in _F64})
+        return out
+
+    def final_state(self):
+        """Same-step mode: the state of each env's terminal row, as its last ended episode
+        left it before the in-step reset (valid for the envs that have ended)."""
+        out = {n: self._view("final_" + n, np.int32, (self.N,)) for n in _FINAL[:4]}
+        out.update({n: self._view("final_" + n, np.float64, (self.N,)) for n in _FINAL[4:]})
         return out
 
     def close(self):
