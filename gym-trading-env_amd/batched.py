@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi, spaces, staging
+from .batched_history import history_column, history_columns
 from .config import make_config
 
 _NP = {"int32": np.int32, "float64": np.float64}
@@ -27,6 +28,25 @@ def _as_staged(ds, n_dyn, name="Stock"):
                                     high=ds[2] if len(ds) == 4 else None,
                                     low=ds[3] if len(ds) == 4 else None)
     return staging.stage_dataframe(ds, n_dyn=n_dyn, name=name)  # a pandas DataFrame
+
+
+def _device_view(ptr, shape, typestr, device, strides=None):
+    """torch view of device memory at `ptr` (no copy), through the CUDA array interface
+    torch.as_tensor understands (also on ROCm)."""
+    import torch
+
+    class _Raw:
+        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "version": 2,
+                                    "strides": strides, "data": (int(ptr), False)}
+    return torch.as_tensor(_Raw(), device=device)
+
+
+def info_column(env, key, final: bool = False) -> np.ndarray:
+    """`info[key]` for every env, on the host: History column `key` of the current state or
+    (final) of the terminal records, with the last step's f64 reward."""
+    state = env.final_state if final else env.state
+    return history_column(key, lambda f: env.read_output("reward64") if f == "reward" else state(f),
+                          np.asarray(env.positions, dtype=np.float64), env)
 
 
 class LazyInfo(dict):
@@ -74,7 +94,7 @@ class LazyInfo(dict):
             # marks the envs for which `key` is present — here always all of them
             v = np.ones(e.num_envs, dtype=bool)
         elif key in self._KEYS:
-            v = e._info_value(key, e.state, e.read_output("reward64") if key == "reward" else None)
+            v = info_column(e, key)
         else:
             raise KeyError(key)
         self[key] = v
@@ -208,7 +228,6 @@ class BatchedTradingEnv(_VectorEnvBase):
             kernel_variant=kernel_variant, debug_flags=debug_flags,
             affinity_period=affinity_period, final_obs=final_obs, log_steps=log_steps)
         self.log_metrics = []
-        from .batched_history import history_columns
         self.info_keys = history_columns(self) + ["dataset_index"]
         self._ds_offsets = np.concatenate([[0], np.cumsum([d.T for d in self.datasets])]).astype(np.int64)
         self._host_columns, self._dev_columns = {}, {}
@@ -225,18 +244,21 @@ class BatchedTradingEnv(_VectorEnvBase):
         for d, s in enumerate(self.datasets):
             self.upload_dataset(d, s)
 
-        self._final_view, self._final_epoch, self._final_tensors = _abi.GteStateView(), -1, {}
-        self._logv, self._log_tensors, self._pos_table = _abi.GteLogView(), {}, None
+        self._logv, self._log_tensors = _abi.GteLogView(), {}
         self._log_cursor = None  # torch view of gte_log_view.cursor (i64 [2]), made on first need
         self._log_back = None    # arange(-L, 0) on the device, made before a capture (StepGraph)
-        self._state = _abi.GteStateView()
-        self._epoch, self._state_epoch = 0, -1  # state snapshots are taken lazily
+        # state snapshots, taken lazily: [view, epoch] of the current state and of the terminal records
+        self._snapshots = {False: [_abi.GteStateView(), -1], True: [_abi.GteStateView(), -1]}
+        self._snapshot_tensors = {}  # torch views of the snapshots, by (final, name)
+        self._epoch = 0
         self._snap_epoch, self._snap, self._snap_obs = -1, None, None  # numpy mode, per step
-        self._state_tensors = {}  # torch views of the state snapshot (state_tensor)
         self._torch = None
         self._t = {}
         if output == "torch":
             self._bind_torch_outputs()
+        # the values `position` takes, on the device in torch mode
+        self._pos_table = np.asarray(self.positions, dtype=np.float64) if self._torch is None else \
+            self._torch.tensor(self.positions, dtype=self._torch.float64, device=self._t["obs"].device)
         self._out = _abi.GteOutputs()
         _abi.check(self._lib, self._lib.gte_get_outputs(self._h, C.byref(self._out)))
         self._was_reset = False
@@ -342,15 +364,30 @@ class BatchedTradingEnv(_VectorEnvBase):
                                                          out.ctypes.data, out.nbytes))
         return out
 
+    def _read_snapshot(self, name: str, final: bool = False, tensor: bool = False):
+        """One per-env array of the library's struct-of-arrays snapshot of the current state
+        (`gte_get_state`) or of the terminal records (`gte_get_final_state`), taken once per
+        step/reset on first use: a host copy, or (tensor) a torch view of it on the device."""
+        dt = _abi.STATE_DTYPES[name]
+        snap = self._snapshots[final]
+        if snap[1] != self._epoch:
+            get = self._lib.gte_get_final_state if final else self._lib.gte_get_state
+            _abi.check(self._lib, get(self._h, C.byref(snap[0])))
+            snap[1] = self._epoch
+        if not tensor:
+            return self._to_host(getattr(snap[0], name), _NP[dt], self.num_envs)
+        t = self._snapshot_tensors.get((final, name))
+        if t is None:
+            t = _device_view(getattr(snap[0], name), (self.num_envs,), np.dtype(dt).str,
+                             self._t["obs"].device)
+            self._snapshot_tensors[(final, name)] = t
+        return t
+
     def state(self, name: str) -> np.ndarray:
         """Host copy of one per-env state array (struct gte_state_view member)."""
-        dt = _NP[_abi.STATE_DTYPES[name]]
-        if self._snap_epoch == self._epoch:  # numpy mode: already fetched with the results
-            return np.ascontiguousarray(self._snap[name])
-        if self._state_epoch != self._epoch:  # snapshot once per step/reset, not per field
-            _abi.check(self._lib, self._lib.gte_get_state(self._h, C.byref(self._state)))
-            self._state_epoch = self._epoch
-        return self._to_host(getattr(self._state, name), dt, self.num_envs)
+        if self._snap_epoch == self._epoch and name in _abi.STATE_DTYPES:
+            return np.ascontiguousarray(self._snap[name])  # numpy mode: fetched with the results
+        return self._read_snapshot(name)
 
     def state_tensor(self, name: str):
         """One per-env state array as a torch tensor ON THE DEVICE, without a copy: a view of the
@@ -358,21 +395,9 @@ class BatchedTradingEnv(_VectorEnvBase):
         first use).  For device-side reward shaping / extra observation features:
         `envs.state_tensor("portfolio_valuation")`, `"real_position"`, `"idx"`, ...  The view is
         overwritten by the snapshot taken after a later step."""
-        torch = self._torch
-        if torch is None:
+        if self._torch is None:
             raise ValueError("state_tensor needs output='torch'")
-        if self._state_epoch != self._epoch:
-            _abi.check(self._lib, self._lib.gte_get_state(self._h, C.byref(self._state)))
-            self._state_epoch = self._epoch
-        if name not in self._state_tensors:
-            dt = _abi.STATE_DTYPES[name]
-
-            class _Raw:  # the CUDA array interface torch.as_tensor understands (also on ROCm)
-                __cuda_array_interface__ = {
-                    "shape": (self.num_envs,), "typestr": "<i4" if dt == "int32" else "<f8",
-                    "data": (int(getattr(self._state, name)), False), "version": 2, "strides": None}
-            self._state_tensors[name] = torch.as_tensor(_Raw(), device=self._t["obs"].device)
-        return self._state_tensors[name]
+        return self._read_snapshot(name, tensor=True)
 
     def read_output(self, name: str) -> np.ndarray:
         """Host copy of one output array of the last step/reset."""
@@ -460,54 +485,10 @@ class BatchedTradingEnv(_VectorEnvBase):
             ds, idx = ds.cpu().numpy(), idx.cpu().numpy()
         return col[self._ds_offsets[np.asarray(ds)] + np.asarray(idx)]
 
-    def _info_value(self, key, state, reward=None):
-        """One `info` / History column for every env from a struct-of-arrays state reader
-        (`state(name) -> host array`): the current state, or the terminal one."""
-        if key in ("idx", "step", "position_index", "real_position", "portfolio_valuation",
-                   "dataset_index"):
-            return state(key)
-        if key == "position":
-            return np.asarray(self.positions, dtype=np.float64)[state("position_index")]
-        if key == "reward":
-            return reward
-        if key == "date" or key.startswith("data_"):
-            return self._dataset_column(key, state("dataset_index"), state("idx"))
-        if key.startswith("portfolio_distribution_"):
-            # Portfolio.get_portfolio_distribution, portfolio.py:49-57
-            f = key[len("portfolio_distribution_"):]
-            if f in ("interest_asset", "interest_fiat"):
-                return state(f)
-            src = state("asset" if f.endswith("asset") else "fiat")
-            return np.maximum(0.0, -src if f.startswith("borrowed") else src)
-        raise KeyError(key)
-
     def final_state(self, name: str) -> np.ndarray:
         """Host copy of one per-env array of the TERMINAL states (`gte_get_final_state`): row e
         is env e as it was when its last episode ended (same-step mode with final_obs)."""
-        if self._final_epoch != self._epoch:
-            _abi.check(self._lib, self._lib.gte_get_final_state(self._h, C.byref(self._final_view)))
-            self._final_epoch = self._epoch
-        return self._to_host(getattr(self._final_view, name), _NP[_abi.STATE_DTYPES[name]],
-                             self.num_envs)
-
-    def _final_tensor(self, name):
-        """torch view [N] of one array of the terminal records (`gte_get_final_state`, refreshed
-        once per step)."""
-        torch = self._torch
-        if self._final_epoch != self._epoch:
-            _abi.check(self._lib, self._lib.gte_get_final_state(self._h, C.byref(self._final_view)))
-            self._final_epoch = self._epoch
-        t = self._final_tensors.get(name)
-        if t is None:
-            dt = _abi.STATE_DTYPES[name]
-
-            class _Raw:
-                __cuda_array_interface__ = {
-                    "shape": (self.num_envs,), "typestr": "<i4" if dt == "int32" else "<f8",
-                    "data": (int(getattr(self._final_view, name)), False), "version": 2, "strides": None}
-            t = torch.as_tensor(_Raw(), device=self._t["obs"].device)
-            self._final_tensors[name] = t
-        return t
+        return self._read_snapshot(name, final=True)
 
     def _overlay(self, v, name, only=None):
         """`v` (a History column at the newest row, [N]) with the entries of the envs that ended
@@ -517,30 +498,14 @@ class BatchedTradingEnv(_VectorEnvBase):
         ended = self._t["terminated"] | self._t["truncated"]
         if only is not None:
             ended = ended & only
-        f = self._final_tensor
-        if name in ("idx", "step", "position_index", "dataset_index", "portfolio_valuation",
-                    "real_position"):
-            t = f(name)
-        elif name == "position":
-            t = self._positions_table()[f("position_index").long()]
-        elif name == "reward":
-            t = self._t["reward64"]  # the terminal step's reward (the log row under it is a reset row: 0)
-        elif name == "date" or name.startswith("data_"):
-            t = self._dataset_column(name, f("dataset_index"), f("idx"))
-            if not isinstance(t, torch.Tensor):  # host column (dates, objects)
-                m = ended.cpu().numpy()
-                out = np.array(v, copy=True)
-                out[m] = np.asarray(t)[m]
-                return out
-        elif name.startswith("portfolio_distribution_"):
-            k = name[len("portfolio_distribution_"):]
-            if k in ("interest_asset", "interest_fiat"):
-                t = f(k)
-            else:
-                src = f("asset" if k.endswith("asset") else "fiat")
-                t = (-src if k.startswith("borrowed") else src).clamp_min(0.0)
-        else:
-            return v
+        # the terminal step's reward (the log row under it is a reset row: 0)
+        t = history_column(name, lambda f: self._t["reward64"] if f == "reward" else
+                           self._read_snapshot(f, final=True, tensor=True), self._pos_table, self)
+        if not isinstance(t, torch.Tensor):  # host column (dates, objects)
+            m = ended.cpu().numpy()
+            out = np.array(v, copy=True)
+            out[m] = np.asarray(t)[m]
+            return out
         return torch.where(ended, t.to(v.dtype), v)
 
     def _final_entries(self) -> dict:
@@ -554,9 +519,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         f_obs = np.full(N, None, dtype=object)
         f_info = np.full(N, None, dtype=object)
         if len(ids):
-            reward = self.read_output("reward64")  # the terminal step's reward (same-step mode)
-            cols = {k: np.asarray(self._info_value(k, self.final_state, reward))[ids]
-                    for k in self.info_keys}
+            cols = {k: np.asarray(info_column(self, k, final=True))[ids] for k in self.info_keys}
             for j, e in enumerate(ids):
                 f_obs[e] = last[j]
                 f_info[e] = {k: v[j] for k, v in cols.items()}
@@ -578,10 +541,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         own rows.  Needs a full log."""
         torch = self._torch
         if self._log_cursor is None:
-            class _Raw:
-                __cuda_array_interface__ = {"shape": (2,), "typestr": "<i8", "version": 2,
-                                            "strides": None, "data": (int(view.cursor), False)}
-            self._log_cursor = torch.as_tensor(_Raw(), device=self._t["obs"].device)
+            self._log_cursor = _device_view(view.cursor, (2,), "<i8", self._t["obs"].device)
         slot, L = int(view.cursor_slot), int(view.L)
         count = self._log_cursor[slot:slot + 1]
         back = self._log_back if self._log_back is not None else torch.arange(-L, 0, device=count.device)
@@ -602,15 +562,10 @@ class BatchedTradingEnv(_VectorEnvBase):
         """torch view [L, N] of one log array (no copy)."""
         t = self._log_tensors.get(name)
         if t is None:
-            v, dt = self._log_view(), np.dtype(_abi.LOG_DTYPES[name])
-
+            v = self._log_view()
             # the log is one array of records [L, N]: a column is a strided view of it
-            class _Raw:
-                __cuda_array_interface__ = {
-                    "shape": (int(v.L), int(v.N)), "typestr": dt.str, "version": 2,
-                    "strides": (int(v.row_stride), int(v.env_stride)),
-                    "data": (int(getattr(v, name)), False)}
-            t = self._torch.as_tensor(_Raw(), device=self._t["obs"].device)
+            t = _device_view(getattr(v, name), (int(v.L), int(v.N)), np.dtype(_abi.LOG_DTYPES[name]).str,
+                             self._t["obs"].device, (int(v.row_stride), int(v.env_stride)))
             self._log_tensors[name] = t
         return t
 
@@ -637,29 +592,12 @@ class BatchedTradingEnv(_VectorEnvBase):
         whole = rows_to_host(0, int(v.L))
         return whole[order] if phys is None else whole[np.asarray(phys), np.arange(N)]
 
-    def _log_row(self, name, phys, raw=False):
-        return self._log_rows(name, phys, None)
-
     def _wrap(self, x):
         """What user callables receive: DeviceArray around device tensors, host arrays as is."""
         if self._torch is not None and isinstance(x, self._torch.Tensor):
             from .device_array import DeviceArray
             return DeviceArray(x)
         return x
-
-    def _positions_table(self):
-        if self._torch is None:
-            return np.asarray(self.positions, dtype=np.float64)
-        if self._pos_table is None:
-            self._pos_table = self._torch.tensor(self.positions, dtype=self._torch.float64,
-                                                 device=self._t["obs"].device)
-        return self._pos_table
-
-    def _take(self, table, index):
-        return table[index.long()] if self._torch is not None else table[index]
-
-    def _relu(self, x):
-        return x.clamp_min(0.0) if self._torch is not None else np.maximum(0.0, x)
 
     def _stack(self, cols):
         return self._torch.stack(cols, dim=-1) if self._torch is not None else np.stack(cols, axis=-1)
@@ -807,42 +745,15 @@ class BatchedTradingEnv(_VectorEnvBase):
                 raise ValueError(f"env {int(ids[bad[0]])} did not end in the last step")
         R = b["idx"].shape[1]
         valid = np.arange(R)[None, :] < n[:, None]
-        raw = {}
-
-        def flat(name):  # the valid rows of every env, env after env (copied out of the staging buffer)
-            v = raw.get(name)
-            if v is None:
-                v = raw[name] = b[name][valid]
-            return v
-        for name in ("dataset_index", "idx"):  # the lookups below outlive the staging buffer
-            flat(name)
+        # the valid rows of every env, env after env, copied out of the staging buffer now (the next
+        # read rewrites it): one boolean-mask copy per raw column, 12 small arrays
+        flat = {name: b[name][valid] for name in _abi.LOG_DTYPES}
         pos_table = np.empty(len(self.positions), dtype=object)
         pos_table[:] = self.positions
-        dist = lambda src, sign: (lambda: np.maximum(0, sign * flat(src)))
         # Every column is built on first use, over all the episodes at once, and cut per env: a
         # metric that reads `h["position"]` never pays for dates or portfolio distributions.
-        builders = {"idx": lambda: flat("idx"), "step": lambda: flat("step"),
-                    "date": lambda: self._dataset_column("date", flat("dataset_index"), flat("idx")),
-                    "position_index": lambda: flat("position_index"),
-                    "position": lambda: pos_table[flat("position_index")],
-                    "real_position": lambda: flat("real_position")}
-        for c in self.datasets[0].info_columns or ["close"]:
-            builders[f"data_{c}"] = (lambda c=c: self._dataset_column(
-                f"data_{c}", flat("dataset_index"), flat("idx")))
-        builders["portfolio_valuation"] = lambda: flat("portfolio_valuation")
-        # Portfolio.get_portfolio_distribution, portfolio.py:49-57
-        builders["portfolio_distribution_asset"] = dist("asset", 1.0)
-        builders["portfolio_distribution_fiat"] = dist("fiat", 1.0)
-        builders["portfolio_distribution_borrowed_asset"] = dist("asset", -1.0)
-        builders["portfolio_distribution_borrowed_fiat"] = dist("fiat", -1.0)
-        builders["portfolio_distribution_interest_asset"] = lambda: flat("interest_asset")
-        builders["portfolio_distribution_interest_fiat"] = lambda: flat("interest_fiat")
-        builders["reward"] = lambda: flat("reward")
-        # the staging buffer is rewritten by the next read: take the raw columns out of it now (one
-        # boolean-mask copy each, 12 small arrays), the derived columns stay lazy
-        for name in _abi.LOG_DTYPES:
-            flat(name)
-        block = ColumnBlock(builders)
+        block = ColumnBlock({c: (lambda c=c: history_column(c, flat.__getitem__, pos_table, self))
+                             for c in history_columns(self)})
         ends = np.cumsum(n).tolist()
         out, lo = [], 0
         for hi in ends:

@@ -40,9 +40,8 @@ import numpy as np
 from . import _abi
 
 _DIST = ("asset", "fiat", "borrowed_asset", "borrowed_fiat", "interest_asset", "interest_fiat")
-_LOG_COLUMNS = {"idx": "idx", "step": "step", "position_index": "position_index",
-                "dataset_index": "dataset_index", "portfolio_valuation": "portfolio_valuation",
-                "real_position": "real_position", "reward": "reward"}
+# History columns that are raw per-env fields as they are
+_RAW = ("idx", "step", "position_index", "dataset_index", "real_position", "portfolio_valuation", "reward")
 
 
 def history_columns(env) -> list:
@@ -52,6 +51,35 @@ def history_columns(env) -> list:
     return (["idx", "step", "date", "position_index", "position", "real_position"]
             + [f"data_{c}" for c in info] + ["portfolio_valuation"]
             + [f"portfolio_distribution_{k}" for k in _DIST] + ["reward"])
+
+
+def history_column(name, raw, positions, env, captured=False):
+    """History column `name` (or dataset_index) derived from the raw per-env fields by the
+    reference's rules (environments.py:186-197, 253-264; portfolio.py:49-57), whatever they come
+    from: a state snapshot, the terminal records, the device log or a `read_log_envs` batch.
+
+    raw(field) -> that field (idx, step, position_index, dataset_index, real_position,
+    portfolio_valuation, asset, fiat, interest_asset, interest_fiat, reward); `positions`: the
+    table `position` indexes.  Torch tensors are computed on the device, ndarrays on the host.
+    captured: inside a graph capture, where `date` / `data_*` must already be on the device."""
+    if name in _RAW:
+        return raw(name)
+    if name == "position":
+        i = raw("position_index")
+        return positions[i] if isinstance(i, np.ndarray) else positions[i.long()]
+    if name.startswith("portfolio_distribution_"):
+        k = name[len("portfolio_distribution_"):]
+        if k in ("interest_asset", "interest_fiat"):
+            return raw(k)
+        if k in _DIST:  # Portfolio.get_portfolio_distribution, portfolio.py:49-57
+            src = raw("asset" if k.endswith("asset") else "fiat")
+            src = -src if k.startswith("borrowed") else src
+            return np.maximum(0.0, src) if isinstance(src, np.ndarray) else src.clamp_min(0.0)
+    if name == "date" or name.startswith("data_"):
+        if captured:
+            env._require_device_column(name)
+        return env._dataset_column(name, raw("dataset_index"), raw("idx"))
+    raise ValueError(f"Feature {name} does not exist ... Check the available features : {env.info_keys}")
 
 
 class BatchedHistory:
@@ -97,7 +125,7 @@ class BatchedHistory:
         if self._dev is not None:
             raise ValueError(f"h[column, {t}] cannot be captured into a graph: its bounds check reads "
                              "the device (use negative indices, or h[column] with episode_mask())")
-        step = self._env._log_row("step", (self._rows - 1) % self._L, raw=True)
+        step = self._env._log_rows("step", (self._rows - 1) % self._L, None)
         if self._terminal:
             step = self._env._overlay(step, "step")
         back = step - t  # rows between the wanted row and the newest one
@@ -133,23 +161,8 @@ class BatchedHistory:
 
     def _log_column_rows(self, name, phys, order):
         e = self._env
-        if name in _LOG_COLUMNS:
-            return e._log_rows(name, phys, order)
-        if name == "position":
-            return e._take(e._positions_table(), e._log_rows("position_index", phys, order))
-        if name.startswith("portfolio_distribution_"):
-            k = name[len("portfolio_distribution_"):]
-            if k in ("interest_asset", "interest_fiat"):
-                return e._log_rows(k, phys, order)
-            if k in _DIST:  # Portfolio.get_portfolio_distribution, portfolio.py:49-57
-                src = e._log_rows("asset" if k.endswith("asset") else "fiat", phys, order)
-                return e._relu(-src if k.startswith("borrowed") else src)
-        if name == "date" or name.startswith("data_"):
-            if self._dev is not None:
-                e._require_device_column(name)
-            return e._dataset_column(name, e._log_rows("dataset_index", phys, order),
-                                     e._log_rows("idx", phys, order))
-        raise ValueError(f"Feature {name} does not exist ... Check the available features : {self.columns}")
+        return history_column(name, lambda f: e._log_rows(f, phys, order), e._pos_table, e,
+                              captured=self._dev is not None)
 
     def _order(self):
         """Physical rows of the logged window, oldest first."""

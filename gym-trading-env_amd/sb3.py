@@ -16,7 +16,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import spaces
-from .batched import BatchedTradingEnv
+from .batched import BatchedTradingEnv, info_column
 
 try:  # pragma: no cover - exercised only where SB3 is installed
     from stable_baselines3.common.vec_env import VecEnv as _Base
@@ -144,8 +144,7 @@ class SB3TradingVecEnv(_Base):
             # (environments.py:272), with terminal_observation added; the shared columns already
             # describe the episode the in-launch reset started, so the terminal values (from the
             # terminal records, gte_get_final_state) are stored in the dict, shadowing the columns
-            r64 = env.read_output("reward64") if "reward" in self.info_keys else None
-            final = {k: np.asarray(env._info_value(k, env.final_state, r64))[ids] for k in self.info_keys}
+            final = {k: np.asarray(info_column(env, k, final=True))[ids] for k in self.info_keys}
             ids, last = ids.tolist(), self._host(last)
             for j, (e, o) in enumerate(zip(ids, last)):
                 d = infos[e]

@@ -51,10 +51,8 @@ class StepGraph:
                              f"eager steps (reset included) first, {int(env._logv.rows)} rows are logged")
         self.env, self.n_steps = env, int(n_steps)
         dev = env._t["obs"].device
-        if L:  # made on first use, outside the capture (a host->device copy cannot be captured)
-            env._positions_table()
-            if env._log_back is None:
-                env._log_back = torch.arange(-L, 0, device=dev)
+        if L and env._log_back is None:  # made outside the capture
+            env._log_back = torch.arange(-L, 0, device=dev)
         saved = self._schedule()
         self._slot = int(saved.term_slot)
         home = torch.cuda.current_stream(dev)

@@ -896,3 +896,79 @@ def test_batched_history_reward_assignment_writes_the_newest_log_row():
     for c, v in before.items():
         np.testing.assert_array_equal(np.asarray(h2[c, -1]), v, err_msg=c)
     env.close()
+
+
+def test_every_history_column_agrees_across_info_batched_history_and_histories():
+    """The four places the History columns are served from agree on EVERY column of
+    `history_columns()` (+ dataset_index where a path has it), in value, dtype and object-ness:
+    `info` / `final_info` (state snapshots), `batched_history()` and its same-step terminal view
+    (the device log, the terminal records), and `histories()` (one `gte_read_log_envs` transfer).
+    Short and leveraged positions make asset and fiat negative (non-zero `borrowed_*` columns); a
+    string column keeps an object-valued `data_*` on the host next to `date`."""
+    import torch
+    import gym_trading_env_amd as gte
+    from gym_trading_env_amd.batched_history import history_columns
+    from gym_trading_env_amd.device_array import DeviceArray
+    dfs = []
+    for seed, T in ((61, 240), (62, 300)):
+        df = make_df(*_walk(seed, T, 4, sigma=3e-2), seed=seed)
+        df["tag"] = np.where(np.arange(T) % 3 == 0, "a", "b").astype(object)
+        dfs.append(df)
+    N, L = 64, 16
+    env = gte.BatchedTradingEnv(dfs, N, positions=[-1, 0, 1, 2], windows=4, trading_fees=1e-3,
+                                borrow_interest_rate=1e-3, max_episode_duration=7, seed=4,
+                                autoreset="same_step", final_obs=True, log_steps=L, output="torch",
+                                verbose=0)
+    cols = history_columns(env)
+    assert "data_tag" in cols and "data_close" in cols
+    ints = ("idx", "step", "position_index", "dataset_index")
+    host = {"date": np.dtype("datetime64[ns]"), "data_tag": np.dtype(object)}
+
+    def info_dtype(c):
+        return np.dtype(np.int32) if c in ints else host.get(c, np.dtype(np.float64))
+
+    def history_type(c):  # a History holds Python scalars; `position` keeps the given Python ints
+        if c in host:
+            return np.datetime64 if c == "date" else str
+        return int if c in ints or c == "position" else float
+
+    def batched(x, c):  # BatchedHistory: device values, except the host-valued columns
+        if c in host:
+            assert isinstance(x, np.ndarray) and x.dtype == host[c], c
+            return x
+        assert isinstance(x, DeviceArray) and x.dtype == info_dtype(c), c
+        return x.numpy()
+
+    env.reset()
+    rng = np.random.default_rng(3)
+    ended_total, borrowed = 0, set()
+    for k in range(20):
+        _, _, term, trunc, info = env.step(torch.from_numpy(rng.integers(-1, 4, N).astype(np.int32)).cuda())
+        ended = (term | trunc).cpu().numpy()
+        live, done = np.nonzero(~ended)[0], np.nonzero(ended)[0]
+        h, ht = env.batched_history(), env.batched_history(terminal=True)
+        hs = env.histories(live)
+        hf = env.histories(done, finished=True) if len(done) else []
+        for c in cols + ["dataset_index"]:
+            iv = info[c]
+            assert isinstance(iv, np.ndarray) and iv.dtype == info_dtype(c) and iv.shape == (N,), c
+            hv, tv = batched(h[c, -1], c), batched(ht[c, -1], c)
+            # envs that did not end: info == newest log row == newest History row (an ended env's
+            # info reward is the terminal step's, its newest log row the reset row)
+            np.testing.assert_array_equal(iv[live], hv[live], err_msg=c)
+            # ended envs: the terminal view == final_info == the finished History's last row
+            fi = np.array([info["final_info"][e][c] for e in done], dtype=iv.dtype)
+            np.testing.assert_array_equal(tv[done], fi, err_msg=c)
+            for j, e in enumerate(done):
+                assert type(info["final_info"][e][c]) is type(iv[e]), c
+            if c == "dataset_index":  # not a History column
+                continue
+            for hist, ids, want in ((hs, live, iv), (hf, done, tv)):
+                got = [hist[j][c, -1] for j in range(len(ids))]
+                assert all(type(g) is history_type(c) for g in got), c
+                np.testing.assert_array_equal(np.array(got, dtype=iv.dtype), want[ids], err_msg=c)
+            if c.startswith("portfolio_distribution_borrowed") and np.any(iv != 0):
+                borrowed.add(c)
+        ended_total += len(done)
+    assert ended_total >= N and len(borrowed) == 2
+    env.close()
