@@ -1078,6 +1078,11 @@ static void choose_rollout_epw(gte_env* E, const Params& p, int nt) {
   }
 }
 
+// GTE_DEBUG_GEOMETRY: name the path each gte_rollout call takes (the tests assert it)
+static void report_rollout_path(const char* path, int32_t n_steps) {
+  if (getenv("GTE_DEBUG_GEOMETRY")) fprintf(stderr, "[gte] rollout path: %s, %d steps\n", path, n_steps);
+}
+
 // gte_rollout's launches, after its checks
 static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_rollout_bufs* b) {
   const size_t N = (size_t)E->p.N;
@@ -1108,11 +1113,13 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
   };
   if (!L.fused_rollout) {
     // same results, one launch per step
+    report_rollout_path("per-step", n_steps);
     for (int32_t k = 0; k < n_steps; ++k) TRY(step_row(k));
   } else if (!b->obs) {
     // Backtest: no observation is kept but the last one.  n_steps - 1 steps of pure state machine
     // from registers (gte_rollout_state_kernel), then the last step as an ordinary launch, which
     // also produces the observation and the terminal list.
+    report_rollout_path(n_steps > 1 ? "state-only" : "per-step", n_steps);
     if (n_steps > 1) {
       TRY(age_order(E, n_steps - 1));
       gte::RolloutArgs r = {actions, n_steps - 1, nullptr, b->reward, b->reward64, b->terminated,
@@ -1135,6 +1142,7 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
     Params p = E->p;
     if (L.resident_epb[nt] == 0) choose_resident_epb(E, p, nt);
     advance_term_slot(E, p);
+    report_rollout_path(L.resident_epb[nt] > 0 ? "resident" : "gather", n_steps);
     if (L.resident_epb[nt] > 0) {
       // identity processing order: the L2-affinity order exists for the table reads of the
       // per-step gather; here one row per env and step is read, and consecutive envs make each

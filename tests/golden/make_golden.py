@@ -192,7 +192,8 @@ def run_trace(make_env, positions, n_envs, n_calls, action_rng, p_none=0.1,
     return rec
 
 
-def save(name, cfg, datasets, rec, note):
+def fixture_arrays(cfg, datasets, rec, note):
+    """The arrays of one fixture file (the trace format above)."""
     out = {"cfg_json": np.array(json.dumps(cfg)), "note": np.array(note)}
     for d, ds in enumerate(datasets):
         out[f"feat_{d}"] = np.asarray(ds[0], np.float32)
@@ -201,15 +202,23 @@ def save(name, cfg, datasets, rec, note):
             out[f"high_{d}"] = np.asarray(ds[2], np.float64)
             out[f"low_{d}"] = np.asarray(ds[3], np.float64)
     out.update(rec)
+    return out
+
+
+def save(name, cfg, datasets, rec, note):
+    write(name, fixture_arrays(cfg, datasets, rec, note))
+
+
+def write(name, out):
     path = os.path.join(HERE, name + ".npz")
     np.savez_compressed(path, **out)
-    if "op" not in rec:  # not a trace (e.g. the metrics fixture)
+    if "op" not in out:  # not a trace (e.g. the metrics fixture)
         print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB")
         return
-    ends = int((rec["done"] | rec["truncated"]).sum())
-    assert rec["op"].ndim == 2
-    print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB, calls={rec['op'].shape}, "
-          f"resets={int((rec['op'] == 0).sum())}, ends={ends}, done={int(rec['done'].sum())}")
+    ends = int((out["done"] | out["truncated"]).sum())
+    assert out["op"].ndim == 2
+    print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB, calls={out['op'].shape}, "
+          f"resets={int((out['op'] == 0).sum())}, ends={ends}, done={int(out['done'].sum())}")
 
 
 def ref_kwargs(cfg):
@@ -395,6 +404,227 @@ def main():
                  f"MultiDatasetTradingEnv, 5 datasets of different lengths, switch every "
                  f"{switch} episode(s); with switch > 1 a dataset's _obs_array "
                  f"lives across episodes, so that trace needs dyn_persist")
+
+
+
+# -- the sweep: one trace per row group of the strata table (tests/strata.py) ----------------
+SWEEP_SEED = 20261015
+SWEEP_KIB_PER_FIXTURE = 200
+SWEEP_KIB_TOTAL = 3 * 1024
+
+
+def reward_scaled(k):
+    def r(history):  # luckymodel/scripts/test_env.py:20-22, factor k
+        return k * np.log(history["portfolio_valuation", -1] / history["portfolio_valuation", -2])
+    return r
+
+
+def reward_clipped(k, lo, hi):
+    def r(history):  # luckymodel/envs/env.py:16-18, factor k
+        lr = np.log(history["portfolio_valuation", -1] / history["portfolio_valuation", -2])
+        return np.clip(k * lr, lo, hi)
+    return r
+
+
+def _ref_reward(rf):
+    from gym_trading_env.environments import basic_reward_function
+    if rf == "basic_reward_function":
+        return basic_reward_function
+    if rf[0] == "scaled_log_return":
+        return reward_scaled(rf[1])
+    return reward_clipped(*rf[1:])
+
+
+def _ref_dynamic(kinds):
+    from gym_trading_env.environments import (dynamic_feature_last_position_taken,
+                                              dynamic_feature_real_position)
+    table = {"last_position_taken": dynamic_feature_last_position_taken,
+             "real_position": dynamic_feature_real_position}
+    return [table[k] for k in kinds]
+
+
+# two orders of the nd = 3 list on 16-byte rows, so that swapping any two dynamic columns shows
+MIX3 = ["real_position", "real_position", "last_position_taken"]
+MIX3B = ["last_position_taken", "real_position", "real_position"]
+MIX4 = ["last_position_taken", "real_position", "real_position", "last_position_taken"]
+MIX4R = ["real_position", "real_position", "last_position_taken", "last_position_taken"]
+P3 = [-1, 0, 1]
+LEV = [-2, -1, 0, 1, 2.5]
+FRAC = [0, 0.25, 0.5, 0.75, 1]
+P20 = [-1.5 + 0.25 * i for i in range(20)]
+
+# (name, dataset, trace, config).  dataset: (T, F_s, sigma, drift) or a list of them (several
+# datasets, MultiDatasetTradingEnv); trace: E envs, K calls, and run_trace options.  DRAW: a
+# parameter the trace's strata do not fix, drawn from the trace's own seed (_draw).
+# The drawdown, limit-order and windowed multi-dataset traces keep 16-byte rows (F_obs % 4 == 0,
+# nd > 0, no dyn_persist), so that the fused rollout kernels replay them (strata.py,
+# resident_done etc.).
+DRAW = "draw"
+DRAWN = {"trading_fees": [0, 1e-4, 1e-3, 1e-2], "borrow_interest_rate": [0, 3e-6, 1e-4, 1e-3]}
+SWEEP = [
+    ("lean_nd1", (300, 7, 1e-2, 0), dict(E=4, K=150),
+     dict(positions=P3, windows=32, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=30, dynamic_feature_functions=["real_position"])),
+    ("lean_nd2_clipped", (260, 14, 1.5e-2, 0), dict(E=4, K=160),
+     dict(positions=LEV, windows=16, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          max_episode_duration=40, reward_function=["clipped_log_return", 2.0, -0.004, 0.006])),
+    ("lean_nd3", (300, 9, 1e-2, 0), dict(E=4, K=150),
+     dict(positions=FRAC, windows=32, trading_fees=1e-2, borrow_interest_rate=0,
+          max_episode_duration=25, dynamic_feature_functions=MIX3)),
+    ("lean_nd4_w64", (400, 16, 1e-2, 0), dict(E=3, K=140),
+     dict(positions=LEV, windows=64, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          portfolio_initial_value=1e6, max_episode_duration=50, dynamic_feature_functions=MIX4)),
+    ("fobs9_fractional", (200, 7, 8e-3, 0), dict(E=4, K=180),
+     dict(positions=FRAC, windows=6, trading_fees=0, borrow_interest_rate=0,
+          max_episode_duration=30)),
+    ("fobs10_w2_value1", (220, 8, 1e-2, 0), dict(E=4, K=180),
+     dict(positions=[-1.5, -0.5, 0, 0.5, 1.5], windows=2, trading_fees=1e-3,
+          borrow_interest_rate=1e-3, portfolio_initial_value=1, max_episode_duration=35)),
+    ("fobs63_wide", (160, 61, 1e-2, 0), dict(E=3, K=100),
+     dict(positions=P3, windows=3, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=30)),
+    ("fobs62_nd4_nowindow", (160, 58, 1e-2, 0), dict(E=3, K=100),
+     dict(positions=LEV, windows=None, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=20, dynamic_feature_functions=MIX4R)),
+    ("fobs12_w1_nd3", (200, 9, 1e-2, 0), dict(E=4, K=180),
+     dict(positions=LEV, windows=1, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          max_episode_duration=8, dynamic_feature_functions=MIX3B)),
+    ("nd0_p20", (240, 8, 1.5e-2, 0), dict(E=4, K=180),
+     dict(positions=P20, windows=8, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=30, dynamic_feature_functions=[])),
+    ("nd0_scaled_nowindow", (200, 6, 1e-2, 0), dict(E=4, K=200),
+     dict(positions=P3, windows=None, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=30, dynamic_feature_functions=[],
+          reward_function=["scaled_log_return", 100.0])),
+    ("scaled_w10_nd1", (200, 7, 1e-2, 0), dict(E=4, K=180),
+     dict(positions=LEV, windows=10, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=30, dynamic_feature_functions=["last_position_taken"],
+          reward_function=["scaled_log_return", 50.0])),
+    ("clipped_nowindow_nd4", (200, 10, 1e-2, 0), dict(E=4, K=200),
+     dict(positions=FRAC, windows=None, trading_fees=1e-4, borrow_interest_rate=0,
+          max_episode_duration=30, dynamic_feature_functions=MIX4,
+          reward_function=["clipped_log_return", 1.0, -0.002, 0.005])),
+    ("basic_nowindow_drawdown", (150, 6, 2.5e-2, -5e-3), dict(E=4, K=300, p_none=0.3),
+     dict(positions=[-2, -1, 0, 1, 2, 3], windows=None, trading_fees=1e-2,
+          borrow_interest_rate=1e-3)),
+    ("drawdown_w4_1e6", (120, 6, 2.5e-2, -4e-3), dict(E=4, K=240, p_none=0.3),
+     dict(positions=[-3, -1, 0, 1, 3], windows=4, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          portfolio_initial_value=1e6)),
+    ("tight_start_one_row", (100, 6, 1e-2, 0), dict(E=4, K=200),
+     dict(positions=P3, windows=5, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=91)),
+    ("tight_start_two_rows", (60, 6, 1e-2, 0), dict(E=4, K=200),
+     dict(positions=P3, windows=None, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=58)),
+    ("duration5_w3", (150, 5, 1e-2, 0), dict(E=4, K=150),
+     dict(positions=P3, windows=3, trading_fees=1e-4, max_episode_duration=5)),
+    ("fixed_initial_autoreset", (200, 6, 1.5e-2, -2e-3), dict(E=4, K=200),
+     dict(positions=[-1, 0, 1, 2], windows=5, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          initial_position=2, max_episode_duration=20)),
+    # (no auto-reset: K <= max_episode_duration + W keeps every env inside its data)
+    ("no_autoreset_done", (300, 6, 3e-2, -6e-3), dict(E=4, K=94, autoreset=False, p_none=0.4),
+     dict(positions=[-1, 0, 1, 2], windows=4, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          max_episode_duration=90)),
+    ("persist_w8", (160, 6, 1e-2, 0), dict(E=4, K=260),
+     dict(positions=P3, windows=8, trading_fees=1e-4, max_episode_duration=15, dyn_persist=True)),
+    ("long_trace", (300, 6, 1e-2, 0), dict(E=2, K=640),
+     dict(positions=[-1, 0, 0.5, 1, 2], windows=5, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=25)),
+    ("limit_orders_market", (260, 6, 1e-2, 0), dict(E=4, K=240, p_none=0.2, p_order=0.35),
+     dict(positions=[-1, -0.5, 0, 1, 2], windows=3, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=40)),
+    ("multids_switch1", [(90, 6, 1e-2, 0), (110, 6, 1e-2, 0), (130, 6, 1e-2, 0)], dict(E=4, K=200),
+     dict(positions=P3, windows=4, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=20, episodes_between_dataset_switch=1)),
+    ("multids_switch2_persist", [(95, 5, 1e-2, 0), (120, 5, 1e-2, 0), (140, 5, 1e-2, 0),
+                                 (75, 5, 1e-2, 0)], dict(E=4, K=200),
+     dict(positions=P3, windows=5, trading_fees=1e-4, max_episode_duration=15,
+          episodes_between_dataset_switch=2, dyn_persist=True)),
+    ("multids_switch3_nowindow", [(80, 6, 1e-2, 0), (100, 6, 1e-2, 0)], dict(E=4, K=200),
+     dict(positions=[-1, 0, 1, 2], windows=None, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=12, episodes_between_dataset_switch=3)),
+    ("multids_limit_orders", [(120, 6, 1.2e-2, 0), (150, 6, 1.2e-2, 0), (170, 6, 1.2e-2, 0)],
+     dict(E=4, K=220, p_none=0.3, p_order=0.3),
+     dict(positions=[-1, 0, 0.5, 1], windows=3, trading_fees=DRAW, borrow_interest_rate=DRAW,
+          max_episode_duration=25, episodes_between_dataset_switch=1)),
+]
+
+
+def _draw(over, seed):
+    """The trace's configuration with every DRAW parameter drawn (seeded per trace)."""
+    r = np.random.default_rng(seed)
+    return {k: (DRAWN[k][int(r.integers(len(DRAWN[k])))] if v == DRAW else v) for k, v in over.items()}
+
+
+def _sweep_dataset(seed, spec, high_low):
+    T, Fs, sigma, drift = spec
+    feat, close = random_walk(seed, T, Fs, sigma=sigma, drift=drift)
+    if not high_low:
+        return (feat, close)
+    r = np.random.default_rng(seed + 1)
+    return (feat, close, close * (1 + np.abs(r.normal(0, 8e-3, T))),
+            close * (1 - np.abs(r.normal(0, 8e-3, T))))
+
+
+def sweep_traces():
+    """tests/golden/sweep_NN.npz: every row of the strata table in tests/strata.py, each trace
+    generated by the reference from its own seeds (the fixtures above are not touched)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import replay
+    import strata
+    rng = np.random.default_rng(SWEEP_SEED)
+    loaded, total = [], 0
+    for n, (tag, dspec, tspec, over) in enumerate(SWEEP):
+        name = f"sweep_{n:02d}"
+        cfg = base_cfg(**_draw(over, SWEEP_SEED + 101 * n))
+        kinds = cfg.get("dynamic_feature_functions", strata.DEFAULT_DYN)
+        kw = ref_kwargs(cfg)
+        kw.update(reward_function=_ref_reward(cfg["reward_function"]),
+                  dynamic_feature_functions=_ref_dynamic(kinds))
+        tspec = dict(tspec)
+        E, K = tspec.pop("E"), tspec.pop("K")
+        high_low = tspec.get("p_order", 0) > 0
+        seed_base = 60000 + 1000 * n
+        # a fresh reference env per episode keeps the dynamic columns of earlier episodes out of
+        # the window (dyn_persist=False); the same object keeps them (dyn_persist=True)
+        fresh = not cfg.get("dyn_persist", False)
+        if isinstance(dspec, list):
+            sets = [_sweep_dataset(SWEEP_SEED % 997 + 10 * n + d, s, high_low) for d, s in enumerate(dspec)]
+            assert len({len(s[1]) for s in sets}) == len(sets), "datasets are identified by length"
+            with tempfile.TemporaryDirectory() as tmp:
+                names = []
+                for d, s in enumerate(sets):
+                    names.append(f"sym{d}.pkl")
+                    make_df(*s).to_pickle(os.path.join(tmp, names[-1]))
+                switch = cfg["episodes_between_dataset_switch"]
+
+                def mk(e, tmp=tmp, switch=switch, kw=kw, n=n):
+                    np.random.seed(555 + 31 * n + e)
+                    return MultiDatasetTradingEnv(os.path.join(tmp, "*.pkl"),
+                                                  episodes_between_dataset_switch=switch, **kw)
+                rec = run_trace(mk, cfg["positions"], n_envs=E, n_calls=K, action_rng=rng,
+                                ds_names=[len(s[1]) for s in sets], seed_base=seed_base, **tspec)
+                import glob as _glob
+                rec["glob_order"] = np.array([names.index(os.path.basename(q))
+                                              for q in _glob.glob(os.path.join(tmp, "*.pkl"))], np.int32)
+        else:
+            sets = [_sweep_dataset(SWEEP_SEED % 997 + 10 * n, dspec, high_low)]
+            df = make_df(*sets[0])
+            rec = run_trace(lambda e, df=df, kw=kw: TradingEnv(df=df, **kw), cfg["positions"],
+                            n_envs=E, n_calls=K, action_rng=rng, seed_base=seed_base,
+                            fresh_env_each_episode=fresh and tspec.get("autoreset", True), **tspec)
+        out = fixture_arrays(cfg, sets, rec, "")
+        g = replay.from_arrays(out)
+        out["note"] = np.array(f"sweep trace {tag}; strata: {', '.join(strata.rows_of(g))}")
+        write(name, out)
+        kib = os.path.getsize(os.path.join(HERE, name + ".npz")) / 1024
+        assert kib <= SWEEP_KIB_PER_FIXTURE, f"{name}: {kib:.0f} KiB"
+        total += kib
+        loaded.append(g)
+    assert total <= SWEEP_KIB_TOTAL, f"sweep: {total:.0f} KiB"
+    gaps = strata.missing(loaded)
+    assert not gaps, f"strata rows not covered: {gaps}"
+    print(f"sweep: {len(SWEEP)} traces, {total:.0f} KiB")
 
 
 def portfolio_vectors():
@@ -649,6 +879,9 @@ def staging_fixture():
 
 
 if __name__ == "__main__":
+    if "--sweep" in sys.argv:
+        sweep_traces()
+        sys.exit(0)
     if "--only-vector" in sys.argv:
         vector_example_fixture()
         sys.exit(0)

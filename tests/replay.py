@@ -32,7 +32,12 @@ def golden_names():
 
 def load(name):
     z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False)
-    g = {k: z[k] for k in z.files}
+    return from_arrays({k: z[k] for k in z.files})
+
+
+def from_arrays(arrays):
+    """A trace from the arrays of its fixture file (not modified)."""
+    g = dict(arrays)
     g["cfg"] = json.loads(str(g.pop("cfg_json")))
     d = 0
     sets = []
@@ -85,9 +90,37 @@ def injection_queue(g, tile: int = 1):
     return {f: np.tile(a, (tile, 1)) for f, a in q.items()}, n
 
 
+def ulp_distance(a, b):
+    """Integer distance of the IEEE bit patterns of f64 arrays a and b (0.0 and -0.0 are one
+    value; NaN is not expected): how many representable doubles lie between them."""
+    def key(x):
+        i = np.ascontiguousarray(x, np.float64).view(np.int64).astype(object)
+        return np.where(i < 0, -(i & 0x7FFFFFFFFFFFFFFF), i)
+    return np.abs(key(a) - key(b)).astype(np.float64)
+
+
+def reward_ulp_bound(g):
+    """How many ulp reward64 may lie from the trace's: the log-return itself is within 1 ulp
+    (device / libm log against NumPy's; measured).  A factor k that is not a power of two
+    (scaled_log_return k=100) spreads that ulp: |k*lr' - k*lr| <= |k| ulp(lr) <= 2^-52 |k lr|,
+    at most 2 ulp of the product, plus half an ulp from each of the two roundings -> 3.  (Clipping
+    only replaces values by the bounds, which are exact.)"""
+    rf = g["cfg"].get("reward_function", "basic_reward_function")
+    k = 1.0 if isinstance(rf, str) else float(rf[1])
+    return 1 if np.frexp(abs(k))[0] == 0.5 else 3
+
+
 def replay(adapter, g, tile: int = 1, rtol: float = 1e-12, obs_exact: bool = True,
-           check_state: bool = True):
-    """Drive `adapter` through trace g; assert parity at every call."""
+           check_state: bool = True, reward_ulps: int | None = None, stats: dict | None = None):
+    """Drive `adapter` through trace g; assert parity at every call.
+
+    reward_ulps=n: the exact mode.  The fp64 state is compared bit for bit (rtol is not used),
+    reward64 within n ulp of the trace (an integer distance of the bit patterns) and exactly 0.0
+    where the trace's reward is 0 (resets, `done`), and, when the adapter has reward32(), the f32
+    reward equals float32 of the adapter's own reward64.  stats["reward_ulps"] receives the
+    worst distance seen."""
+    exact = reward_ulps is not None
+    worst_ulp = 0.0
     K, E = g["op"].shape
     t = lambda a: np.tile(a, tile)
     assert (g["op"][0] == 0).all()
@@ -117,14 +150,35 @@ def replay(adapter, g, tile: int = 1, rtol: float = 1e-12, obs_exact: bool = Tru
                 err = np.abs(got - ref) / np.maximum(np.abs(ref), 1e-300)
                 err = np.where(ref == got, 0.0, err)
                 worst = max(worst, float(err.max()))
-                np.testing.assert_allclose(got, ref, rtol=rtol, atol=1e-14 if rtol > 0 else 0,
-                                           err_msg=f"{tag} {gk}")
-        np.testing.assert_allclose(adapter.reward64(), t(g["reward"][k]), rtol=max(rtol, 1e-12),
-                                   atol=1e-15, err_msg=f"{tag} reward")
+                if exact:
+                    bad = np.nonzero(got != ref)[0]
+                    assert bad.size == 0, (f"{tag} {gk}: {bad.size} envs differ, first env {bad[0]}: "
+                                           f"{got[bad[0]]!r} != {ref[bad[0]]!r}")
+                else:
+                    np.testing.assert_allclose(got, ref, rtol=rtol, atol=1e-14 if rtol > 0 else 0,
+                                               err_msg=f"{tag} {gk}")
+        r64 = adapter.reward64()
+        ref_r = t(g["reward"][k])
+        if exact:
+            zero = ref_r == 0.0
+            assert (r64[zero] == 0.0).all(), f"{tag} reward: not exactly 0.0 where the trace's is"
+            d = ulp_distance(r64, ref_r)
+            worst_ulp = max(worst_ulp, float(d.max()))
+            assert d.max() <= reward_ulps, (f"{tag} reward64: {d.max():.0f} ulp from the trace "
+                                            f"(bound {reward_ulps}) at env {int(d.argmax())}: "
+                                            f"{r64[d.argmax()]!r} vs {ref_r[d.argmax()]!r}")
+            if hasattr(adapter, "reward32"):
+                np.testing.assert_array_equal(adapter.reward32(), r64.astype(np.float32),
+                                              err_msg=f"{tag} f32 reward != float32(reward64)")
+        else:
+            np.testing.assert_allclose(r64, ref_r, rtol=max(rtol, 1e-12), atol=1e-15,
+                                       err_msg=f"{tag} reward")
         obs = adapter.obs()
         ref_obs = np.tile(g["obs"][k], (tile,) + (1,) * (g["obs"][k].ndim - 1))
         if obs_exact:
             np.testing.assert_array_equal(obs, ref_obs, err_msg=f"{tag} obs")
         else:
             np.testing.assert_allclose(obs, ref_obs, rtol=1e-6, atol=1e-7, err_msg=f"{tag} obs")
+    if stats is not None:
+        stats["reward_ulps"] = max(stats.get("reward_ulps", 0.0), worst_ulp)
     return worst

@@ -1,0 +1,197 @@
+"""The strata table of the reference-generated sweep (tests/golden/sweep_NN.npz).
+
+Every row names one corner of the configuration space the HIP kernels branch on and a
+predicate over a loaded trace (replay.load) that says whether the trace covers it.  The
+predicates read only the trace's configuration, its data shapes and its recorded flags, so
+tests/test_sweep_strata.py can assert that the committed fixtures still cover every row, and
+make_golden.py can assert it before it writes them.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+DEFAULT_DYN = ["last_position_taken", "real_position"]
+
+
+def facts(g):
+    """Derived shape / configuration facts of a loaded trace."""
+    cfg = g["cfg"]
+    kinds = cfg.get("dynamic_feature_functions", DEFAULT_DYN)
+    nd = len(kinds)
+    Fs = g["datasets"][0][0].shape[1]
+    W = cfg["windows"]
+    rf = cfg.get("reward_function", "basic_reward_function")
+    reward = "basic" if isinstance(rf, str) else rf[0].split("_")[0]
+    Ts = [len(ds[1]) for ds in g["datasets"]]
+    op = g["op"]
+    K, E = op.shape
+    positions = cfg["positions"]
+    dur = cfg["max_episode_duration"]
+    ends = (g["done"] | g["truncated"]).astype(bool)
+    last_row = np.array([[Ts[d] - 1 for d in row] for row in g["dataset"]])
+    return dict(cfg=cfg, kinds=kinds, nd=nd, Fs=Fs, Fobs=Fs + nd, W=W, Wn=W or 1, reward=reward,
+                Ts=Ts, D=len(Ts), K=K, E=E, positions=positions, dur=dur,
+                autoreset=bool((op[1:] == 0).any()), persist=bool(cfg.get("dyn_persist", False)),
+                switch=cfg.get("episodes_between_dataset_switch", 1),
+                limit="lo_pos" in g, high_low=len(g["datasets"][0]) == 4,
+                episodes=(op == 0).sum(axis=0), ends=ends,
+                trunc_end=bool((g["truncated"].astype(bool) & (g["idx"] == last_row)).any()),
+                trunc_dur=bool((g["truncated"].astype(bool) & (g["idx"] < last_row)).any()))
+
+
+def _lean(f, nd):
+    # the lean copy loop (gte_kernels.hip): 16-byte vectors, raw rings staged in LDS (not
+    # dyn_persist), a window of at least one wave instruction (256 floats)
+    return (f["nd"] == nd and f["Fobs"] % 4 == 0 and f["W"] is not None and f["W"] * f["Fobs"] >= 256
+            and not f["persist"])
+
+
+def _tight(f):
+    # randint(low, T - max_dur - low) (environments.py:173-177) leaves one or two start rows
+    if f["dur"] == "max":
+        return False
+    low = f["Wn"] - 1
+    return all(1 <= T - f["dur"] - 2 * low <= 2 for T in f["Ts"])
+
+
+def _fill_with_market_action(g, f):
+    # a step whose market action moved the position and whose final position is not the action's
+    # target: a limit order filled after the market trade of the same step (environments.py:234-238)
+    if not f["limit"]:
+        return False
+    op, a, pi = g["op"], g["action"], g["pos_index"]
+    prev = pi[:-1]
+    step = op[1:] == 1
+    moved = (a[1:] >= 0) & (a[1:] != prev)
+    return bool((step & moved & (pi[1:] != a[1:])).any())
+
+
+def _several_orders(g, f):
+    # at least two limit orders added to one env inside one episode
+    if not f["limit"]:
+        return False
+    lo, op = g["lo_pos"], g["op"]
+    for e in range(f["E"]):
+        episode = np.cumsum(op[:, e] == 0)
+        have = lo[:, e] >= 0
+        if have.any() and np.bincount(episode[have]).max() >= 2:
+            return True
+    return False
+
+
+def _steps_after_end(g, f):
+    if f["autoreset"]:
+        return False
+    ended = np.maximum.accumulate(f["ends"], axis=0)
+    return bool((ended[:-1] & (g["op"][1:] == 1)).any())
+
+
+#: gte_rollout's paths by (kernel_variant, keep_obs) of the rollout() call
+ROLLOUT_MODES = {"resident": (0, True), "gather": (256, True), "state": (0, False), "per-step": (128, True)}
+
+
+def hot_shape(f):
+    """The shape the fused rollout kernels are written for (gte_api.hip, plan_launches): 16-byte
+    rows and dynamic columns staged raw in LDS (nd > 0, not dyn_persist), given a cooperative
+    phase A (envs_per_wave <= 16)."""
+    return f["Fobs"] % 4 == 0 and f["nd"] > 0 and not f["persist"]
+
+
+def rollout_path(f, mode, n_steps=2):
+    """The path gte_rollout takes for a trace in one of ROLLOUT_MODES: the window-resident kernel
+    needs a window of 2 rows or more; a state-only call of one step is a plain step launch."""
+    kv, keep = ROLLOUT_MODES[mode]
+    if not hot_shape(f) or kv & 128:
+        return "per-step"
+    if not keep:
+        return "state-only" if n_steps > 1 else "per-step"
+    return "resident" if (f["Wn"] >= 2 and not kv & 256) else "gather"
+
+
+def _fused(f, mode):
+    return rollout_path(f, mode) == {"resident": "resident", "gather": "gather", "state": "state-only"}[mode]
+
+
+STRATA = {
+    "lean_nd1": lambda g, f: _lean(f, 1),
+    "lean_nd2": lambda g, f: _lean(f, 2),
+    "lean_nd3": lambda g, f: _lean(f, 3),
+    "lean_nd4": lambda g, f: _lean(f, 4),
+    "fobs_mod4_1": lambda g, f: f["Fobs"] % 4 == 1,
+    "fobs_mod4_2": lambda g, f: f["Fobs"] % 4 == 2,
+    "fobs_mod4_3": lambda g, f: f["Fobs"] % 4 == 3,
+    "fobs_4byte_ge61": lambda g, f: f["Fobs"] % 4 != 0 and f["Fobs"] >= 61,
+    "nd0": lambda g, f: f["nd"] == 0,
+    "nd3_mixed": lambda g, f: f["nd"] == 3 and len(set(f["kinds"])) == 2,
+    "nd4_mixed": lambda g, f: f["nd"] == 4 and len(set(f["kinds"])) == 2,
+    "real_position_first": lambda g, f: f["nd"] >= 2 and f["kinds"][0] == "real_position",
+    "window_none": lambda g, f: f["W"] is None,
+    "window_1": lambda g, f: f["W"] == 1,
+    "window_2": lambda g, f: f["W"] == 2,
+    "window_ge64": lambda g, f: f["W"] is not None and f["W"] >= 64,
+    "leverage_above_1": lambda g, f: max(f["positions"]) > 1,
+    "leverage_below_m1": lambda g, f: min(f["positions"]) < -1,
+    "fractional_positions": lambda g, f: any(p != int(p) for p in f["positions"]),
+    "positions_ge16": lambda g, f: len(f["positions"]) >= 16,
+    "fees_0": lambda g, f: f["cfg"]["trading_fees"] == 0,
+    "fees_1e-2": lambda g, f: f["cfg"]["trading_fees"] == 1e-2,
+    "borrow_0": lambda g, f: f["cfg"]["borrow_interest_rate"] == 0,
+    "borrow_1e-3": lambda g, f: f["cfg"]["borrow_interest_rate"] == 1e-3,
+    "initial_value_1": lambda g, f: f["cfg"]["portfolio_initial_value"] == 1,
+    "initial_value_1e6_leverage": lambda g, f: (f["cfg"]["portfolio_initial_value"] == 1e6
+                                                and (max(f["positions"]) > 1 or min(f["positions"]) < -1)),
+    "fixed_initial_position_autoreset": lambda g, f: (f["cfg"]["initial_position"] != "random"
+                                                      and f["autoreset"]),
+    "duration_max": lambda g, f: f["dur"] == "max",
+    "duration_le10": lambda g, f: f["dur"] != "max" and f["dur"] <= 10,
+    "duration_tight_start": lambda g, f: _tight(f),
+    "truncated_end_of_data": lambda g, f: f["trunc_end"],
+    "truncated_by_duration": lambda g, f: f["trunc_dur"],
+    "reward_basic_window": lambda g, f: f["reward"] == "basic" and f["W"] is not None,
+    "reward_basic_nowindow": lambda g, f: f["reward"] == "basic" and f["W"] is None,
+    "reward_clipped_window": lambda g, f: f["reward"] == "clipped" and f["W"] is not None,
+    "reward_clipped_nowindow": lambda g, f: f["reward"] == "clipped" and f["W"] is None,
+    "reward_scaled_window": lambda g, f: f["reward"] == "scaled" and f["W"] is not None,
+    "reward_scaled_nowindow": lambda g, f: f["reward"] == "scaled" and f["W"] is None,
+    "multids_switch1": lambda g, f: f["D"] > 1 and f["switch"] == 1,
+    "multids_switch2": lambda g, f: f["D"] > 1 and f["switch"] == 2,
+    "multids_switch3": lambda g, f: f["D"] > 1 and f["switch"] == 3,
+    "multids_persist": lambda g, f: f["D"] > 1 and f["persist"],
+    "multids_no_persist": lambda g, f: f["D"] > 1 and not f["persist"],
+    "multids_limit_orders": lambda g, f: f["D"] > 1 and f["limit"] and f["high_low"],
+    "limit_several_per_env": lambda g, f: _several_orders(g, f),
+    "limit_fill_with_market_action": lambda g, f: _fill_with_market_action(g, f),
+    "no_autoreset_steps_after_end": lambda g, f: _steps_after_end(g, f),
+    "dyn_persist_single_ds_window": lambda g, f: (f["D"] == 1 and f["persist"] and f["W"] is not None
+                                                  and f["W"] > 1),
+    "long_trace": lambda g, f: f["K"] >= 600 and int(f["episodes"].min()) >= 10,
+}
+
+# every fused rollout kernel replays the reference's hardest rollout semantics directly: drawdown
+# terminations, limit-order fills, dataset switches
+for _kernel in ("resident", "gather", "state"):
+    STRATA[f"{_kernel}_done"] = lambda g, f, k=_kernel: _fused(f, k) and bool(g["done"].any())
+    STRATA[f"{_kernel}_limit_orders"] = lambda g, f, k=_kernel: _fused(f, k) and f["limit"]
+    STRATA[f"{_kernel}_multids"] = lambda g, f, k=_kernel: _fused(f, k) and f["D"] > 1
+STRATA["resident_multids_limit_orders"] = lambda g, f: _fused(f, "resident") and f["D"] > 1 and f["limit"]
+
+#: rows that must hold in at least this many traces (all others: one)
+MIN_TRACES = {"drawdown_done": 3}
+
+
+def rows_of(g):
+    """The strata rows trace g covers."""
+    f = facts(g)
+    rows = [name for name, pred in STRATA.items() if pred(g, f)]
+    if g["done"].any():
+        rows.append("drawdown_done")
+    return rows
+
+
+def missing(traces):
+    """Rows of the table (and MIN_TRACES) that the given loaded traces leave uncovered."""
+    count = {name: 0 for name in list(STRATA) + list(MIN_TRACES)}
+    for g in traces:
+        for r in rows_of(g):
+            count[r] += 1
+    return {name: n for name, n in count.items() if n < MIN_TRACES.get(name, 1)}

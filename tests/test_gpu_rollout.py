@@ -159,8 +159,8 @@ def test_rollout_with_limit_orders_and_oracle(oracle_mod):
         np.testing.assert_array_equal(out["reward"][k].cpu().numpy(), ora.reward)
         np.testing.assert_array_equal(out["terminated"][k].cpu().numpy(), ora.terminated.astype(bool))
         np.testing.assert_array_equal(out["truncated"][k].cpu().numpy(), ora.truncated.astype(bool))
-        np.testing.assert_allclose(out["valuation"][k].cpu().numpy(), ora.state()["portfolio_valuation"],
-                                   rtol=1e-12)
+        np.testing.assert_array_equal(out["valuation"][k].cpu().numpy(), ora.state()["portfolio_valuation"],
+                                      err_msg=f"step {k} valuation")
     st = ora.state()
     np.testing.assert_array_equal(env.state("idx"), st["idx"])
     np.testing.assert_array_equal(env.state("position_index"), st["position_index"])
