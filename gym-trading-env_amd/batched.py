@@ -284,8 +284,9 @@ class BatchedTradingEnv(_VectorEnvBase):
         """The batched `MultiDatasetTradingEnv` (environments.py:365-400): every file matched
         by the glob `dataset_dir` is loaded (`pd.read_pickle`), passed through `preprocess`
         and kept RESIDENT in HBM; each env moves to another dataset every
-        `episodes_between_dataset_switch` episodes, visiting all of them once per round in
-        random order (== uniform among the least-used ones, :383-388)."""
+        `episodes_between_dataset_switch` episodes, visiting all of them once per round of
+        D picks in uniformly random order: each pick is uniform among the datasets the round
+        has not visited yet (== uniform among the least-used ones, :383-388)."""
         import glob
         from pathlib import Path
 

@@ -600,6 +600,12 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   chk(hipEventCreate(&E->ev0) == hipSuccess && hipEventCreate(&E->ev1) == hipSuccess
           ? GTE_OK : fail(GTE_ERR_HIP, "hipEventCreate failed"));
   chk(dev_alloc(E, &p.rec, N));  // zero-filled: every counter starts at 0
+  // the datasets each env has picked in its current round of D (gte_device.h, pick_dataset)
+  if (p.D > 1) {
+    const size_t words = N * (size_t)((p.D + 31) / 32);
+    chk(words <= 0xFFFFFFFFull ? GTE_OK : fail(GTE_ERR_INVALID, "n_envs x ceil(n_datasets / 32) must be < 2^32"));
+    chk(dev_alloc(E, &p.ds_used, words));
+  }
   chk(alloc_soa(E, &E->soa, N));
   // (the library's own observation buffers are allocated on first use, ensure_owned_obs: a caller
   // that binds its own — the torch path — never pays for a second copy of [N, W, F_obs])

@@ -119,8 +119,9 @@ struct Params {
   // shared-TU step kernel only).  log.idx == null: none (the host appends it with gte_log_kernel)
   LogArrays log;
   int64_t* log_cursor;   // the slot of the log cursor this launch reads (log_cursor_other below)
+  uint32_t* ds_used;     // u32 [N, ceil(D/32)]: datasets picked in the env's current round (D > 1 only)
 };
-static_assert(offsetof(Params, log) == 384 && offsetof(Params, log_cursor) == 392 && sizeof(Params) == 400,
+static_assert(offsetof(Params, log) == 384 && offsetof(Params, log_cursor) == 392 && sizeof(Params) == 408,
               "Params keeps its layout (log_cursor replaced log_row_base in place)");
 
 // The trajectory log's row count lives on the device, so that a replayed graph appends where the
@@ -176,29 +177,44 @@ __device__ inline int32_t bounded(uint32_t x, int32_t span) {
   return (int32_t)__umulhi(x, (uint32_t)span);
 }
 
-// k-th element of the keyed pseudo-random permutation of [0, D) for pick round
-// `round` of env e (MultiDatasetTradingEnv.next_dataset, environments.py:380-388:
-// uniform among the least-used datasets == every dataset once per round of D
-// picks, in random order).
-__device__ inline int32_t perm_pick(const Params& p, int32_t e, int32_t round, int32_t k) {
+// Dataset pick number n of env e (MultiDatasetTradingEnv.next_dataset, environments.py:380-388):
+// uniform among the least-used datasets.  Every round of D picks visits each dataset once, so
+// the least-used ones are those the round has not picked yet; p.ds_used holds them as one bitset
+// of ceil(D/32) words per env.  Pick k = n % D draws j uniform in [0, D - k) and takes the j-th
+// unused dataset: a uniformly random order of each round.  An injected pick marks its dataset
+// (one outside [0, D) marks nothing).  An injected pick that repeats one of the round leaves more
+// than D - k datasets unused, so the j-th unused one always exists.
+// The bitset is indexed with 32-bit word numbers (gte_create keeps N * ceil(D/32) below 2^32): a
+// 32-bit offset from the uniform base is one VGPR where a per-lane pointer is two, and with two the
+// window-resident rollout kernel spills.
+__device__ inline int32_t pick_dataset(const Params& p, int32_t e, int32_t n, int32_t inj_ds) {
   const int32_t D = p.D;
-  if (D == 1) return 0;
-  int b = 32 - __clz(D - 1);
-  if (b < 1) b = 1;
-  const uint32_t mask = (b == 32) ? 0xFFFFFFFFu : ((1u << b) - 1u);
-  uint32_t r[4];
-  reset_draws(p, e, round, 0x44534554u, r);
-  uint32_t x = (uint32_t)k;
-  const int sh = (b + 1) / 2;
-  do {  // a bijection on b bits; cycle-walk into [0, D): terminates, < 2 rounds expected
-    x = (x * (r[0] | 1u) + r[1]) & mask;
-    x ^= x >> sh;
-    x = (x * (r[2] | 1u) + r[3]) & mask;
-    x ^= x >> sh;
-    x = (x * 0x9E3779B1u + (r[0] >> 7)) & mask;
-    x ^= x >> sh;
-  } while (x >= (uint32_t)D);
-  return (int32_t)x;
+  const int32_t k = n % D;
+  const uint32_t nw = (uint32_t)(D + 31) >> 5;
+  const uint32_t w0 = (uint32_t)e * nw;
+  if (k == 0)
+    for (uint32_t w = 0; w < nw; ++w) p.ds_used[w0 + w] = 0u;
+  int32_t d = inj_ds;
+  if (d < 0) {
+    uint32_t r[4];
+    reset_draws(p, e, n, 0x44534554u, r);  // 'DSET'
+    int32_t j = bounded(r[0], D - k);
+    d = 0;
+    // the j-th unused dataset in increasing order; bits >= D of the last word read as unused but
+    // come after all D - k (or more) unused datasets, so j never reaches them
+    for (uint32_t w = 0; w < nw; ++w) {
+      uint32_t avail = ~p.ds_used[w0 + w];
+      const int32_t c = __popc(avail);
+      if (j < c) {
+        for (; j > 0; --j) avail &= avail - 1u;  // drop the j lowest unused
+        d = (int32_t)(w << 5) + __ffs(avail) - 1;
+        break;
+      }
+      j -= c;
+    }
+  }
+  if ((uint32_t)d < (uint32_t)D) p.ds_used[w0 + ((uint32_t)d >> 5)] |= 1u << (d & 31);
+  return d;
 }
 
 // ---------------------------------------------------------------------------

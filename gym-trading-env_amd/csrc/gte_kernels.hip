@@ -135,7 +135,7 @@ __device__ inline void next_dataset(const Params& p, int e, int32_t inj_ds, EnvR
   EnvRec* r = &p.rec[e];
   const int32_t n = r->n_picks;
   r->n_picks = n + 1;
-  s.dsi = (inj_ds >= 0) ? inj_ds : perm_pick(p, e, n / p.D, n % p.D);
+  s.dsi = pick_dataset(p, e, n, inj_ds);
   r->eps_on_ds = 0;                 // :381
   if (p.persist) fresh = true;      // _set_df rebuilds _obs_array (:135-141)
 }

@@ -37,6 +37,7 @@ typedef struct gto_env {
   /* state */
   int32_t *idx, *step, *pos, *ds, *start, *episode, *needs_reset, *eps_on_ds,
       *n_picks;
+  uint32_t* ds_used; /* [N, ceil(D/32)] datasets picked in the current round (D > 1) */
   double *asset, *fiat, *ia, *ifi, *pv, *realpos;
   float* ring; /* [N, depth, nd] */
   /* outputs */
@@ -105,30 +106,32 @@ static int32_t bounded(uint32_t x, int32_t span) {
   return (int32_t)(((uint64_t)x * (uint64_t)(uint32_t)span) >> 32);
 }
 
-/* k-th element of the pseudo-random permutation of [0, D) used for pick round
- * `round` of env e: a keyed bijection on b bits (odd multiply, add, xorshift)
- * with cycle walking.  Restates MultiDatasetTradingEnv.next_dataset
- * (environments.py:380-388): "uniform among the least-used datasets" visits
- * every dataset once per round of D picks in uniformly random order. */
-static int32_t perm_pick(const gto_env* E, int32_t e, int32_t round, int32_t k) {
-  int32_t D = E->D;
-  if (D == 1) return 0;
-  int b = 1;
-  while ((1 << b) < D) ++b;
-  uint32_t mask = (b == 32) ? 0xFFFFFFFFu : ((1u << b) - 1u);
-  uint32_t r[4];
-  reset_draws(E, e, round, 0x44534554u /* 'DSET' */, r);
-  uint32_t x = (uint32_t)k;
-  int sh = (b + 1) / 2;
-  do {
-    x = (x * (r[0] | 1u) + r[1]) & mask;
-    x ^= x >> sh;
-    x = (x * (r[2] | 1u) + r[3]) & mask;
-    x ^= x >> sh;
-    x = (x * 0x9E3779B1u + (r[0] >> 7)) & mask;
-    x ^= x >> sh;
-  } while (x >= (uint32_t)D);
-  return (int32_t)x;
+/* Dataset pick number n of env e.  Restates MultiDatasetTradingEnv.next_dataset
+ * (environments.py:380-388), "uniform among the least-used datasets": every round
+ * of D picks visits each dataset once, so the least-used ones are those the round
+ * has not picked yet (ds_used: one bitset of ceil(D/32) words per env).  Pick
+ * k = n % D draws j uniform in [0, D - k) and takes the j-th unused dataset in
+ * increasing order, so each round is a uniformly random permutation.  An injected
+ * pick marks its dataset (one outside [0, D) marks nothing). */
+static int32_t pick_dataset(gto_env* E, int32_t e, int32_t n, int32_t inj_ds) {
+  const int32_t D = E->D;
+  const int32_t k = n % D;
+  const int32_t nw = (D + 31) / 32;
+  uint32_t* used = E->ds_used + (int64_t)e * nw;
+  if (k == 0) memset(used, 0, sizeof(uint32_t) * nw);
+  int32_t d = inj_ds;
+  if (d < 0) {
+    uint32_t r[4];
+    reset_draws(E, e, n, 0x44534554u /* 'DSET' */, r);
+    int32_t j = bounded(r[0], D - k);
+    d = 0;
+    for (int32_t c = 0; c < D; ++c) {
+      if (used[c / 32] >> (c % 32) & 1u) continue;
+      if (j-- == 0) { d = c; break; }
+    }
+  }
+  if (d >= 0 && d < D) used[d / 32] |= 1u << (d % 32);
+  return d;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -223,7 +226,7 @@ static void get_obs(gto_env* E, int32_t e) {
 /* MultiDatasetTradingEnv.next_dataset, environments.py:380-391 */
 static void next_dataset(gto_env* E, int32_t e, int32_t inj_ds) {
   int32_t n = E->n_picks[e]++;
-  int32_t d = (inj_ds >= 0) ? inj_ds : perm_pick(E, e, n / E->D, n % E->D);
+  int32_t d = pick_dataset(E, e, n, inj_ds);
   E->ds[e] = d;
   E->eps_on_ds[e] = 0; /* :381 */
   if (E->cfg.dyn_persist && E->nd > 0) /* _set_df rebuilds _obs_array :135-141 */
@@ -429,6 +432,7 @@ gto_env* gto_create(const gte_config* cfg) {
 #define F64(name) E->name = (double*)zalloc(sizeof(double) * N)
   I32(idx); I32(step); I32(pos); I32(ds); I32(start); I32(episode);
   I32(needs_reset); I32(eps_on_ds); I32(n_picks); I32(term_ids); I32(q_head); I32(lo_n);
+  if (E->D > 1) E->ds_used = (uint32_t*)zalloc(sizeof(uint32_t) * N * ((E->D + 31) / 32));
   E->lo_pos = (int32_t*)zalloc(sizeof(int32_t) * N * cfg->n_positions);
   E->lo_limit = (double*)zalloc(sizeof(double) * N * cfg->n_positions);
   E->lo_persist = (uint8_t*)zalloc(N * cfg->n_positions);
@@ -604,6 +608,7 @@ void gto_destroy(gto_env* E) {
   free(E->lo_n); free(E->lo_pos); free(E->lo_limit); free(E->lo_persist);
   free(E->idx); free(E->step); free(E->pos); free(E->ds); free(E->start);
   free(E->episode); free(E->needs_reset); free(E->eps_on_ds); free(E->n_picks);
+  free(E->ds_used);
   free(E->asset); free(E->fiat); free(E->ia); free(E->ifi); free(E->pv);
   free(E->realpos); free(E->ring); free(E->obs); free(E->final_obs); free(E->reward);
   free(E->reward64); free(E->terminated); free(E->truncated); free(E->term_ids);
