@@ -14,23 +14,31 @@ env group e % 500 at prologue step e % 500), so every step of every window —
 the driver's 20-step one included — carries its share of episode ends and
 auto-resets (about N/500 per step) instead of a reset storm every 500 steps.
 
-Prints ONE JSON line (rank 0).  `roofline`:
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure needs: set-up,
+the de-synchronising prologue, warm-up, the timed steps, --dump-outputs, the line.  Its `roofline`
+block is derived from the timed steps' own HIP events and the counters recorded under profiles/.
+Every other measurement sits behind `--full` (off by default): the live `rocprofv3 --pmc` child
+passes, the 262 144-env HBM-regime leg, `cpu_baseline`, and on N > 1 GPUs the gather modes and
+the observation-gather variant reported beside `value`.  --no-pmc, --no-hbm-regime,
+--no-cpu-baseline and --one-gather-mode drop single legs of a --full run.
+
+`roofline`:
   achieved   ALGORITHMIC bytes of SURVEY §8d (5 250 B per env-step at this shape, no reuse
              of the feature table credited) / kernel time — kept as the survey defines it;
              with the table served from L2 it exceeds what the memory system really moves;
   traffic    bytes per launch from the PMC counters (FETCH_SIZE x 1024 x 2 — the gfx950
-             half-count of wide reads — plus WRITE_SIZE x 1024), collected by THIS run in
-             separate `rocprofv3 --pmc` child passes of the same workload (falls back to
-             profiles/hbm_traffic.json, and says so, when rocprofv3 is unavailable);
+             half-count of wide reads — plus WRITE_SIZE x 1024): with --full collected by THIS
+             run in separate `rocprofv3 --pmc` child passes of the same workload; a plain run,
+             or one that cannot run rocprofv3, reads profiles/hbm_traffic.json, and says so;
   frac       traffic / kernel time / 8 TB/s — the headline fraction, physical (<= 1);
   frac_compulsory   the bytes no implementation can avoid (SURVEY §8d lower-bound
              variant: obs store + one new table row + state + ring + returns = 2 970 B
              per env-step) / kernel time / 8 TB/s;
   regime     where the observation buffer lives: at 65 536 envs its 168 MB fit the 256 MiB
              Infinity Cache (the counters then measure fabric traffic, not DRAM traffic);
-  hbm_regime the same kernel at 262 144 envs (671 MB of observations per launch, streamed
-             to HBM with non-temporal stores), with its own counters.
-`cpu_baseline` is the oracle's C restatement (oracle/, a "port") timed on this box's
+  hbm_regime (--full) the same kernel at 262 144 envs (671 MB of observations per launch,
+             streamed to HBM with non-temporal stores), with its own counters.
+`cpu_baseline` (--full) is the oracle's C restatement (oracle/, a "port") timed on this box's
 host cores on a bounded sample of the same workload.
 
 Multi-GPU (torchrun, one rank per GPU): envs shard with no data-path collective
@@ -38,7 +46,7 @@ except the RCCL all-gather of the returns (reward, terminated, truncated: 6 byte
 per env and step), which is what the north star names.  `value` is measured with per-step
 returns through the C ABI's own RCCL communicator (gte_allgather_returns): synchronously after
 every step (`--gather-mode step`) or overlapping the next step (`step-overlap`), whichever a short
-probe finds faster on the node (`auto`, the default); `block` moves a --gather-every (32) step
+probe finds faster on the node (`auto`, the default); with --full `block` moves a --gather-every (32) step
 block at a time on RCCL's stream while the following steps run and is reported
 beside it (config.other_gather_modes);
 --gather-obs adds the observation all-gather (xGMI-bound).  Weak scaling: 65 536 envs/GPU.
@@ -380,14 +388,20 @@ def main():
     ap.add_argument("--debug-flags", type=int, default=0, help="gte_config.debug_flags (timing probes: results are wrong)")
     ap.add_argument("--affinity", type=int, default=0,
                     help="L2-affinity re-sort period in steps (0 = default 128, -1 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything the headline figure does not need: the live rocprofv3 "
+                         "--pmc child passes, the 262 144-env HBM-regime leg, the CPU baseline and, "
+                         "on N>1 GPUs, the other gather modes and the observation-gather variant. "
+                         "Off by default: a plain run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints its line")
     ap.add_argument("--sync-episodes", action="store_true",
                     help="skip the de-synchronising prologue: all envs start together, resets "
                          "arrive as a storm every max_episode_duration steps (round-1 behaviour)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not spawn the rocprofv3 --pmc child passes (traffic then comes from "
-                         "profiles/hbm_traffic.json, or is null)")
+                    help="--full: do not spawn the rocprofv3 --pmc child passes (traffic then comes "
+                         "from profiles/hbm_traffic.json, or is null, as in a plain run)")
     ap.add_argument("--no-hbm-regime", action="store_true",
-                    help="skip the 262 144-env leg (observations streamed to HBM)")
+                    help="--full: skip the 262 144-env leg (observations streamed to HBM)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--gather-obs", action="store_true",
                     help="also all-gather the observations after every step (N>1; xGMI-bound: 2 560 B "
@@ -407,10 +421,10 @@ def main():
                          "torch.distributed; 'auto' (default) = the faster of the two PER-STEP forms "
                          "'step' and 'step-overlap', decided by a short untimed probe on this node "
                          "(synchronous gathers pay RCCL's cross-GPU latency in every step, overlapped "
-                         "ones two cross-stream events).  The other modes are measured too and "
-                         "reported under config.other_gather_modes")
+                         "ones two cross-stream events).  With --full the other modes are measured "
+                         "too and reported under config.other_gather_modes")
     ap.add_argument("--one-gather-mode", action="store_true",
-                    help="N>1: measure only --gather-mode")
+                    help="N>1, --full: measure only --gather-mode (a plain run always does)")
     ap.add_argument("--gather-every", type=int, default=32,
                     help="block mode: all-gather the returns in blocks of this many steps (every "
                          "step's reward/flags still cross xGMI inside the timed region)")
@@ -425,7 +439,8 @@ def main():
                     help="after the timed steps, write what the last one returned (rank 0's envs) "
                          "as DIR/<name>.npy: obs, reward, terminated, truncated and info_<column>, "
                          "under 64 MB (a fixed, seeded sample of envs when the batch is larger)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-python-loop", type=float, default=0.0, metavar="SECONDS",
                     help="cpu_baseline calibration only, no GPU: time the interpreter-bound per-env loop "
                          "(oracle/py_loop.py) on one core for SECONDS and print env-steps/s "
@@ -453,7 +468,7 @@ def main():
     F_obs = wl["n_static"] + n_dyn
     shape = (W, F_obs, wl["n_static"], n_dyn)
     cycle = wl["max_episode_duration"]
-    hbm_leg = (world == 1 and not args.pmc_child and not args.no_hbm_regime
+    hbm_leg = (args.full and world == 1 and not args.pmc_child and not args.no_hbm_regime
                and args.workload == "c3" and N == wl["envs"])
 
     # Counter passes first, while this process has not touched the GPU: each is a child
@@ -463,7 +478,7 @@ def main():
                 or any(k.startswith(("ROCPROF", "ROCPROFILER")) for k in os.environ))
     if profiled:  # this process is itself being profiled: no nested profiler runs
         print("[bench] running under a profiler: traffic comes from profiles/hbm_traffic.json", file=sys.stderr)
-    if world == 1 and not args.pmc_child and not args.no_pmc and not profiled:
+    if args.full and world == 1 and not args.pmc_child and not args.no_pmc and not profiled:
         for n in [N] + ([HBM_REGIME_ENVS] if hbm_leg else []):
             t = pmc_traffic(args, n)
             if not t:
@@ -498,12 +513,14 @@ def main():
                          f"its own ranks) or under torchrun with --nproc-per-node {args.gpus}")
     # the observation all-gather: asked for, or part of the workload (c4)
     want_obs = use_dist and (args.gather_obs or (bool(wl.get("gather_obs")) and not args.no_gather_obs))
-    both_obs = use_dist and bool(wl.get("gather_obs")) and not args.gather_obs  # c4 reports both
+    both_obs = (args.full and use_dist and bool(wl.get("gather_obs"))
+                and not args.gather_obs)  # c4 reports both
 
+    one_mode = args.one_gather_mode or not args.full  # only the mode `value` is measured in
     modes = []
     if use_dist:
         first = "step" if args.gather_mode == "auto" else args.gather_mode
-        modes = [first] + ([] if args.one_gather_mode and args.gather_mode != "auto" else
+        modes = [first] + ([] if one_mode and args.gather_mode != "auto" else
                            [m for m in ("step", "step-overlap", "block") if m != first])
         if backend != "nccl":  # the library's communicator is RCCL: gloo rehearsals use torch's
             modes = [m for m in modes if m in ("block", "torch-step")] or ["block"]
@@ -622,8 +639,8 @@ def main():
         best = min(probe, key=probe.get)
         print(f"[bench] per-step gather probe: {probe} -> {best}", file=sys.stderr)
         modes = [best] + [m for m in modes if m != best]
-        if args.one_gather_mode:
-            modes = modes[:1]
+    if one_mode:
+        modes = modes[:1]
     episodes0 = int(env.state("episode").sum())
     el, ev_ms = timed(modes[0] if modes else None, 0)
     episodes = int(env.state("episode").sum()) - episodes0
@@ -687,7 +704,7 @@ def main():
             "metric": "env-steps/sec", "value": world * N * args.steps / el, "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": el * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": what +
                                    f"{wl['n_datasets']} dataset(s)/GPU of T={wl['T']}, positions [-1,0,1], "
                                    f"fees 1e-4, borrow 3e-6, max_episode_duration {cycle}, next-step autoreset",
@@ -718,7 +735,7 @@ def main():
                 + (")" if want_obs else ",obs)") + how[mode])
         if hbm:
             out["roofline"]["hbm_regime"] = hbm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl)
             # the reference's OWN Python step() cannot run on this box (its files do not
             # travel); quote the timing taken in the build container (tools/time_reference.py)

@@ -299,7 +299,8 @@ def test_bench_gpus_2_from_a_bare_shell_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GTE_BENCH_BACKEND="gloo", GTE_BENCH_SHARE_DEVICE="1")
-    for workload, extra in (("c3", ["--envs", "8192"]), ("c4", ["--envs", "4096"])):
+    # c4 with --full: the run with the observation gather switched is measured beside `value`
+    for workload, extra in (("c3", ["--envs", "8192"]), ("c4", ["--envs", "4096", "--full"])):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20",
                             "--warmup", "5", "--workload", workload, "--no-cpu-baseline", "--no-pmc"] + extra,
                            capture_output=True, text=True, timeout=600, env=env)

@@ -13,7 +13,7 @@ shift || true
 OUT=gpurun_out/prof
 rm -rf "$OUT" && mkdir -p "$OUT"
 export TMPDIR=/tmp
-python3 bench.py --workload $WL "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full --workload $WL "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "[collect] bench done"
 SIZES="0"
 if [ "$WL" = "c3" ]; then SIZES="0 262144"; fi
