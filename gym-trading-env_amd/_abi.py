@@ -33,6 +33,19 @@ AUTORESET_DISABLED = 0
 AUTORESET_NEXT_STEP = 1
 AUTORESET_SAME_STEP = 2
 
+# gte_config.kernel_variant bits (enum gte_kernel_variant): reference structures of the kernels
+KV_PER_WAVE_PHASE_A = 1
+KV_NO_LDS_STAGING = 2
+KV_RETIRED_OVERLAPPED = 4
+KV_SHARED_TU = 64
+KV_ROLLOUT_PER_STEP = 128
+KV_ROLLOUT_GATHER = 256
+KV_LOG_SEPARATE = 1024
+KV_LOG_FUSED = 2048
+KV_GENERIC_COPY = 4096
+KV_RECORD_DIRECT = 8192
+KV_DENSE_FLAGS = 16384
+
 
 class GteError(RuntimeError):
     """A libgte call failed (status code + the library's message)."""

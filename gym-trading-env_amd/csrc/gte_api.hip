@@ -18,72 +18,7 @@
 #include <utility>
 #include <vector>
 
-#include "gte_device.h"
-
-namespace gte {
-hipError_t launch_step(const Params& p, int vec, int nt, bool coop, int stage, int blocks,
-                       int threads, hipStream_t stream);
-hipError_t launch_reset(const Params& p, int vec, int nt, bool coop, int stage, int blocks,
-                        int threads, hipStream_t stream);
-size_t lds_bytes(const Params& p, int stage);
-hipError_t launch_step_hot(const Params& p, int blocks, int threads, size_t smem, hipStream_t stream);
-hipError_t launch_step_hot_nt(const Params& p, int blocks, int threads, size_t smem, hipStream_t stream);
-int hot_blocks_per_cu(size_t smem);
-int hot_blocks_per_cu_nt(size_t smem);
-struct RolloutArgs {  // mirrors gte_rollout.hip
-  const int32_t* actions; int32_t K; float* obs; float* reward; double* reward64;
-  uint8_t* terminated; uint8_t* truncated; double* valuation; int32_t epb;
-  int32_t n_groups; int32_t* group_counter;
-};
-size_t resident_lds_bytes(const Params& p, int epb);
-int resident_blocks_per_cu(const Params& p, int epb, int nt);
-hipError_t launch_rollout_resident(const Params& p, const RolloutArgs& r, int nt, int blocks,
-                                   hipStream_t stream);
-hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_steps, int epw,
-                                hipStream_t stream);
-hipError_t launch_set_dynamic_columns(const Params& p, const void* const* cols, const int32_t* is_f64,
-                                      hipStream_t stream);
-hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* rows, const int64_t* last,
-                               int terminal_view, hipStream_t stream);
-hipError_t launch_set_log_reward(LogRow* rows, const int64_t* last, int L, int n, const double* reward,
-                                 hipStream_t stream);
-hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, int threads,
-                          hipStream_t stream);
-int rollout_blocks_per_cu(const Params& p, int nt);
-struct StateSoA {
-  int32_t *idx, *step, *pos, *dsi, *start, *episode, *needs_reset;
-  double *asset, *fiat, *ia, *ifi, *pv, *realpos;
-};
-hipError_t launch_extract_state(const EnvRec* rec, int n, const StateSoA& o, hipStream_t stream);
-hipError_t launch_rewind_queue(EnvRec* rec, int n, hipStream_t stream);
-hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                      const uint8_t* trunc, int n, const int64_t* cursor, int L, const LogArrays& o,
-                      const uint8_t* mask, hipStream_t stream);
-hipError_t launch_snapshot(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                           const uint8_t* trunc, const float* obs, int64_t obs_elems, int first,
-                           int count, void* dst, float* dst_obs, hipStream_t stream);
-struct LogPack {
-  int32_t* n_rows;
-  int32_t *idx, *step, *pos, *dsi;
-  double *pv, *realpos, *reward, *asset, *fiat, *ia, *ifi;
-  uint8_t* flags;
-};
-hipError_t launch_pack_log(const LogArrays& log, int N, int L, long long rows_written, const int32_t* ids,
-                           int n_ids, int max_rows, int finished, int frozen_runs, const EnvRec* final_rec,
-                           const double* reward64, const LogPack& o, hipStream_t stream);
-const char* rccl_load();
-const char* rccl_error(int code);
-int rccl_unique_id(uint8_t* out128);
-int rccl_comm_init(void** comm, const uint8_t* id128, int rank, int world);
-int rccl_allgather_bytes(void* comm, const void* src, void* dst, size_t bytes, hipStream_t stream);
-int rccl_comm_destroy(void* comm);
-hipError_t launch_set_dynamic(const Params& p, const float* values, uint32_t mask, hipStream_t stream);
-hipError_t launch_affinity_rebuild(const Params& p, int32_t* bins, int n_bins_per_ds,
-                                   const int32_t* slot_of_rank, int32_t* perm_out,
-                                   hipStream_t stream);
-hipError_t launch_add_orders(const Params& p, const int32_t* pos_index, const double* limit,
-                             const uint8_t* persistent, hipStream_t stream);
-}  // namespace gte
+#include "gte_launch.h"
 
 using gte::DatasetDesc;
 using gte::EnvRec;
@@ -442,11 +377,11 @@ static void step_geometry(gte_env* E, bool hot_ok, bool lean_ok) {
           if (lean_ok) {
             int lean_e = 0;
             for (int c = 1; c <= 64 / GTE_WAVES; ++c)
-              if (((int64_t)c * vpe) % 256 == 0 && (int64_t)c * p.W <= 512) { lean_e = c; break; }
+              if (((int64_t)c * vpe) % (64 * GTE_LEAN_U) == 0 && (int64_t)c * p.W <= gte::LEAN_MAX_ROWS) { lean_e = c; break; }
             if (lean_e) {
               int c = lean_e;
-              while (c * 2 <= 64 / GTE_WAVES && (int64_t)c * vpe < 1280 && (int64_t)c * 2 * p.W <= 512) c *= 2;
-              if ((int64_t)p.N >= 200000 && c * 2 <= 64 / GTE_WAVES && (int64_t)c * 2 * p.W <= 512) c *= 2;
+              while (c * 2 <= 64 / GTE_WAVES && (int64_t)c * vpe < 1280 && (int64_t)c * 2 * p.W <= gte::LEAN_MAX_ROWS) c *= 2;
+              if ((int64_t)p.N >= 200000 && c * 2 <= 64 / GTE_WAVES && (int64_t)c * 2 * p.W <= gte::LEAN_MAX_ROWS) c *= 2;
               epw = c;
             }
           }
@@ -505,7 +440,7 @@ static int setup_affinity(gte_env* E) {
 }
 
 // Every launch choice of the env (LaunchPlan).  The only reader of cfg.kernel_variant, whose bits select
-// reference structures for A/B timing and the tests' twins (include/gte.h; 16384 = flags always dense).
+// reference structures for A/B timing and the tests' twins (GTE_KV_*, include/gte.h).
 static int plan_launches(gte_env* E) {
   LaunchPlan& L = E->plan;
   Params& p = E->p;
@@ -517,29 +452,28 @@ static int plan_launches(gte_env* E) {
   // non-temporal ones win (81 920 envs, 210 MB: 48 us vs 58 us; 262 144 envs: 162 us vs 261 us)
   L.store = cfg.nontemporal_obs;
   if (L.store == 3) L.store = ((size_t)p.N * p.W * p.Fobs * sizeof(float) > ((size_t)190 << 20)) ? 1 : 2;
-  step_geometry(E, !(kv & (1 | 2)), !(kv & 4096));
+  step_geometry(E, !(kv & (GTE_KV_PER_WAVE_PHASE_A | GTE_KV_NO_LDS_STAGING)), !(kv & GTE_KV_GENERIC_COPY));
   p.debug = cfg.debug_flags;
-  L.coop = (p.epw * GTE_WAVES <= 64) && !(kv & 1);
-  L.stage = (p.nd > 0 && gte::lds_bytes(p, 1) <= 48 * 1024 && !(kv & 2)) ? (p.persist ? 2 : 1) : 0;
+  L.coop = (p.epw * GTE_WAVES <= 64) && !(kv & GTE_KV_PER_WAVE_PHASE_A);
+  L.stage = (p.nd > 0 && gte::lds_bytes(p, 1) <= 48 * 1024 && !(kv & GTE_KV_NO_LDS_STAGING)) ? (p.persist ? 2 : 1) : 0;
   // the lean copy loop (gte_kernels.hip): 16-byte vectors with the raw rings staged in LDS (stage 1;
   // dyn_persist takes stage 2)
-  p.lean_rows = (L.vec == 4 && L.stage == 1 && !(kv & 4096)) ? 1 : 0;
-  p.hot_lds = (kv & 8192) ? 0 : 1;  // (8192: A/B, the stepping lane stores its record itself)
+  p.lean_rows = (L.vec == 4 && L.stage == 1 && !(kv & GTE_KV_GENERIC_COPY)) ? 1 : 0;
+  p.hot_lds = (kv & GTE_KV_RECORD_DIRECT) ? 0 : 1;  // (A/B: the stepping lane stores its record itself)
   // the shape the isolated hot instantiations (gte_hot.hip) and the fused rollouts are written for
   const bool hot_shape = L.vec == 4 && L.coop && L.stage == 1;
-  L.hot_tu = hot_shape && !(kv & 64);  // (64: A/B, the shared-TU instantiation instead)
+  L.hot_tu = hot_shape && !(kv & GTE_KV_SHARED_TU);  // (A/B: the shared-TU instantiation instead)
   // With a trajectory log the step kernel writes the row itself (shared-TU instantiation): the lane
   // that stepped the env puts its 80-byte record into LDS and the copy waves write it out, five
   // lanes per env.  At the config-3 shape, us per step: 38.5 against 43.2 with the separate
   // gte_log_kernel launch (and 37.5 without a log; profiles/r03_log_ab.log).  (Rounds 1-2 kept the
   // log as twelve [L, N] columns: twelve scattered stores per env from the stepping lane, which
   // beyond 16 384 envs lost to the separate launch.)
-  // kernel_variant bit 1024 keeps the separate launch (A/B), 2048 = the default now.
-  L.fused_log = cfg.log_steps > 0 && !(kv & 1024);
-  L.always_dense = (kv & 16384) != 0;  // (A/B of the sparse flag stores)
-  // kernel_variant 128 = never fused (A/B and tests of the per-launch path)
-  L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & 128);
-  L.resident_rollout = p.W >= 2 && !(kv & 256);  // (256: the gather-per-step kernel instead)
+  // GTE_KV_LOG_SEPARATE keeps the separate launch (A/B); GTE_KV_LOG_FUSED is the default now.
+  L.fused_log = cfg.log_steps > 0 && !(kv & GTE_KV_LOG_SEPARATE);
+  L.always_dense = (kv & GTE_KV_DENSE_FLAGS) != 0;  // (A/B of the sparse flag stores)
+  L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & GTE_KV_ROLLOUT_PER_STEP);
+  L.resident_rollout = p.W >= 2 && !(kv & GTE_KV_ROLLOUT_GATHER);
   return setup_affinity(E);
 }
 
@@ -1034,8 +968,8 @@ static void choose_resident_epb(gte_env* E, const Params& p, int nt) {
   const char* force = getenv("GTE_RESIDENT_EPB");  // tuning: envs per group, no search
   for (int e = 64; e >= 1; --e) {
     if (force && atoi(force) != e) continue;
-    if ((int64_t)e * FV > 2 * 192) continue;  // RES_NEW * RES_OWNERS newest-row vectors
-    if (gte::resident_lds_bytes(p, e) > (size_t)160 * 1024) continue;
+    if ((int64_t)e * FV > gte::RES_NEW * gte::RES_OWNERS) continue;  // newest-row vectors the owner threads carry
+    if (gte::resident_lds_bytes(p, e) > gte::RES_LDS_MAX) continue;
     const int per_cu = gte::resident_blocks_per_cu(p, e, nt);
     if (per_cu <= 0) continue;
     const int64_t slots = (int64_t)per_cu * prop.multiProcessorCount;
@@ -1078,7 +1012,7 @@ static void choose_rollout_epw(gte_env* E, const Params& p, int nt) {
     q.epw = e;
     if ((int64_t)e * p.W * p.Fobs / 4 < 64) continue;
     const int per_cu = gte::rollout_blocks_per_cu(q, nt);
-    const int64_t wgs = ((int64_t)p.N + 4 * e - 1) / (4 * e);
+    const int64_t wgs = ((int64_t)p.N + gte::ROLLOUT_WAVES * e - 1) / (gte::ROLLOUT_WAVES * e);
     if (per_cu > 0 && wgs <= (int64_t)per_cu * prop.multiProcessorCount) { L.rollout_epw = e; break; }
     if (e == 16) L.rollout_epw = 16;  // more envs than one round holds: biggest workgroups
   }
@@ -1169,10 +1103,10 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
     } else {
       if (L.rollout_epw == 0) choose_rollout_epw(E, p, nt);
       p.epw = L.rollout_epw;
-      const int r_blocks = (int)((((int64_t)p.N + p.epw - 1) / p.epw + 3) / 4);
+      const int r_blocks = (int)((((int64_t)p.N + p.epw - 1) / p.epw + gte::ROLLOUT_WAVES - 1) / gte::ROLLOUT_WAVES);
       gte::RolloutArgs r = {actions, n_steps, b->obs, b->reward, b->reward64, b->terminated,
                             b->truncated, b->valuation, 0, 0, nullptr};
-      const hipError_t le = gte::launch_rollout(p, r, nt, r_blocks, L.threads, E->stream);
+      const hipError_t le = gte::launch_rollout(p, r, nt, r_blocks, E->stream);
       if (le != hipSuccess) return fail(GTE_ERR_HIP, "rollout launch: %s", hipGetErrorString(le));
     }
   }

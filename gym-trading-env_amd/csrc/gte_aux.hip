@@ -1,7 +1,7 @@
 // gte_aux.hip — auxiliary kernels of libgte, deliberately in their OWN translation unit:
 // adding a kernel to gte_kernels.hip perturbs the register allocation of the step kernel
 // compiled next to it (measured: 78 -> 83 VGPRs, occupancy 6 -> 5 waves/SIMD, +4 us per step).
-#include "gte_device.h"
+#include "gte_launch.h"
 
 namespace gte {
 
@@ -161,13 +161,7 @@ hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* ro
 // which the env ended): the newest log row already describes the next episode's reset row; the
 // episode that just FINISHED is the rows before it plus the terminal row from the env's terminal
 // record, with that step's reward.
-struct LogPack {
-  int32_t* n_rows;                 // [n_ids]
-  int32_t *idx, *step, *pos, *dsi; // [n_ids, max_rows], rows 0 .. n_rows-1 valid, oldest first
-  double *pv, *realpos, *reward, *asset, *fiat, *ia, *ifi;
-  uint8_t* flags;
-};
-
+// The destination is a LogPack (gte_launch.h).
 __global__ __launch_bounds__(256) void gte_pack_log_kernel(const LogArrays log, int N, int L,
                                                            long long rows_written, const int32_t* ids,
                                                            int max_rows, int finished, int frozen_runs,

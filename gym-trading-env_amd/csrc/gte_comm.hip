@@ -28,7 +28,7 @@
 #include <cstring>
 #include <string>
 
-#include "gte_device.h"
+#include "gte_launch.h"
 
 namespace gte {
 

@@ -116,7 +116,7 @@ struct Params {
                          // (EnvRec.flags_out), so a step stores only the flags that change (gte_step decides)
   int32_t log_L;         // rows of the trajectory log (gte_config.log_steps; fills what was padding)
   // --- trajectory row written by THIS launch's phase A (a gte_step with log_steps > 0; the
-  // shared-TU step kernel only).  log.idx == null: none (the host appends it with gte_log_kernel)
+  // shared-TU step kernel only).  log.rows == null: none (the host appends it with gte_log_kernel)
   LogArrays log;
   int64_t* log_cursor;   // the slot of the log cursor this launch reads (log_cursor_other below)
   uint32_t* ds_used;     // u32 [N, ceil(D/32)]: datasets picked in the env's current round (D > 1 only)

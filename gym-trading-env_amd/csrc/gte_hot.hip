@@ -21,16 +21,15 @@ hipError_t GTE_HOT_NAME(launch_step_hot)(const Params& p, int blocks, int thread
                                          hipStream_t stream) {
   if (!hot_tu_covers(p)) return hipErrorInvalidValue;  // features compiled out of this TU (gte_device.h)
   const uint32_t V = (uint32_t)(p.W * p.Fobs);
-  auto magic = [](uint32_t d) { return ((1ull << 40) + d - 1) / d; };
-  const uint64_t vm = magic(V / 4), fm = magic((uint32_t)p.Fobs / 4),
-                 wm = magic((uint32_t)(p.W * (p.nd ? p.nd : 1)));
+  const uint64_t vm = magic40(V / 4), fm = magic40((uint32_t)p.Fobs / 4),
+                 wm = magic40((uint32_t)(p.W * (p.nd ? p.nd : 1)));
   hipLaunchKernelGGL((gte_kernel<MODE_STEP, 4, GTE_HOT_NT, true, STAGE_RAW>), dim3(blocks),
                      dim3(threads), smem, stream, p, vm, fm, wm);
   return hipGetLastError();
 }
 
 // Workgroups of this kernel one CU holds at once (registers, LDS): the launch geometry sizes
-// the workgroups so that all of them are resident together (gte_api.hip, choose_epw).
+// the workgroups so that all of them are resident together (gte_api.hip, step_geometry).
 int GTE_HOT_NAME(hot_blocks_per_cu)(size_t smem) {
   int n = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(

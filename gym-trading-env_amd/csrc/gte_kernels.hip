@@ -30,7 +30,7 @@
 //
 // The path is HBM-bound (no contraction, so no MFMA): >= 97 % of its bytes are the
 // window gather + observation store.  See DESIGN.md for roofline and measurements.
-#include "gte_device.h"
+#include "gte_launch.h"
 
 namespace gte {
 
@@ -769,8 +769,7 @@ __device__ inline void phase_b(const Params& p, const WgLds& L, int s_first,
 //     counters instead of dividing;
 //   * no per-vector validity branches (the caller checks the whole wave once).
 // Results are the generic loop's, bit for bit (the parity suite runs through it).
-constexpr int LEAN_MAX_ROWS = 512;  // window rows of one wave's envs the in-place resolve holds in registers
-
+// (LEAN_MAX_ROWS and GTE_LEAN_U, the vectors in flight per lane, are in gte_launch.h: the host's geometry search uses them)
 template <int ND>
 __device__ inline void resolve_dynamic_rows(const Params& p, const WgLds& L, int s_first, int n_env,
                                             int lane, uint64_t wnd_magic) {
@@ -812,9 +811,6 @@ __device__ inline void resolve_dynamic_rows(const Params& p, const WgLds& L, int
   }
 }
 
-#ifndef GTE_LEAN_U
-#define GTE_LEAN_U 4  // vectors in flight per lane in the lean copy loop
-#endif
 template <int NT, int ND>
 __device__ inline void phase_b_lean(const Params& p, const WgLds& L, int s_first, int n_env, int lane) {
   constexpr int U = GTE_LEAN_U;
@@ -1157,12 +1153,7 @@ hipError_t launch_affinity_rebuild(const Params& p, int32_t* bins, int n_bins_pe
 }
 
 // ---------------------------------------------------------------------------
-// struct-of-arrays views of the state for the host (gte_get_state)
-struct StateSoA {
-  int32_t *idx, *step, *pos, *dsi, *start, *episode, *needs_reset;
-  double *asset, *fiat, *ia, *ifi, *pv, *realpos;
-};
-
+// struct-of-arrays views of the state for the host (gte_get_state): StateSoA, gte_launch.h
 __global__ void gte_extract_state_kernel(const EnvRec* rec, int n, StateSoA o) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
@@ -1190,8 +1181,6 @@ hipError_t launch_rewind_queue(EnvRec* rec, int n, hipStream_t stream) {
 
 // ---------------------------------------------------------------------------
 // launchers (called from gte_api.hip)
-
-static uint64_t magic40(uint32_t d) { return ((1ull << 40) + d - 1) / d; }
 
 size_t lds_bytes(const Params& p, int stage) {
   const size_t EPB = (size_t)p.epw * GTE_WAVES;

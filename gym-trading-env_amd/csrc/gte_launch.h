@@ -1,0 +1,104 @@
+// gte_launch.h — the interface BETWEEN the translation units of libgte, stated once: the structs that
+// cross a file boundary by value into kernel arguments, the limits the host's geometry search shares
+// with the kernels, and the prototype of every host function one .hip file defines and another calls.
+// gte_api.hip and every defining file include it, so a definition cannot disagree with what its
+// callers see (tests/test_host_cpu.py: no second struct body, no prototype elsewhere, every
+// definition declared here with the same signature).  Device-side code stays in gte_device.h.
+#pragma once
+#include "gte_device.h"
+
+namespace gte {
+
+// lean copy loop (gte_kernels.hip): window rows of one wave's envs the in-place resolve holds in registers,
+// and the vectors in flight per lane (a wave copies whole passes of 64 * GTE_LEAN_U)
+constexpr int LEAN_MAX_ROWS = 512;
+#ifndef GTE_LEAN_U
+#define GTE_LEAN_U 4
+#endif
+// rollout kernels (gte_rollout.hip): workgroups of four wavefronts, whatever GTE_WAVES is
+constexpr int ROLLOUT_WAVES = 4;
+// window-resident kernel: waves 1..3 (RES_OWNERS threads) carry the newest window rows of the workgroup's envs,
+// at most RES_NEW vectors each; a geometry with more of them than RES_NEW * RES_OWNERS would drop some
+constexpr int RES_NEW = 2;
+constexpr int RES_OWNERS = 192;
+constexpr size_t RES_LDS_MAX = 160 * 1024;  // LDS of a gfx950 CU: the most a workgroup's image may take
+constexpr size_t LDS_OPT_IN = 64 * 1024;    // dynamic LDS beyond this is opted into, per instantiation
+
+// 40-bit magic of the kernels' divisions by a launch constant (fastdiv40, gte_kernels.hip)
+inline uint64_t magic40(uint32_t d) { return ((1ull << 40) + d - 1) / d; }
+
+// --- gte_kernels.hip (shared translation unit): every step / reset shape, helper kernels
+hipError_t launch_step(const Params& p, int vec, int nt, bool coop, int stage, int blocks, int threads,
+                       hipStream_t stream);
+hipError_t launch_reset(const Params& p, int vec, int nt, bool coop, int stage, int blocks, int threads,
+                        hipStream_t stream);
+size_t lds_bytes(const Params& p, int stage);
+hipError_t launch_add_orders(const Params& p, const int32_t* pos_index, const double* limit,
+                             const uint8_t* persistent, hipStream_t stream);
+hipError_t launch_affinity_rebuild(const Params& p, int32_t* bins, int n_bins_per_ds, const int32_t* slot_of_rank,
+                                   int32_t* perm_out, hipStream_t stream);
+struct StateSoA {  // struct-of-arrays views of the state for the host (gte_get_state)
+  int32_t *idx, *step, *pos, *dsi, *start, *episode, *needs_reset;
+  double *asset, *fiat, *ia, *ifi, *pv, *realpos;
+};
+hipError_t launch_extract_state(const EnvRec* rec, int n, const StateSoA& o, hipStream_t stream);
+hipError_t launch_rewind_queue(EnvRec* rec, int n, hipStream_t stream);
+
+// --- gte_hot.hip / gte_hot_nt.hip: the headline instantiation alone, sc1 / non-temporal stores
+hipError_t launch_step_hot(const Params& p, int blocks, int threads, size_t smem, hipStream_t stream);
+hipError_t launch_step_hot_nt(const Params& p, int blocks, int threads, size_t smem, hipStream_t stream);
+int hot_blocks_per_cu(size_t smem);
+int hot_blocks_per_cu_nt(size_t smem);
+
+// --- gte_rollout.hip: K steps in one launch
+struct RolloutArgs {
+  const int32_t* actions;  // [K][N]
+  int32_t K;
+  float* obs;              // [K][N][W][Fobs] or nullptr (last step only, into p.obs)
+  float* reward;           // [K][N] or nullptr (p.reward, overwritten every step)
+  double* reward64;
+  uint8_t *terminated, *truncated;
+  double* valuation;       // [K][N] or nullptr
+  int32_t epb;             // resident kernel: envs per workgroup
+  int32_t n_groups;        // resident kernel: ceil(N / epb) groups of envs, handed out through ...
+  int32_t* group_counter;  // ... this device counter (zeroed before the launch)
+};
+size_t resident_lds_bytes(const Params& p, int epb);
+int resident_blocks_per_cu(const Params& p, int epb, int nt);
+hipError_t launch_rollout_resident(const Params& p, const RolloutArgs& r, int nt, int blocks, hipStream_t stream);
+hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_steps, int epw, hipStream_t stream);
+int rollout_blocks_per_cu(const Params& p, int nt);
+hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, hipStream_t stream);
+
+// --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
+hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
+                      const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);
+hipError_t launch_set_log_reward(LogRow* rows, const int64_t* last, int L, int n, const double* reward,
+                                 hipStream_t stream);
+hipError_t launch_set_dynamic(const Params& p, const float* values, uint32_t mask, hipStream_t stream);
+hipError_t launch_set_dynamic_columns(const Params& p, const void* const* cols, const int32_t* is_f64,
+                                      hipStream_t stream);
+hipError_t launch_apply_reward(const Params& p, const double* reward, LogRow* rows, const int64_t* last,
+                               int terminal_view, hipStream_t stream);
+struct LogPack {  // where gte_pack_log_kernel puts the logged episode of each listed env
+  int32_t* n_rows;                 // [n_ids]
+  int32_t *idx, *step, *pos, *dsi; // [n_ids, max_rows], rows 0 .. n_rows-1 valid, oldest first
+  double *pv, *realpos, *reward, *asset, *fiat, *ia, *ifi;
+  uint8_t* flags;
+};
+hipError_t launch_pack_log(const LogArrays& log, int N, int L, long long rows_written, const int32_t* ids,
+                           int n_ids, int max_rows, int finished, int frozen_runs, const EnvRec* final_rec,
+                           const double* reward64, const LogPack& o, hipStream_t stream);
+hipError_t launch_snapshot(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc,
+                           const float* obs, int64_t obs_elems, int first, int count, void* dst, float* dst_obs,
+                           hipStream_t stream);
+
+// --- gte_comm.hip: RCCL, bound at run time
+const char* rccl_load();
+const char* rccl_error(int code);
+int rccl_unique_id(uint8_t* out128);
+int rccl_comm_init(void** comm, const uint8_t* id128, int rank, int world);
+int rccl_allgather_bytes(void* comm, const void* src, void* dst, size_t bytes, hipStream_t stream);
+int rccl_comm_destroy(void* comm);
+
+}  // namespace gte

@@ -28,22 +28,18 @@
 // back to K launches of the step kernel otherwise.
 #define GTE_HOT_ONLY 1
 #include "gte_kernels.hip"
+#include <type_traits>
 
 namespace gte {
 
-struct RolloutArgs {
-  const int32_t* actions;  // [K][N]
-  int32_t K;
-  float* obs;              // [K][N][W][Fobs] or nullptr (last step only, into p.obs)
-  float* reward;           // [K][N] or nullptr (p.reward, overwritten every step)
-  double* reward64;
-  uint8_t* terminated;
-  uint8_t* truncated;
-  double* valuation;       // [K][N] or nullptr
-  int32_t epb;             // resident kernel: envs per workgroup
-  int32_t n_groups;        // resident kernel: ceil(N / epb) groups of envs, handed out through ...
-  int32_t* group_counter;  // ... this device counter (zeroed before the launch)
-};
+// The observation store policy (store_out<NT>) as a compile-time constant for this file's launch,
+// attribute and occupancy call sites: f(std::integral_constant<int, nt>).
+template <class F>
+static hipError_t with_store_policy(int nt, F f) {
+  if (nt == 2) return f(std::integral_constant<int, 2>());
+  if (nt == 1) return f(std::integral_constant<int, 1>());
+  return f(std::integral_constant<int, 0>());
+}
 
 // LDS: two sets of job records (wave 0 runs phase A one step ahead of the gather), two chunk
 // counters, one copy of the rings.
@@ -78,8 +74,8 @@ __device__ inline RollLds carve_roll(unsigned char* b, int EPB) {
   return R;
 }
 
-size_t rollout_lds_bytes(const Params& p) {
-  const size_t EPB = (size_t)p.epw * 4;
+static size_t rollout_lds_bytes(const Params& p) {
+  const size_t EPB = (size_t)p.epw * ROLLOUT_WAVES;
   return 2 * EPB * (16 + 4 * GTE_MAX_DYN + 4) + 16 + EPB * (size_t)p.W * (size_t)(p.nd ? p.nd : 1) * 4;
 }
 
@@ -216,11 +212,6 @@ size_t resident_lds_bytes(const Params& p, int epb) {
   return (size_t)epb * (16 + 4 * GTE_MAX_DYN + sizeof(ResAux)) + 16 +
          (size_t)epb * (size_t)(p.W - 1) * (size_t)p.Fobs * 4;
 }
-
-// threads that carry the newest window row of the workgroup's envs from the table to the
-// observation and then into the LDS ring: waves 1..3, at most RES_NEW vectors each
-#define RES_NEW 2
-#define RES_OWNERS 192
 
 // One group of r.epb envs through all K steps (a workgroup takes group after group, below).
 template <int NT>
@@ -497,11 +488,10 @@ __global__ __launch_bounds__(256) void gte_rollout_state_kernel(const Params p0,
   for (int k = 0; k < n_steps; ++k) run_a(k);
 }
 
-hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_steps, int epw,
-                                hipStream_t stream) {
+hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_steps, int epw, hipStream_t stream) {
   if (!hot_tu_covers(p)) return hipErrorInvalidValue;  // this TU is compiled with GTE_HOT_ONLY (gte_device.h)
-  const int waves = (p.N + epw - 1) / epw;
-  hipLaunchKernelGGL(gte_rollout_state_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, p, r, n_steps, epw);
+  const int blocks = ((p.N + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES;  // epw envs per wavefront
+  hipLaunchKernelGGL(gte_rollout_state_kernel, dim3(blocks), dim3(64 * ROLLOUT_WAVES), 0, stream, p, r, n_steps, epw);
   return hipGetLastError();
 }
 
@@ -526,25 +516,25 @@ __global__ __launch_bounds__(256, 4) void gte_rollout_resident_kernel(const Para
   }
 }
 
+// Dynamic LDS beyond the default limit has to be opted into, per instantiation (up to RES_LDS_MAX).
+static hipError_t lds_opt_in(const void* kernel, size_t smem) {
+  return smem <= LDS_OPT_IN ? hipSuccess
+                            : hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+}
+
 int resident_blocks_per_cu(const Params& p, int epb, int nt) {
   int n = 0;
   const size_t smem = resident_lds_bytes(p, epb);
-  hipError_t e = hipSuccess;
-  if (smem > 64 * 1024) {  // beyond the default dynamic-LDS limit: opt in (160 KiB per CU on gfx950)
-    if (nt == 2) e = hipFuncSetAttribute((const void*)gte_rollout_resident_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    else if (nt == 1) e = hipFuncSetAttribute((const void*)gte_rollout_resident_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    else e = hipFuncSetAttribute((const void*)gte_rollout_resident_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
-  }
-  if (nt == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gte_rollout_resident_kernel<2>, 256, smem);
-  else if (nt == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gte_rollout_resident_kernel<1>, 256, smem);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gte_rollout_resident_kernel<0>, 256, smem);
+  const hipError_t e = with_store_policy(nt, [&](auto c) {
+    const auto kernel = gte_rollout_resident_kernel<decltype(c)::value>;
+    const hipError_t a = lds_opt_in((const void*)kernel, smem);
+    return a != hipSuccess ? a : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 64 * ROLLOUT_WAVES, smem);
+  });
   if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
   return n;
 }
 
-hipError_t launch_rollout_resident(const Params& p, const RolloutArgs& r, int nt, int blocks,
-                                   hipStream_t stream) {
+hipError_t launch_rollout_resident(const Params& p, const RolloutArgs& r, int nt, int blocks, hipStream_t stream) {
   if (!hot_tu_covers(p)) return hipErrorInvalidValue;  // this TU is compiled with GTE_HOT_ONLY (gte_device.h)
   // identity processing order: the windows live in LDS for the whole launch, so the L2-affinity
   // order has one table row per env-step left to serve, while it scatters every step's return
@@ -552,51 +542,39 @@ hipError_t launch_rollout_resident(const Params& p, const RolloutArgs& r, int nt
   Params q = p;
   q.perm = nullptr;
   const size_t smem = resident_lds_bytes(p, r.epb);
-  auto magic = [](uint32_t d) { return ((1ull << 40) + d - 1) / d; };
   const uint32_t FV = (uint32_t)p.Fobs / 4u;
-  const uint64_t vlm = magic((uint32_t)(p.W - 1) * FV), fm = magic(FV);
-  if (smem > 64 * 1024) {  // the geometry search probed other sizes after this one: opt in again
-    hipError_t e;
-    if (nt == 2) e = hipFuncSetAttribute((const void*)gte_rollout_resident_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    else if (nt == 1) e = hipFuncSetAttribute((const void*)gte_rollout_resident_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    else e = hipFuncSetAttribute((const void*)gte_rollout_resident_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  if (nt == 2)
-    hipLaunchKernelGGL((gte_rollout_resident_kernel<2>), dim3(blocks), dim3(256), smem, stream, q, r, vlm, fm);
-  else if (nt == 1)
-    hipLaunchKernelGGL((gte_rollout_resident_kernel<1>), dim3(blocks), dim3(256), smem, stream, q, r, vlm, fm);
-  else
-    hipLaunchKernelGGL((gte_rollout_resident_kernel<0>), dim3(blocks), dim3(256), smem, stream, q, r, vlm, fm);
-  return hipGetLastError();
+  const uint64_t vlm = magic40((uint32_t)(p.W - 1) * FV), fm = magic40(FV);
+  return with_store_policy(nt, [&](auto c) {
+    const auto kernel = gte_rollout_resident_kernel<decltype(c)::value>;
+    // (the geometry search probed other sizes after this one: opt in again)
+    if (const hipError_t e = lds_opt_in((const void*)kernel, smem); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * ROLLOUT_WAVES), smem, stream, q, r, vlm, fm);
+    return hipGetLastError();
+  });
 }
 
 // Workgroups of the rollout kernel one CU holds at once with p.epw envs per wavefront.
 int rollout_blocks_per_cu(const Params& p, int nt) {
   int n = 0;
   const size_t smem = rollout_lds_bytes(p);
-  hipError_t e;
-  if (nt == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gte_rollout_kernel<2>, 256, smem);
-  else if (nt == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gte_rollout_kernel<1>, 256, smem);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gte_rollout_kernel<0>, 256, smem);
+  const hipError_t e = with_store_policy(nt, [&](auto c) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gte_rollout_kernel<decltype(c)::value>,
+                                                        64 * ROLLOUT_WAVES, smem);
+  });
   return e == hipSuccess ? n : 0;
 }
 
-hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, int threads,
-                          hipStream_t stream) {
+hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, hipStream_t stream) {
   if (!hot_tu_covers(p)) return hipErrorInvalidValue;  // this TU is compiled with GTE_HOT_ONLY (gte_device.h)
   const size_t smem = rollout_lds_bytes(p);
   const uint32_t V = (uint32_t)(p.W * p.Fobs);
-  auto magic = [](uint32_t d) { return ((1ull << 40) + d - 1) / d; };
-  const uint64_t vm = magic(V / 4), fm = magic((uint32_t)p.Fobs / 4),
-                 wm = magic((uint32_t)(p.W * (p.nd ? p.nd : 1)));
-  if (nt == 2)
-    hipLaunchKernelGGL((gte_rollout_kernel<2>), dim3(blocks), dim3(threads), smem, stream, p, r, vm, fm, wm);
-  else if (nt == 1)
-    hipLaunchKernelGGL((gte_rollout_kernel<1>), dim3(blocks), dim3(threads), smem, stream, p, r, vm, fm, wm);
-  else
-    hipLaunchKernelGGL((gte_rollout_kernel<0>), dim3(blocks), dim3(threads), smem, stream, p, r, vm, fm, wm);
-  return hipGetLastError();
+  const uint64_t vm = magic40(V / 4), fm = magic40((uint32_t)p.Fobs / 4),
+                 wm = magic40((uint32_t)(p.W * (p.nd ? p.nd : 1)));
+  return with_store_policy(nt, [&](auto c) {
+    hipLaunchKernelGGL((gte_rollout_kernel<decltype(c)::value>), dim3(blocks), dim3(64 * ROLLOUT_WAVES), smem,
+                       stream, p, r, vm, fm, wm);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace gte

@@ -74,6 +74,32 @@ typedef enum gte_autoreset {
                                   and reward are the terminal step's           */
 } gte_autoreset;
 
+/* gte_config.kernel_variant: bits that select a reference structure of the kernels, for A/B
+ * timing and for the tests' twins.  Results never depend on them; 0 is the product. */
+typedef enum gte_kernel_variant {
+  GTE_KV_PER_WAVE_PHASE_A = 1,   /* every wave runs phase A for its own envs (default: wave 0
+                                    runs it for the whole workgroup, cooperative phase A)    */
+  GTE_KV_NO_LDS_STAGING = 2,     /* no LDS staging of the dynamic columns                    */
+  GTE_KV_RETIRED_OVERLAPPED = 4, /* accepted, ignored: was the overlapped step kernel
+                                    (measured slower, removed)                               */
+  GTE_KV_SHARED_TU = 64,         /* launch the shared-TU instantiation of the hot kernel
+                                    instead of the isolated one (gte_hot.hip)                */
+  GTE_KV_ROLLOUT_PER_STEP = 128, /* gte_rollout runs as one launch per step even where the
+                                    fused kernels apply                                      */
+  GTE_KV_ROLLOUT_GATHER = 256,   /* gte_rollout uses the gather-per-step fused kernel instead
+                                    of the window-resident one                               */
+  GTE_KV_LOG_SEPARATE = 1024,    /* gte_step appends the trajectory row with a separate small
+                                    launch (default: the step kernel writes it, through LDS)  */
+  GTE_KV_LOG_FUSED = 2048,       /* accepted, means that default                             */
+  GTE_KV_GENERIC_COPY = 4096,    /* always the generic copy loop (not the lean one that full
+                                    waves of 16-byte-vector windows take)                    */
+  GTE_KV_RECORD_DIRECT = 8192,   /* the lane that stepped an env stores its record itself
+                                    (default: the record's per-step half goes through LDS and
+                                    the copy waves write it, one 64-byte request per env)    */
+  GTE_KV_DENSE_FLAGS = 16384     /* every step stores every env's terminated / truncated
+                                    (default: only the flags that change)                    */
+} gte_kernel_variant;
+
 /* Constructor arguments of TradingEnv (environments.py:79-93) for a batch. */
 typedef struct gte_config {
   int32_t abi_version;      /* = GTE_ABI_VERSION                               */
@@ -114,25 +140,8 @@ typedef struct gte_config {
                                store_out in csrc/gte_kernels.hip), 3 = automatic:
                                sc1 while the observation buffer fits the Infinity
                                Cache (<= 190 MB), non-temporal beyond             */
-  int32_t kernel_variant;   /* 0 = auto.  Bits for A/B timing of the kernel structure:
-                               1 = every wave runs phase A for its own envs (no
-                               cooperative phase A), 2 = no LDS staging of the
-                               dynamic columns, 4 = retired (was the overlapped step
-                               kernel, measured slower, removed in round 2; ignored),
-                               64 = launch the shared-TU instantiation of the hot
-                               kernel instead of the isolated one (gte_hot.hip),
-                               128 = gte_rollout runs as one launch per step even
-                               where the fused kernels apply, 256 = gte_rollout uses
-                               the gather-per-step fused kernel instead of the
-                               window-resident one, 1024 = gte_step always appends
-                               the trajectory row with a separate small launch
-                               (default: the step kernel writes it, through LDS; 2048
-                               is accepted and means the default), 4096 = always the
-                               generic copy loop (not the lean one that full waves of
-                               16-byte-vector windows take), 8192 = the lane that
-                               stepped an env stores its record itself (default: the
-                               record's per-step half goes through LDS and is
-                               written by the copy waves, one 64-byte request per env) */
+  int32_t kernel_variant;   /* 0 = auto, else GTE_KV_* bits (above): reference
+                               structures for A/B timing and the tests' twins */
   int32_t debug_flags;      /* timing ablations only (results become wrong):
                                1 = skip the observation gather, 2 = skip the
                                dynamic-column patch, 8 = skip the window loads

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from gym_trading_env_amd import _abi
+
 DEFAULT_DYN = ["last_position_taken", "real_position"]
 
 
@@ -87,7 +89,8 @@ def _steps_after_end(g, f):
 
 
 #: gte_rollout's paths by (kernel_variant, keep_obs) of the rollout() call
-ROLLOUT_MODES = {"resident": (0, True), "gather": (256, True), "state": (0, False), "per-step": (128, True)}
+ROLLOUT_MODES = {"resident": (0, True), "gather": (_abi.KV_ROLLOUT_GATHER, True), "state": (0, False),
+                 "per-step": (_abi.KV_ROLLOUT_PER_STEP, True)}
 
 
 def hot_shape(f):
@@ -101,11 +104,11 @@ def rollout_path(f, mode, n_steps=2):
     """The path gte_rollout takes for a trace in one of ROLLOUT_MODES: the window-resident kernel
     needs a window of 2 rows or more; a state-only call of one step is a plain step launch."""
     kv, keep = ROLLOUT_MODES[mode]
-    if not hot_shape(f) or kv & 128:
+    if not hot_shape(f) or kv & _abi.KV_ROLLOUT_PER_STEP:
         return "per-step"
     if not keep:
         return "state-only" if n_steps > 1 else "per-step"
-    return "resident" if (f["Wn"] >= 2 and not kv & 256) else "gather"
+    return "resident" if (f["Wn"] >= 2 and not kv & _abi.KV_ROLLOUT_GATHER) else "gather"
 
 
 def _fused(f, mode):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import draw_laws as L
+from gym_trading_env_amd import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -144,7 +145,7 @@ def test_step_autoreset_draws_equal_the_oracle(oracle_mod, autoreset):
     ora.close()
 
 
-ROLLOUTS = {"resident": (0, True), "gather": (256, True), "state-only": (0, False)}
+ROLLOUTS = {"resident": (0, True), "gather": (_abi.KV_ROLLOUT_GATHER, True), "state-only": (0, False)}
 
 
 @pytest.mark.parametrize("autoreset", ["next_step", "same_step"])

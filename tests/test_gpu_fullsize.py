@@ -4,6 +4,7 @@ longer run."""
 import numpy as np
 import pytest
 
+from gym_trading_env_amd import _abi
 from test_gpu_parity import _compare_with_oracle, _synthetic
 
 pytestmark = pytest.mark.gpu
@@ -88,7 +89,7 @@ def test_config4_total_size_on_one_gpu_vs_oracle(oracle_mod):
 def test_config3_full_size_rollout_paths_agree():
     """65 536 envs x obs (20, 32): a rollout that keeps every observation (168 MB per step,
     fused kernel, streaming stores), one that keeps only the last, one forced through separate
-    launches (kernel_variant 128) and plain single steps must agree bit for bit, episodes
+    launches (kernel_variant KV_ROLLOUT_PER_STEP) and plain single steps must agree bit for bit, episodes
     ending and restarting on the way."""
     import torch
     from gym_trading_env_amd.batched import BatchedTradingEnv
@@ -96,7 +97,7 @@ def test_config3_full_size_rollout_paths_agree():
     N, K = 65_536, 12
     kw = dict(num_envs=N, seed=21, max_episode_duration=7, **C3)
     envs = [BatchedTradingEnv(ds, **kw), BatchedTradingEnv(ds, **kw),
-            BatchedTradingEnv(ds, kernel_variant=128, **kw), BatchedTradingEnv(ds, **kw)]
+            BatchedTradingEnv(ds, kernel_variant=_abi.KV_ROLLOUT_PER_STEP, **kw), BatchedTradingEnv(ds, **kw)]
     for e in envs:
         e.reset()
     gen = torch.Generator(device="cuda")

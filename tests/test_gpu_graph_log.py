@@ -8,6 +8,7 @@ import pandas as pd
 import pytest
 
 import custom_callables as cc
+from gym_trading_env_amd import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -100,10 +101,10 @@ def _run(eager, graphed, K, rounds=4, warm=None):
     return g
 
 
-@pytest.mark.parametrize("kernel_variant,mode", [(0, "next_step"), (1024, "next_step"), (0, "same_step")])
+@pytest.mark.parametrize("kernel_variant,mode", [(0, "next_step"), (_abi.KV_LOG_SEPARATE, "next_step"), (0, "same_step")])
 def test_user_log_graph_equals_eager_steps(kernel_variant, mode):
     """log_steps = 5 with K = 6: a replay starts at a different row of the log every time (K is no
-    multiple of L), so the row index can only come from the device.  1024: the separate log launch."""
+    multiple of L), so the row index can only come from the device.  KV_LOG_SEPARATE: the separate log launch."""
     eager, graphed = _twins(log_steps=5, kernel_variant=kernel_variant, autoreset=mode)
     g = _run(eager, graphed, K=6)
     # the odd-eager-step guard still fires, and one more step makes the graph usable again

@@ -8,6 +8,7 @@ step path against the oracle.  Needs an MI355X."""
 import numpy as np
 import pytest
 
+from gym_trading_env_amd import _abi
 from log_model import COLUMNS, LogModel
 
 pytestmark = pytest.mark.gpu
@@ -176,8 +177,8 @@ def test_next_step_log_equals_model(oracle_mod):
 
 
 def test_next_step_separate_log_launch_equals_model(oracle_mod):
-    """kernel_variant 1024: the row comes from the separate gte_log_kernel launch."""
-    _next_step_case(oracle_mod, 1024)
+    """kernel_variant KV_LOG_SEPARATE: the row comes from the separate gte_log_kernel launch."""
+    _next_step_case(oracle_mod, _abi.KV_LOG_SEPARATE)
 
 
 def test_same_step_log_equals_model(oracle_mod):
@@ -350,10 +351,11 @@ def test_captured_steps_on_a_logged_env_equal_model(oracle_mod):
 _SPECS = [("scaled_log_return", 3.7), ("clipped_log_return", 50.0, -0.02, 0.015)]
 # step: the isolated hot instantiation; variant64: the shared-TU one; variant1: per-wave phase A;
 # the three fused rollout kernels: window-resident (keep_obs), gather-per-step (keep_obs with
-# kernel_variant 256, which turns residency off) and state-only (no keep_obs); logged: the step
+# kernel_variant KV_ROLLOUT_GATHER, which turns residency off) and state-only (no keep_obs); logged: the step
 # kernel that writes the log row, whose reward column is checked too
 _PATHS = ["step", "variant64", "variant1", "rollout_resident", "rollout_gather", "rollout_state", "logged"]
-_KERNEL_VARIANT = {"variant64": 64, "variant1": 1, "rollout_gather": 256}
+_KERNEL_VARIANT = {"variant64": _abi.KV_SHARED_TU, "variant1": _abi.KV_PER_WAVE_PHASE_A,
+                   "rollout_gather": _abi.KV_ROLLOUT_GATHER}
 
 
 @pytest.mark.parametrize("path", _PATHS)

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import replay
+from gym_trading_env_amd import _abi
 from gym_trading_env_amd.config import make_config
 
 pytestmark = pytest.mark.gpu
@@ -304,8 +305,10 @@ def test_hip_vs_oracle_shape_sweep(oracle_mod, shape, autoreset):
                          max_episode_duration=max_dur, autoreset=autoreset)
 
 
-@pytest.mark.parametrize("variant,store", [(0, 1), (0, 2), (0, 0), (1, 2), (2, 2), (3, 1), (64, 2),
-                                           (64, 1), (8192, 2), (8192 + 1, 2), (4096, 2)])
+@pytest.mark.parametrize("variant,store", [
+    (0, 1), (0, 2), (0, 0), (_abi.KV_PER_WAVE_PHASE_A, 2), (_abi.KV_NO_LDS_STAGING, 2),
+    (_abi.KV_PER_WAVE_PHASE_A | _abi.KV_NO_LDS_STAGING, 1), (_abi.KV_SHARED_TU, 2), (_abi.KV_SHARED_TU, 1),
+    (_abi.KV_RECORD_DIRECT, 2), (_abi.KV_RECORD_DIRECT | _abi.KV_PER_WAVE_PHASE_A, 2), (_abi.KV_GENERIC_COPY, 2)])
 def test_hip_vs_oracle_kernel_variants(oracle_mod, variant, store):
     """Every selectable kernel structure (isolated / shared-TU hot kernel, per-wave phase A, no
     LDS staging, record stored by the stepping lane instead of through LDS, generic copy loop) and

@@ -6,6 +6,8 @@ dynamic-feature rings the fused kernel kept in LDS must have reached HBM unchang
 import numpy as np
 import pytest
 
+from gym_trading_env_amd import _abi
+
 pytestmark = pytest.mark.gpu
 
 STATE = ("idx", "step", "position_index", "dataset_index", "start_idx", "episode", "needs_reset",
@@ -90,7 +92,7 @@ CASES = {
     "streaming_kernel": dict(data=lambda: _data(1, 700, 30)[:2], N=1000,
                              kw=dict(positions=[-1, 0, 1], windows=20, trading_fees=1e-4,
                                      borrow_interest_rate=3e-6, max_episode_duration=40,
-                                     kernel_variant=256)),
+                                     kernel_variant=_abi.KV_ROLLOUT_GATHER)),
     # shapes the fused kernels do not cover: K launches of the step kernel, same results
     "persist_fallback": dict(data=lambda: _data(5, 200, 2)[:2], N=256,
                              kw=dict(positions=[-1, 0, 1], windows=6, trading_fees=1e-4,
@@ -99,7 +101,7 @@ CASES = {
                                    kw=dict(positions=[0, 1], windows=7, max_episode_duration=30)),
     "forced_fallback": dict(data=lambda: _data(7, 400, 6)[:2], N=400,
                             kw=dict(positions=[-1, 0, 1], windows=5, max_episode_duration=30,
-                                    kernel_variant=128)),
+                                    kernel_variant=_abi.KV_ROLLOUT_PER_STEP)),
 }
 
 

@@ -1,7 +1,7 @@
 """Sparse terminated / truncated stores (gte_kernels.hip store_flags, gte_api.hip "Flag ledger"): a
 step stores only the flags that change when the host has proved that the buffers hold what the env's
 previous step stored there.  Every case below runs an env next to an untouched twin that always
-stores densely (kernel_variant 16384) and compares all four return arrays and the terminal list
+stores densely (kernel_variant KV_DENSE_FLAGS) and compares all four return arrays and the terminal list
 after every call, through L2-affinity re-sorts and auto-resets, while the buffers rotate, are rebound,
 shared with another env, replayed from a graph or written by a rollout.  Needs an MI355X."""
 import ctypes as C
@@ -9,9 +9,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gym_trading_env_amd import _abi
+
 pytestmark = pytest.mark.gpu
 
-DENSE = 16384  # kernel_variant bit: never sparse
+DENSE = _abi.KV_DENSE_FLAGS  # kernel_variant bit: never sparse
 
 
 def _data(seed=3, T=900, Fs=30):
@@ -42,7 +44,6 @@ def _outputs(env):
 
 
 def _check(env, rc):
-    from gym_trading_env_amd import _abi
     _abi.check(env._lib, rc)
 
 

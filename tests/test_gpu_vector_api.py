@@ -9,6 +9,7 @@ import pandas as pd
 import pytest
 
 import replay
+from gym_trading_env_amd import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -509,7 +510,7 @@ def test_reset_rows_of_the_log_carry_reward_zero_in_same_step_mode(Fs):
     host = lambda x: x.numpy() if isinstance(x, DeviceArray) else np.asarray(x)
     feat, close = _walk(48, 300, Fs, sigma=2e-2)
     N = 500
-    for variant in (1024, 2048):  # separate log launch / row written by the step kernel
+    for variant in (_abi.KV_LOG_SEPARATE, _abi.KV_LOG_FUSED):  # separate log launch / row written by the step kernel
         env = BatchedTradingEnv((feat, close), N, positions=[-1, 0, 1], windows=4, trading_fees=1e-3,
                                 max_episode_duration=7, seed=3, autoreset="same_step", final_obs=True,
                                 log_steps=16, kernel_variant=variant)
@@ -645,7 +646,7 @@ def test_apply_reward_and_dynamic_columns_entry_points():
                                     ("next_step", 20_000), ("same_step", 20_000)])
 def test_trajectory_row_written_by_the_step_kernel_equals_the_separate_launch(mode, N):
     """With `log_steps` the step kernel's phase A writes the trajectory row itself; kernel_variant
-    bit 1024 keeps round 1's separate log launch.  Every column of every row must be identical,
+    KV_LOG_SEPARATE keeps round 1's separate log launch.  Every column of every row must be identical,
     resets and frozen envs included."""
     import torch
     from gym_trading_env_amd import _abi
@@ -657,8 +658,8 @@ def test_trajectory_row_written_by_the_step_kernel_equals_the_separate_launch(mo
     kw = dict(num_envs=N, seed=4, positions=[-1, 0, 0.5, 2], windows=3 if N < 1000 else 16, trading_fees=1e-3,
               borrow_interest_rate=1e-3, max_episode_duration=9, output="torch", log_steps=L,
               autoreset=mode, final_obs=(mode == "same_step"))
-    a = BatchedTradingEnv((feat, close), kernel_variant=2048, **kw)   # row written in the kernel
-    b = BatchedTradingEnv((feat, close), kernel_variant=1024, **kw)   # separate launch
+    a = BatchedTradingEnv((feat, close), kernel_variant=_abi.KV_LOG_FUSED, **kw)   # row written in the kernel
+    b = BatchedTradingEnv((feat, close), kernel_variant=_abi.KV_LOG_SEPARATE, **kw)   # separate launch
     a.reset(); b.reset()
     g = torch.Generator(device="cuda").manual_seed(2)
     for k in range(40 if N < 1000 else 14):

@@ -1,4 +1,5 @@
 """Host-side logic and the C-ABI surface, no GPU needed (no compute call is made)."""
+import ast
 import ctypes as C
 import os
 import re
@@ -250,6 +251,173 @@ def test_features_compiled_out_of_the_hot_translation_units_are_guarded():
         assert launchers
         for m in re.finditer(r"hipError_t (?:GTE_HOT_NAME\()?launch_[a-z_]+\)?\(const Params& p.*?\n\}", src, re.S):
             assert "if (!hot_tu_covers(p)) return hipErrorInvalidValue;" in m.group(0), m.group(0)[:80]
+
+
+def _csrc_sources():
+    """name -> text of every .hip / .h under csrc/, comments removed"""
+    csrc = os.path.join(ROOT, "gym-trading-env_amd", "csrc")
+    strip = lambda s: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", s, flags=re.S))
+    return {n: strip(open(os.path.join(csrc, n)).read()) for n in sorted(os.listdir(csrc))
+            if n.endswith((".hip", ".h"))}
+
+
+def _signatures(text):
+    """`ret name(params)` of every function declared or defined at column 0 inside `namespace gte`
+    that is not static / inline / a template / device code -> {name: (signature, is_definition)},
+    white space normalised.  GTE_HOT_NAME(x) stands for x and x_nt (gte_hot.hip is compiled twice).
+
+    Known limits — this reads the way csrc/ is written, it is no C++ parser: the return type and the
+    name stand on ONE line that starts at column 0; a `template <...>` head is on the line above;
+    an attribute or a macro in front of the return type is not understood.  A function written
+    otherwise is not seen at all, which test_cross_file_functions_are_declared_once_in_gte_launch_h
+    reports as "declares a function no file defines" (or misses, for a function that is not declared
+    either: then it cannot be called across files).  Parameter NAMES are compared as well as types:
+    stricter than the compiler, on purpose — the header is the one place a reader looks them up."""
+    out = {}
+    inside = text.split("namespace gte {", 1)[1] if "namespace gte {" in text else ""
+    skip = r"static\b|template\b|inline\b|__global__|__device__|struct\b|typedef\b|enum\b|constexpr\b|using\b|return\b"
+    for m in re.finditer(rf"^(?!{skip})([A-Za-z_][\w \*&:<>]*?[\s\*&])(GTE_HOT_NAME\(\w+\)|\w+)\(", inside, re.M):
+        if re.search(r"^template\b[^\n]*\n\Z", inside[:m.start()], re.M):
+            continue  # (the line above opens a template)
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"(": 1, ")": -1}.get(inside[i], 0)
+            i += 1
+        after = inside[i:].lstrip()[:1]
+        if after not in "{;":
+            continue
+        ret, name, params = " ".join(m.group(1).split()), m.group(2), " ".join(inside[m.end():i - 1].split())
+        names = [name]
+        if name.startswith("GTE_HOT_NAME("):
+            names = [name[13:-1], name[13:-1] + "_nt"]
+        for n in names:
+            assert n not in out, f"{n} appears twice"
+            out[n] = (f"{ret} {n}({params})", after == "{")
+    return out
+
+
+def test_every_struct_under_csrc_is_defined_in_exactly_one_file():
+    """A struct that crosses a translation-unit boundary by value (RolloutArgs, StateSoA, LogPack:
+    kernel arguments) has ONE body, in gte_launch.h: with a copy per file, a member added on one side
+    still links and the kernel reads garbage."""
+    seen = {}
+    for name, src in _csrc_sources().items():
+        for s in re.findall(r"^\s*struct\s+(?:alignas\(\d+\)\s+)?(\w+)\s*\{", src, re.M):
+            seen.setdefault(s, []).append(name)
+    assert {"RolloutArgs", "StateSoA", "LogPack", "Params", "EnvRec"} <= set(seen)
+    assert {s: f for s, f in seen.items() if len(f) != 1} == {}
+    for s in ("RolloutArgs", "StateSoA", "LogPack"):
+        assert seen[s] == ["gte_launch.h"]
+
+
+def test_gte_api_declares_no_gte_function_itself():
+    """The host file takes every prototype from gte_launch.h: it opens no `namespace gte` and has no
+    function declaration at file scope (the hand-copied block it had was checked against nothing)."""
+    api = _csrc_sources()["gte_api.hip"]
+    assert '#include "gte_launch.h"' in api and "namespace gte" not in api
+    protos = re.findall(r"^(?!static_assert)[A-Za-z_][^\n;{}]*\([^;{}]*\)\s*;", api, re.M)
+    assert protos == [], protos
+    assert _signatures(api) == {}
+
+
+def test_cross_file_functions_are_declared_once_in_gte_launch_h():
+    """Every non-static gte:: function a .hip file defines is declared in gte_launch.h with the same
+    signature — and the defining file includes that header (directly or through gte_kernels.hip), so
+    the compiler checks the return type as well."""
+    src = _csrc_sources()
+    declared = _signatures(src["gte_launch.h"])
+    assert len(declared) >= 30 and not any(is_def for _, is_def in declared.values())
+    defined = {}
+    for name in ("gte_kernels.hip", "gte_hot.hip", "gte_aux.hip", "gte_rollout.hip", "gte_comm.hip"):
+        text = src[name]
+        assert '#include "gte_launch.h"' in text or '#include "gte_kernels.hip"' in text, name
+        for fn, (sig, is_def) in _signatures(text).items():
+            assert is_def, f"{name} declares {fn} itself"
+            assert fn not in defined, f"{fn} is defined in {name} and in {defined[fn]}"
+            defined[fn] = name
+            assert fn in declared, f"{name}: {fn} is not declared in gte_launch.h"
+            assert declared[fn][0] == sig, f"{name}: {sig}  !=  {declared[fn][0]}"
+    assert "launch_step_hot_nt" in defined and "rccl_load" in defined and "launch_pack_log" in defined
+    assert sorted(declared) == sorted(defined), "gte_launch.h declares a function no file defines"
+    assert "gte_launch.h" in open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
+
+
+_HOLDS_VARIANT = re.compile(r"(?i:variant)|^kv$|^DENSE$|^ROLLOUT")  # names of things that hold kernel_variant bits
+
+
+def _bare_variant_literals(text):
+    """(line, value) of every non-zero integer literal of a Python source that stands where a
+    kernel_variant is expected.  Such places are recognised by NAME: the value assigned to, or looped
+    over by, a name that matches _HOLDS_VARIANT (containers searched throughout: `ROLLOUT_MODES =
+    {"gather": (256, True)}`); a keyword argument or a dict entry of such a name; a positional
+    argument of a function of the same file whose parameter has such a name; the column of such a
+    name in a `parametrize` list; either side of `&` / `|` with such a name or a `KV_*` constant."""
+    tree = ast.parse(text)
+    ident = lambda n: n.id if isinstance(n, ast.Name) else n.attr if isinstance(n, ast.Attribute) else None
+    named = lambda s: isinstance(s, str) and bool(_HOLDS_VARIANT.search(s))
+    params = {f.name: [a.arg for a in f.args.args if a.arg not in ("self", "cls")]
+              for f in ast.walk(tree) if isinstance(f, ast.FunctionDef)}
+    holds = []
+    for n in ast.walk(tree):
+        if isinstance(n, (ast.Assign, ast.AnnAssign)):
+            if any(named(ident(t)) for t in (n.targets if isinstance(n, ast.Assign) else [n.target])):
+                holds.append(n.value)
+        elif isinstance(n, (ast.For, ast.comprehension)) and named(ident(n.target)):
+            holds.append(n.iter)
+        elif isinstance(n, ast.Dict):
+            holds += [v for k, v in zip(n.keys, n.values) if isinstance(k, ast.Constant) and named(k.value)]
+        elif isinstance(n, ast.BinOp) and isinstance(n.op, (ast.BitAnd, ast.BitOr)):
+            if any(named(ident(s)) or str(ident(s)).startswith("KV_") for s in (n.left, n.right)):
+                holds += [n.left, n.right]
+        elif isinstance(n, ast.Call):
+            holds += [k.value for k in n.keywords if named(k.arg)]
+            holds += [a for a, p in zip(n.args, params.get(ident(n.func), [])) if named(p)]
+            if ident(n.func) == "parametrize" and isinstance(n.args[0], ast.Constant) \
+                    and isinstance(n.args[1], (ast.List, ast.Tuple)):
+                names = [s.strip() for s in n.args[0].value.split(",")]
+                for case in n.args[1].elts:
+                    row = case.args if isinstance(case, ast.Call) else case.elts if len(names) > 1 else [case]
+                    holds += [v for v, s in zip(row, names) if named(s)]
+    return sorted({(c.lineno, c.value) for h in holds if h is not None for c in ast.walk(h)
+                   if isinstance(c, ast.Constant) and type(c.value) is int and c.value != 0})
+
+
+def test_kernel_variant_bits_have_one_set_of_names():
+    """`_abi.KV_*` mirror `enum gte_kernel_variant` of include/gte.h, and nobody passes or tests a
+    bit as a bare number: not plan_launches, not a test, not a Python tool (see
+    _bare_variant_literals for what counts; the forms this project used to write are tried first)."""
+    hdr = open(os.path.join(ROOT, "include", "gte.h")).read()
+    body = re.search(r"typedef enum gte_kernel_variant \{(.*?)\} gte_kernel_variant;", hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    enum = {k: int(v) for k, v in re.findall(r"\bGTE_(KV_[A-Z_0-9]+)\s*=\s*(\d+)", body)}
+    mirror = {k: v for k, v in vars(_abi).items() if k.startswith("KV_")}
+    assert enum == mirror
+    assert sorted(enum.values()) == [1, 2, 4, 64, 128, 256, 1024, 2048, 4096, 8192, 16384]
+    api = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "gte_api.hip")).read()
+    plan = api.split("static int plan_launches(gte_env* E) {")[1].split("\n}\n")[0]
+    assert plan.count("kernel_variant") == 1  # read once, into `kv`; every use of `kv` tests named bits
+    uses = re.findall(r"\bkv\b\s*([^\n]{0,10})", re.sub(r"//[^\n]*", "", plan).split("kv = cfg.kernel_variant;")[1])
+    assert len(uses) >= 10 and all(re.match(r"&\s*\(?GTE_KV_", u) for u in uses), uses
+
+    head = "import pytest\n"
+    for bad, n in (('_KERNEL_VARIANT = {"variant64": 64, "variant1": 1}', 2), ("DENSE = 16384", 1),
+                   ("VARIANTS = [1, 2, 64, 4096, 8192]", 5), ("for variant in (1024, 2048): pass", 2),
+                   ('ROLLOUT_MODES = {"resident": (0, True), "gather": (256, True)}', 1),
+                   ('@pytest.mark.parametrize("variant,store", [(0, 1), (64, 2), (1 | 2, 1)])\ndef t(): pass', 3),
+                   ('@pytest.mark.parametrize("kernel_variant", [0, 1024])\ndef t(): pass', 1),
+                   ("Env(kernel_variant=128)", 1), ('kw = {**kw, "kernel_variant": 128}', 1),
+                   ("def case(o, kernel_variant): pass\ncase(o, 1024)", 1), ("if kv & 128: pass", 1),
+                   ("x = _abi.KV_SHARED_TU | 2", 1)):
+        assert len(_bare_variant_literals(head + bad)) == n, bad
+    for good in ('@pytest.mark.parametrize("variant,store", [(0, 1), (_abi.KV_SHARED_TU, 2)])\ndef t(): pass',
+                 "Env(kernel_variant=_abi.KV_LOG_SEPARATE | _abi.KV_SHARED_TU, envs_per_wave=4)",
+                 "def case(o, kernel_variant): pass\ncase(1024, 0)"):
+        assert _bare_variant_literals(head + good) == [], good
+    for folder in ("tests", "tools"):
+        for name in sorted(os.listdir(os.path.join(ROOT, folder))):
+            if name.endswith(".py"):
+                text = open(os.path.join(ROOT, folder, name)).read()
+                assert _bare_variant_literals(text) == [], f"{folder}/{name}"
 
 
 def test_inline_asm_wide_stores_carry_their_wait_states():

@@ -1,15 +1,16 @@
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import bench
 import torch
+from gym_trading_env_amd import _abi
 from gym_trading_env_amd.batched import BatchedTradingEnv
 for envs in (8192, 16384, 32768, 65536):
     wl = dict(bench.WORKLOADS["c3"], envs=envs)
     feat, close = bench.synthetic_dataset(0, wl["T"], wl["n_static"])
     acts = torch.randint(0, 3, (64, envs), dtype=torch.int32, device="cuda")
-    for name, kw in (("kernel row", dict(log_steps=2)), ("separate launch", dict(log_steps=2, kernel_variant=1024)),
+    for name, kw in (("kernel row", dict(log_steps=2)), ("separate launch", dict(log_steps=2, kernel_variant=_abi.KV_LOG_SEPARATE)),
                      ("kernel row, affinity off", dict(log_steps=2, affinity_period=-1)),
-                     ("separate, affinity off", dict(log_steps=2, kernel_variant=1024, affinity_period=-1))):
+                     ("separate, affinity off", dict(log_steps=2, kernel_variant=_abi.KV_LOG_SEPARATE, affinity_period=-1))):
         k = dict(bench.env_kwargs(wl)); k.update(kw)
         env = BatchedTradingEnv((feat, close), num_envs=envs, seed=1, output="torch", **k)
         env.reset(); bench.desynchronise(env, acts, wl["max_episode_duration"])

@@ -11,6 +11,7 @@ import bench  # noqa: E402
 
 def main():
     import torch
+    from gym_trading_env_amd import _abi
     from gym_trading_env_amd.batched import BatchedTradingEnv
     envs = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
     wl = dict(bench.WORKLOADS["c3"], envs=envs)
@@ -19,7 +20,7 @@ def main():
     base = bench.env_kwargs(wl)
     cases = [
         ("next_step (headline)", {}),
-        ("next_step, shared-TU build of the kernel", dict(kernel_variant=64)),
+        ("next_step, shared-TU build of the kernel", dict(kernel_variant=_abi.KV_SHARED_TU)),
         ("same_step", dict(autoreset="same_step")),
         ("same_step + final_obs", dict(autoreset="same_step", final_obs=True)),
         ("next_step + log_steps=2", dict(log_steps=2)),

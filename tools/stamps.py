@@ -29,7 +29,7 @@ def main():
     D = wl["n_datasets"]
     data = [bench.synthetic_dataset(d, wl["T"], wl["n_static"]) for d in range(D)]
     env = BatchedTradingEnv(data if D > 1 else data[0], num_envs=N, seed=1, output="torch", library_path=lib_path,
-                            kernel_variant=64, affinity_period=affinity, **bench.env_kwargs(wl))
+                            kernel_variant=_abi.KV_SHARED_TU, affinity_period=affinity, **bench.env_kwargs(wl))
     print(f"# workload {name}, {N} envs, affinity_period {affinity}")
     lib = env._lib
     lib.gte_debug_set_stamps.argtypes = [C.c_void_p, C.c_void_p]

@@ -23,7 +23,7 @@ def main():
     N = wl["envs"]
     feat, close = bench.synthetic_dataset(0, wl["T"], wl["n_static"])
     env = BatchedTradingEnv((feat, close), num_envs=N, seed=1, output="torch", library_path=lib_path,
-                            kernel_variant=64, **bench.env_kwargs(wl))
+                            kernel_variant=_abi.KV_SHARED_TU, **bench.env_kwargs(wl))
     lib = env._lib
     lib.gte_debug_set_stamps.argtypes = [C.c_void_p, C.c_void_p]
     blocks = env.launch_info()["n_blocks"]
