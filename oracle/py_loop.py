@@ -76,7 +76,12 @@ class PyEnv:
     def __init__(self, table, close, positions, windows=None, trading_fees=0.0,
                  borrow_interest_rate=0.0, portfolio_initial_value=1000.0,
                  initial_position="random", max_episode_duration="max", dyn=("position", "real"),
-                 reward=("log",), persist=True):
+                 reward=("log",), persist=True, number=float):
+        """`number` is the type prices are read as.  float: plain Python floats (the timed loop).
+        np.float64: the reference's own scalar type (its prices come out of a NumPy array), whose
+        division by zero gives inf / NaN where a Python float raises ZeroDivisionError; every
+        other operation is the same IEEE double arithmetic."""
+        self.number = number
         self.table, self.close = table, close
         self.T, self.n_dyn = len(close), len(dyn)
         self.fs = table.shape[1] - self.n_dyn
@@ -105,7 +110,7 @@ class PyEnv:
             if self.max_dur != "max":
                 idx = np.random.randint(low=first, high=self.T - self.max_dur - first)
         self.idx = int(idx)
-        price = float(self.close[self.idx])
+        price = self.number(self.close[self.idx])
         self.book = Book(position, self.v0, price)
         self.log = [dict(idx=self.idx, step=0, position=position, real_position=position,
                          portfolio_valuation=self.v0, reward=0, data_close=price)]
@@ -118,11 +123,11 @@ class PyEnv:
         if position_index is not None and position_index >= 0:  # _take_action :213-215
             target = self.positions[position_index]
             if target != self.position:  # value compare; _trade :204-211 at close[idx]
-                self.book.retarget(target, float(self.close[self.idx]), self.fees)
+                self.book.retarget(target, self.number(self.close[self.idx]), self.fees)
                 self.position = target
         self.idx += 1
         self.step_no += 1
-        price = float(self.close[self.idx])  # IndexError past the last row, like the reference
+        price = self.number(self.close[self.idx])  # IndexError past the last row, like the reference
         self.book.accrue(self.rate)
         value = self.book.worth(price)
         done = truncated = False
@@ -143,7 +148,7 @@ class PyEnv:
         return self._observe(), entry["reward"], done, truncated, entry
 
     def _reward(self, value, before):
-        lr = float(np.log(value / before))  # basic_reward_function :17-18
+        lr = self.number(np.log(value / before))  # basic_reward_function :17-18
         kind = self.reward_spec[0]
         if kind == "scaled":
             return self.reward_spec[1] * lr

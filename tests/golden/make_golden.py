@@ -627,6 +627,159 @@ def sweep_traces():
     print(f"sweep: {len(SWEEP)} traces, {total:.0f} KiB")
 
 
+# -- the numeric family: the value space the arithmetic and the copy loops run on ---------------
+NUMERIC_SEED = 20261017
+NUMERIC_KIB_PER_FIXTURE = 200
+NUMERIC_KIB_TOTAL = 1536
+CRASH = [-3, -1, 0, 1, 3]
+
+# (name, dataset, trace, config) as in SWEEP.  A dataset is a dict: T rows, Fs static features and
+#   scale, sigma, drift   close = scale * exp(cumsum(N(drift, sigma) + jumps))
+#   jump                  the share of rows whose log return gets a further +-U(0.5, 0.6)
+#   flat                  (first, last) rows that repeat the price of row `first`
+#   zeros                 how many rows have a close of exactly 0.0 (a data gap)
+#   special               special f32 words in about 15 % of the feature cells (tests/special_words.py)
+NUMERIC = [
+    ("crash_fused_done", dict(T=300, Fs=6, sigma=2e-2, jump=0.07), dict(E=4, K=200, p_none=0.3),
+     dict(positions=CRASH, windows=4, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          portfolio_initial_value=3.0)),
+    ("crash_p20_limit_orders", dict(T=300, Fs=6, sigma=2e-2, jump=0.07),
+     dict(E=4, K=200, p_none=0.2, p_order=0.3),
+     dict(positions=P20, windows=3, trading_fees=1e-3, borrow_interest_rate=1e-4,
+          max_episode_duration=40)),
+    ("tiny_price_value_nowindow", dict(T=200, Fs=10, sigma=1e-2, scale=3e-7, special=True),
+     dict(E=4, K=160, p_none=0.5),
+     dict(positions=LEV, windows=None, trading_fees=1e-2, borrow_interest_rate=1e-3,
+          portfolio_initial_value=3e-9, max_episode_duration=30, dynamic_feature_functions=MIX3)),
+    ("subnormal_value_4byte", dict(T=200, Fs=7, sigma=1e-2, special=True), dict(E=4, K=160),
+     dict(positions=LEV, windows=3, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          portfolio_initial_value=1e-304, max_episode_duration=30)),
+    ("huge_price_value_lean", dict(T=300, Fs=6, sigma=1e-2, scale=7e8, special=True), dict(E=4, K=150),
+     dict(positions=LEV, windows=32, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          portfolio_initial_value=7e15, max_episode_duration=30)),
+    ("tiny_returns_flat", dict(T=300, Fs=5, sigma=3e-15, flat=(100, 160)), dict(E=4, K=200),
+     dict(positions=[-1, 0, 1, 2], windows=5, trading_fees=0, borrow_interest_rate=0,
+          max_episode_duration=40, dynamic_feature_functions=["real_position"])),
+    ("multids_scales_high_fees", [dict(T=120, Fs=6, sigma=2e-2, scale=1e-4),
+                                  dict(T=150, Fs=6, sigma=2e-2, scale=5e7)], dict(E=4, K=200, p_none=0.6),
+     dict(positions=[-0.5, 0, 0.25, 0.5, 1.25], windows=4, trading_fees=0.3, borrow_interest_rate=0.05,
+          max_episode_duration=20, episodes_between_dataset_switch=1)),
+    ("zero_close_basic", dict(T=200, Fs=6, sigma=1e-2, zeros=6), dict(E=4, K=200),
+     dict(positions=[-1, 0, 1, 2], windows=4, trading_fees=1e-3, borrow_interest_rate=1e-4,
+          max_episode_duration=25)),
+    ("zero_close_clipped", dict(T=200, Fs=5, sigma=1e-2, zeros=6), dict(E=4, K=200),
+     dict(positions=[-1, 0, 1, 2], windows=None, trading_fees=1e-3, borrow_interest_rate=1e-4,
+          max_episode_duration=25, dynamic_feature_functions=MIX3B,
+          reward_function=["clipped_log_return", 2.0, -0.004, 0.006])),
+    # a buy towards position -1 at fees 0.5 divides by 1 - fees + fees * position == 0
+    ("fee_denominator_zero_scaled", dict(T=200, Fs=6, sigma=1e-2), dict(E=4, K=200, p_none=0.6),
+     dict(positions=[-2, -1, 0, 1], windows=2, trading_fees=0.5, borrow_interest_rate=1e-3,
+          max_episode_duration=25, reward_function=["scaled_log_return", 50.0])),
+]
+
+
+def _numeric_dataset(seed, spec, high_low):
+    import special_words
+    T, Fs = spec["T"], spec["Fs"]
+    rng = np.random.default_rng(seed)
+    lr = rng.normal(spec.get("drift", 0.0), spec["sigma"], T)
+    feat = rng.normal(0.0, 1.0, (T, Fs)).astype(np.float32)
+    if spec.get("jump"):
+        hit = rng.random(T) < spec["jump"]
+        lr = lr + hit * rng.choice([-1.0, 1.0], T) * rng.uniform(0.5, 0.6, T)
+    close = spec.get("scale", 100.0) * np.exp(np.cumsum(lr))
+    if "flat" in spec:
+        a, b = spec["flat"]
+        close[a:b + 1] = close[a]
+    if spec.get("zeros"):
+        close[rng.choice(T, spec["zeros"], replace=False)] = 0.0
+    if spec.get("special"):
+        feat = special_words.place_special_words(feat, seed + 7)
+    if not high_low:
+        return (feat, close)
+    return (feat, close, close * (1 + np.abs(rng.normal(0, 8e-3, T))),
+            close * (1 - np.abs(rng.normal(0, 8e-3, T))))
+
+
+def _assert_static_columns_unaltered(name, sets, rec):
+    """The newest observation row's static columns, as the reference returned them, are the
+    dataset's row bit for bit at every call: no fixture holds an input the reference itself alters
+    (it quiets signalling NaNs on the way through pandas)."""
+    Fs = sets[0][0].shape[1]
+    obs = rec["obs"]
+    newest = obs[:, :, -1, :Fs] if obs.ndim == 4 else obs[:, :, :Fs]
+    for d, ds in enumerate(sets):
+        at = rec["dataset"] == d
+        want = np.ascontiguousarray(ds[0])[rec["idx"][at]]
+        assert (np.ascontiguousarray(newest[at]).view(np.uint32) == want.view(np.uint32)).all(), \
+            f"{name}: the reference altered static feature words"
+
+
+def numeric_traces():
+    """tests/golden/numeric_NN.npz: every row of NUMERIC_STRATA (tests/strata.py), each trace
+    generated by the reference from its own seeds.  The other fixtures are not touched."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import replay
+    import strata
+    rng = np.random.default_rng(NUMERIC_SEED)
+    assert 8 <= len(NUMERIC) <= 10
+    loaded, total = [], 0
+    for n, (tag, dspec, tspec, over) in enumerate(NUMERIC):
+        name = f"numeric_{n:02d}"
+        cfg = base_cfg(**over)
+        kinds = cfg.get("dynamic_feature_functions", strata.DEFAULT_DYN)
+        kw = ref_kwargs(cfg)
+        kw.update(reward_function=_ref_reward(cfg["reward_function"]),
+                  dynamic_feature_functions=_ref_dynamic(kinds))
+        tspec = dict(tspec)
+        E, K = tspec.pop("E"), tspec.pop("K")
+        assert E <= 4 and K <= 200
+        high_low = tspec.get("p_order", 0) > 0
+        seed_base = 80000 + 1000 * n
+        seed = NUMERIC_SEED % 997 + 10 * n
+        # a fresh reference env per episode, as in the sweep (no dyn_persist here)
+        if isinstance(dspec, list):
+            sets = [_numeric_dataset(seed + d, s, high_low) for d, s in enumerate(dspec)]
+            assert len({len(s[1]) for s in sets}) == len(sets), "datasets are identified by length"
+            with tempfile.TemporaryDirectory() as tmp:
+                names = []
+                for d, s in enumerate(sets):
+                    names.append(f"sym{d}.pkl")
+                    make_df(*s).to_pickle(os.path.join(tmp, names[-1]))
+                switch = cfg["episodes_between_dataset_switch"]
+
+                def mk(e, tmp=tmp, switch=switch, kw=kw, n=n):
+                    np.random.seed(777 + 31 * n + e)
+                    return MultiDatasetTradingEnv(os.path.join(tmp, "*.pkl"),
+                                                  episodes_between_dataset_switch=switch, **kw)
+                rec = run_trace(mk, cfg["positions"], n_envs=E, n_calls=K, action_rng=rng,
+                                ds_names=[len(s[1]) for s in sets], seed_base=seed_base, **tspec)
+                import glob as _glob
+                rec["glob_order"] = np.array([names.index(os.path.basename(q))
+                                              for q in _glob.glob(os.path.join(tmp, "*.pkl"))], np.int32)
+        else:
+            sets = [_numeric_dataset(seed, dspec, high_low)]
+            df = make_df(*sets[0])
+            rec = run_trace(lambda e, df=df, kw=kw: TradingEnv(df=df, **kw), cfg["positions"],
+                            n_envs=E, n_calls=K, action_rng=rng, seed_base=seed_base,
+                            fresh_env_each_episode=True, **tspec)
+        assert all(len(s[1]) <= 400 for s in sets)
+        _assert_static_columns_unaltered(name, sets, rec)
+        out = fixture_arrays(cfg, sets, rec, "")
+        g = replay.from_arrays(out)
+        out["note"] = np.array(f"numeric trace {tag}; strata: {', '.join(strata.numeric_rows_of(g))}")
+        write(name, out)
+        print("   ", str(out["note"]))
+        kib = os.path.getsize(os.path.join(HERE, name + ".npz")) / 1024
+        assert kib <= NUMERIC_KIB_PER_FIXTURE, f"{name}: {kib:.0f} KiB"
+        total += kib
+        loaded.append(g)
+    assert total <= NUMERIC_KIB_TOTAL, f"numeric: {total:.0f} KiB"
+    gaps = strata.numeric_missing(loaded)
+    assert not gaps, f"numeric strata rows not covered: {gaps}"
+    print(f"numeric: {len(NUMERIC)} traces, {total:.0f} KiB")
+
+
 def portfolio_vectors():
     """Random known answers straight from the reference's Portfolio class
     (utils/portfolio.py:1-66, which imports nothing): every branch of trade_to_position
@@ -881,6 +1034,10 @@ def staging_fixture():
 if __name__ == "__main__":
     if "--sweep" in sys.argv:
         sweep_traces()
+        sys.exit(0)
+    if "--numeric" in sys.argv:
+        with np.errstate(all="ignore"):  # the reference divides by zero prices on purpose here
+            numeric_traces()
         sys.exit(0)
     if "--only-vector" in sys.argv:
         vector_example_fixture()

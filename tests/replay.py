@@ -90,13 +90,98 @@ def injection_queue(g, tile: int = 1):
     return {f: np.tile(a, (tile, 1)) for f, a in q.items()}, n
 
 
+def _bits(x):
+    x = np.ascontiguousarray(x)
+    assert x.dtype in (np.float32, np.float64), x.dtype
+    return x.view(np.uint32 if x.dtype == np.float32 else np.uint64)
+
+
+def same_bits(a, b):
+    """Elementwise: a and b (f32 or f64 arrays of one dtype and shape) have the identical bit
+    pattern.  -0.0 is not 0.0; a NaN equals only the NaN of the same sign and payload."""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype, a.shape, b.shape)
+    return _bits(a) == _bits(b)
+
+
+def same_value(a, b):
+    """Elementwise: identical bit pattern, or both NaN.  The rule for COMPUTED values: the sign
+    and payload of a NaN an arithmetic unit produces are the unit's choice (x86 sets the sign bit,
+    the GPU does not); everything else, the sign of zero included, is part of the value."""
+    a, b = np.asarray(a), np.asarray(b)
+    return same_bits(a, b) | (np.isnan(a) & np.isnan(b))
+
+
+def _assert_all(ok, got, ref, err_msg, what):
+    if ok.all():
+        return
+    got, ref = np.asarray(got), np.asarray(ref)
+    bad = np.argwhere(~ok)
+    i = tuple(int(j) for j in bad[0])
+    width = 2 * got.dtype.itemsize
+    raise AssertionError(f"{err_msg}: {len(bad)} of {ok.size} elements differ ({what}); first at index "
+                         f"{i if len(i) != 1 else i[0]}: got {float(got[i])!r} (0x{int(_bits(got)[i]):0{width}x}), "
+                         f"expected {float(ref[i])!r} (0x{int(_bits(ref)[i]):0{width}x})")
+
+
+def assert_same_value(got, ref, err_msg=""):
+    """same_value everywhere; reports the first differing index and both bit patterns."""
+    _assert_all(same_value(got, ref), got, ref, err_msg, "bit pattern, any NaN equal to any NaN")
+
+
+def assert_same_bits(got, ref, err_msg=""):
+    """same_bits everywhere (no NaN clause): for values that are only ever copied."""
+    _assert_all(same_bits(got, ref), got, ref, err_msg, "bit pattern")
+
+
 def ulp_distance(a, b):
     """Integer distance of the IEEE bit patterns of f64 arrays a and b (0.0 and -0.0 are one
-    value; NaN is not expected): how many representable doubles lie between them."""
+    value): how many representable doubles lie between them.  Where either is NaN or infinite no
+    such count exists: the distance is 0 if they are the same value (both NaN, or the same
+    infinity) and inf otherwise, so that a bound on the result also rejects a non-finite value
+    standing in for a finite one."""
+    a = np.ascontiguousarray(a, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    special = ~(np.isfinite(a) & np.isfinite(b))
+
     def key(x):
-        i = np.ascontiguousarray(x, np.float64).view(np.int64).astype(object)
+        i = np.where(special, 0.0, x).view(np.int64).astype(object)
         return np.where(i < 0, -(i & 0x7FFFFFFFFFFFFFFF), i)
-    return np.abs(key(a) - key(b)).astype(np.float64)
+    d = np.abs(key(a) - key(b)).astype(np.float64)
+    same = (np.isnan(a) & np.isnan(b)) | (a == b)
+    return np.where(special, np.where(same, 0.0, np.inf), d)
+
+
+def assert_reward64(got, ref, bound, tag):
+    """reward64 against the trace's: the very bits where the trace's is zero (resets and `done`
+    are +0.0), NaN where it is NaN, equal where it is infinite, within `bound` ulp elsewhere.
+    Returns the worst finite distance."""
+    got = np.ascontiguousarray(got, np.float64)
+    ref = np.ascontiguousarray(ref, np.float64)
+    zero = ref == 0.0
+    assert_same_bits(got[zero], ref[zero], f"{tag} reward64 where the trace's is exactly zero")
+    nan = np.isnan(ref)
+    assert np.isnan(got[nan]).all(), f"{tag} reward64: not NaN where the trace's is"
+    inf = np.isinf(ref)
+    assert (got[inf] == ref[inf]).all(), f"{tag} reward64: {got[inf]!r} where the trace's is {ref[inf]!r}"
+    d = ulp_distance(got, ref)
+    assert d.max() <= bound, (f"{tag} reward64: {d.max():.0f} ulp from the trace (bound {bound}) at env "
+                              f"{int(d.argmax())}: {got[d.argmax()]!r} vs {ref[d.argmax()]!r}")
+    return float(d.max())
+
+
+def to_float32(r64):
+    """float32(r64) as the device casts: round to nearest, overflow to inf, no warning."""
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        return np.asarray(r64, np.float64).astype(np.float32)
+
+
+def assert_obs(got, ref, n_static, err_msg):
+    """An observation against the trace's: the static feature columns are only ever copied
+    (assert_same_bits), the dynamic ones are computed (assert_same_value)."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    assert_same_bits(got[..., :n_static], ref[..., :n_static], err_msg + " static columns")
+    assert_same_value(got[..., n_static:], ref[..., n_static:], err_msg + " dynamic columns")
 
 
 def reward_ulp_bound(g):
@@ -114,11 +199,12 @@ def replay(adapter, g, tile: int = 1, rtol: float = 1e-12, obs_exact: bool = Tru
            check_state: bool = True, reward_ulps: int | None = None, stats: dict | None = None):
     """Drive `adapter` through trace g; assert parity at every call.
 
-    reward_ulps=n: the exact mode.  The fp64 state is compared bit for bit (rtol is not used),
-    reward64 within n ulp of the trace (an integer distance of the bit patterns) and exactly 0.0
-    where the trace's reward is 0 (resets, `done`), and, when the adapter has reward32(), the f32
-    reward equals float32 of the adapter's own reward64.  stats["reward_ulps"] receives the
-    worst distance seen."""
+    reward_ulps=n: the exact mode.  The fp64 state is compared by value (same_value: the bit
+    pattern, any NaN for any NaN; rtol is not used), the static observation columns bit for bit and
+    the dynamic ones by value, reward64 as assert_reward64 says (within n ulp of the trace, the
+    very bits where the trace's reward is zero, NaN / inf where it is), and, when the adapter has
+    reward32(), the f32 reward is float32 of the adapter's own reward64.  stats["reward_ulps"]
+    receives the worst distance seen."""
     exact = reward_ulps is not None
     worst_ulp = 0.0
     K, E = g["op"].shape
@@ -147,35 +233,29 @@ def replay(adapter, g, tile: int = 1, rtol: float = 1e-12, obs_exact: bool = Tru
             for gk, sk in STATE_F64.items():
                 ref = t(g[gk][k])
                 got = st[sk]
-                err = np.abs(got - ref) / np.maximum(np.abs(ref), 1e-300)
-                err = np.where(ref == got, 0.0, err)
-                worst = max(worst, float(err.max()))
                 if exact:
-                    bad = np.nonzero(got != ref)[0]
-                    assert bad.size == 0, (f"{tag} {gk}: {bad.size} envs differ, first env {bad[0]}: "
-                                           f"{got[bad[0]]!r} != {ref[bad[0]]!r}")
+                    assert_same_value(got, ref, f"{tag} {gk}")
                 else:
+                    err = np.abs(got - ref) / np.maximum(np.abs(ref), 1e-300)
+                    err = np.where(ref == got, 0.0, err)
+                    worst = max(worst, float(err.max()))
                     np.testing.assert_allclose(got, ref, rtol=rtol, atol=1e-14 if rtol > 0 else 0,
                                                err_msg=f"{tag} {gk}")
         r64 = adapter.reward64()
         ref_r = t(g["reward"][k])
         if exact:
-            zero = ref_r == 0.0
-            assert (r64[zero] == 0.0).all(), f"{tag} reward: not exactly 0.0 where the trace's is"
-            d = ulp_distance(r64, ref_r)
-            worst_ulp = max(worst_ulp, float(d.max()))
-            assert d.max() <= reward_ulps, (f"{tag} reward64: {d.max():.0f} ulp from the trace "
-                                            f"(bound {reward_ulps}) at env {int(d.argmax())}: "
-                                            f"{r64[d.argmax()]!r} vs {ref_r[d.argmax()]!r}")
+            worst_ulp = max(worst_ulp, assert_reward64(r64, ref_r, reward_ulps, tag))
             if hasattr(adapter, "reward32"):
-                np.testing.assert_array_equal(adapter.reward32(), r64.astype(np.float32),
-                                              err_msg=f"{tag} f32 reward != float32(reward64)")
+                assert_same_value(adapter.reward32(), to_float32(r64),
+                                  f"{tag} f32 reward != float32(reward64)")
         else:
             np.testing.assert_allclose(r64, ref_r, rtol=max(rtol, 1e-12), atol=1e-15,
                                        err_msg=f"{tag} reward")
         obs = adapter.obs()
         ref_obs = np.tile(g["obs"][k], (tile,) + (1,) * (g["obs"][k].ndim - 1))
-        if obs_exact:
+        if exact:
+            assert_obs(obs, ref_obs, g["datasets"][0][0].shape[1], f"{tag} obs")
+        elif obs_exact:
             np.testing.assert_array_equal(obs, ref_obs, err_msg=f"{tag} obs")
         else:
             np.testing.assert_allclose(obs, ref_obs, rtol=1e-6, atol=1e-7, err_msg=f"{tag} obs")

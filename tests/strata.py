@@ -1,4 +1,6 @@
-"""The strata table of the reference-generated sweep (tests/golden/sweep_NN.npz).
+"""The strata tables of the reference-generated fixture families: STRATA for the configuration
+sweep (tests/golden/sweep_NN.npz), NUMERIC_STRATA further down for the numeric family
+(numeric_NN.npz).
 
 Every row names one corner of the configuration space the HIP kernels branch on and a
 predicate over a loaded trace (replay.load) that says whether the trace covers it.  The
@@ -198,3 +200,118 @@ def missing(traces):
         for r in rows_of(g):
             count[r] += 1
     return {name: n for name, n in count.items() if n < MIN_TRACES.get(name, 1)}
+
+
+# -- the numeric family (tests/golden/numeric_NN.npz, make_golden.py --numeric) ------------------
+# STRATA above sweeps the configurations the kernels branch on; these rows sweep the VALUES the
+# arithmetic and the copy loops run on.  Predicates read the fixture's data and recorded values.
+DBL_MIN = 2.2250738585072014e-308
+
+
+def _closes(g):
+    return [ds[1] for ds in g["datasets"]]
+
+
+def _dyn_obs(g, f, kind=None):
+    """The recorded dynamic observation columns (of one kind, if given)."""
+    cols = [f["Fs"] + i for i, k in enumerate(f["kinds"]) if kind is None or k == kind]
+    return g["obs"][..., cols]
+
+
+def _finite_abs(x):
+    x = np.asarray(x, np.float64)
+    return np.abs(x[np.isfinite(x)])
+
+
+def _subnormal_state(g, f):
+    v = np.abs(np.stack([g[k] for k in ("asset", "fiat", "interest_asset", "interest_fiat")]))
+    return bool(((v > 0) & (v < DBL_MIN)).any())
+
+
+def _tiny_rewards(g, f):
+    r = np.abs(g["reward"])
+    return int(((r > 0) & (r <= 1e-13)).sum()) >= 100
+
+
+def _zero_reward_on_step(g, f):
+    # a step inside an episode (not the reset, not `done`), the position held since the call
+    # before and not 0, and a reward of exactly 0.0
+    pos = np.asarray(f["positions"])[g["pos_index"]]
+    held = (g["op"][1:] == 1) & (g["done"][1:] == 0) & (g["pos_index"][1:] == g["pos_index"][:-1])
+    return bool((held & (pos[1:] != 0) & (g["reward"][1:] == 0.0) & ~np.signbit(g["reward"][1:])).any())
+
+
+def _nonfinite(g, f):
+    return bool(np.isnan(g["portfolio_valuation"]).any() and np.isnan(g["reward"]).any()
+                and f["nd"] > 0 and np.isnan(_dyn_obs(g, f)).any())
+
+
+def _special_features(g, f):
+    import special_words
+    return all(special_words.has_every_special_word(ds[0]) for ds in g["datasets"])
+
+
+def _negative_valuation(g, f):
+    return bool((g["portfolio_valuation"] < 0).any())
+
+
+def _price_le_1e_6(g, f):
+    return max(float(c.max()) for c in _closes(g)) <= 1e-6
+
+
+def _reward_ge_half(g, f):
+    return bool((_finite_abs(g["reward"]) >= 0.5).any())
+
+
+def _extreme_fused(g, f):
+    return (hot_shape(f) and f["W"] is not None and f["W"] >= 2
+            and (_negative_valuation(g, f) or _price_le_1e_6(g, f) or _reward_ge_half(g, f)))
+
+
+def _price_scales_apart(g, f):
+    if f["D"] < 2:
+        return False
+    lo = min(float(c.max()) for c in _closes(g))
+    hi = max(float(c.min()) for c in _closes(g))
+    return lo > 0 and hi / lo >= 1e10
+
+
+NUMERIC_STRATA = {
+    "price_le_1e-6": _price_le_1e_6,
+    "price_ge_1e8": lambda g, f: min(float(c.min()) for c in _closes(g)) >= 1e8,
+    "value0_le_1e-8": lambda g, f: f["cfg"]["portfolio_initial_value"] <= 1e-8,
+    "value0_ge_1e15": lambda g, f: f["cfg"]["portfolio_initial_value"] >= 1e15,
+    # the `pv / V0 <= 0.7` division decided on a real quotient
+    "value0_not_pow2_done": lambda g, f: (np.frexp(float(f["cfg"]["portfolio_initial_value"]))[0] != 0.5
+                                          and bool(g["done"].any())),
+    "subnormal_state": _subnormal_state,
+    "negative_valuation": _negative_valuation,   # a leveraged crash inside one step
+    "reward_abs_ge_0.5": _reward_ge_half,
+    "reward_abs_le_1e-13": _tiny_rewards,        # valuation ratios of 1 +- a few ulp
+    "reward_exact_zero_on_step": _zero_reward_on_step,
+    "real_position_ge_10": lambda g, f: bool((_finite_abs(_dyn_obs(g, f, "real_position")) >= 10).any()),
+    "fees_ge_0.1": lambda g, f: f["cfg"]["trading_fees"] >= 0.1,
+    "borrow_ge_1e-2": lambda g, f: f["cfg"]["borrow_interest_rate"] >= 1e-2,
+    "zero_close_nonfinite": lambda g, f: any((c == 0.0).any() for c in _closes(g)) and _nonfinite(g, f),
+    "nonfinite_clipped": lambda g, f: f["reward"] == "clipped" and _nonfinite(g, f),
+    "nonfinite_scaled": lambda g, f: f["reward"] == "scaled" and _nonfinite(g, f),
+    "special_features_lean": lambda g, f: _special_features(g, f) and _lean(f, f["nd"]) and 1 <= f["nd"] <= 4,
+    "special_features_4byte": lambda g, f: _special_features(g, f) and f["Fobs"] % 4 != 0,
+    "special_features_nowindow": lambda g, f: _special_features(g, f) and f["W"] is None,
+    # the resident, gather and state-only rollout kernels see these numbers
+    "extreme_fused_done": lambda g, f: _extreme_fused(g, f) and bool(g["done"].any()),
+    "extreme_fused_limit_orders": lambda g, f: _extreme_fused(g, f) and f["limit"],
+    "extreme_multids": _price_scales_apart,
+}
+
+
+def numeric_rows_of(g):
+    """The NUMERIC_STRATA rows trace g covers."""
+    f = facts(g)
+    return [name for name, pred in NUMERIC_STRATA.items() if pred(g, f)]
+
+
+def numeric_missing(traces):
+    """Rows of NUMERIC_STRATA that none of the given loaded traces covers."""
+    covered = {r for g in traces for r in numeric_rows_of(g)}
+    return [name for name in NUMERIC_STRATA if name not in covered]

@@ -97,8 +97,9 @@ SINGLE = ["c1_btc_default", "c1_btc_example", "c2_nowindow", "c3_window20", "dra
           "no_autoreset", "persist_dynamic", "reward_scaled_onedyn", "reward_clipped_nodyn",
           "limit_orders",
           "hostcb_custom_callables"]  # custom Python dynamic features + reward, run by the reference
-# the single-dataset traces of the reference-generated sweep (make_golden.py --sweep)
-SINGLE += [n for n in replay.golden_names() if n.startswith("sweep_")
+# the single-dataset traces of the reference-generated sweep and numeric family (make_golden.py
+# --sweep, --numeric)
+SINGLE += [n for n in replay.golden_names() if n.startswith(("sweep_", "numeric_"))
            and "feat_1" not in np.load(os.path.join(replay.GOLDEN_DIR, n + ".npz")).files]
 
 

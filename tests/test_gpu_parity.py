@@ -412,6 +412,43 @@ def test_same_step_final_observation(oracle_mod, windows, persist, output):
         BatchedTradingEnv((f, c), num_envs=4, autoreset="next_step", final_obs=True, output="numpy")
 
 
+@pytest.mark.parametrize("n_static,windows", [(6, 4), (6, 32), (4, 3)], ids=["W4_Fobs8", "W32_Fobs8", "W3_Fobs5"])
+def test_same_step_final_observation_moves_special_words(oracle_mod, n_static, windows):
+    """The terminal observation of same-step auto-reset (a path no trace replays) with special f32
+    words in the static features (quiet NaN payloads of both signs, +-inf, -0.0, subnormals, FLT_MAX,
+    FLT_MIN) and leveraged crashes in the dynamic ones: 16-byte rows with a short and a lean-sized
+    window, and 4-byte rows.  Static columns are only copied: bit for bit; dynamic columns by value."""
+    import special_words
+    from gym_trading_env_amd.batched import BatchedTradingEnv
+    T, N, nd = 400, 257, 1 if n_static == 4 else 2
+    rng = np.random.default_rng(83)
+    lr = rng.normal(-2e-3, 2e-2, T) + (rng.random(T) < 0.05) * rng.choice([-0.55, 0.55], T)
+    close = 100.0 * np.exp(np.cumsum(lr))
+    f = special_words.place_special_words(rng.normal(0, 1, (T, n_static)), seed=84)
+    assert special_words.has_every_special_word(f)
+    kw = dict(windows=windows, positions=[-3, -1, 0, 1, 3], trading_fees=1e-3, borrow_interest_rate=1e-4,
+              max_episode_duration=14, autoreset="same_step", final_obs=True, seed=9,
+              dynamic_feature_functions=["last_position_taken", "real_position"][2 - nd:])
+    env = BatchedTradingEnv((f, close), num_envs=N, output="numpy", **kw)
+    assert (env.cfg.n_static + env.cfg.n_dyn) % 4 == (1 if n_static == 4 else 0)
+    full = np.zeros((T, n_static + nd), np.float32); full[:, :n_static] = f
+    ora = oracle_mod.OracleEnv(env.cfg, [(full, close)])
+    env.reset(); ora.reset()
+    replay.assert_obs(env.read_output("obs"), ora.obs, n_static, "reset obs")
+    seen = crashed = 0
+    for k in range(36):
+        a = rng.integers(-1, 5, N).astype(np.int32)
+        env.step(a); ora.step(a)
+        ids, fin = env.final_observations()
+        np.testing.assert_array_equal(ids, np.sort(ora.term_ids))
+        replay.assert_obs(fin, ora.final_obs[ids], n_static, f"step {k} final_obs")
+        replay.assert_obs(env.read_output("obs"), ora.obs, n_static, f"step {k} obs")
+        seen += len(ids)
+        crashed += int((np.abs(fin[..., -1]) > 4).sum())  # real_position beyond every target: a crash
+    assert seen > 2 * N and crashed > 0
+    env.close()
+
+
 @pytest.mark.parametrize("seed", range(24))
 def test_hip_vs_oracle_random_configurations(oracle_mod, seed):
     """Random position sets, fees, interest rates, initial values, window lengths, feature

@@ -1,8 +1,12 @@
-"""Every sweep trace (tests/golden/sweep_NN.npz, generated by the reference itself; the strata it
-covers are in tests/strata.py) through the HIP library on every step and rollout path, held to
-what the code claims: indices, flags and observations exact, the fp64 portfolio state and the
-valuation bit-exact, reward64 within replay.reward_ulp_bound ulp of the reference (1 for the log
-return itself), the f32 reward equal to float32 of the kernel's own reward64.  Needs an MI355X.
+"""Every sweep trace (tests/golden/sweep_NN.npz: the configurations the kernels branch on) and every
+numeric trace (numeric_NN.npz: the values the arithmetic and the copy loops run on), all generated
+by the reference itself (strata in tests/strata.py), through the HIP library on every step and
+rollout path, held to what the code claims: indices and flags exact, static observation columns
+bit for bit (NaN payloads, -0.0 and subnormals included), the fp64 portfolio state, the valuation
+and the dynamic observation columns equal by value (replay.same_value: the bit pattern, any NaN for
+any NaN), reward64 within replay.reward_ulp_bound ulp of the reference (1 for the log return
+itself; NaN, inf and the sign of a zero as the reference's), the f32 reward equal to float32 of the
+kernel's own reward64.  Needs an MI355X.
 
   (a) the default step, untiled
   (b) the envs tiled x67 at envs-per-wave geometries with full waves (the lean copy loop's shape
@@ -27,6 +31,8 @@ from test_gpu_parity import GpuAdapter
 pytestmark = pytest.mark.gpu
 
 SWEEP = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(replay.GOLDEN_DIR, "sweep_*.npz")))
+NUMERIC = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(replay.GOLDEN_DIR, "numeric_*.npz")))
+TRACES = SWEEP + NUMERIC
 WORST_ULPS = {}
 
 
@@ -56,7 +62,7 @@ def _lean_epws(f):
     return [e for e in range(1, 17) if e * f["W"] <= 512 and (e * vpe) % 256 == 0]
 
 
-@pytest.mark.parametrize("name", SWEEP)
+@pytest.mark.parametrize("name", TRACES)
 def test_step_untiled(name):
     g = replay.load(name)
     a = GpuAdapter(g)
@@ -66,7 +72,7 @@ def test_step_untiled(name):
 
 def _tiled_cases():
     out = []
-    for name in SWEEP:
+    for name in TRACES:
         f = strata.facts(replay.load(name))
         lean = _lean_epws(f)
         for epw in (lean[:2] if lean else [3, 16]):
@@ -91,14 +97,15 @@ def test_step_tiled(name, epw):
     a.env.close()
 
 
-VARIANT_TRACES = ["sweep_03", "sweep_06", "sweep_12", "sweep_23", "sweep_26"]
+# (numeric_04: special f32 words in the lean shape; numeric_00: leveraged crashes, negative valuations)
+VARIANT_TRACES = ["sweep_03", "sweep_06", "sweep_12", "sweep_23", "sweep_26", "numeric_04", "numeric_00"]
 VARIANTS = [_abi.KV_PER_WAVE_PHASE_A, _abi.KV_NO_LDS_STAGING, _abi.KV_SHARED_TU, _abi.KV_GENERIC_COPY,
             _abi.KV_RECORD_DIRECT]
 
 
 def _variant_cases():
     # each (variant, store) on the nd=4 lean trace, the wide 4-byte one, the nd=4 4-byte one, a
-    # multi-dataset one, and one more that rotates over the rest of the sweep
+    # multi-dataset one, the two numeric ones, and one more that rotates over the rest of the sweep
     out = []
     rest = [n for n in SWEEP if n not in VARIANT_TRACES]
     i = 0
@@ -141,7 +148,7 @@ def _chunks(g, rng):
 
 
 @pytest.mark.parametrize("mode", sorted(strata.ROLLOUT_MODES))
-@pytest.mark.parametrize("name", SWEEP)
+@pytest.mark.parametrize("name", TRACES)
 def test_rollout(name, mode, monkeypatch, capfd):
     import torch
     from gym_trading_env_amd.batched import BatchedTradingEnv
@@ -188,23 +195,21 @@ def test_rollout(name, mode, monkeypatch, capfd):
         val = out["valuation"].cpu().numpy()
         for j, k in enumerate(range(start, stop)):
             tag = f"{name} {mode} call {k}"
-            ref = t(g["reward"][k])
-            assert (r64[j][ref == 0.0] == 0.0).all(), tag
-            d = replay.ulp_distance(r64[j], ref)
-            worst = max(worst, float(d.max()))
-            assert d.max() <= bound, f"{tag}: reward64 {d.max():.0f} ulp from the reference (bound {bound})"
-            np.testing.assert_array_equal(r32[j], r64[j].astype(np.float32), err_msg=tag)
+            worst = max(worst, replay.assert_reward64(r64[j], t(g["reward"][k]), bound, tag))
+            replay.assert_same_value(r32[j], replay.to_float32(r64[j]), tag + " f32 reward")
             np.testing.assert_array_equal(term[j], t(g["done"][k]).astype(bool), err_msg=tag)
             np.testing.assert_array_equal(trunc[j], t(g["truncated"][k]).astype(bool), err_msg=tag)
-            np.testing.assert_array_equal(val[j], t(g["portfolio_valuation"][k]), err_msg=tag + " valuation")
+            replay.assert_same_value(val[j], t(g["portfolio_valuation"][k]), tag + " valuation")
             if keep:
-                np.testing.assert_array_equal(out["obs"][j].cpu().numpy(), tt(g["obs"][k]), err_msg=tag + " obs")
+                replay.assert_obs(out["obs"][j].cpu().numpy(), tt(g["obs"][k]), f["Fs"], tag + " obs")
         if not keep:
-            np.testing.assert_array_equal(out["obs"].cpu().numpy(), tt(g["obs"][stop - 1]),
-                                          err_msg=f"{name} {mode} call {stop - 1} obs")
-        for gk, sk in list(replay.STATE_I32.items()) + list(replay.STATE_F64.items()):
+            replay.assert_obs(out["obs"].cpu().numpy(), tt(g["obs"][stop - 1]), f["Fs"],
+                              f"{name} {mode} call {stop - 1} obs")
+        for gk, sk in replay.STATE_I32.items():
             np.testing.assert_array_equal(env.state(sk), t(g[gk][stop - 1]),
                                           err_msg=f"{name} {mode} after call {stop - 1}: {sk}")
+        for gk, sk in replay.STATE_F64.items():
+            replay.assert_same_value(env.state(sk), t(g[gk][stop - 1]), f"{name} {mode} after call {stop - 1}: {sk}")
     WORST_ULPS[f"{name} rollout {mode}"] = worst
     print(f"[sweep] {name} rollout {mode}: path taken {', '.join(sorted(taken))}, "
           f"worst reward64 distance {worst:.0f} ulp")

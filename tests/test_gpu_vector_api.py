@@ -598,6 +598,11 @@ def test_apply_reward_and_dynamic_columns_entry_points():
     close = 100 * np.exp(np.cumsum(rng.normal(0, 2e-2, T)))
     kw = dict(num_envs=N, seed=9, positions=[-1, 0, 1], windows=4, trading_fees=1e-3,
               borrow_interest_rate=1e-4, max_episode_duration=7, output="torch", log_steps=3)
+    inf = float("inf")
+    special64 = torch.tensor([float("nan"), -float("nan"), inf, -inf, -0.0, 1e-46, -1e-46, 1e39, -1e39, 1e-40],
+                             dtype=torch.float64)
+    special32 = torch.from_numpy(np.array([0x7FC12345, 0xFFC00001, 0x7F800000, 0xFF800000, 0x80000000,
+                                           0x00000001, 0x807FFFFF, 0x7F7FFFFF], np.uint32).view(np.float32))
     for mode in ("next_step", "same_step"):
         a = BatchedTradingEnv((feat, close), autoreset=mode, **kw)
         b = BatchedTradingEnv((feat, close), autoreset=mode, **kw)
@@ -627,18 +632,26 @@ def test_apply_reward_and_dynamic_columns_entry_points():
             # dynamic columns: feature 0 from an f64 column, feature 1 from an f32 column
             c0 = torch.randn(N, dtype=torch.float64, device="cuda", generator=g)
             c1 = torch.randn(N, dtype=torch.float32, device="cuda", generator=g)
+            at = torch.from_numpy(rng.permutation(N)[:2 * len(special64)]).cuda()
+            c0[at[:len(special64)]] = special64.cuda()
+            c1[at[len(special64):len(special64) + len(special32)]] = special32.cuda()
             packed = torch.stack([c0.to(torch.float32), c1], dim=1).contiguous()
             _abi.check(a._lib, a._lib.gte_set_dynamic_features(a._h, C.c_void_p(packed.data_ptr()), 3))
             cols = (C.c_void_p * 2)(c0.data_ptr(), c1.data_ptr())
             is64 = (C.c_int32 * 2)(1, 0)
             _abi.check(b._lib, b._lib.gte_set_dynamic_columns(b._h, cols, is64))
             torch.cuda.synchronize()
-            assert torch.equal(a._t["obs"], b._t["obs"])
+            # (torch.equal would take NaN != NaN for a difference and -0.0 for 0.0)
+            obs_a, obs_b = a._t["obs"].cpu().numpy(), b._t["obs"].cpu().numpy()
+            replay.assert_same_bits(obs_a, obs_b, f"{mode} step {k}: packed against columns")
+            replay.assert_same_value(obs_b[:, -1, 3], c0.cpu().to(torch.float32).numpy(),
+                                     f"{mode} step {k}: f64 column against the host's cast")
+            replay.assert_same_bits(obs_b[:, -1, 4], c1.cpu().numpy(), f"{mode} step {k}: f32 column")
         # later windows read the stored values: the twins stay identical
         for k in range(6):
             act = torch.randint(0, 3, (N,), dtype=torch.int32, device="cuda", generator=g)
             oa = a.step(act)[0]; ob = b.step(act)[0]
-            assert torch.equal(oa, ob)
+            replay.assert_same_bits(oa.cpu().numpy(), ob.cpu().numpy(), f"{mode} later step {k}")
         a.close(); b.close()
 
 

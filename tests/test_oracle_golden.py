@@ -53,7 +53,7 @@ class PyLoopAdapter:
     """oracle/py_loop.py (one interpreter-bound Python object per env) behind the replay
     interface: next-step auto-reset and injected draws are done here, as a user loop would."""
 
-    def __init__(self, g):
+    def __init__(self, g, number=float):
         from oracle.py_loop import PyEnv
         cfg = dict(g["cfg"])
         rf = cfg.get("reward_function", "basic_reward_function")
@@ -75,7 +75,8 @@ class PyLoopAdapter:
                                    portfolio_initial_value=cfg["portfolio_initial_value"],
                                    initial_position=cfg["initial_position"],
                                    max_episode_duration=cfg["max_episode_duration"], dyn=dyn,
-                                   reward=reward, persist=bool(cfg.get("dyn_persist", False))))
+                                   reward=reward, persist=bool(cfg.get("dyn_persist", False)),
+                                   number=number))
         self.q, self.head = None, [0] * E
         self._obs = [None] * E
 
@@ -127,7 +128,14 @@ def test_python_loop_matches_reference_trace(name):
     """The second restatement (pure-Python, one object per env) against the reference's
     vectors: state bit-exact, as for the C oracle."""
     g = replay.load(name)
-    worst = replay.replay(PyLoopAdapter(g), g, rtol=1e-12, reward_ulps=replay.reward_ulp_bound(g))
+    try:
+        worst = replay.replay(PyLoopAdapter(g), g, rtol=1e-12, reward_ulps=replay.reward_ulp_bound(g))
+    except ZeroDivisionError:
+        # a zero price or a zero fee denominator (the numeric family): the reference computes on
+        # np.float64 scalars, which give inf / NaN there; the whole trace again on that type
+        with np.errstate(all="ignore"):
+            worst = replay.replay(PyLoopAdapter(g, number=np.float64), g, rtol=1e-12,
+                                  reward_ulps=replay.reward_ulp_bound(g))
     assert worst == 0.0
 
 
