@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Backtest thousands of precomputed strategies in one launch per K steps (`rollout`):
+"""Backtest thousands of precomputed strategies in one launch per chunk of steps (`backtest`):
 every env follows its own moving-average crossover with different window lengths over the
-same price series, started at the same row; only rewards, flags and valuations are kept.
+same price series, started at the same row.  No per-step row is kept: each env's return,
+drawdown and trade count are reduced on the device while it steps, and the action sequence
+is fed in two chunks (a table too long for one action buffer is fed the same way).
 
     python examples/backtest_rollout.py [--strategies 4096]
 """
@@ -39,12 +41,16 @@ def main(strategies=4096, K=2000):
     env.reset(inject_idx=np.full(strategies, first, np.int32),
               inject_position_index=np.ones(strategies, np.int32))
     actions = torch.from_numpy(crossover_actions(close, fast, slow, first, K)).cuda()
-    out = env.rollout(actions, valuation=True)        # one launch for all K steps
-    final = out["valuation"][-1].cpu().numpy()
+    stats = env.backtest(actions[:K // 2])                  # one launch per chunk of steps ...
+    stats = env.backtest(actions[K // 2:], resume=True)     # ... the statistics carry on
+    final = stats.valuation_last.cpu().numpy()
     best = int(np.argmax(final))
     print(f"{strategies} strategies x {K} steps; best: SMA({fast[best]}) / SMA({slow[best]}) "
-          f"-> {final[best]:.1f} from 1000.0; median {np.median(final):.1f}")
-    total_log_return = out["reward"].double().sum(0).cpu().numpy()
+          f"-> {final[best]:.1f} from 1000.0 (return {stats.total_return[best].item() - 1:+.1%}, "
+          f"max drawdown {stats.max_drawdown[best].item():.1%}, {stats.trades[best].item()} trades); "
+          f"median {np.median(final):.1f}")
+    total_log_return = stats.reward_sum.cpu().numpy()
+    assert (stats.steps == K).all()
     assert np.allclose(np.log(final / 1000.0), total_log_return, rtol=1e-3, atol=1e-4)
     env.close()
     return final

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-GTE_ABI_VERSION = 3
+GTE_ABI_VERSION = 4
 GTE_MAX_POSITIONS = 32
 GTE_MAX_DYN = 4
 GTE_COMM_ID_BYTES = 128
@@ -116,6 +116,21 @@ class GteRolloutBufs(C.Structure):
     """struct gte_rollout_bufs (include/gte.h): optional per-step result arrays."""
     _fields_ = [("obs", C.c_void_p), ("reward", C.c_void_p), ("reward64", C.c_void_p),
                 ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("valuation", C.c_void_p)]
+
+
+#: struct gte_backtest_stats (include/gte.h), in declaration order: one 128-byte record per env
+BACKTEST_FIELDS = [("steps", "<i8")] + \
+    [(n, "<f8") for n in ("reward_sum", "reward_sq_sum", "peak", "max_drawdown", "cur_return",
+                          "ep_return_sum", "ep_return_sq_sum", "valuation_last", "prev_position")] + \
+    [(n, "<i4") for n in ("trades", "episodes", "terminations", "ended", "episode_seen", "step_seen")]
+#: numpy view of an array of gte_backtest_stats (gte_read_backtest_stats)
+BACKTEST_DTYPE = BACKTEST_FIELDS + [("reserved", "<i4", (6,))]
+
+
+class GteBacktestStats(C.Structure):
+    """struct gte_backtest_stats (include/gte.h)."""
+    _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in BACKTEST_FIELDS] + \
+               [("reserved", C.c_int32 * 6)]
 
 
 class GteOutputs(C.Structure):
@@ -234,6 +249,8 @@ SYMBOLS = {
     "gte_read_envs_view": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      _P(C.c_void_p), _P(C.c_void_p)]),
     "gte_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _P(GteRolloutBufs)]),
+    "gte_backtest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
+    "gte_read_backtest_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gte_bind_returns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_comm_unique_id": (C.c_int, [C.c_void_p]),
     "gte_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),

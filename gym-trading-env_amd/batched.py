@@ -1026,6 +1026,27 @@ class BatchedTradingEnv(_VectorEnvBase):
             self._h, int(env_index), C.byref(snap), obs.ctypes.data if with_obs else None))
         return snap, obs
 
+    def _sequence_actions(self, actions, what):
+        """The [K, N] action sequence of rollout() / backtest() as a contiguous int32 device tensor
+        (None = hold, like step()); refuses what a launch of K steps cannot serve."""
+        torch = self._torch
+        if torch is None:
+            raise ValueError(f"{what} needs output='torch'")
+        if self._reward_callable is not None or self._dyn_callables:
+            raise NotImplementedError(f"a fused {what} runs all steps on the device: custom Python "
+                                      "reward / dynamic-feature callables need step()")
+        dev = self._t["obs"].device
+        if not (isinstance(actions, torch.Tensor) and actions.is_cuda):
+            a = np.asarray([[-1 if x is None else x for x in row] for row in actions]
+                           if isinstance(actions, (list, tuple)) else actions, dtype=np.int32)
+            if a.size and (a.max() >= len(self.positions) or a.min() < -1):
+                raise IndexError("list index out of range")
+            actions = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        actions = actions.to(torch.int32).contiguous()
+        if actions.dim() != 2 or actions.shape[1] != self.num_envs or actions.shape[0] < 1:
+            raise ValueError(f"expected actions of shape (K, {self.num_envs})")
+        return actions
+
     def rollout(self, actions, *, keep_obs=False, valuation=False, reward64=False, out=None):
         """K consecutive step() calls for action sequences known in advance, in ONE launch
         (`gte_rollout`: backtests of precomputed strategies, random-policy collection).
@@ -1039,21 +1060,8 @@ class BatchedTradingEnv(_VectorEnvBase):
         written again instead of allocating new ones (K x 168 MB of observations at the headline
         shape; where a buffer lands in memory also moves the store rate by a few percent)."""
         torch = self._torch
-        if torch is None:
-            raise ValueError("rollout needs output='torch'")
-        if self._reward_callable is not None or self._dyn_callables:
-            raise NotImplementedError("a fused rollout runs all steps on the device: custom Python "
-                                      "reward / dynamic-feature callables need step()")
+        actions = self._sequence_actions(actions, "rollout")
         dev = self._t["obs"].device
-        if not (isinstance(actions, torch.Tensor) and actions.is_cuda):
-            a = np.asarray([[-1 if x is None else x for x in row] for row in actions]
-                           if isinstance(actions, (list, tuple)) else actions, dtype=np.int32)
-            if a.size and (a.max() >= len(self.positions) or a.min() < -1):
-                raise IndexError("list index out of range")
-            actions = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        actions = actions.to(torch.int32).contiguous()
-        if actions.dim() != 2 or actions.shape[1] != self.num_envs or actions.shape[0] < 1:
-            raise ValueError(f"expected actions of shape (K, {self.num_envs})")
         K, N = int(actions.shape[0]), self.num_envs
         want = {"reward": ((K, N), torch.float32), "terminated": ((K, N), torch.bool),
                 "truncated": ((K, N), torch.bool)}
@@ -1082,6 +1090,29 @@ class BatchedTradingEnv(_VectorEnvBase):
         if not keep_obs:
             out["obs"] = self._t["obs"]
         return out
+
+    def backtest(self, actions, *, resume=False):
+        """K consecutive step() calls like `rollout(actions)` that keep, instead of per-step rows,
+        one record of running statistics per env (`gte_backtest`): transitions, reward sum and sum
+        of squares, peak and maximum drawdown, trades, finished episodes and their returns.
+        The statistics are reduced where the state lives, in registers, so a backtest costs one
+        store per env and call whatever its length, and it can be fed in chunks of actions:
+
+            stats = env.backtest(actions[:4096])
+            stats = env.backtest(actions[4096:], resume=True)
+
+        resume=False clears the records first (they then start from the env's current state);
+        resume=True continues them — an env that was `reset()` in between restarts its peak and
+        its position for the trade count and keeps its sums.  State, return buffers, terminal
+        list and observation afterwards are those of K single steps.  Returns a `BacktestStats`."""
+        from .backtest_stats import BacktestStats
+        actions = self._sequence_actions(actions, "backtest")
+        ptr = C.c_void_p()
+        self._keep = (actions,)  # alive until the launch has consumed them
+        _abi.check(self._lib, self._lib.gte_backtest(self._h, C.c_void_p(actions.data_ptr()),
+                                                     int(actions.shape[0]), 0 if resume else 1, C.byref(ptr)))
+        self._epoch += 1
+        return BacktestStats(self, ptr.value)
 
     # -- misc ---------------------------------------------------------------------------
     def synchronize(self):

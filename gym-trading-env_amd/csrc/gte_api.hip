@@ -106,6 +106,10 @@ struct gte_env {
   int64_t* log_cursor = nullptr;
   int64_t log_rows = 0;
   int32_t* d_group_counter = nullptr; // the resident kernel's work queue (next group of envs)
+  // gte_backtest: the statistics records and, in same-step mode without final_obs, terminal records
+  // of its own (the terminal valuation is read from them); allocated by the first call
+  gte_backtest_stats* bt_stats = nullptr;
+  EnvRec* bt_final_rec = nullptr;
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -880,11 +884,15 @@ static int age_order(gte_env* E, int32_t steps) {
   return GTE_OK;
 }
 
-// The one place a step is launched (gte_step; gte_rollout one launch per step), with store policy `store`
-static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool capturing) {
+// The one place a step is launched (gte_step; gte_rollout and gte_backtest one launch per step), with
+// store policy `store`.  terminal_rec: terminal records for this launch where the env keeps none
+// (gte_backtest in same-step mode).
+static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool capturing,
+                        EnvRec* terminal_rec = nullptr) {
   const LaunchPlan& L = E->plan;
   TRY(age_order(E, 1));
   Params p = E->p;  // (after the re-sort: it sets p.perm)
+  if (terminal_rec) p.final_rec = terminal_rec;
   p.actions = t.actions; p.obs = t.obs; p.reward = t.reward; p.reward64 = t.reward64;
   p.terminated = t.terminated; p.truncated = t.truncated;
   advance_term_slot(E, p);
@@ -1133,6 +1141,78 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
   const size_t N = (size_t)E->p.N, rows = (size_t)n_steps * N;
   flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}, {b->terminated, rows}, {b->truncated, rows}});
   return rc;
+}
+
+// gte_backtest's launches, after its checks: the steps of gte_rollout(actions, n_steps, NULL), each
+// folded into the statistics records
+static int backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t clear) {
+  const size_t N = (size_t)E->p.N;
+  const LaunchPlan& L = E->plan;
+  if (!E->bt_stats) {
+    TRY(dev_alloc(E, &E->bt_stats, N));
+    if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->bt_final_rec, N));
+    HIPCHK(hipDeviceSynchronize());  // (the zero-fill ran on the null stream)
+    clear = 1;
+  }
+  // same-step mode: the terminal valuation comes from the terminal records, the env's or our own
+  EnvRec* const terminal = E->p.final_rec ? E->p.final_rec : E->bt_final_rec;
+  Params ps = E->p;
+  ps.perm = nullptr;  // identity order, as in the state-only rollout: per-env loads and stores coalesce
+  ps.final_rec = terminal;
+  hipError_t le = gte::BacktestLaunch::begin(ps, E->bt_stats, clear, E->stream);
+  if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
+  // one step as an ordinary launch (it also produces the observation and the terminal list), then
+  // its results into the records
+  auto step_and_fold = [&](int32_t k) -> int {
+    TRY(enqueue_step(E, own_targets(E, actions + (size_t)k * N), L.store, false, E->bt_final_rec));
+    const hipError_t fe = gte::BacktestLaunch::fold(ps, E->bt_stats, E->stream);
+    if (fe != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(fe));
+    return GTE_OK;
+  };
+  if (!L.fused_rollout) {
+    report_rollout_path("backtest per-step", n_steps);
+    for (int32_t k = 0; k < n_steps; ++k) TRY(step_and_fold(k));
+    return GTE_OK;
+  }
+  report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
+  if (n_steps > 1) {
+    TRY(age_order(E, n_steps - 1));
+    // envs per wavefront: launch_rollout_state's choice (profiles/r02_state_epw.log)
+    const int sepw = (E->p.N >= 64 * 1024) ? 64 : 32;
+    le = gte::BacktestLaunch::summary(ps, actions, E->bt_stats, n_steps - 1, sepw, E->stream);
+    if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
+  }
+  return step_and_fold(n_steps - 1);
+}
+
+int gte_backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t clear,
+                 gte_backtest_stats** stats_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_backtest before gte_reset");
+  if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
+  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
+  if (stream_capturing(E))
+    return fail(GTE_ERR_STATE, "gte_backtest inside a stream capture: a backtest is one launch already, "
+                               "run it eagerly");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const int rc = backtest(E, actions, n_steps, clear);
+  // the fused kernel writes flags into the env's buffers (flag ledger)
+  const size_t N = (size_t)E->p.N;
+  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}});
+  if (stats_device) *stats_device = E->bt_stats;
+  return rc;
+}
+
+int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backtest_stats* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (!E->bt_stats) return fail(GTE_ERR_STATE, "gte_read_backtest_stats before gte_backtest");
+  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
+    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(hipStreamSynchronize(E->stream));
+  if (count > 0)
+    HIPCHK(hipMemcpy(out, E->bt_stats + first, sizeof(gte_backtest_stats) * (size_t)count, hipMemcpyDeviceToHost));
+  return GTE_OK;
 }
 
 int gte_add_limit_orders(gte_env* E, const int32_t* pos_index, const double* limit,

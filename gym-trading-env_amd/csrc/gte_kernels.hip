@@ -216,6 +216,7 @@ __device__ inline void fill_limit_orders(const Params& p, int e, const DatasetDe
 }
 
 #ifndef GTE_HOT_ONLY
+#ifndef GTE_PHASE_A_ONLY  // (gte_backtest.hip: phase A with nothing compiled out, none of this file's own kernels)
 // TradingEnv.add_limit_order, environments.py:227-231: `orders[position] = {...}` — an
 // existing key (a position VALUE) keeps its place in the iteration order, a new one
 // goes last.  One thread per env.
@@ -235,6 +236,7 @@ __global__ void gte_add_orders_kernel(const Params p, const int32_t* pos_index,
   p.lo_persist[(int64_t)e * p.P + j] = persistent ? persistent[e] : 0;
 }
 
+#endif  // GTE_PHASE_A_ONLY
 #endif  // GTE_HOT_ONLY
 
 __device__ inline void pop_injection(const Params& p, int e, EnvRegs& s, int32_t& qi,
@@ -1078,6 +1080,7 @@ __global__ __launch_bounds__(256) void gte_kernel(const Params p, const uint64_t
 }
 
 #ifndef GTE_HOT_ONLY
+#ifndef GTE_PHASE_A_ONLY
 // ---------------------------------------------------------------------------
 // L2-affinity permutation.  Workgroups are dealt round-robin over the 8 XCDs, each
 // with a private 4 MiB L2 (workgroup b and b+8 share one; observed behaviour, used
@@ -1230,6 +1233,7 @@ hipError_t launch_reset(const Params& p, int vec, int nt, bool coop, int stage, 
   return launch_mode<MODE_RESET>(p, vec, nt, coop, stage, blocks, threads, stream);
 }
 
+#endif  // GTE_PHASE_A_ONLY
 #endif  // GTE_HOT_ONLY
 
 }  // namespace gte

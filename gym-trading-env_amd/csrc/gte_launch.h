@@ -70,6 +70,20 @@ hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_ste
 int rollout_blocks_per_cu(const Params& p, int nt);
 hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, hipStream_t stream);
 
+// --- gte_backtest.hip: K steps in one launch that keep per-env statistics instead of per-step rows
+// (static members: the definitions in gte_backtest.hip are checked against these by the compiler)
+struct BacktestLaunch {
+  // clear != 0: zero the records and anchor them at the envs' current state; else bring the
+  // bookkeeping fields up to date with the records (a gte_reset since the previous call)
+  static hipError_t begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream);
+  // n_steps steps from registers (the geometry of launch_rollout_state); p.final_rec must be set in
+  // same-step mode: the lane that wrote an env's terminal record reads the terminal valuation back
+  static hipError_t summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, int n_steps,
+                            int epw, hipStream_t stream);
+  // ONE step into the records, from what an ordinary step launch left in p's buffers
+  static hipError_t fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream);
+};
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GTE_ABI_VERSION 3
+#define GTE_ABI_VERSION 4
 #define GTE_MAX_POSITIONS 32
 #define GTE_MAX_DYN 4
 
@@ -396,6 +396,67 @@ typedef struct gte_rollout_bufs {
  * fixes the envs per workgroup pass of the window-resident kernel instead of the geometry
  * search in gte_api.hip (profiles/r02_resident_epb.log). */
 int gte_rollout(gte_env* env, const int32_t* actions, int32_t n_steps, const gte_rollout_bufs* bufs);
+
+/* Running statistics of ONE env's backtest (gte_backtest): one 128-byte record per env, owned by
+ * the env on the device and carried from call to call.  An env's timeline is a sequence of
+ * episodes: a reset row (valuation v_0, position value p_0), then transitions t = 1, 2, ... with
+ * the valuation v_t the step computed (environments.py:241, before any same-step reset), the
+ * position value p_t = positions[position_index] after the step (limit-order fills included), the
+ * f64 reward r_t and the two flags.  A TRANSITION is a step in which the env really advanced: a
+ * next-step auto-reset step and a frozen step (a finished env on its last row, auto-reset off) are
+ * none and change no statistic.  A reset of any kind (next-step, same-step inside a launch,
+ * gte_reset between calls) sets peak = v_0 and prev_position = p_0.  Per transition, in this
+ * order, every floating operation one IEEE f64 operation as written:
+ *   steps += 1;  reward_sum += r_t;  reward_sq_sum += r_t * r_t;
+ *   if (p_t != prev_position) trades += 1;  prev_position = p_t;
+ *   if (v_t > peak) peak = v_t;  d = 1.0 - v_t / peak;  if (d > max_drawdown) max_drawdown = d;
+ *   cur_return += r_t;
+ *   at the FIRST transition of an episode that raises a flag:  episodes += 1;
+ *     terminations += terminated;  ep_return_sum += cur_return;
+ *     ep_return_sq_sum += cur_return * cur_return;  cur_return = 0.0;
+ *   valuation_last = v_t;
+ * (plain comparisons: a NaN valuation changes neither peak nor max_drawdown).  Transitions an env
+ * goes on making after its episode ended without a reset (auto-reset off, rows left) count like
+ * any other and end no further episode.  Clearing zeroes the record, then takes peak =
+ * valuation_last = the env's current portfolio_valuation and prev_position = its current position
+ * value. */
+typedef struct gte_backtest_stats {
+  int64_t steps;             /* transitions                                             */
+  double  reward_sum;        /* sum of r_t, in step order                               */
+  double  reward_sq_sum;     /* sum of r_t * r_t                                        */
+  double  peak;              /* highest valuation of the current episode                */
+  double  max_drawdown;      /* largest 1 - v_t / peak seen in any episode              */
+  double  cur_return;        /* sum of r_t of the episode in progress                   */
+  double  ep_return_sum;     /* sum over finished episodes of their return              */
+  double  ep_return_sq_sum;  /* ... and of its square                                   */
+  double  valuation_last;    /* v_t of the last transition                              */
+  double  prev_position;     /* p_t of the last transition (or p_0 of the last reset)   */
+  int32_t trades;            /* transitions whose position value differs from the one before */
+  int32_t episodes;          /* finished episodes                                       */
+  int32_t terminations;      /* ... of them, ended by `terminated` (the 0.7 rule, :246) */
+  int32_t ended;             /* bookkeeping: 1 while the current episode has ended and no reset followed */
+  int32_t episode_seen;      /* bookkeeping: the env's reset count the statistics are up to date with   */
+  int32_t step_seen;         /* bookkeeping: the env's _step after the last step folded in              */
+  int32_t reserved[6];       /* -> 128 bytes                                            */
+} gte_backtest_stats;
+
+/* n_steps consecutive TradingEnv.step calls exactly like gte_rollout(actions, n_steps, NULL) — no
+ * per-step result is kept — that also maintain every env's gte_backtest_stats.  `actions` is a
+ * DEVICE pointer to int32 [n_steps][N].  clear != 0: the records are cleared first (see above);
+ * clear == 0: they continue, so a long backtest can be fed in chunks of actions (an env that was
+ * reset by gte_reset since the previous call restarts peak and prev_position and keeps its sums).
+ * The first call of an env always clears.  *stats_device (may be NULL) receives the DEVICE address
+ * of the N records, which stays the same until gte_destroy.  Where gte_rollout fuses the steps,
+ * n_steps - 1 of them run in one launch with state and statistics in registers
+ * (gte_backtest.hip) and the last one as an ordinary step launch folded in by a small kernel;
+ * elsewhere every step is a step launch plus that fold, with the same records bit for bit.
+ * Afterwards state, dynamic rings, return buffers, terminal list and observation are those of
+ * n_steps gte_step calls.  The buffers are allocated by the first call.  Refused inside a stream
+ * capture (GTE_ERR_STATE): a backtest is one launch already. */
+int gte_backtest(gte_env* env, const int32_t* actions, int32_t n_steps, int32_t clear,
+                 gte_backtest_stats** stats_device);
+/* Records first .. first+count-1 into HOST memory: waits for the env's stream, one transfer. */
+int gte_read_backtest_stats(gte_env* env, int32_t first, int32_t count, gte_backtest_stats* out);
 
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
