@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-GTE_ABI_VERSION = 4
+GTE_ABI_VERSION = 5
 GTE_MAX_POSITIONS = 32
 GTE_MAX_DYN = 4
 GTE_COMM_ID_BYTES = 128
@@ -251,6 +251,9 @@ SYMBOLS = {
     "gte_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _P(GteRolloutBufs)]),
     "gte_backtest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
     "gte_read_backtest_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gte_bind_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64]),
+    "gte_signal_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gte_backtest_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
     "gte_bind_returns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_comm_unique_id": (C.c_int, [C.c_void_p]),
     "gte_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),

@@ -241,6 +241,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         self.action_space = spaces.MultiDiscrete([len(self.positions)] * self.num_envs)
         self.observation_space = spaces.Box(-np.inf, np.inf,
                                             shape=(self.num_envs,) + self.obs_shape)
+        self._signals = {}  # dataset -> the padded int8 [S, stride] device tensor bound to it (bind_signals)
         for d, s in enumerate(self.datasets):
             self.upload_dataset(d, s)
 
@@ -310,6 +311,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         _abi.check(self._lib, self._lib.gte_upload_dataset(
             self._h, d, feat.ctypes.data, close.ctypes.data, ptr(s.high), ptr(s.low), s.T))
         self.datasets[d] = s
+        self._signals.pop(d, None)  # (the library unbound the dataset's signal table: T may differ)
 
     def _bind_torch_outputs(self):
         import torch
@@ -1111,6 +1113,144 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._keep = (actions,)  # alive until the launch has consumed them
         _abi.check(self._lib, self._lib.gte_backtest(self._h, C.c_void_p(actions.data_ptr()),
                                                      int(actions.shape[0]), 0 if resume else 1, C.byref(ptr)))
+        self._epoch += 1
+        return BacktestStats(self, ptr.value)
+
+    # -- signal tables: the action looked up on the device by the row an env stands on -----
+    def bind_signals(self, signals, dataset=None):
+        """Bind per-strategy signal tables (`gte_bind_signals`): ``signals[s][t]`` is the position
+        index strategy ``s`` wants while an env stands on row ``t`` — the action of the step it
+        takes from there, ``env.step(a if 0 <= a < len(positions) else None)``.  Any value outside
+        ``[0, len(positions))`` means hold.
+
+        signals: integers that fit int8, shape [S, T] — a torch CUDA tensor or anything array-like —
+        for dataset `dataset` (default: the only one), or with ``dataset=None`` a list of D such
+        tables, one per resident dataset, all with the same S.  Each table is copied once into an
+        int8 device tensor whose rows are padded to a multiple of 16 bytes, which the env keeps
+        alive.  A table whose T is not its dataset's, or whose S differs from the tables already
+        bound, is refused.  ``signals=None`` unbinds.  Uploading a dataset again unbinds its table."""
+        torch = self._torch
+        if torch is None:
+            raise ValueError("bind_signals needs output='torch'")
+        D = len(self.datasets)
+        if dataset is None:
+            if signals is None:
+                tables = {d: None for d in range(D)}
+            elif isinstance(signals, (list, tuple)) and len(signals) == D and \
+                    all(getattr(t, "ndim", None) == 2 or (isinstance(t, (list, tuple)) and t and
+                                                         isinstance(t[0], (list, tuple))) for t in signals):
+                tables = dict(enumerate(signals))
+            elif D == 1:
+                tables = {0: signals}
+            else:
+                raise ValueError(f"expected a list of {D} signal tables, one per dataset (or dataset=d)")
+        else:
+            if not 0 <= int(dataset) < D:
+                raise IndexError(f"dataset {dataset} out of range")
+            tables = {int(dataset): signals}
+        from . import signals as sig
+        dev = self._t["obs"].device
+        padded = {}
+        for d, t in tables.items():
+            if t is None:
+                continue
+            if isinstance(t, torch.Tensor) and t.is_cuda:
+                if t.dim() != 2 or t.is_floating_point() or t.is_complex():
+                    raise TypeError("a signal table is a two-dimensional integer tensor")
+                if t.dtype != torch.int8 and t.numel() and (int(t.min()) < -128 or int(t.max()) > 127):
+                    raise ValueError("signal table values must fit int8")
+                S, T = int(t.shape[0]), int(t.shape[1])
+                with torch.cuda.device(dev):
+                    buf = torch.full((S, sig.row_stride(T)), -1, dtype=torch.int8, device=dev)
+                buf[:, :T] = t.to(device=dev, dtype=torch.int8)
+            else:
+                host = sig.as_int8_table(t.cpu().numpy() if isinstance(t, torch.Tensor) else t)
+                S, T = host.shape
+                buf = torch.from_numpy(sig.pad_rows(host)).to(dev)
+            if T != self.datasets[d].T:
+                raise ValueError(f"signal table of dataset {d} has {T} columns, the dataset {self.datasets[d].T} rows")
+            padded[d] = buf
+        # one S: over the tables of this call and those that stay bound
+        kept = {d: t for d, t in self._signals.items() if d not in tables}
+        sizes = {int(t.shape[0]) for t in list(padded.values()) + list(kept.values())}
+        if len(sizes) > 1:
+            raise ValueError(f"signal tables must have one number of strategies, got {sorted(sizes)}")
+        if padded:
+            torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
+        for d, t in tables.items():
+            if t is None:
+                _abi.check(self._lib, self._lib.gte_bind_signals(self._h, d, None, 0, 0))
+                self._signals.pop(d, None)
+            else:
+                buf = padded[d]
+                assert buf.data_ptr() % sig.PIECE == 0 and buf.is_contiguous()
+                _abi.check(self._lib, self._lib.gte_bind_signals(self._h, d, C.c_void_p(buf.data_ptr()),
+                                                                 int(buf.shape[0]), int(buf.shape[1])))
+                self._signals[d] = buf
+
+    @property
+    def num_strategies(self) -> int:
+        """S of the bound signal tables (0: none bound)."""
+        return int(next(iter(self._signals.values())).shape[0]) if self._signals else 0
+
+    def _strategy(self, strategy, what):
+        """`strategy` of signal_actions() / backtest_signals() as a device int32 [N] tensor or None
+        (= (env_id_base + e) % S); a host array is checked against [0, S), a CUDA tensor is the
+        caller's contract, as in the C ABI."""
+        torch = self._torch
+        if torch is None:
+            raise ValueError(f"{what} needs output='torch'")
+        if strategy is None:
+            return None
+        if not (isinstance(strategy, torch.Tensor) and strategy.is_cuda):
+            a = np.asarray(strategy.cpu().numpy() if isinstance(strategy, torch.Tensor) else strategy)
+            if a.dtype.kind not in "iu":
+                raise TypeError("strategy must be integers")
+            S = self.num_strategies
+            if a.size and S and (a.min() < 0 or a.max() >= S):
+                raise IndexError(f"strategy outside [0, {S})")
+            strategy = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(self._t["obs"].device)
+        strategy = strategy.to(torch.int32).contiguous()
+        if tuple(strategy.shape) != (self.num_envs,):
+            raise ValueError(f"expected strategy of shape ({self.num_envs},)")
+        return strategy
+
+    def signal_actions(self, strategy=None, out=None):
+        """The action the bound signal tables give every env for its NEXT step, as an int32 [N]
+        device tensor (-1 = hold): `gte_signal_actions`, one small stream-ordered launch that can be
+        captured.  ``env.step(env.signal_actions())`` drives the env closed-loop by signals, with
+        observations; `out` (int32 [N], CUDA, contiguous) is written instead of a new tensor."""
+        strategy = self._strategy(strategy, "signal_actions")
+        torch = self._torch
+        dev = self._t["obs"].device
+        if out is None:
+            with torch.cuda.device(dev):
+                out = torch.empty((self.num_envs,), dtype=torch.int32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32
+                  and tuple(out.shape) == (self.num_envs,) and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous int32 CUDA tensor of shape ({self.num_envs},)")
+        self._keep_strategy = strategy  # alive until the launch has consumed it
+        _abi.check(self._lib, self._lib.gte_signal_actions(
+            self._h, None if strategy is None else C.c_void_p(strategy.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
+    def backtest_signals(self, K, *, strategy=None, resume=False):
+        """`backtest()` of K steps with every step's action looked up on the device in the bound
+        signal tables, at the row (and dataset) the env stands on before the step
+        (`gte_backtest_signals`) — so random episode starts, `max_episode_duration`, dataset
+        switching and auto-reset all stay on, and no [K, N] action tensor exists.  Env e follows
+        strategy ``strategy[e]`` (int32 [N]); None = ``(env_id_base + e) % S``.  Records, `resume`
+        and the state afterwards are those of `backtest()`.  Returns a `BacktestStats`."""
+        from .backtest_stats import BacktestStats
+        if self._reward_callable is not None or self._dyn_callables:
+            raise NotImplementedError("a fused backtest runs all steps on the device: custom Python "
+                                      "reward / dynamic-feature callables need step()")
+        strategy = self._strategy(strategy, "backtest_signals")
+        ptr = C.c_void_p()
+        self._keep_strategy = strategy
+        _abi.check(self._lib, self._lib.gte_backtest_signals(
+            self._h, None if strategy is None else C.c_void_p(strategy.data_ptr()), int(K),
+            0 if resume else 1, C.byref(ptr)))
         self._epoch += 1
         return BacktestStats(self, ptr.value)
 

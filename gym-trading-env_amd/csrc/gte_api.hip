@@ -110,6 +110,12 @@ struct gte_env {
   // of its own (the terminal valuation is read from them); allocated by the first call
   gte_backtest_stats* bt_stats = nullptr;
   EnvRec* bt_final_rec = nullptr;
+  // signal tables (gte_bind_signals): one descriptor per dataset (base null = none bound), the host
+  // copy and the device array the kernels read; the lookup's output for gte_backtest_signals
+  std::vector<gte::SignalTable> h_sig;
+  gte::SignalTable* d_sig = nullptr;
+  int32_t sig_S = 0;  // strategies of every bound table (0 = none bound)
+  int32_t* d_sig_actions = nullptr;
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -600,6 +606,23 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   return GTE_OK;
 }
 
+// Dataset d's signal table becomes t (base null = unbound), on the host and on the device; the
+// caller has waited for the stream.  Nothing changes if the copy fails.
+static int publish_signal_table(gte_env* E, int32_t d, const gte::SignalTable& t) {
+  const gte::SignalTable before = E->h_sig[d];
+  E->h_sig[d] = t;
+  const hipError_t e = hipMemcpy(E->d_sig, E->h_sig.data(), sizeof(gte::SignalTable) * E->h_sig.size(),
+                                 hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    E->h_sig[d] = before;
+    return fail(GTE_ERR_HIP, "publishing the signal table of dataset %d: %s", d, hipGetErrorString(e));
+  }
+  bool any = false;
+  for (const gte::SignalTable& x : E->h_sig) any = any || x.base != nullptr;
+  if (!any) E->sig_S = 0;
+  return GTE_OK;
+}
+
 int gte_upload_dataset(gte_env* E, int32_t d, const float* feat, const double* close,
                        const double* high, const double* low, int64_t T) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
@@ -657,6 +680,8 @@ int gte_upload_dataset(gte_env* E, int32_t d, const float* feat, const double* c
     if (E->ds_allocs[k][d]) (void)hipFree(E->ds_allocs[k][d]);
     E->ds_allocs[k][d] = dev[k];
   }
+  // T may have changed: the dataset's signal table was checked against the old one
+  if (E->d_sig && E->h_sig[d].base) TRY(publish_signal_table(E, d, gte::SignalTable{nullptr, 0}));
   return GTE_OK;
 }
 
@@ -1145,9 +1170,16 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
 
 // gte_backtest's launches, after its checks: the steps of gte_rollout(actions, n_steps, NULL), each
 // folded into the statistics records
-static int backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t clear) {
+// With actions == NULL (gte_backtest_signals) each step's actions are looked up in the bound signal tables
+// for `strategy` instead.
+static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy, int32_t n_steps, int32_t clear) {
   const size_t N = (size_t)E->p.N;
   const LaunchPlan& L = E->plan;
+  const bool signals = actions == nullptr;
+  if (signals && !E->d_sig_actions) {
+    TRY(dev_alloc(E, &E->d_sig_actions, N));
+    HIPCHK(hipDeviceSynchronize());  // (the zero-fill ran on the null stream)
+  }
   if (!E->bt_stats) {
     TRY(dev_alloc(E, &E->bt_stats, N));
     if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->bt_final_rec, N));
@@ -1164,22 +1196,31 @@ static int backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t
   // one step as an ordinary launch (it also produces the observation and the terminal list), then
   // its results into the records
   auto step_and_fold = [&](int32_t k) -> int {
-    TRY(enqueue_step(E, own_targets(E, actions + (size_t)k * N), L.store, false, E->bt_final_rec));
+    if (signals) {
+      const hipError_t se = gte::SignalLaunch::actions(E->p, E->d_sig, E->sig_S, strategy,
+                                                                E->d_sig_actions, E->stream);
+      if (se != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(se));
+    }
+    const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
+    TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->bt_final_rec));
     const hipError_t fe = gte::BacktestLaunch::fold(ps, E->bt_stats, E->stream);
     if (fe != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(fe));
     return GTE_OK;
   };
   if (!L.fused_rollout) {
-    report_rollout_path("backtest per-step", n_steps);
+    report_rollout_path(signals ? "backtest signals per-step" : "backtest per-step", n_steps);
     for (int32_t k = 0; k < n_steps; ++k) TRY(step_and_fold(k));
     return GTE_OK;
   }
-  report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
+  if (signals) report_rollout_path(n_steps > 1 ? "backtest signals summary" : "backtest signals per-step", n_steps);
+  else report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
   if (n_steps > 1) {
     TRY(age_order(E, n_steps - 1));
     // envs per wavefront: launch_rollout_state's choice (profiles/r02_state_epw.log)
     const int sepw = (E->p.N >= 64 * 1024) ? 64 : 32;
-    le = gte::BacktestLaunch::summary(ps, actions, E->bt_stats, n_steps - 1, sepw, E->stream);
+    le = signals ? gte::SignalLaunch::summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats,
+                                                        n_steps - 1, sepw, E->stream)
+                 : gte::BacktestLaunch::summary(ps, actions, E->bt_stats, n_steps - 1, sepw, E->stream);
     if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   }
   return step_and_fold(n_steps - 1);
@@ -1195,10 +1236,79 @@ int gte_backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t cl
     return fail(GTE_ERR_STATE, "gte_backtest inside a stream capture: a backtest is one launch already, "
                                "run it eagerly");
   HIPCHK(hipSetDevice(E->cfg.device));
-  const int rc = backtest(E, actions, n_steps, clear);
+  const int rc = backtest(E, actions, nullptr, n_steps, clear);
   // the fused kernel writes flags into the env's buffers (flag ledger)
   const size_t N = (size_t)E->p.N;
   flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}});
+  if (stats_device) *stats_device = E->bt_stats;
+  return rc;
+}
+
+int gte_bind_signals(gte_env* E, int32_t d, const int8_t* signals_device, int32_t n_strategies,
+                     int64_t row_stride) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  const Params& p = E->p;
+  if (d < 0 || d >= p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bind_signals inside a stream capture");
+  if (signals_device) {
+    const int64_t T = E->h_ds[d].T;
+    if (T <= 0) return fail(GTE_ERR_STATE, "gte_bind_signals: dataset %d was never uploaded", d);
+    if ((uintptr_t)signals_device & 15) return fail(GTE_ERR_INVALID, "signals must be 16-byte aligned");
+    if (row_stride % 16 != 0 || row_stride < (T + 15) / 16 * 16)
+      return fail(GTE_ERR_INVALID, "row_stride %lld: a multiple of 16 and >= %lld (the %lld rows of dataset %d "
+                  "rounded up to 16) required", (long long)row_stride, (long long)((T + 15) / 16 * 16),
+                  (long long)T, d);
+    if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+    for (int o = 0; o < (int)E->h_sig.size(); ++o)
+      if (o != d && E->h_sig[o].base && E->sig_S != n_strategies)
+        return fail(GTE_ERR_INVALID, "n_strategies %d: the table of dataset %d has %d", n_strategies, o, E->sig_S);
+  } else if (!E->d_sig) {
+    return GTE_OK;  // nothing was ever bound
+  }
+  HIPCHK(hipSetDevice(E->cfg.device));
+  if (!E->d_sig) {
+    E->h_sig.assign((size_t)p.D, gte::SignalTable{nullptr, 0});
+    TRY(dev_alloc(E, &E->d_sig, (size_t)p.D));
+  }
+  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight read the descriptors
+  TRY(publish_signal_table(E, d, signals_device ? gte::SignalTable{signals_device, row_stride}
+                                                : gte::SignalTable{nullptr, 0}));
+  if (signals_device) E->sig_S = n_strategies;
+  return GTE_OK;
+}
+
+// every resident dataset has a table: the lookups may run
+static int signals_ready(const gte_env* E, const char* who) {
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "%s before gte_reset", who);
+  for (int d = 0; d < E->p.D; ++d)
+    if (!E->d_sig || !E->h_sig[d].base)
+      return fail(GTE_ERR_STATE, "%s: dataset %d has no signal table (gte_bind_signals)", who, d);
+  return GTE_OK;
+}
+
+int gte_signal_actions(gte_env* E, const int32_t* strategy_device, int32_t* actions_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!actions_device) return fail(GTE_ERR_INVALID, "actions is NULL");
+  TRY(signals_ready(E, "gte_signal_actions"));
+  if (!stream_capturing(E)) HIPCHK(hipSetDevice(E->cfg.device));
+  const hipError_t e = gte::SignalLaunch::actions(E->p, E->d_sig, E->sig_S, strategy_device,
+                                                           actions_device, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal lookup launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_backtest_signals(gte_env* E, const int32_t* strategy_device, int32_t n_steps, int32_t clear,
+                         gte_backtest_stats** stats_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  TRY(signals_ready(E, "gte_backtest_signals"));
+  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
+  if (stream_capturing(E))
+    return fail(GTE_ERR_STATE, "gte_backtest_signals inside a stream capture: a backtest is one launch already, "
+                               "run it eagerly");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const int rc = backtest(E, nullptr, strategy_device, n_steps, clear);
+  const size_t N = (size_t)E->p.N;
+  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}});  // (as gte_backtest)
   if (stats_device) *stats_device = E->bt_stats;
   return rc;
 }

@@ -13,6 +13,11 @@
 //                              (reward64, flags, the record, the terminal record): the last step of a
 //                              call, and every step where gte_rollout itself goes step by step.
 //   gte_backtest_begin_kernel  clears the records, or brings them up to date with a gte_reset.
+//   gte_signal_actions_kernel  the action a signal table (gte_bind_signals) gives every env for its next
+//                              step: one lane per env, the record's idx / dsi -> one byte -> int32.
+//   gte_backtest_signal_kernel gte_backtest_kernel with that lookup, at the env's own row, in place of
+//                              the [K][N] actions: the aligned 16-byte piece of the strategy's row that
+//                              holds idx is carried in registers and the wanted byte shifted out.
 //
 // Both paths run the same backtest_step() on the same values, so they give the same records bit for bit
 // (tests/test_gpu_backtest.py).  This unit is compiled WITHOUT GTE_HOT_ONLY: in same-step mode phase A
@@ -180,6 +185,114 @@ __global__ __launch_bounds__(256) void gte_backtest_begin_kernel(const Params p,
   store_stats(stats + e, a);
 }
 
+// --- signal tables: the action looked up by the row the env stands on (include/gte.h, gte_bind_signals)
+
+// strategy of env e: the caller's array, or (env_id_base + e) % S — what the unsharded run gives that env
+__device__ __forceinline__ int64_t signal_strategy(const Params& p, const int32_t* strategy, int S, int e) {
+  return strategy ? (int64_t)strategy[e] : (p.env_id_base + e) % S;
+}
+
+// a table value as the action of a step: outside [0, P) it means hold (None, environments.py:234)
+__device__ __forceinline__ int32_t signal_action(int32_t v, int32_t P) {
+  return (uint32_t)v < (uint32_t)P ? v : -1;
+}
+
+__global__ __launch_bounds__(256) void gte_signal_actions_kernel(const Params p, const SignalTable* tables,
+                                                                 const int S, const int32_t* strategy,
+                                                                 int32_t* actions) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= p.N) return;
+  const int4_t a = reinterpret_cast<const int4_t*>(&p.rec[e])[0];  // idx, step, pos, dsi
+  const SignalTable t = tables[a[3]];
+  actions[e] = signal_action(t.base[signal_strategy(p, strategy, S, e) * t.stride + a[0]], p.P);
+}
+
+// byte idx & 15 of an aligned 16-byte piece, sign-extended: three selects and one bit-field extract
+__device__ __forceinline__ int32_t signal_byte(const int4_t& w, int32_t idx) {
+  const int j = idx & 15;
+  const int32_t word = j < 8 ? (j < 4 ? w[0] : w[1]) : (j < 12 ? w[2] : w[3]);
+  return (int32_t)(int8_t)(word >> ((j & 3) * 8));
+}
+
+// gte_backtest_kernel (same geometry, same steps, same record handling) with each step's action taken
+// from the env's signal table at s.idx / s.dsi before phase A.  gte_backtest_kernel hides its action
+// load by asking for the next step's a step ahead; here the next row is known only after the step.  So
+// the load is amortised and speculated instead: the lane keeps the aligned 16-byte piece of its
+// strategy's row that holds idx (w; pbase = its first row, pdsi = its dataset) and shifts the wanted
+// byte out.  A plain step moves to idx + 1, so on the last row of a piece the next piece is asked for
+// BEFORE phase A and arrives under it; only after a reset, a dataset switch or a step that did not
+// advance (frozen env) is the piece wrong when the step returns, and then it is loaded again, waited
+// for.  One 16-byte request per 16 steps and env where gte_backtest_kernel issues a 4-byte one per
+// step.  GTE_SIGNAL_BYTE_LOAD builds the plain variant instead (one byte per step, loaded after the
+// step it follows) for the A/B run of tools/signal_bench.py.
+// Reads stay inside the row: the piece at idx & ~15 ends before round_up(T, 16) <= stride, and the
+// speculative one is only asked for while idx + 1 < stride (`lim`).
+__global__ __launch_bounds__(256) void gte_backtest_signal_kernel(const Params p, const SignalTable* tables,
+                                                                  const int S, const int32_t* strategy,
+                                                                  gte_backtest_stats* stats, const int n_steps,
+                                                                  const int epw) {
+  const int lane = threadIdx.x & 63;
+  const int slot = (blockIdx.x * 4 + (threadIdx.x >> 6)) * epw + lane;
+  const bool active = lane < epw && slot < p.N;
+  const int e = active ? slot : 0;
+  EnvRegs s = {};
+  if (active) load_state(p, e, s);
+  gte_backtest_stats a = {};
+  if (active) load_stats(stats + e, a);
+  const int64_t strat = active ? signal_strategy(p, strategy, S, e) : 0;
+  const int8_t* row = nullptr;  // this env's row of the table of dataset pdsi
+  int32_t pdsi = -1;
+#ifndef GTE_SIGNAL_BYTE_LOAD
+  int32_t lim = 0, pbase = 0;
+  int4_t w = {0, 0, 0, 0};
+#else
+  int32_t act = -1;
+#endif
+  auto fetch = [&](int32_t idx) {
+    if (s.dsi != pdsi) {
+      const SignalTable t = tables[s.dsi];
+      row = t.base + strat * t.stride;
+      pdsi = s.dsi;
+#ifndef GTE_SIGNAL_BYTE_LOAD
+      lim = t.stride > 0x7FFFFFFFll ? 0x7FFFFFFF : (int32_t)t.stride;
+#endif
+    }
+#ifndef GTE_SIGNAL_BYTE_LOAD
+    pbase = idx & ~15;
+    w = *reinterpret_cast<const int4_t*>(row + pbase);
+#else
+    act = row[idx];
+#endif
+  };
+  if (active) fetch(s.idx);
+  PriceCarry pc = {0.0, 0.0, -1, 0};
+  ObsJob job;
+  // (a lambda like gte_backtest_kernel's step, for the same reason)
+  auto run_a = [&](int k) {
+#ifndef GTE_SIGNAL_BYTE_LOAD
+    const int32_t now = signal_action(signal_byte(w, s.idx), p.P);
+    if (active && k + 1 < n_steps && (s.idx & 15) == 15 && s.idx + 1 < lim) fetch(s.idx + 1);
+#else
+    const int32_t now = signal_action(act, p.P);
+#endif
+    double pv = 0.0;
+    StepOut so = {};
+    phase_a<MODE_STEP>(p, e, active, lane, job, nullptr, /*compact=*/false, &pv, &s, &now,
+                       /*write_record=*/k == n_steps - 1, &pc, &so);
+    if (active) backtest_step(a, p, e, s.step, pv, s.pos, so.reward, so.flags);
+#ifndef GTE_SIGNAL_BYTE_LOAD
+    if (active && k + 1 < n_steps && (s.dsi != pdsi || (s.idx & ~15) != pbase)) fetch(s.idx);
+#else
+    if (active && k + 1 < n_steps) fetch(s.idx);
+#endif
+  };
+  for (int k = 0; k < n_steps; ++k) run_a(k);
+  if (active) {
+    a.episode_seen = p.rec[e].episode;  // (this lane's own resets wrote it)
+    store_stats(stats + e, a);
+  }
+}
+
 hipError_t BacktestLaunch::begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream) {
   hipLaunchKernelGGL(gte_backtest_begin_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, stats, clear);
   return hipGetLastError();
@@ -195,6 +308,26 @@ hipError_t BacktestLaunch::summary(const Params& p, const int32_t* actions, gte_
   const int blocks = ((p.N + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES;
   hipLaunchKernelGGL(gte_backtest_kernel, dim3(blocks), dim3(64 * ROLLOUT_WAVES), 0, stream, p, actions, stats,
                      n_steps, epw);
+  return hipGetLastError();
+}
+
+hipError_t SignalLaunch::actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                 int32_t* actions, hipStream_t stream) {
+  if (!tables || S < 1 || !actions) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gte_signal_actions_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, tables, S,
+                     strategy, actions);
+  return hipGetLastError();
+}
+
+hipError_t SignalLaunch::summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                 gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream) {
+  // (the refusals of summary(), and a table to read)
+  if (p.log.rows != nullptr || (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) ||
+      epw < 1 || epw > 64 || !tables || S < 1)
+    return hipErrorInvalidValue;
+  const int blocks = ((p.N + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES;
+  hipLaunchKernelGGL(gte_backtest_signal_kernel, dim3(blocks), dim3(64 * ROLLOUT_WAVES), 0, stream, p, tables, S,
+                     strategy, stats, n_steps, epw);
   return hipGetLastError();
 }
 

@@ -84,6 +84,21 @@ struct BacktestLaunch {
   static hipError_t fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream);
 };
 
+// ... and the same with every step's action looked up in signal tables (gte_bind_signals, include/gte.h)
+struct SignalTable {  // one dataset's signal table (gte_bind_signals): row s starts at base + s * stride
+  const int8_t* base;  // null = none bound
+  int64_t stride;      // bytes, a multiple of 16 and >= round_up(T, 16)
+};
+struct SignalLaunch {
+  // the action the tables give every env for its next step (tables: device array [p.D], all bound;
+  // S strategies; strategy: device i32 [N] or null = (env_id_base + e) % S) -> actions i32 [N]
+  static hipError_t actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                            int32_t* actions, hipStream_t stream);
+  // BacktestLaunch::summary with that lookup, at the env's own row, in place of the [K][N] actions
+  static hipError_t summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                            gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream);
+};
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GTE_ABI_VERSION 4
+#define GTE_ABI_VERSION 5
 #define GTE_MAX_POSITIONS 32
 #define GTE_MAX_DYN 4
 
@@ -457,6 +457,53 @@ int gte_backtest(gte_env* env, const int32_t* actions, int32_t n_steps, int32_t 
                  gte_backtest_stats** stats_device);
 /* Records first .. first+count-1 into HOST memory: waits for the env's stream, one transfer. */
 int gte_read_backtest_stats(gte_env* env, int32_t first, int32_t count, gte_backtest_stats* out);
+
+/* ---- backtests from SIGNAL TABLES: the action of a step looked up on the device by the market row
+ * the env stands on, not by the step number.  A table is int8 [n_strategies][T] per resident
+ * dataset: entry (s, t) is the position index strategy s wants while the env is on row t of that
+ * dataset.  In the reference's terms, for env e before every step (environments.py:233-235; the
+ * trade happens at the close of row _idx, :213-215):
+ *     a = signals[dataset_index][strategy[e]][env._idx]
+ *     env.step(a if 0 <= a < n_positions else None)
+ * Any value outside [0, n_positions) means hold (None, :234); nothing in a table is validated and
+ * no table content can index out of `positions`.  Env e follows strategy strategy[e] — a DEVICE
+ * int32 [N] array with values in [0, n_strategies), which the kernels do not check: values outside
+ * that range are the caller's contract (they would read outside the table) — or, with
+ * strategy == NULL, strategy (env_id_base + e) % n_strategies, so the shards of a sharded run
+ * follow the strategies the unsharded run gives the same envs.
+ *
+ * gte_bind_signals borrows caller-owned DEVICE memory for dataset `ds` (nothing is copied, like
+ * gte_bind_outputs): row s starts at signals_device + s * row_stride.  Required: signals_device
+ * 16-byte aligned, row_stride % 16 == 0 and row_stride >= round_up(T_ds, 16) — so an aligned 16-byte
+ * load anywhere in a row is legal, which is what the fused kernel issues —, n_strategies >= 1 and
+ * equal to that of the tables bound to the other datasets (GTE_ERR_INVALID otherwise).  The dataset
+ * must have been uploaded (GTE_ERR_STATE): its T is what is checked, and a later gte_upload_dataset
+ * of `ds` unbinds its table.  signals_device == NULL unbinds.  The call waits for the env's stream
+ * and is refused inside a stream capture (GTE_ERR_STATE).  The caller keeps the memory alive while
+ * launches that read it are in flight. */
+int gte_bind_signals(gte_env* env, int32_t ds, const int8_t* signals_device, int32_t n_strategies,
+                     int64_t row_stride);
+/* One small launch that writes to actions_device (DEVICE int32 [N]) the action the tables give
+ * every env for its NEXT step, from its current record: the table value at the env's _idx and
+ * dataset_index if it lies in [0, n_positions), else -1 (hold) — the argument of the next
+ * TradingEnv.step (environments.py:233-234).  Stream-ordered and capturable: the building block of
+ * the step-by-step path, and what a caller uses to drive gte_step closed-loop.  GTE_ERR_STATE
+ * before gte_reset or while a resident dataset has no table bound. */
+int gte_signal_actions(gte_env* env, const int32_t* strategy_device, int32_t* actions_device);
+/* gte_backtest with that lookup in place of `actions`: n_steps TradingEnv.step calls
+ * (environments.py:233-272), each with the action its table gives the env on the row it stands on
+ * BEFORE the step.  A next-step auto-reset step ignores its action; a same-step reset happens
+ * inside the step and the next step looks up at the new _idx / dataset (:393-400).  Records, their
+ * order and roundings, `clear`, the post-state (records, rings, return buffers, terminal list,
+ * observation of n_steps single steps), frozen envs, limit-order fills and injected draws are
+ * exactly gte_backtest's.  Where gte_rollout fuses, n_steps - 1 steps run in one launch that keeps
+ * the aligned 16-byte piece of the strategy's row around _idx in registers (gte_backtest.hip) and
+ * the last one as gte_signal_actions + a step launch + the fold; elsewhere every step is that
+ * triple, with the same records bit for bit.  The lookup writes a library-owned int32 [N] buffer
+ * allocated by the first call.  GTE_ERR_STATE while a resident dataset has no table bound, before
+ * gte_reset and inside a stream capture. */
+int gte_backtest_signals(gte_env* env, const int32_t* strategy_device, int32_t n_steps, int32_t clear,
+                         gte_backtest_stats** stats_device);
 
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
