@@ -3,7 +3,7 @@
 // Owns the HBM-resident datasets, per-env state and outputs, validates the
 // arguments the way the reference constructor / reset do
 // (environments.py:79-125,163-199) and launches the kernels of
-// gte_kernels.hip.  No CPU path exists: without a gfx950 device every entry
+// the other units (gte_launch.h).  No CPU path exists: without a gfx950 device every entry
 // point that needs one fails with GTE_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
@@ -60,6 +60,7 @@ struct LaunchPlan {
   // L2-affinity processing order (gte_kernels.hip, "L2-affinity permutation")
   int affinity_period = 0;       // 0 = off (also set by finalize and by a failed re-sort)
   int n_bins_per_ds = 0;
+  int state_epw = 0;       // envs per wavefront of the from-registers kernels (state-only rollout, backtest)
   // rollout geometries, chosen by the first rollout that needs them
   int rollout_epw = 0;     // envs per wavefront of the fused rollout kernel (0 = not chosen yet)
   int resident_slots[3] = {0, 0, 0};  // workgroups of that geometry the chip holds at once
@@ -137,7 +138,7 @@ struct gte_env {
 };
 
 // Flag ledger.  A step stores an env's terminated / truncated bytes only where they change
-// (store_flags, gte_kernels.hip) when the two buffers hold exactly what this env's previous step
+// (store_flags, gte_phase_a.h) when the two buffers hold exactly what this env's previous step
 // stored there.  That is true only while nothing else writes them, and the host keeps the proof
 // here, process-wide (several envs may share or rotate buffers):
 //   * an env's eager step records the ranges it wrote: its next step may be sparse if it writes the
@@ -229,6 +230,15 @@ static int dev_alloc(gte_env* E, T** out, size_t count, bool zero = true) {
     int rc_ = (expr);        \
     if (rc_ != GTE_OK) return rc_; \
   } while (0)
+
+// dev_alloc after create, for a buffer the env's stream uses next: the zero-fill ran on the null
+// stream and the env's stream is non-blocking, so wait for it here
+template <typename T>
+static int dev_alloc_late(gte_env* E, T** out, size_t count) {
+  TRY(dev_alloc(E, out, count));
+  HIPCHK(hipDeviceSynchronize());
+  return GTE_OK;
+}
 
 static int validate(const gte_config* c) {
   if (!c) return fail(GTE_ERR_INVALID, "config is NULL");
@@ -380,7 +390,7 @@ static void step_geometry(gte_env* E, bool hot_ok, bool lean_ok) {
           while (e < 64 / GTE_WAVES && (int64_t)e * vpe < 64) ++e;
           epw = e;
           // Round 3: where the lean copy loop applies (whole passes of 4 wave instructions per wave,
-          // gte_kernels.hip) it beats the small workgroups above — 262 144 envs: 4 per wave 149 us,
+          // gte_step.h) it beats the small workgroups above — 262 144 envs: 4 per wave 149 us,
           // 8: 139.8, 16: 137.8; 131 072: 4: 80, 8: 74, 16: 71-78; 100 003: 6: 62, 8: 58.7, 16: 60-67
           // (profiles/r03_epw_hbm.log) — so take the smallest envs-per-wave the lean loop accepts, twice
           // that from 200 000 envs on.
@@ -456,7 +466,7 @@ static int plan_launches(gte_env* E) {
   Params& p = E->p;
   const gte_config& cfg = E->cfg;
   const int kv = cfg.kernel_variant;
-  // observation store policy (gte_kernels.hip, store_out): while the observation buffer fits
+  // observation store policy (gte_step.h, store_out): while the observation buffer fits
   // the 256 MB Infinity Cache next to the feature table, sc1 stores keep it there (65 536 envs,
   // 168 MB: 42.5 us vs 45.8 us with nt); beyond that the stores are a pure stream and
   // non-temporal ones win (81 920 envs, 210 MB: 48 us vs 58 us; 262 144 envs: 162 us vs 261 us)
@@ -466,7 +476,7 @@ static int plan_launches(gte_env* E) {
   p.debug = cfg.debug_flags;
   L.coop = (p.epw * GTE_WAVES <= 64) && !(kv & GTE_KV_PER_WAVE_PHASE_A);
   L.stage = (p.nd > 0 && gte::lds_bytes(p, 1) <= 48 * 1024 && !(kv & GTE_KV_NO_LDS_STAGING)) ? (p.persist ? 2 : 1) : 0;
-  // the lean copy loop (gte_kernels.hip): 16-byte vectors with the raw rings staged in LDS (stage 1;
+  // the lean copy loop (gte_step.h): 16-byte vectors with the raw rings staged in LDS (stage 1;
   // dyn_persist takes stage 2)
   p.lean_rows = (L.vec == 4 && L.stage == 1 && !(kv & GTE_KV_GENERIC_COPY)) ? 1 : 0;
   p.hot_lds = (kv & GTE_KV_RECORD_DIRECT) ? 0 : 1;  // (A/B: the stepping lane stores its record itself)
@@ -484,6 +494,11 @@ static int plan_launches(gte_env* E) {
   L.always_dense = (kv & GTE_KV_DENSE_FLAGS) != 0;  // (A/B of the sparse flag stores)
   L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & GTE_KV_ROLLOUT_PER_STEP);
   L.resident_rollout = p.W >= 2 && !(kv & GTE_KV_ROLLOUT_GATHER);
+  // envs per wavefront from registers: full waves once every SIMD has one (65 536 envs: 5.8 us per step
+  // with 64, 6.0 with 32, 9.2 with 16 — throughput of the scattered record / ring stores);
+  // small batches are a latency chain and two half-filled waves overlap better (4 096 envs:
+  // 3.5 us with 32, 3.9 with 64) — profiles/r02_state_epw.log
+  L.state_epw = (p.N >= 64 * 1024) ? 64 : 32;
   return setup_affinity(E);
 }
 
@@ -1101,12 +1116,7 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
       // per-env loads and stores (actions, rewards, flags) that are coalesced in env order
       Params ps = E->p;
       ps.perm = nullptr;
-      // envs per wavefront: full waves once every SIMD has one (65 536 envs: 5.8 us per step
-      // with 64, 6.0 with 32, 9.2 with 16 — throughput of the scattered record / ring stores);
-      // small batches are a latency chain and two half-filled waves overlap better (4 096 envs:
-      // 3.5 us with 32, 3.9 with 64) — profiles/r02_state_epw.log
-      const int sepw = (E->p.N >= 64 * 1024) ? 64 : 32;
-      const hipError_t le = gte::launch_rollout_state(ps, r, n_steps - 1, sepw, E->stream);
+      const hipError_t le = gte::launch_rollout_state(ps, r, n_steps - 1, L.state_epw, E->stream);
       if (le != hipSuccess) return fail(GTE_ERR_HIP, "rollout launch: %s", hipGetErrorString(le));
     }
     TRY(step_row(n_steps - 1));
@@ -1121,10 +1131,7 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
       // per-step gather; here one row per env and step is read, and consecutive envs make each
       // workgroup's observation stores one contiguous run
       p.perm = nullptr;
-      if (!E->d_group_counter) {
-        TRY(dev_alloc(E, &E->d_group_counter, 4));
-        HIPCHK(hipDeviceSynchronize());  // (the zero-fill ran on the null stream)
-      }
+      if (!E->d_group_counter) TRY(dev_alloc_late(E, &E->d_group_counter, 4));
       HIPCHK(hipMemsetAsync(E->d_group_counter, 0, sizeof(int32_t), E->stream));
       const int epb = L.resident_epb[nt];
       const int n_groups = (p.N + epb - 1) / epb;
@@ -1136,7 +1143,7 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
     } else {
       if (L.rollout_epw == 0) choose_rollout_epw(E, p, nt);
       p.epw = L.rollout_epw;
-      const int r_blocks = (int)((((int64_t)p.N + p.epw - 1) / p.epw + gte::ROLLOUT_WAVES - 1) / gte::ROLLOUT_WAVES);
+      const int r_blocks = gte::rollout_blocks(p.N, p.epw);
       gte::RolloutArgs r = {actions, n_steps, b->obs, b->reward, b->reward64, b->terminated,
                             b->truncated, b->valuation, 0, 0, nullptr};
       const hipError_t le = gte::launch_rollout(p, r, nt, r_blocks, E->stream);
@@ -1176,14 +1183,10 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   const size_t N = (size_t)E->p.N;
   const LaunchPlan& L = E->plan;
   const bool signals = actions == nullptr;
-  if (signals && !E->d_sig_actions) {
-    TRY(dev_alloc(E, &E->d_sig_actions, N));
-    HIPCHK(hipDeviceSynchronize());  // (the zero-fill ran on the null stream)
-  }
+  if (signals && !E->d_sig_actions) TRY(dev_alloc_late(E, &E->d_sig_actions, N));
   if (!E->bt_stats) {
-    TRY(dev_alloc(E, &E->bt_stats, N));
     if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->bt_final_rec, N));
-    HIPCHK(hipDeviceSynchronize());  // (the zero-fill ran on the null stream)
+    TRY(dev_alloc_late(E, &E->bt_stats, N));  // (its wait covers the fill before it too)
     clear = 1;
   }
   // same-step mode: the terminal valuation comes from the terminal records, the env's or our own
@@ -1191,19 +1194,19 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   Params ps = E->p;
   ps.perm = nullptr;  // identity order, as in the state-only rollout: per-env loads and stores coalesce
   ps.final_rec = terminal;
-  hipError_t le = gte::BacktestLaunch::begin(ps, E->bt_stats, clear, E->stream);
+  hipError_t le = gte::launch_backtest_begin(ps, E->bt_stats, clear, E->stream);
   if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   // one step as an ordinary launch (it also produces the observation and the terminal list), then
   // its results into the records
   auto step_and_fold = [&](int32_t k) -> int {
     if (signals) {
-      const hipError_t se = gte::SignalLaunch::actions(E->p, E->d_sig, E->sig_S, strategy,
-                                                                E->d_sig_actions, E->stream);
+      const hipError_t se = gte::launch_signal_actions(E->p, E->d_sig, E->sig_S, strategy, E->d_sig_actions,
+                                                       E->stream);
       if (se != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(se));
     }
     const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
     TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->bt_final_rec));
-    const hipError_t fe = gte::BacktestLaunch::fold(ps, E->bt_stats, E->stream);
+    const hipError_t fe = gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
     if (fe != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(fe));
     return GTE_OK;
   };
@@ -1216,14 +1219,27 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   else report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
   if (n_steps > 1) {
     TRY(age_order(E, n_steps - 1));
-    // envs per wavefront: launch_rollout_state's choice (profiles/r02_state_epw.log)
-    const int sepw = (E->p.N >= 64 * 1024) ? 64 : 32;
-    le = signals ? gte::SignalLaunch::summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats,
-                                                        n_steps - 1, sepw, E->stream)
-                 : gte::BacktestLaunch::summary(ps, actions, E->bt_stats, n_steps - 1, sepw, E->stream);
+    le = signals ? gte::launch_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, n_steps - 1,
+                                              L.state_epw, E->stream)
+                 : gte::launch_backtest_summary(ps, actions, E->bt_stats, n_steps - 1, L.state_epw, E->stream);
     if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   }
   return step_and_fold(n_steps - 1);
+}
+
+// what gte_backtest and gte_backtest_signals (`who`) share once their own arguments are checked
+static int backtest_entry(gte_env* E, const char* who, const int32_t* actions, const int32_t* strategy,
+                          int32_t n_steps, int32_t clear, gte_backtest_stats** stats_device) {
+  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
+  if (stream_capturing(E))
+    return fail(GTE_ERR_STATE, "%s inside a stream capture: a backtest is one launch already, run it eagerly", who);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const int rc = backtest(E, actions, strategy, n_steps, clear);
+  // the fused kernel writes flags into the env's buffers (flag ledger)
+  const size_t N = (size_t)E->p.N;
+  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}});
+  if (stats_device) *stats_device = E->bt_stats;
+  return rc;
 }
 
 int gte_backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t clear,
@@ -1231,17 +1247,7 @@ int gte_backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t cl
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_backtest before gte_reset");
   if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
-  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
-  if (stream_capturing(E))
-    return fail(GTE_ERR_STATE, "gte_backtest inside a stream capture: a backtest is one launch already, "
-                               "run it eagerly");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const int rc = backtest(E, actions, nullptr, n_steps, clear);
-  // the fused kernel writes flags into the env's buffers (flag ledger)
-  const size_t N = (size_t)E->p.N;
-  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}});
-  if (stats_device) *stats_device = E->bt_stats;
-  return rc;
+  return backtest_entry(E, "gte_backtest", actions, nullptr, n_steps, clear, stats_device);
 }
 
 int gte_bind_signals(gte_env* E, int32_t d, const int8_t* signals_device, int32_t n_strategies,
@@ -1291,8 +1297,8 @@ int gte_signal_actions(gte_env* E, const int32_t* strategy_device, int32_t* acti
   if (!actions_device) return fail(GTE_ERR_INVALID, "actions is NULL");
   TRY(signals_ready(E, "gte_signal_actions"));
   if (!stream_capturing(E)) HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::SignalLaunch::actions(E->p, E->d_sig, E->sig_S, strategy_device,
-                                                           actions_device, E->stream);
+  const hipError_t e = gte::launch_signal_actions(E->p, E->d_sig, E->sig_S, strategy_device, actions_device,
+                                                  E->stream);
   if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal lookup launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
@@ -1301,16 +1307,7 @@ int gte_backtest_signals(gte_env* E, const int32_t* strategy_device, int32_t n_s
                          gte_backtest_stats** stats_device) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   TRY(signals_ready(E, "gte_backtest_signals"));
-  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
-  if (stream_capturing(E))
-    return fail(GTE_ERR_STATE, "gte_backtest_signals inside a stream capture: a backtest is one launch already, "
-                               "run it eagerly");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const int rc = backtest(E, nullptr, strategy_device, n_steps, clear);
-  const size_t N = (size_t)E->p.N;
-  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}});  // (as gte_backtest)
-  if (stats_device) *stats_device = E->bt_stats;
-  return rc;
+  return backtest_entry(E, "gte_backtest_signals", nullptr, strategy_device, n_steps, clear, stats_device);
 }
 
 int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backtest_stats* out) {

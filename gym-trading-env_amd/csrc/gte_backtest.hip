@@ -23,8 +23,7 @@
 // (tests/test_gpu_backtest.py).  This unit is compiled WITHOUT GTE_HOT_ONLY: in same-step mode phase A
 // has already reset the env when it returns, and the terminal valuation is what it stored in the
 // terminal record (p.final_rec) just before — the lane that wrote it reads it back in program order.
-#define GTE_PHASE_A_ONLY 1
-#include "gte_kernels.hip"
+#include "gte_phase_a.h"
 
 namespace gte {
 
@@ -293,25 +292,27 @@ __global__ __launch_bounds__(256) void gte_backtest_signal_kernel(const Params p
   }
 }
 
-hipError_t BacktestLaunch::begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream) {
+hipError_t launch_backtest_begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream) {
   hipLaunchKernelGGL(gte_backtest_begin_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, stats, clear);
   return hipGetLastError();
 }
 
-hipError_t BacktestLaunch::summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, int n_steps,
+// what the from-registers kernels do not do: trajectory rows (the step kernel writes them, gte_kernel);
+// and in same-step mode they need somewhere for the terminal records
+static bool summary_refused(const Params& p, int epw) {
+  return p.log.rows != nullptr || (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) ||
+         epw < 1 || epw > 64;
+}
+
+hipError_t launch_backtest_summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, int n_steps,
                                    int epw, hipStream_t stream) {
-  // what this kernel does not do: trajectory rows (the step kernel writes them, gte_kernel); and in
-  // same-step mode it needs somewhere for the terminal records
-  if (p.log.rows != nullptr || (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) ||
-      epw < 1 || epw > 64)
-    return hipErrorInvalidValue;
-  const int blocks = ((p.N + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES;
-  hipLaunchKernelGGL(gte_backtest_kernel, dim3(blocks), dim3(64 * ROLLOUT_WAVES), 0, stream, p, actions, stats,
-                     n_steps, epw);
+  if (summary_refused(p, epw)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gte_backtest_kernel, dim3(rollout_blocks(p.N, epw)), dim3(64 * ROLLOUT_WAVES), 0, stream, p,
+                     actions, stats, n_steps, epw);
   return hipGetLastError();
 }
 
-hipError_t SignalLaunch::actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+hipError_t launch_signal_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
                                  int32_t* actions, hipStream_t stream) {
   if (!tables || S < 1 || !actions) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gte_signal_actions_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, tables, S,
@@ -319,19 +320,15 @@ hipError_t SignalLaunch::actions(const Params& p, const SignalTable* tables, int
   return hipGetLastError();
 }
 
-hipError_t SignalLaunch::summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+hipError_t launch_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
                                  gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream) {
-  // (the refusals of summary(), and a table to read)
-  if (p.log.rows != nullptr || (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) ||
-      epw < 1 || epw > 64 || !tables || S < 1)
-    return hipErrorInvalidValue;
-  const int blocks = ((p.N + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES;
-  hipLaunchKernelGGL(gte_backtest_signal_kernel, dim3(blocks), dim3(64 * ROLLOUT_WAVES), 0, stream, p, tables, S,
-                     strategy, stats, n_steps, epw);
+  if (summary_refused(p, epw) || !tables || S < 1) return hipErrorInvalidValue;  // ... and a table to read
+  hipLaunchKernelGGL(gte_backtest_signal_kernel, dim3(rollout_blocks(p.N, epw)), dim3(64 * ROLLOUT_WAVES), 0, stream,
+                     p, tables, S, strategy, stats, n_steps, epw);
   return hipGetLastError();
 }
 
-hipError_t BacktestLaunch::fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream) {
+hipError_t launch_backtest_fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream) {
   if (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gte_backtest_fold_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, stats);
   return hipGetLastError();

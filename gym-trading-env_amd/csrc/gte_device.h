@@ -110,7 +110,7 @@ struct Params {
   const int32_t* perm; // processing slot -> env id (L2-affinity order), or null = identity
   int32_t epw;         // environments per wavefront
   int32_t debug;       // gte_config.debug_flags (timing ablations)
-  int32_t lean_rows;   // != 0: full waves of 16-byte-vector windows take the lean copy loop (gte_kernels.hip)
+  int32_t lean_rows;   // != 0: full waves of 16-byte-vector windows take the lean copy loop (gte_step.h)
   int32_t hot_lds;     // != 0: a step's record stores go through LDS, one 64-byte request per env (gte_kernel)
   int32_t flags_sparse;  // != 0: terminated / truncated hold what each env's previous step stored there
                          // (EnvRec.flags_out), so a step stores only the flags that change (gte_step decides)
@@ -143,7 +143,7 @@ __device__ inline int64_t log_row(int64_t count, int L) {
 // (p.final_rec, environments.py:272 in same-step mode) and the trajectory row written by the
 // kernel itself (p.log).  This is the ONE statement of that list: gte_step picks the kernel with
 // it, the hot launchers refuse any launch it does not cover (hipErrorInvalidValue -> GTE_ERR_HIP),
-// and every `#ifndef GTE_HOT_ONLY` block inside phase A names a field tested here.  Round 2
+// and every `#ifndef GTE_HOT_ONLY` block (gte_phase_a.h, gte_step.h) names a field tested here.  Round 2
 // shipped a launch predicate that had drifted from the compiled-out store: final_info read
 // zero-filled records at every 16-byte-vector shape.
 inline bool hot_tu_covers(const Params& p) { return p.final_rec == nullptr && p.log.rows == nullptr; }

@@ -9,7 +9,7 @@
 
 namespace gte {
 
-// lean copy loop (gte_kernels.hip): window rows of one wave's envs the in-place resolve holds in registers,
+// lean copy loop (gte_step.h): window rows of one wave's envs the in-place resolve holds in registers,
 // and the vectors in flight per lane (a wave copies whole passes of 64 * GTE_LEAN_U)
 constexpr int LEAN_MAX_ROWS = 512;
 #ifndef GTE_LEAN_U
@@ -17,6 +17,10 @@ constexpr int LEAN_MAX_ROWS = 512;
 #endif
 // rollout kernels (gte_rollout.hip): workgroups of four wavefronts, whatever GTE_WAVES is
 constexpr int ROLLOUT_WAVES = 4;
+// ... and how many of them give every env a lane at epw envs per wavefront
+inline int rollout_blocks(int n_envs, int epw) {
+  return (int)((((int64_t)n_envs + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES);
+}
 // window-resident kernel: waves 1..3 (RES_OWNERS threads) carry the newest window rows of the workgroup's envs,
 // at most RES_NEW vectors each; a geometry with more of them than RES_NEW * RES_OWNERS would drop some
 constexpr int RES_NEW = 2;
@@ -24,7 +28,7 @@ constexpr int RES_OWNERS = 192;
 constexpr size_t RES_LDS_MAX = 160 * 1024;  // LDS of a gfx950 CU: the most a workgroup's image may take
 constexpr size_t LDS_OPT_IN = 64 * 1024;    // dynamic LDS beyond this is opted into, per instantiation
 
-// 40-bit magic of the kernels' divisions by a launch constant (fastdiv40, gte_kernels.hip)
+// 40-bit magic of the kernels' divisions by a launch constant (fastdiv40, gte_step.h)
 inline uint64_t magic40(uint32_t d) { return ((1ull << 40) + d - 1) / d; }
 
 // --- gte_kernels.hip (shared translation unit): every step / reset shape, helper kernels
@@ -71,33 +75,28 @@ int rollout_blocks_per_cu(const Params& p, int nt);
 hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, hipStream_t stream);
 
 // --- gte_backtest.hip: K steps in one launch that keep per-env statistics instead of per-step rows
-// (static members: the definitions in gte_backtest.hip are checked against these by the compiler)
-struct BacktestLaunch {
-  // clear != 0: zero the records and anchor them at the envs' current state; else bring the
-  // bookkeeping fields up to date with the records (a gte_reset since the previous call)
-  static hipError_t begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream);
-  // n_steps steps from registers (the geometry of launch_rollout_state); p.final_rec must be set in
-  // same-step mode: the lane that wrote an env's terminal record reads the terminal valuation back
-  static hipError_t summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, int n_steps,
-                            int epw, hipStream_t stream);
-  // ONE step into the records, from what an ordinary step launch left in p's buffers
-  static hipError_t fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream);
-};
+// clear != 0: zero the records and anchor them at the envs' current state; else bring the
+// bookkeeping fields up to date with the records (a gte_reset since the previous call)
+hipError_t launch_backtest_begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream);
+// n_steps steps from registers (the geometry of launch_rollout_state); p.final_rec must be set in
+// same-step mode: the lane that wrote an env's terminal record reads the terminal valuation back
+hipError_t launch_backtest_summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, int n_steps,
+                                   int epw, hipStream_t stream);
+// ONE step into the records, from what an ordinary step launch left in p's buffers
+hipError_t launch_backtest_fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream);
 
 // ... and the same with every step's action looked up in signal tables (gte_bind_signals, include/gte.h)
 struct SignalTable {  // one dataset's signal table (gte_bind_signals): row s starts at base + s * stride
   const int8_t* base;  // null = none bound
   int64_t stride;      // bytes, a multiple of 16 and >= round_up(T, 16)
 };
-struct SignalLaunch {
-  // the action the tables give every env for its next step (tables: device array [p.D], all bound;
-  // S strategies; strategy: device i32 [N] or null = (env_id_base + e) % S) -> actions i32 [N]
-  static hipError_t actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                            int32_t* actions, hipStream_t stream);
-  // BacktestLaunch::summary with that lookup, at the env's own row, in place of the [K][N] actions
-  static hipError_t summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                            gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream);
-};
+// the action the tables give every env for its next step (tables: device array [p.D], all bound;
+// S strategies; strategy: device i32 [N] or null = (env_id_base + e) % S) -> actions i32 [N]
+hipError_t launch_signal_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                 int32_t* actions, hipStream_t stream);
+// launch_backtest_summary with that lookup, at the env's own row, in place of the [K][N] actions
+hipError_t launch_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                 gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream);
 
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,

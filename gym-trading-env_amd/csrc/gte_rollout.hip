@@ -27,7 +27,7 @@
 // Shapes: 16-byte vectors, W-deep rings (no dyn_persist), no final_obs; gte_rollout() falls
 // back to K launches of the step kernel otherwise.
 #define GTE_HOT_ONLY 1
-#include "gte_kernels.hip"
+#include "gte_step.h"
 #include <type_traits>
 
 namespace gte {
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(256) void gte_rollout_state_kernel(const Params p0,
 
 hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_steps, int epw, hipStream_t stream) {
   if (!hot_tu_covers(p)) return hipErrorInvalidValue;  // this TU is compiled with GTE_HOT_ONLY (gte_device.h)
-  const int blocks = ((p.N + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES;  // epw envs per wavefront
+  const int blocks = rollout_blocks(p.N, epw);  // epw envs per wavefront
   hipLaunchKernelGGL(gte_rollout_state_kernel, dim3(blocks), dim3(64 * ROLLOUT_WAVES), 0, stream, p, r, n_steps, epw);
   return hipGetLastError();
 }

@@ -44,7 +44,7 @@ def facts(g):
 
 
 def _lean(f, nd):
-    # the lean copy loop (gte_kernels.hip): 16-byte vectors, raw rings staged in LDS (not
+    # the lean copy loop (gte_step.h): 16-byte vectors, raw rings staged in LDS (not
     # dyn_persist), a window of at least one wave instruction (256 floats)
     return (f["nd"] == nd and f["Fobs"] % 4 == 0 and f["W"] is not None and f["W"] * f["Fobs"] >= 256
             and not f["persist"])

@@ -2,7 +2,6 @@
 and a hand-computed sequence, and the ABI struct's layout against the C header.  No GPU."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -158,19 +157,3 @@ def test_backtest_stats_layout_matches_the_c_header(tmp_path):
     # the model names the public fields of the record, and no other
     assert set(bm.FIELDS) == {n for n, _ in _abi.BACKTEST_FIELDS} - {"ended", "episode_seen", "step_seen"}
 
-
-def test_backtest_launchers_are_declared_in_gte_launch_h_and_built():
-    """The new translation unit's launchers cross a file boundary: declared once, in gte_launch.h
-    (as static members, so the compiler holds the definitions to them), defined in
-    gte_backtest.hip, which the Makefile builds."""
-    csrc = os.path.join(ROOT, "gym-trading-env_amd", "csrc")
-    read = lambda f: open(os.path.join(csrc, f)).read()
-    body = re.search(r"struct BacktestLaunch \{(.*?)\n\};", read("gte_launch.h"), re.S).group(1)
-    names = re.findall(r"static hipError_t (\w+)\(", body)
-    assert sorted(names) == ["begin", "fold", "summary"]
-    unit, api = read("gte_backtest.hip"), read("gte_api.hip")
-    for n in names:
-        assert re.search(rf"^hipError_t BacktestLaunch::{n}\(", unit, re.M), n
-        assert f"gte::BacktestLaunch::{n}(" in api, n
-    assert "#define GTE_HOT_ONLY" not in unit  # phase A with the terminal-record store compiled in
-    assert "gte_backtest.hip" in read("Makefile")

@@ -55,7 +55,7 @@ def _replay_exact(a, g, tile=1, tag=""):
 
 def _lean_epws(f):
     """envs per wave (<= 16, cooperative phase A) at which whole waves take the lean copy loop
-    (gte_kernels.hip: n_env * W <= 512 rows, whole passes of 4 wave instructions)."""
+    (gte_step.h: n_env * W <= 512 rows, whole passes of 4 wave instructions)."""
     if not strata._lean(f, f["nd"]) or f["nd"] == 0:
         return []
     vpe = f["W"] * f["Fobs"] // 4

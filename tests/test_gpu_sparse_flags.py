@@ -1,4 +1,4 @@
-"""Sparse terminated / truncated stores (gte_kernels.hip store_flags, gte_api.hip "Flag ledger"): a
+"""Sparse terminated / truncated stores (gte_phase_a.h store_flags, gte_api.hip "Flag ledger"): a
 step stores only the flags that change when the host has proved that the buffers hold what the env's
 previous step stored there.  Every case below runs an env next to an untouched twin that always
 stores densely (kernel_variant KV_DENSE_FLAGS) and compares all four return arrays and the terminal list

@@ -210,12 +210,14 @@ def _resource_usage(source):
 
 
 @pytest.mark.parametrize("source,min_occupancy", [("gte_hot.hip", 6), ("gte_hot_nt.hip", 6),
-                                                  ("gte_rollout.hip", 4)])
+                                                  ("gte_rollout.hip", 4), ("gte_backtest.hip", 3)])
 def test_kernel_register_budget(source, min_occupancy):
     """The step kernel's speed hangs on its register allocation: one occupancy step costs
     10+ us per step, and scratch use doubles the store traffic.  A change to the
     shared device code that pushes the hot instantiations over their budget fails here, on the
-    CPU, before anything is measured."""
+    CPU, before anything is measured.  gte_backtest.hip: its two from-registers kernels carry an env
+    and its statistics record through all fused steps (142 and 152 VGPRs, 3 waves/SIMD); written as
+    a plain loop body the compiler kept the env's registers in scratch memory."""
     for k in _resource_usage(source):
         assert k["scratch"] == 0, k
         assert k["occupancy"] >= min_occupancy, k
@@ -232,21 +234,24 @@ def test_features_compiled_out_of_the_hot_translation_units_are_guarded():
     read = lambda f: open(os.path.join(csrc, f)).read()
     dev = read("gte_device.h")
     body = re.search(r"inline bool hot_tu_covers\(const Params& p\) \{(.*?)\}", dev, re.S).group(1)
-    kernels = read("gte_kernels.hip")
-    # blocks inside device code carry `// p.<field>:`; the two file-scope blocks (host launchers,
-    # helper kernels of the shared TU) do not touch phase A
-    blocks = re.findall(r"#ifndef GTE_HOT_ONLY(.*)", kernels)
+    # every block, in whichever file, carries `// p.<field>:` (the shared device code lives in headers:
+    # no block merely fences off what an including file must not get)
+    blocks = [b for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))
+              for b in re.findall(r"^#ifndef GTE_HOT_ONLY(.*)", read(f), re.M)]
     fields = [re.match(r"\s*//\s*p\.([a-z_]+)", b) for b in blocks]
     named = [m.group(1) for m in fields if m]
-    assert len(blocks) - len(named) == 2, "an #ifndef GTE_HOT_ONLY block inside phase A does not name its field"
+    assert len(blocks) >= 4 and len(blocks) - len(named) == 0, "an #ifndef GTE_HOT_ONLY block does not name its field"
     assert sorted(set(named)) == ["final_rec", "log"]
     for f in set(named):
         assert re.search(rf"p\.{f}\b", body), f"hot_tu_covers does not test p.{f}"
     api = read("gte_api.hip")
     assert re.search(r"const bool hot = [^;]*gte::hot_tu_covers\(p\)", api)
-    for tu in ("gte_hot.hip", "gte_rollout.hip"):
-        src = read(tu)
-        assert "#define GTE_HOT_ONLY 1" in src
+    # (the two hot units are macro definitions plus the include of their launcher)
+    for tu, holds_launcher in (("gte_hot.hip", "gte_hot_body.h"), ("gte_hot_nt.hip", "gte_hot_body.h"),
+                               ("gte_rollout.hip", "gte_rollout.hip")):
+        assert "#define GTE_HOT_ONLY 1" in read(tu)
+        assert holds_launcher == tu or f'#include "{holds_launcher}"' in read(tu)
+        src = read(holds_launcher)
         launchers = re.findall(r"hipError_t (?:GTE_HOT_NAME\()?(launch_[a-z_]+)\)?\(const Params& p.*?\n\}", src, re.S)
         assert launchers
         for m in re.finditer(r"hipError_t (?:GTE_HOT_NAME\()?launch_[a-z_]+\)?\(const Params& p.*?\n\}", src, re.S):
@@ -320,17 +325,53 @@ def test_gte_api_declares_no_gte_function_itself():
     assert _signatures(api) == {}
 
 
+def _makefile_srcs():
+    makefile = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
+    return re.search(r"^SRCS = (.*)$", makefile, re.M).group(1).split()
+
+
+def _included(src, name):
+    """every file of csrc/ that `name` includes, directly or through another"""
+    seen, todo = set(), [name]
+    while todo:
+        for inc in re.findall(r'^#include "([^"/]+)"', src[todo.pop()], re.M):
+            if inc not in seen:
+                seen.add(inc)
+                todo.append(inc)
+    return seen
+
+
+def test_device_code_is_shared_through_headers_only():
+    """No translation unit doubles as the header of another: nothing includes a .hip, every .hip under
+    csrc/ is a unit the Makefile builds, and the macro that fenced gte_kernels.hip's own kernels off from
+    an including file is gone with the include."""
+    csrc = os.path.join(ROOT, "gym-trading-env_amd", "csrc")
+    texts = {n: open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc))
+             if n.endswith((".hip", ".h")) or n == "Makefile"}
+    for name, text in texts.items():
+        assert not re.search(r'#\s*include\s*"[^"]*\.hip"', text), f"{name} includes a .hip file"
+        assert "GTE_PHASE_A_ONLY" not in text, name
+    assert sorted(n for n in texts if n.endswith(".hip")) == sorted(_makefile_srcs())
+
+
 def test_cross_file_functions_are_declared_once_in_gte_launch_h():
-    """Every non-static gte:: function a .hip file defines is declared in gte_launch.h with the same
-    signature — and the defining file includes that header (directly or through gte_kernels.hip), so
-    the compiler checks the return type as well."""
+    """Every non-static gte:: function a translation unit of the Makefile's SRCS defines (itself, or in a
+    header that holds its body: gte_hot_body.h) is declared in gte_launch.h with the same signature —
+    and the defining file includes that header (directly or through another), so the compiler checks
+    the return type as well."""
     src = _csrc_sources()
     declared = _signatures(src["gte_launch.h"])
     assert len(declared) >= 30 and not any(is_def for _, is_def in declared.values())
+    units = [u for u in _makefile_srcs() if u != "gte_api.hip"]
+    assert "gte_backtest.hip" in units and "gte_hot_nt.hip" in units and len(units) >= 7
+    # gte_hot.hip and gte_hot_nt.hip compile one body under two names: GTE_HOT_NAME(x) = x and x_nt
+    assert [u for u in units if "gte_hot_body.h" in _included(src, u)] == ["gte_hot.hip", "gte_hot_nt.hip"]
+    assert "#define GTE_HOT_NAME(x) x\n" in src["gte_hot.hip"] and "#define GTE_HOT_NAME(x) x##_nt\n" in src["gte_hot_nt.hip"]
+    assert not any(d.endswith(".hip") for d in src if d not in _makefile_srcs())
     defined = {}
-    for name in ("gte_kernels.hip", "gte_hot.hip", "gte_aux.hip", "gte_rollout.hip", "gte_comm.hip"):
+    for name in units + sorted(h for h in src if h.endswith(".h") and h != "gte_launch.h"):
         text = src[name]
-        assert '#include "gte_launch.h"' in text or '#include "gte_kernels.hip"' in text, name
+        assert name == "gte_device.h" or "gte_launch.h" in _included(src, name), name
         for fn, (sig, is_def) in _signatures(text).items():
             assert is_def, f"{name} declares {fn} itself"
             assert fn not in defined, f"{fn} is defined in {name} and in {defined[fn]}"
@@ -338,8 +379,17 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
             assert fn in declared, f"{name}: {fn} is not declared in gte_launch.h"
             assert declared[fn][0] == sig, f"{name}: {sig}  !=  {declared[fn][0]}"
     assert "launch_step_hot_nt" in defined and "rccl_load" in defined and "launch_pack_log" in defined
+    assert defined["launch_step_hot"] == defined["hot_blocks_per_cu_nt"] == "gte_hot_body.h"
+    for fn in ("launch_backtest_begin", "launch_backtest_summary", "launch_backtest_fold",
+               "launch_signal_actions", "launch_signal_summary"):
+        assert defined.get(fn) == "gte_backtest.hip", fn
+        assert f"gte::{fn}(" in src["gte_api.hip"], fn
     assert sorted(declared) == sorted(defined), "gte_launch.h declares a function no file defines"
-    assert "gte_launch.h" in open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
+    # gte_backtest.hip runs phase A with the terminal-record store compiled in
+    assert "#define GTE_HOT_ONLY" not in src["gte_backtest.hip"]
+    makefile = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
+    hdrs = re.search(r"^HDRS = (.*)$", makefile, re.M).group(1).split()
+    assert sorted(h for h in src if h.endswith(".h")) == sorted(h for h in hdrs if "/" not in h)
 
 
 _HOLDS_VARIANT = re.compile(r"(?i:variant)|^kv$|^DENSE$|^ROLLOUT")  # names of things that hold kernel_variant bits
