@@ -92,6 +92,7 @@ class GteConfig(C.Structure):
         ("log_steps", C.c_int32),
         ("reserved2", C.c_int32),
         ("final_obs", C.c_int32),
+        ("obs_slack_rows", C.c_int32),
     ]
 
 
@@ -149,6 +150,13 @@ class GteOutputs(C.Structure):
         ("reserved0", C.c_int32),
         ("final_obs", C.c_void_p),
     ]
+
+
+class GteObsView(C.Structure):
+    """struct gte_obs_view_t: where the current observation lives (sliding observation buffer)."""
+
+    _fields_ = [("base", C.c_void_p), ("rows_per_env", C.c_int32), ("head", C.c_int32),
+                ("sliding", C.c_int32), ("slack_rows", C.c_int32)]
 
 
 class GteStateView(C.Structure):
@@ -244,6 +252,8 @@ SYMBOLS = {
     "gte_get_outputs": (C.c_int, [C.c_void_p, _P(GteOutputs)]),
     "gte_get_state": (C.c_int, [C.c_void_p, _P(GteStateView)]),
     "gte_bind_outputs": (C.c_int, [C.c_void_p, _P(GteOutputs)]),
+    "gte_obs_view": (C.c_int, [C.c_void_p, _P(GteObsView)]),
+    "gte_bind_sliding_obs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "gte_read_env": (C.c_int, [C.c_void_p, C.c_int32, _P(GteEnvSnapshot), C.c_void_p]),
     "gte_read_envs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gte_read_envs_view": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

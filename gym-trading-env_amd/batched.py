@@ -150,7 +150,8 @@ class BatchedTradingEnv(_VectorEnvBase):
                  episodes_between_dataset_switch=1, dyn_persist=False, seed=0,
                  env_id_base=0, device=0, output="torch", envs_per_wave=0,
                  nontemporal_obs=3, kernel_variant=0, library_path=None, debug_flags=0,
-                 affinity_period=0, final_obs=False, log_steps=0, return_slots=1, copy=True):
+                 affinity_period=0, final_obs=False, log_steps=0, return_slots=1, copy=True,
+                 obs_slack_rows=0):
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         if output not in ("torch", "numpy"):
             raise ValueError("output must be 'torch' or 'numpy'")
@@ -226,7 +227,8 @@ class BatchedTradingEnv(_VectorEnvBase):
             dyn_persist=dyn_persist, seed=seed, env_id_base=env_id_base, device=device,
             envs_per_wave=envs_per_wave, nontemporal_obs=nontemporal_obs,
             kernel_variant=kernel_variant, debug_flags=debug_flags,
-            affinity_period=affinity_period, final_obs=final_obs, log_steps=log_steps)
+            affinity_period=affinity_period, final_obs=final_obs, log_steps=log_steps,
+            obs_slack_rows=obs_slack_rows)
         self.log_metrics = []
         self.info_keys = history_columns(self) + ["dataset_index"]
         self._ds_offsets = np.concatenate([[0], np.cumsum([d.T for d in self.datasets])]).astype(np.int64)
@@ -255,6 +257,9 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._snap_epoch, self._snap, self._snap_obs = -1, None, None  # numpy mode, per step
         self._torch = None
         self._t = {}
+        # sliding observation buffer (torch output, where the library grants it): [N, W + M, F_obs] and
+        # its M + 1 window views, one per head; _t["obs"] is the view at the library's current head
+        self._obs_slab, self._obs_views, self._obs_view = None, None, _abi.GteObsView()
         if output == "torch":
             self._bind_torch_outputs()
         # the values `position` takes, on the device in torch mode
@@ -339,8 +344,16 @@ class BatchedTradingEnv(_VectorEnvBase):
             # outputs start bound to row 0 (reset writes there); the first step rotates to it
             self._ret_slot = self.return_slots - 1
             self.packed_returns = self._packed[0]
+            # obs: a sliding buffer where the library grants one (gte.h, gte_bind_sliding_obs), bound below
+            _abi.check(self._lib, self._lib.gte_obs_view(self._h, C.byref(self._obs_view)))
+            M = int(self._obs_view.slack_rows)
+            if M > 0:
+                W, F = self.obs_shape
+                self._obs_slab = torch.zeros((N, W + M, F), dtype=torch.float32, device=dev)
+                self._obs_views = [self._obs_slab[:, h:h + W, :] for h in range(M + 1)]
             self._t = {
-                "obs": torch.zeros((N,) + self.obs_shape, dtype=torch.float32, device=dev),
+                "obs": self._obs_views[0] if M > 0 else
+                torch.zeros((N,) + self.obs_shape, dtype=torch.float32, device=dev),
                 "reward": self.packed_returns[:4 * N].view(torch.float32),
                 "reward64": torch.zeros(N, dtype=torch.float64, device=dev),
                 "terminated": self.packed_returns[4 * N:5 * N].view(torch.bool),
@@ -355,10 +368,54 @@ class BatchedTradingEnv(_VectorEnvBase):
             b = _abi.GteOutputs()
             for k, t in self._t.items():
                 setattr(b, k, t.data_ptr())
+            if M > 0:  # (the slab's start, so that the library allocates no buffer of its own meanwhile)
+                b.obs = self._obs_slab.data_ptr()
             _abi.check(self._lib, self._lib.gte_bind_outputs(self._h, C.byref(b)))
+            if M > 0:
+                _abi.check(self._lib, self._lib.gte_bind_sliding_obs(
+                    self._h, C.c_void_p(self._obs_slab.data_ptr()), self.obs_shape[0] + M))
             # run on torch's current stream so torch ops and env launches are ordered
             _abi.check(self._lib, self._lib.gte_set_stream(
                 self._h, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    # -- sliding observation buffer ---------------------------------------------------
+    @property
+    def sliding_obs(self) -> bool:
+        """True while observations live in a sliding buffer: `obs` is then a strided view
+        [N, W, F_obs] of a [N, W + M, F_obs] tensor (contiguous within an env, chronological)."""
+        return self._obs_views is not None
+
+    def _follow_head(self):
+        """_t["obs"] = the window at the library's head (after every reset, step and rollout)."""
+        v = self._obs_view
+        _abi.check(self._lib, self._lib.gte_obs_view(self._h, C.byref(v)))
+        if v.sliding:
+            self._t["obs"] = self._obs_views[v.head]
+        else:  # somebody bound a classic buffer through the C ABI: follow it for good
+            self._t["obs"] = _device_view(v.base, (self.num_envs,) + self.obs_shape, "<f4",
+                                          self._t["obs"].device)
+            self._obs_views = None
+
+    def _leave_sliding(self):
+        """Back to a contiguous [N, W, F_obs] observation buffer for good: the current window is
+        copied once and bound the classic way (a HIP graph reads `_t["obs"]` at capture time and
+        RCCL sends a contiguous buffer: neither can follow a moving head)."""
+        if self._obs_views is None:
+            return
+        torch = self._torch
+        obs = self._t["obs"].contiguous()
+        torch.cuda.synchronize(obs.device)
+        b = _abi.GteOutputs()
+        for k, t in self._t.items():
+            setattr(b, k, (obs if k == "obs" else t).data_ptr())
+        # the bind clears the two-slot terminal counter and rewinds it to slot 0: keep the last count readable
+        _abi.check(self._lib, self._lib.gte_get_outputs(self._h, C.byref(self._out)))
+        last = self._t["term_count"][int(self._out.term_slot)].clone()
+        _abi.check(self._lib, self._lib.gte_bind_outputs(self._h, C.byref(b)))
+        self._t["term_count"][0] = last
+        self._t["obs"] = obs
+        self._obs_slab = self._obs_views = None
+        _abi.check(self._lib, self._lib.gte_get_outputs(self._h, C.byref(self._out)))
 
     # -- data movement helpers -------------------------------------------------------
     def _to_host(self, dev_ptr: int, dtype, count: int) -> np.ndarray:
@@ -410,6 +467,10 @@ class BatchedTradingEnv(_VectorEnvBase):
                 "reward": (np.float32, N), "reward64": (np.float64, N),
                 "terminated": (np.uint8, N), "truncated": (np.uint8, N),
                 "term_count": (np.int32, 2), "term_ids": (np.int32, N)}[name]
+        if name == "obs" and self._obs_views is not None:  # a strided view: gte_read_obs packs it
+            a = np.empty((N,) + self.obs_shape, np.float32)
+            _abi.check(self._lib, self._lib.gte_read_obs(self._h, 0, N, a.ctypes.data))
+            return a
         a = self._to_host(getattr(self._out, name), *spec)
         return a.reshape((N,) + self.obs_shape) if name in ("obs", "final_obs") else a
 
@@ -882,6 +943,8 @@ class BatchedTradingEnv(_VectorEnvBase):
         _abi.check(self._lib, self._lib.gte_reset(self._h, mp, ap, bp, cp))
         self._was_reset = True
         self._epoch += 1
+        if self._obs_views is not None:
+            self._follow_head()
         self._apply_callables(after_reset=True)
         return self._results()[0], LazyInfo(self)
 
@@ -979,6 +1042,8 @@ class BatchedTradingEnv(_VectorEnvBase):
         else:
             _abi.check(self._lib, self._lib.gte_step(self._h, a.ctypes.data, 0))
         self._epoch += 1
+        if self._obs_views is not None:
+            self._follow_head()
 
     def capture_steps(self, body, n_steps: int):
         """Record `body(i)` for i in range(n_steps) — each call taking ONE `step()` with a CUDA
@@ -992,6 +1057,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         are merged with torch.where.  Inside the capture `verbose` reports are skipped (a report
         synchronises); `return_slots` > 1 is refused.  See step_graph.py."""
         from .step_graph import StepGraph
+        self._leave_sliding()  # (the captured body reads _t["obs"]: one buffer for every replay)
         return StepGraph(self, body, n_steps)
 
     def read_envs(self, first: int = 0, count=None, with_obs: bool = True, view: bool = False):
@@ -1089,6 +1155,8 @@ class BatchedTradingEnv(_VectorEnvBase):
         _abi.check(self._lib, self._lib.gte_rollout(self._h, C.c_void_p(actions.data_ptr()), K,
                                                     C.byref(b)))
         self._epoch += 1
+        if self._obs_views is not None:
+            self._follow_head()
         if not keep_obs:
             out["obs"] = self._t["obs"]
         return out
@@ -1114,6 +1182,8 @@ class BatchedTradingEnv(_VectorEnvBase):
         _abi.check(self._lib, self._lib.gte_backtest(self._h, C.c_void_p(actions.data_ptr()),
                                                      int(actions.shape[0]), 0 if resume else 1, C.byref(ptr)))
         self._epoch += 1
+        if self._obs_views is not None:
+            self._follow_head()
         return BacktestStats(self, ptr.value)
 
     # -- signal tables: the action looked up on the device by the row an env stands on -----
@@ -1252,6 +1322,8 @@ class BatchedTradingEnv(_VectorEnvBase):
             self._h, None if strategy is None else C.c_void_p(strategy.data_ptr()), int(K),
             0 if resume else 1, C.byref(ptr)))
         self._epoch += 1
+        if self._obs_views is not None:
+            self._follow_head()
         return BacktestStats(self, ptr.value)
 
     # -- misc ---------------------------------------------------------------------------

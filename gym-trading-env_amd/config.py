@@ -112,7 +112,8 @@ def make_config(*, n_envs: int, n_static: int, n_datasets: int = 1,
                 device: int = 0, envs_per_wave: int = 0,
                 nontemporal_obs: int = 3, kernel_variant: int = 0,
                 debug_flags: int = 0, affinity_period: int = 0,
-                final_obs: bool = False, log_steps: int = 0) -> _abi.GteConfig:
+                final_obs: bool = False, log_steps: int = 0,
+                obs_slack_rows: int = 0) -> _abi.GteConfig:
     positions = list(positions)
     if not 0 < len(positions) <= _abi.GTE_MAX_POSITIONS:
         raise ValueError(f"1..{_abi.GTE_MAX_POSITIONS} positions supported")
@@ -180,4 +181,7 @@ def make_config(*, n_envs: int, n_static: int, n_datasets: int = 1,
     if log_steps < 0:
         raise ValueError("log_steps must be >= 0")
     cfg.log_steps = int(log_steps)
+    if obs_slack_rows < -1:
+        raise ValueError("obs_slack_rows must be -1 (off), 0 (automatic) or > 0")
+    cfg.obs_slack_rows = int(obs_slack_rows)  # spare rows of a sliding observation buffer
     return cfg

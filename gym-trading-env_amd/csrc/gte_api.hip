@@ -55,6 +55,8 @@ struct LaunchPlan {
   bool hot_tu = false;     // the step may go to the isolated hot instantiations (hot_tu_covers permitting)
   bool fused_log = false;  // the step kernel writes the trajectory row itself
   bool always_dense = false;     // every step stores all flags (flag ledger below)
+  int slide_rows = 0;            // M: spare rows a sliding observation buffer may have (0 = this env never slides)
+  bool full_windows = false;     // a sliding buffer moves its head but every step writes full windows (A/B)
   bool fused_rollout = false;    // gte_rollout may use the fused kernels ...
   bool resident_rollout = false; // ... and among them the window-resident one
   // L2-affinity processing order (gte_kernels.hip, "L2-affinity permutation")
@@ -135,6 +137,10 @@ struct gte_env {
   bool flags_sparse_ok = false;
   const uint8_t* flags_term = nullptr;   // ... into these two buffers, which this env's last step
   const uint8_t* flags_trunc = nullptr;  //     wrote and nothing has written since
+  // sliding observation buffer (gte_bind_sliding_obs; window ledger below).  p.obs is its base, p.obs_rows
+  // = W + M and p.obs_head the head the last launch wrote at
+  bool sliding = false;
+  bool slide_valid = false;  // (g_flag_mu) the buffer holds every env's window at p.obs_head, written by this env
 };
 
 // Flag ledger.  A step stores an env's terminated / truncated bytes only where they change
@@ -174,6 +180,41 @@ void flags_forget_locked(const gte_env* E) {
   g_flag_last.resize(k);
 }
 }  // namespace
+
+// Window ledger, in the manner of the flag ledger.  A step of an env with a sliding observation buffer may
+// store only the newest row of the envs that advanced (Params.slide) when the buffer holds, at the current
+// head h < M, exactly the windows this env's previous reset or step wrote there:
+//   * an unmasked reset and every full step write all windows at head 0 and establish that;
+//   * a masked reset writes the masked envs' windows at the current head and changes nothing else;
+//   * a rebind, a rollout or backtest (their fused steps advance the envs without writing the buffer), a
+//     stream capture (a replay writes at times the host does not see: captured steps write in full at
+//     head 0), gte_set_schedule and any OTHER env's launch that writes into the buffer withdraw it.
+// One full step restores the invariant whatever came before.
+namespace {
+std::vector<FlagRange> g_slide_bufs;  // (g_flag_mu) the sliding buffers bound at the moment
+void slide_forget_locked(const gte_env* E) {
+  size_t k = 0;
+  for (size_t i = 0; i < g_slide_bufs.size(); ++i)
+    if (g_slide_bufs[i].env != E) g_slide_bufs[k++] = g_slide_bufs[i];
+  g_slide_bufs.resize(k);
+}
+}  // namespace
+// E's launch writes observations into [ptr, ptr + bytes): other envs sliding there write in full next
+static void obs_written(const gte_env* E, const void* ptr, size_t bytes) {
+  if (!ptr || !bytes) return;
+  std::lock_guard<std::mutex> lock(g_flag_mu);
+  const uintptr_t lo = (uintptr_t)ptr, hi = lo + bytes;
+  for (const FlagRange& r : g_slide_bufs)
+    if (r.env != E && ranges_overlap(lo, hi, r.lo, r.hi)) r.env->slide_valid = false;
+}
+static void slide_invalidate(gte_env* E) {
+  std::lock_guard<std::mutex> lock(g_flag_mu);
+  E->slide_valid = false;
+}
+// bytes of E's own observation buffer, whichever layout it has
+static size_t own_obs_bytes(const gte_env* E) {
+  return sizeof(float) * (size_t)E->p.N * (size_t)obs_env_stride(E->p);
+}
 
 // A launch that is not a plain eager step writes (or may write) flag bytes: [ptr, ptr + n) for each
 // pair given; the env's own next step stores densely.
@@ -283,6 +324,8 @@ static int validate(const gte_config* c) {
     return fail(GTE_ERR_INVALID, "final_obs needs autoreset = same-step");
   if (c->envs_per_wave < 0 || c->envs_per_wave > 64)
     return fail(GTE_ERR_INVALID, "envs_per_wave must be 0 (automatic) or 1..64");
+  if (c->obs_slack_rows < -1 || c->obs_slack_rows > 32768)
+    return fail(GTE_ERR_INVALID, "obs_slack_rows must be -1 (off), 0 (automatic) or 1..32768");
   return GTE_OK;
 }
 
@@ -492,6 +535,19 @@ static int plan_launches(gte_env* E) {
   // GTE_KV_LOG_SEPARATE keeps the separate launch (A/B); GTE_KV_LOG_FUSED is the default now.
   L.fused_log = cfg.log_steps > 0 && !(kv & GTE_KV_LOG_SEPARATE);
   L.always_dense = (kv & GTE_KV_DENSE_FLAGS) != 0;  // (A/B of the sparse flag stores)
+  // Sliding observation buffer (gte.h, gte_bind_sliding_obs): where the hot instantiation's shape runs —
+  // 16-byte vectors, windows of at least one wave instruction, cooperative phase A, raw rings in LDS —
+  // and nothing hot_tu_covers() excludes or that needs whole windows elsewhere (terminal observations, a
+  // trajectory log and with it Python callables, T-deep dynamic columns, no window at all).
+  // Automatic M = 2 W / 5: a period of M + 1 steps has one full write, and the buffer is (W + M) / W =
+  // 1.4 x the classic one (8 spare rows at W = 20).
+  L.slide_rows = 0;
+  if (hot_shape && (int64_t)p.W * p.Fobs / 4 >= 64 && p.has_window && !p.persist && !cfg.final_obs &&
+      cfg.log_steps == 0 && cfg.obs_slack_rows >= 0)
+    L.slide_rows = cfg.obs_slack_rows > 0 ? cfg.obs_slack_rows : 2 * p.W / 5;
+  // A/B: the head still moves, every step writes full windows (an environment variable like
+  // GTE_AFFINITY_BINS, not a GTE_KV_* bit: results and layout are the sliding ones)
+  L.full_windows = getenv("GTE_SLIDE_FULL_WINDOWS") != nullptr;  // (read here, at gte_create, once per env)
   L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & GTE_KV_ROLLOUT_PER_STEP);
   L.resident_rollout = p.W >= 2 && !(kv & GTE_KV_ROLLOUT_GATHER);
   // envs per wavefront from registers: full waves once every SIMD has one (65 536 envs: 5.8 us per step
@@ -606,6 +662,7 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   // (the LDS image has a FinalJob per env then, lds_bytes)
   p.final_obs = cfg->final_obs ? (float*)(uintptr_t)16 : nullptr;
   p.obs = nullptr; p.reward = E->owned.reward; p.reward64 = E->owned.reward64;
+  p.obs_rows = p.W; p.obs_head = 0; p.slide = 0;  // classic layout until gte_bind_sliding_obs
   p.terminated = E->owned.terminated; p.truncated = E->owned.truncated;
   E->term_base = E->owned.term_count; p.term_ids = E->owned.term_ids;
   E->h_ds.assign((size_t)p.D, DatasetDesc{nullptr, nullptr, nullptr, nullptr, 0});
@@ -820,7 +877,13 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   TRY(ensure_owned_obs(E));
   TRY(finalize(E));
   TRY(check_injection(E, (size_t)E->p.N, inj_idx, inj_pos_index, inj_dataset));
-  Params p = E->p;
+  obs_written(E, E->p.obs, own_obs_bytes(E));
+  Params p = E->p;  // (a masked reset writes the masked envs' windows at the current head)
+  const bool fresh_run = E->sliding && !mask;  // every window is written: a fresh run of slides from head 0
+  if (fresh_run) {
+    p.obs_head = 0;
+    slide_invalidate(E);  // (until the launch below has gone out: a failed reset proves nothing)
+  }
   const size_t N = (size_t)p.N;
   p.mask = nullptr; p.inj_idx = p.inj_pos = p.inj_ds = nullptr;
   if (mask) { TRY(stage(E, E->d_mask, mask, N)); p.mask = E->d_mask; }
@@ -835,6 +898,11 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   flags_unsure(E, {{p.terminated, N}, {p.truncated, N}});  // (masked envs get zero flags, flags_out untouched)
   const LaunchPlan& L = E->plan;
   HIPCHK(gte::launch_reset(p, L.vec, L.store, L.coop, L.stage, L.blocks, L.threads, E->stream));
+  if (fresh_run) {  // window ledger: the buffer holds every env's window at head 0 now
+    std::lock_guard<std::mutex> lock(g_flag_mu);
+    E->p.obs_head = 0;
+    E->slide_valid = true;
+  }
   TRY(append_log(E, p, p.mask));
   if (L.affinity_period > 0) TRY(resort(E));  // new start rows: re-sort the processing order
   // host staging buffers may be reused by the caller right away: pageable copies above
@@ -908,10 +976,11 @@ struct StepTargets {
   float *obs, *reward;
   double* reward64;
   uint8_t *terminated, *truncated;
+  bool own_obs;  // obs is the env's own buffer (its layout and the window ledger apply), not a rollout's row
 };
 
 static StepTargets own_targets(const gte_env* E, const int32_t* actions) {
-  return {actions, E->p.obs, E->p.reward, E->p.reward64, E->p.terminated, E->p.truncated};
+  return {actions, E->p.obs, E->p.reward, E->p.reward64, E->p.terminated, E->p.truncated, true};
 }
 
 // The processing order ages with every step, fused or not: re-sort once it is due
@@ -935,6 +1004,29 @@ static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool captur
   if (terminal_rec) p.final_rec = terminal_rec;
   p.actions = t.actions; p.obs = t.obs; p.reward = t.reward; p.reward64 = t.reward64;
   p.terminated = t.terminated; p.truncated = t.truncated;
+  if (!t.own_obs) {  // a rollout's per-step row: a classic [N, W, F_obs] block
+    p.obs_rows = p.W; p.obs_head = 0;
+    obs_written(E, t.obs, sizeof(float) * (size_t)p.N * p.W * p.Fobs);
+  } else if (E->sliding) {
+    // window ledger: slide while the buffer provably holds this env's windows at a head below M;
+    // otherwise (and at head M: the wrap) every window in full at head 0, which makes it so again
+    obs_written(E, t.obs, own_obs_bytes(E));
+    std::lock_guard<std::mutex> lock(g_flag_mu);
+    if (!capturing && E->slide_valid && E->p.obs_head < L.slide_rows) {
+      E->p.obs_head += 1;
+      // JOB_SLIDES shares bit 1 of the job record with dyn_persist's "zero the store" (gte_device.h):
+      // plan_launches never grants slide_rows with dyn_persist, and only this launch ever sets p.slide
+      if (p.persist || p.final_obs)
+        return fail(GTE_ERR_STATE, "internal: a sliding step with dyn_persist or final_obs (plan_launches grants neither)");
+      p.slide = L.full_windows ? 0 : 1;
+    } else {
+      E->p.obs_head = 0;
+      E->slide_valid = !capturing;
+    }
+    p.obs_head = E->p.obs_head;
+  } else {
+    obs_written(E, t.obs, own_obs_bytes(E));
+  }
   advance_term_slot(E, p);
   if (L.fused_log) {
     p.log = E->log;
@@ -990,6 +1082,7 @@ int gte_set_schedule(gte_env* E, const gte_schedule* s) {
   E->term_slot = s->term_slot;
   E->steps_since_rebuild = s->steps_since_rebuild;
   flags_unsure(E, {});  // the flag ledger may have recorded captured steps as run: the next step is dense
+  slide_invalidate(E);  // ... and the window ledger: the next step writes full windows at head 0
   return GTE_OK;
 }
 
@@ -1080,11 +1173,14 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
   // (non-temporal stores where the caller left the policy automatic)
   const int nt = (b->obs && E->cfg.nontemporal_obs == 3) ? 1 : L.store;
   const bool capturing = stream_capturing(E);
+  // the fused steps advance the envs without writing the env's own observation buffer (window ledger)
+  slide_invalidate(E);
+  if (b->obs) obs_written(E, b->obs, sizeof(float) * (size_t)n_steps * N * V);
   // one step as its own launch, writing row k of every per-step buffer (what the unfused path
   // does for every step, and the backtest path for its last one)
   auto step_row = [&](int32_t k) -> int {
     StepTargets t = own_targets(E, actions + (size_t)k * N);
-    if (b->obs) t.obs = b->obs + (size_t)k * N * V;
+    if (b->obs) { t.obs = b->obs + (size_t)k * N * V; t.own_obs = false; }
     if (b->reward) t.reward = b->reward + (size_t)k * N;
     if (b->reward64) t.reward64 = b->reward64 + (size_t)k * N;
     if (b->terminated) t.terminated = b->terminated + (size_t)k * N;
@@ -1183,6 +1279,7 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   const size_t N = (size_t)E->p.N;
   const LaunchPlan& L = E->plan;
   const bool signals = actions == nullptr;
+  slide_invalidate(E);  // (window ledger: the summary kernels advance the envs without writing observations)
   if (signals && !E->d_sig_actions) TRY(dev_alloc_late(E, &E->d_sig_actions, N));
   if (!E->bt_stats) {
     if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->bt_final_rec, N));
@@ -1504,7 +1601,8 @@ int gte_get_outputs(gte_env* E, gte_outputs* out) {
   HIPCHK(hipSetDevice(E->cfg.device));
   TRY(ensure_owned_obs(E));
   const Params& p = E->p;
-  out->obs = p.obs; out->reward = p.reward; out->reward64 = p.reward64;
+  out->obs = p.obs;  // (the BASE of a sliding buffer: gte_obs_view says where the window is)
+  out->reward = p.reward; out->reward64 = p.reward64;
   out->terminated = p.terminated; out->truncated = p.truncated;
   out->term_count = E->term_base; out->term_ids = p.term_ids;
   out->obs_elems_per_env = (int64_t)p.W * p.Fobs;
@@ -1520,7 +1618,15 @@ int gte_bind_outputs(gte_env* E, const gte_outputs* b) {
   Params& p = E->p;
   if (b->obs && ((uintptr_t)b->obs & 15)) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
   flags_unsure(E, {});
+  {  // back to the classic layout, whatever was bound
+    std::lock_guard<std::mutex> lock(g_flag_mu);
+    slide_forget_locked(E);
+    E->sliding = false;
+    E->slide_valid = false;
+  }
+  p.obs_rows = p.W; p.obs_head = 0;
   p.obs = b->obs;  // NULL: back to the library's own buffers (allocated on first need)
+  if (b->obs) obs_written(E, b->obs, own_obs_bytes(E));
   if (E->cfg.final_obs) p.final_obs = b->final_obs;
   if (E->was_reset) TRY(ensure_owned_obs(E));
   p.reward = b->reward ? b->reward : E->owned.reward;
@@ -1533,6 +1639,41 @@ int gte_bind_outputs(gte_env* E, const gte_outputs* b) {
   HIPCHK(hipDeviceSynchronize());
   E->term_slot = 0;
   p.term_ids = b->term_ids ? b->term_ids : E->owned.term_ids;
+  return GTE_OK;
+}
+
+int gte_obs_view(gte_env* E, gte_obs_view_t* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  out->base = E->p.obs;
+  out->rows_per_env = E->p.obs_rows;
+  out->head = E->p.obs_head;
+  out->sliding = E->sliding ? 1 : 0;
+  out->slack_rows = E->plan.slide_rows;
+  return GTE_OK;
+}
+
+int gte_bind_sliding_obs(gte_env* E, float* base, int32_t rows_per_env) {
+  if (!E || !base) return fail(GTE_ERR_INVALID, "NULL argument");
+  const LaunchPlan& L = E->plan;
+  if (L.slide_rows <= 0)
+    return fail(GTE_ERR_STATE, "this env does not slide (gte_obs_view().slack_rows is 0): bind a classic buffer");
+  Params& p = E->p;
+  if (rows_per_env != p.W + L.slide_rows)
+    return fail(GTE_ERR_INVALID, "rows_per_env must be window + slack_rows = %d", p.W + L.slide_rows);
+  if ((uintptr_t)base & 15) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bind_sliding_obs inside a stream capture");
+  HIPCHK(hipStreamSynchronize(E->stream));
+  p.obs = base;
+  p.obs_rows = rows_per_env;
+  p.obs_head = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_flag_mu);
+    slide_forget_locked(E);
+    E->sliding = true;
+    E->slide_valid = false;  // the next step writes every window in full at head 0
+    g_slide_bufs.push_back({E, (uintptr_t)base, (uintptr_t)base + own_obs_bytes(E)});
+  }
+  obs_written(E, base, own_obs_bytes(E));
   return GTE_OK;
 }
 
@@ -1561,9 +1702,9 @@ static int read_envs_impl(gte_env* E, int32_t first, int32_t count, int32_t want
     E->h_snap_bytes = want;
   }
   float* h_obs = (float*)((char*)E->h_snap + head);
-  HIPCHK(gte::launch_snapshot(E->p.rec, E->p.reward64, E->p.terminated, E->p.truncated, E->p.obs,
-                              (int64_t)elems, first, count, E->h_snap, want_obs ? h_obs : nullptr,
-                              E->stream));
+  HIPCHK(gte::launch_snapshot(E->p.rec, E->p.reward64, E->p.terminated, E->p.truncated, obs_window0(E->p),
+                              (int64_t)elems, obs_env_stride(E->p), first, count, E->h_snap,
+                              want_obs ? h_obs : nullptr, E->stream));
   HIPCHK(hipStreamSynchronize(E->stream));
   *out = (const gte_env_snapshot*)E->h_snap;
   if (obs) *obs = want_obs ? h_obs : nullptr;
@@ -1726,6 +1867,9 @@ int gte_allgather_obs(gte_env* E, float* dst_device, int32_t mode) {
   if (!E || !dst_device) return fail(GTE_ERR_INVALID, "NULL argument");
   const Params& p = E->p;
   if (!p.obs) return fail(GTE_ERR_STATE, "gte_allgather_obs before gte_reset (no observation exists yet)");
+  if (E->sliding)
+    return fail(GTE_ERR_STATE, "gte_allgather_obs on a sliding observation buffer: the windows are not contiguous "
+                               "(bind a classic buffer with gte_bind_outputs first)");
   return gte_allgather(E, p.obs, dst_device, sizeof(float) * (size_t)p.N * p.W * p.Fobs, mode);
 }
 
@@ -1809,7 +1953,13 @@ int gte_read_obs(gte_env* E, int32_t first_env, int32_t n, float* host_dst) {
   const size_t per = (size_t)p.W * p.Fobs;
   if (!p.obs) return fail(GTE_ERR_STATE, "gte_read_obs before gte_reset (no observation exists yet)");
   HIPCHK(hipStreamSynchronize(E->stream));
-  HIPCHK(hipMemcpy(host_dst, p.obs + per * first_env, sizeof(float) * per * n, hipMemcpyDeviceToHost));
+  const size_t stride = (size_t)obs_env_stride(p);
+  const float* src = obs_window0(p) + stride * first_env;
+  if (stride == per || n == 0)  // classic buffer: one contiguous copy
+    HIPCHK(hipMemcpy(host_dst, src, sizeof(float) * per * n, hipMemcpyDeviceToHost));
+  else
+    HIPCHK(hipMemcpy2D(host_dst, sizeof(float) * per, src, sizeof(float) * stride, sizeof(float) * per, (size_t)n,
+                       hipMemcpyDeviceToHost));
   return GTE_OK;
 }
 
@@ -1861,6 +2011,7 @@ void gte_destroy(gte_env* E) {
   {
     std::lock_guard<std::mutex> lock(g_flag_mu);
     flags_forget_locked(E);
+    slide_forget_locked(E);
   }
   delete E;
 }

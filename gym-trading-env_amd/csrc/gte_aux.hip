@@ -68,7 +68,7 @@ __global__ void gte_set_dynamic_kernel(const Params p, const float* values, uint
   const int32_t idx = p.rec[e].idx;
   const int64_t slot = p.persist ? (int64_t)idx : (int64_t)(idx % p.W);
   float* ring = p.ring + ((int64_t)e * p.depth + slot) * p.nd;
-  float* row = p.obs + ((int64_t)e * p.W + (p.W - 1)) * p.Fobs + p.Fs;
+  float* row = obs_window0(p) + (int64_t)e * obs_env_stride(p) + (int64_t)(p.W - 1) * p.Fobs + p.Fs;
   for (int i = 0; i < p.nd; ++i)
     if (mask & (1u << i)) {
       const float v = values[(int64_t)e * p.nd + i];
@@ -96,7 +96,7 @@ __global__ void gte_set_dynamic_columns_kernel(const Params p, const DynColumns 
   const int32_t idx = p.rec[e].idx;
   const int64_t slot = p.persist ? (int64_t)idx : (int64_t)(idx % p.W);
   float* ring = p.ring + ((int64_t)e * p.depth + slot) * p.nd;
-  float* row = p.obs + ((int64_t)e * p.W + (p.W - 1)) * p.Fobs + p.Fs;
+  float* row = obs_window0(p) + (int64_t)e * obs_env_stride(p) + (int64_t)(p.W - 1) * p.Fobs + p.Fs;
   for (int i = 0; i < p.nd; ++i)
     if (c.col[i]) {
       // (float)double rounds to nearest even, like the reference's cast into its f32 _obs_array
@@ -233,7 +233,7 @@ struct SnapshotPacked {
 };
 
 __global__ void gte_snapshot_kernel(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                                    const uint8_t* trunc, const float* obs, int64_t obs_elems,
+                                    const uint8_t* trunc, const float* obs, int64_t obs_elems, int64_t obs_stride,
                                     int first, SnapshotPacked* dst, float* dst_obs) {
   const int e = first + blockIdx.x;  // one workgroup per env
   if (threadIdx.x == 0) {
@@ -248,14 +248,14 @@ __global__ void gte_snapshot_kernel(const EnvRec* rec, const double* reward64, c
   }
   if (dst_obs)
     for (int64_t i = threadIdx.x; i < obs_elems; i += blockDim.x)
-      dst_obs[(int64_t)blockIdx.x * obs_elems + i] = obs[(int64_t)e * obs_elems + i];
+      dst_obs[(int64_t)blockIdx.x * obs_elems + i] = obs[(int64_t)e * obs_stride + i];
 }
 
 hipError_t launch_snapshot(const EnvRec* rec, const double* reward64, const uint8_t* term,
-                           const uint8_t* trunc, const float* obs, int64_t obs_elems, int first,
+                           const uint8_t* trunc, const float* obs, int64_t obs_elems, int64_t obs_stride, int first,
                            int count, void* dst, float* dst_obs, hipStream_t stream) {
   hipLaunchKernelGGL(gte_snapshot_kernel, dim3(count), dim3(256), 0, stream, rec, reward64, term,
-                     trunc, obs, obs_elems, first, (SnapshotPacked*)dst, dst_obs);
+                     trunc, obs, obs_elems, obs_stride, first, (SnapshotPacked*)dst, dst_obs);
   return hipGetLastError();
 }
 

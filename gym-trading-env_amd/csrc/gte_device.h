@@ -120,9 +120,26 @@ struct Params {
   LogArrays log;
   int64_t* log_cursor;   // the slot of the log cursor this launch reads (log_cursor_other below)
   uint32_t* ds_used;     // u32 [N, ceil(D/32)]: datasets picked in the env's current round (D > 1 only)
+  // --- layout of `obs` (obs_window0 / obs_env_stride below are the only readers): env e's window is rows
+  // obs_head .. obs_head + W - 1 of its slab of obs_rows rows.  Classic buffer: obs_rows = W, head 0.
+  int32_t obs_rows;      // rows per env (W + M for a sliding buffer, gte_bind_sliding_obs)
+  int32_t obs_head;      // first row of the window THIS launch writes (host state, like term_slot)
+  int32_t slide;         // != 0 (this launch only): an env that merely advanced stores its newest row alone —
+                         // the host has proved that the buffer holds its previous window at obs_head - 1
+  int32_t pad_obs;
 };
-static_assert(offsetof(Params, log) == 384 && offsetof(Params, log_cursor) == 392 && sizeof(Params) == 408,
-              "Params keeps its layout (log_cursor replaced log_row_base in place)");
+static_assert(offsetof(Params, log) == 384 && offsetof(Params, log_cursor) == 392 &&
+                  offsetof(Params, obs_rows) == 408 && sizeof(Params) == 424,
+              "Params keeps its layout (log_cursor replaced log_row_base in place; the obs layout at the end)");
+
+// The ONE statement of where an env's observation lives: every kernel and every host read of the env's
+// own buffer goes through these two.
+inline __host__ __device__ float* obs_window0(const Params& p) {  // env 0's current window
+  return p.obs + (int64_t)p.obs_head * p.Fobs;
+}
+inline __host__ __device__ int64_t obs_env_stride(const Params& p) {  // floats from env e to env e + 1
+  return (int64_t)p.obs_rows * p.Fobs;
+}
 
 // The trajectory log's row count lives on the device, so that a replayed graph appends where the
 // log really is: a 16-byte-aligned pair int64_t[2] (gte_env::log_cursor, gte_api.hip) used with the
@@ -284,9 +301,11 @@ struct ObsJob {
   int32_t idx;        // current row
   int32_t slot0;      // slot of the window's first row in the env's dynamic store
   int32_t n_zero;     // leading window rows whose dynamic columns read as zero
-  int32_t flags;      // bit0: copy the window; bit1: zero the env's dynamic store
+  int32_t flags;      // bit0: copy the window; bit1: zero the env's dynamic store (dyn_persist) /
+                      // JOB_SLIDES (W-deep rings, a launch with p.slide)
   float cur[GTE_MAX_DYN];  // dynamic features of the current row (f32, :154)
 };
+enum { JOB_COPY = 1, JOB_ZERO_STORE = 2, JOB_SLIDES = 2 };
 
 // Same-step auto-reset with final_obs: the window of the TERMINAL state, gathered into
 // final_obs[env] next to the reset observation.

@@ -118,8 +118,8 @@ hipError_t launch_pack_log(const LogArrays& log, int N, int L, long long rows_wr
                            int n_ids, int max_rows, int finished, int frozen_runs, const EnvRec* final_rec,
                            const double* reward64, const LogPack& o, hipStream_t stream);
 hipError_t launch_snapshot(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc,
-                           const float* obs, int64_t obs_elems, int first, int count, void* dst, float* dst_obs,
-                           hipStream_t stream);
+                           const float* obs, int64_t obs_elems, int64_t obs_stride, int first, int count, void* dst,
+                           float* dst_obs, hipStream_t stream);
 
 // --- gte_comm.hip: RCCL, bound at run time
 const char* rccl_load();

@@ -304,6 +304,7 @@ __device__ inline void phase_a(const Params& p, int e, bool active, int lane, Ob
     if (action >= p.P) action = -1;
     bool fresh = false;
     bool stepped = true;
+    bool slides = false;  // this call is a plain advance (same dataset, idx + 1, no reset, not frozen)
     if (s.needs_reset) {
       if (p.autoreset == GTE_AUTORESET_NEXT_STEP) {
         int32_t qi, qp, qd;
@@ -367,6 +368,7 @@ __device__ inline void phase_a(const Params& p, int e, bool active, int lane, Ob
       store_flags(p, e, s, (done ? 1 : 0) | (trunc ? 2 : 0));
       if (so) { so->reward = rew; so->flags = (done ? 1 : 0) | (trunc ? 2 : 0); }
       ended = done || trunc;
+      slides = !(ended && p.autoreset == GTE_AUTORESET_SAME_STEP);
       if (ended) { s.needs_reset = 1; p.rec[e].needs_reset = 1; }
       if (ended && p.autoreset == GTE_AUTORESET_SAME_STEP) {
         // the reference's step() runs _get_obs (:272) before any wrapper resets the env:
@@ -410,6 +412,10 @@ __device__ inline void phase_a(const Params& p, int e, bool active, int lane, Ob
       so->asset = s.q.asset; so->fiat = s.q.fiat; so->ia = s.q.ia; so->ifi = s.q.ifi;
     }
     make_job(p, e, s, fresh, job);
+    // the window moved up one row and nothing else: with p.slide its newest row is all that changed
+    // (JOB_SLIDES shares bit 1 with "zero the dynamic store", which only dyn_persist raises; the host
+    // never sets p.slide with dyn_persist)
+    if (slides && p.slide) job.flags |= JOB_SLIDES;
     GTE_STAMP(5);  // record, ring and job stores done
   }
 

@@ -87,7 +87,11 @@ __device__ inline Params step_params(const Params& p0, const RolloutArgs& r, int
   if (r.reward64) p.reward64 = r.reward64 + (int64_t)k * N;
   if (r.terminated) p.terminated = r.terminated + (int64_t)k * N;
   if (r.truncated) p.truncated = r.truncated + (int64_t)k * N;
-  if (r.obs) p.obs = r.obs + (int64_t)k * N * (int64_t)p0.W * p0.Fobs;
+  if (r.obs) {  // a per-step row: a classic [N, W, Fobs] block whatever the env's own buffer is
+    p.obs = r.obs + (int64_t)k * N * (int64_t)p0.W * p0.Fobs;
+    p.obs_rows = p0.W;
+    p.obs_head = 0;
+  }
   return p;
 }
 
@@ -347,7 +351,8 @@ __device__ __forceinline__ void resident_group(const Params& p0, const RolloutAr
   }
 
   auto emit = [&](int k) {
-    float* obs_k = r.obs ? r.obs + (int64_t)k * p0.N * V : p0.obs;
+    float* obs_k = r.obs ? r.obs + (int64_t)k * p0.N * V : obs_window0(p0);
+    const int64_t ES = r.obs ? V : obs_env_stride(p0);  // (per-step rows are classic [N, W, Fobs] blocks)
     // the newest row of every env: table -> registers (in flight during the LDS part)
     int32_t n_env[RES_NEW];
 #pragma unroll
@@ -386,7 +391,7 @@ __device__ __forceinline__ void resident_group(const Params& p0, const RolloutAr
         ls -= (ls >= W1) ? W1 : 0;
         ok[u] = in && (j.meta & 1u);
         v[u] = *(const float4_t*)(L.win + ((int64_t)el * W1 + ls) * p0.Fobs + c * 4u);
-        dst[u] = (int64_t)j.env * V + (int64_t)q * 4;
+        dst[u] = (int64_t)j.env * ES + (int64_t)q * 4;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -402,7 +407,7 @@ __device__ __forceinline__ void resident_group(const Params& p0, const RolloutAr
         for (int d = 0; d < GTE_MAX_DYN; ++d) x[d] = L.cur[n_el[i] * GTE_MAX_DYN + d];
         set_tail(nv[i], p0.nd, x);
       }
-      store_out<NT>((float4_t*)(obs_k + (int64_t)n_env[i] * V + ((int64_t)VL + n_c[i]) * 4), nv[i]);
+      store_out<NT>((float4_t*)(obs_k + (int64_t)n_env[i] * ES + ((int64_t)VL + n_c[i]) * 4), nv[i]);
     }
     // (n_ok stays; n_env < 0 marks "nothing loaded" for the ring update below)
 #pragma unroll

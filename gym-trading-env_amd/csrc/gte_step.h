@@ -71,7 +71,7 @@ __device__ inline void set_tail(float __attribute__((ext_vector_type(4))) & v, i
 struct alignas(16) JobRec {
   uint64_t src;   // first row of the window in the feature table
   int32_t env;    // env id processed in this slot (perm[slot], or the slot itself); -1 = none
-  uint32_t meta;  // bit0 copy the window, bit1 zero the env's dynamic store,
+  uint32_t meta;  // bit0 copy the window, bit1 zero the env's dynamic store (dyn_persist) / JOB_SLIDES,
                   // bits 2..16 n_zero (W < 32768, gte_create checks), bits 17..31 slot0 of the
                   // W-deep ring (meaningless with dyn_persist: dyn_value uses the row itself)
 };
@@ -256,6 +256,8 @@ __device__ inline void phase_b(const Params& p, const WgLds& L, int s_first,
   const uint32_t VPE = V / VEC;                // vectors per env
   const uint32_t FV = (uint32_t)p.Fobs / VEC;  // vectors per row
   const uint32_t total = min((uint32_t)n_env * VPE, k_hi);
+  float* const obs0 = obs_window0(p);
+  const int64_t ES = obs_env_stride(p);
 
   for (uint32_t k0 = k_lo; k0 < total; k0 += 64u * U) {
     vec_t v[U];
@@ -283,7 +285,7 @@ __device__ inline void phase_b(const Params& p, const WgLds& L, int s_first,
       const int s = s_first + (int)ee[u];
       const float* ring_e = p.ring + (int64_t)env[u] * p.depth * p.nd;
       patch_dynamic<VEC, STAGE>(p, L, v[u], s, mm[u], ring_e, (int)w, col);
-      store_out<NT>((vec_t*)(p.obs + (int64_t)env[u] * V + (int64_t)jj[u] * VEC), v[u]);
+      store_out<NT>((vec_t*)(obs0 + (int64_t)env[u] * ES + (int64_t)jj[u] * VEC), v[u]);
     }
   }
 }
@@ -349,13 +351,13 @@ __device__ inline void phase_b_lean(const Params& p, const WgLds& L, int s_first
   constexpr int U = GTE_LEAN_U;
   const uint32_t W = (uint32_t)p.W, FV = (uint32_t)p.Fobs / 4u, VPE = W * FV;
   const uint32_t total = (uint32_t)n_env * VPE;          // a multiple of 64 * U (checked by the caller)
-  const uint32_t VB = VPE * 16u;                          // bytes per observation
+  const uint32_t SB = (uint32_t)obs_env_stride(p) * 4u;   // bytes from env to env (VPE * 16 in a classic buffer)
   // running position of this lane's vector: env slot `ee`, vector in env `jj`, row `w`, vector in row `r`
   uint32_t ee = (uint32_t)lane / VPE;                     // VPE >= 64: 0
   uint32_t jj = (uint32_t)lane - ee * VPE;
   uint32_t w = jj / FV, r = jj - w * FV;
   const uint32_t w_inc = 64u / FV, r_inc = 64u - w_inc * FV;  // one step of 64 vectors
-  char* const obs = (char*)p.obs;
+  char* const obs = (char*)obs_window0(p);
   // (one fixed pass shape, the loop written out: as a generic lambda with a tail pass for other
   // multiples of 64 the same code compiled 5 % slower at config 5)
   for (uint32_t k0 = 0u; k0 < total; k0 += 64u * U) {
@@ -385,7 +387,53 @@ __device__ inline void phase_b_lean(const Params& p, const WgLds& L, int s_first
       // the dynamic columns are the last ND components of a row's last vector
 #pragma unroll
       for (int c = 0; c < ND; ++c) o[4 - ND + c] = last[u] ? t[u][c] : o[4 - ND + c];
-      store_out<NT>((float4_t*)(obs + (uint64_t)(uint32_t)env[u] * VB + jj16[u]), o);
+      store_out<NT>((float4_t*)(obs + (uint64_t)(uint32_t)env[u] * SB + jj16[u]), o);
+    }
+  }
+}
+
+// Slide loop (a launch with p.slide): the window of an env that merely advanced (JOB_SLIDES) is, at the
+// new head, the one at the old head moved up a row — already in the buffer — plus the newest row.  The
+// wave moves that row alone for those envs: n_env * F_obs / 4 vectors (128 for 16 envs of 32 columns
+// where the full windows are 2 560), the row's last vector patched with phase A's current values.
+// Neither the staged rings nor resolve_dynamic_rows are needed.  Two vectors in flight per lane.  The
+// wave's other envs (a reset, a frozen env) get their full windows from the caller.
+template <int NT>
+__device__ inline void phase_b_slide(const Params& p, const WgLds& L, int s_first, int n_env, int lane,
+                                     uint64_t fv_magic) {
+  const uint32_t FV = (uint32_t)p.Fobs / 4u;
+  const uint32_t total = (uint32_t)n_env * FV;
+  const int64_t row = (int64_t)(p.W - 1) * FV;  // the newest row, in vectors from the window's start
+  float4_t* const obs0 = (float4_t*)obs_window0(p) + row;
+  const int64_t ES4 = obs_env_stride(p) / 4;
+  for (uint32_t k0 = 0u; k0 < total; k0 += 128u) {
+    float4_t v[2];
+    uint32_t rr[2];
+    int32_t env[2], sl[2];
+    bool ok[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const uint32_t k = k0 + (uint32_t)u * 64u + (uint32_t)lane;
+      ok[u] = k < total;
+      const uint32_t kk = ok[u] ? k : 0u;
+      const uint32_t el = fastdiv40(kk, fv_magic);
+      rr[u] = kk - el * FV;
+      sl[u] = s_first + (int)el;
+      const JobRec j = L.job[sl[u]];
+      env[u] = j.env;
+      ok[u] = ok[u] && (j.meta & (uint32_t)JOB_SLIDES);
+      if (ok[u]) v[u] = load_global<float4_t>(j.src, row + (int64_t)rr[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (!ok[u]) continue;
+      if (rr[u] == FV - 1u) {
+        float x[GTE_MAX_DYN];
+#pragma unroll
+        for (int i = 0; i < GTE_MAX_DYN; ++i) x[i] = L.cur[sl[u] * GTE_MAX_DYN + i];
+        set_tail(v[u], p.nd, x);
+      }
+      store_out<NT>(obs0 + (int64_t)env[u] * ES4 + (int64_t)rr[u], v[u]);
     }
   }
 }
@@ -581,6 +629,25 @@ __global__ __launch_bounds__(256) void gte_kernel(const Params p, const uint64_t
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   bool lean = false;
+  if constexpr (MODE == MODE_STEP && VEC == 4) {
+    // p.slide: the envs that merely advanced store their newest row alone (about 97 % of the waves at
+    // one reset per 500 steps have no other env); an env that reset or stands frozen gets its full window
+    // at the new head, one env at a time (rare) through the generic loop
+    if (p.slide && !p.debug) {
+      phase_b_slide<NT>(p, L, s_first, n_env, lane, fv_magic);
+      const uint32_t m = L.job[s_first + (lane < n_env ? lane : 0)].meta;
+      unsigned long long full = __ballot(lane < n_env && (m & 1u) && !(m & (uint32_t)JOB_SLIDES));
+      const uint32_t VPE = (uint32_t)(p.W * p.Fobs) / 4u;
+      while (full) {  // wave-uniform
+        const uint32_t el = (uint32_t)(__ffsll((long long)full) - 1);
+        full &= full - 1ull;
+        phase_b<VEC, NT, STAGE, GTE_GATHER_U>(p, L, s_first, n_env, lane, vpe_magic, fv_magic, el * VPE,
+                                              (el + 1u) * VPE);
+      }
+      GTE_STAMP(7);
+      return;  // (p.final_obs is null in a launch that slides)
+    }
+  }
   if constexpr (MODE == MODE_STEP && VEC == 4 && STAGE == STAGE_RAW) {
     // the lean loop takes whole waves of envs that all copy, in whole passes of U wave instructions
     // (windows of at least one wave instruction: the running counters wrap at most once per step of 64)

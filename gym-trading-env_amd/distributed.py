@@ -112,7 +112,10 @@ class ReturnGather:
         return PendingReturns(self, buf, work)
 
     def gather_obs(self, obs: torch.Tensor) -> torch.Tensor:
-        """obs f32 [n, ...] -> [world*n, ...] (config 4: xGMI-bound, 2 560 B per env)."""
+        """obs f32 [n, ...] -> [world*n, ...] (config 4: xGMI-bound, 2 560 B per env).  Pass a
+        contiguous tensor: whoever owns the env and this gather calls `env._leave_sliding()` once
+        (ShardedTradingEnv, ReturnPipeline and NativeReturnGather do); a strided sliding-window view
+        would be copied here on every call."""
         if self.obs_buf is None:
             raise ValueError("constructed without obs_shape")
         dist.all_gather_into_tensor(self.obs_buf, obs.contiguous(), group=self.group)
@@ -157,6 +160,11 @@ class NativeReturnGather:
         self.n = int(env.num_envs)
         self.mode = int(mode)
         self.lay = packed_layout(self.n)
+        if with_obs:
+            # RCCL sends one contiguous buffer: an env with a sliding observation buffer goes classic
+            leave = getattr(env, "_leave_sliding", None)
+            if leave is not None:
+                leave()
         ident = (C.c_uint8 * _abi.GTE_COMM_ID_BYTES)()
         if self.rank == 0:
             _abi.check(self.lib, self.lib.gte_comm_unique_id(ident))
@@ -235,6 +243,12 @@ class ReturnPipeline:
                              "be built with the same block and depth")
         self.env, self.returns, self.block, self.depth = env, returns, block, depth
         self._pending = [None] * depth
+        if returns.obs_buf is not None:
+            # the gather's owner also gathers observations (ReturnGather.gather_obs sends a contiguous
+            # buffer): a sliding env goes classic once, here, instead of paying a copy per step
+            leave = getattr(env, "_leave_sliding", None)
+            if leave is not None:
+                leave()
 
     def before_step(self):
         s = self.env.return_slot
@@ -306,6 +320,8 @@ class ShardedTradingEnv:
                                      device=dev_index, output="torch",
                                      return_slots=self.pipeline * self.block, **kw)
         self.gather_obs = gather_obs
+        if gather_obs:  # ReturnGather.gather_obs / RCCL send one contiguous buffer: no sliding window
+            self.env._leave_sliding()
         dev = self.env.packed_returns.device
         obs_shape = self.env.obs_shape if gather_obs else None
         # step(): synchronous per-step gather; step_async(): the pipeline (own buffers)

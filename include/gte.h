@@ -159,6 +159,10 @@ typedef struct gte_config {
                                observation of every env that ends, in
                                gte_outputs.final_obs (Gymnasium `final_observation`,
                                SB3 `terminal_observation`)                        */
+  int32_t obs_slack_rows;   /* M: spare rows per env of a sliding observation buffer
+                               (gte_bind_sliding_obs).  0 = automatic (2 * W / 5), -1 = off,
+                               > 0 = explicit.  Only read by gte_obs_view().slack_rows: an env
+                               slides only once such a buffer is bound                 */
 } gte_config;
 
 /* Device pointers of the per-step return values of TradingEnv.step
@@ -552,6 +556,44 @@ int gte_read_env(gte_env* env, int32_t env_index, gte_env_snapshot* out, float* 
  * the first gte_reset or gte_get_outputs that finds none bound — so a caller that binds its
  * own before resetting never pays for a second copy. */
 int gte_bind_outputs(gte_env* env, const gte_outputs* bufs);
+
+/* Sliding observation buffer.  A step moves every window one row forward and, for an env that
+ * merely advanced, differs from the previous observation in ONE row; a classic [N, W, F_obs]
+ * buffer still rewrites all W.  Give every env W + M rows instead: the observation of env e is
+ * rows head .. head + W - 1 of its slab, with ONE head for the whole batch,
+ *     obs(e) = base + (e * rows_per_env + head) * F_obs,     W * F_obs floats, chronological,
+ * i.e. a strided [N, W, F_obs] tensor with strides (rows_per_env * F_obs, F_obs, 1).  A step
+ * that finds head < M moves the head up by one and stores only row head + W - 1 of the envs that
+ * advanced (full windows for those that reset or stand frozen); at head == M, and whenever the
+ * library cannot prove that the buffer holds this env's previous observation at the current
+ * head (a rebind, a rollout, a stream capture, another env writing the buffer), the step writes
+ * every window in full at head 0.  A masked gte_reset writes the masked envs' windows at the
+ * current head; an unmasked one returns to head 0.  The values are those of the classic buffer,
+ * bit for bit.
+ *
+ * gte_obs_view reports where the current observation is; slack_rows is the M this env may use
+ * (0: the shape or the configuration does not slide — anything but 16-byte-vector windows of at
+ * least 64 vectors on the cooperative LDS-staged step kernel, dyn_persist, final_obs, a
+ * trajectory log, window == 0, obs_slack_rows == -1).  gte_bind_sliding_obs binds a caller-owned,
+ * 16-byte-aligned f32 [N, rows_per_env, F_obs] buffer with rows_per_env == W + slack_rows
+ * (GTE_ERR_STATE where slack_rows is 0); gte_bind_outputs, with or without an obs pointer, returns
+ * to the classic layout.  While a sliding buffer is bound gte_get_outputs().obs is the BASE of the
+ * buffer (use gte_obs_view for the window), the gte_read_* calls return the current window, and
+ * gte_allgather_obs fails (RCCL sends a contiguous buffer).
+ *
+ * A/B and twin runs: with GTE_SLIDE_FULL_WINDOWS set in the environment when gte_create runs, the env
+ * keeps the sliding layout and the moving head, but every step writes every window in full (the
+ * enum gte_kernel_variant keeps its values: tests pin them; this is a tuning switch like
+ * GTE_AFFINITY_BINS). */
+typedef struct gte_obs_view_t {
+  float*  base;          /* the bound observation buffer (NULL before one exists)            */
+  int32_t rows_per_env;  /* W + M while sliding, else W                                      */
+  int32_t head;          /* first row of the current window in every env's slab              */
+  int32_t sliding;       /* 1 while a sliding buffer is bound                                */
+  int32_t slack_rows;    /* the M gte_bind_sliding_obs accepts for this env, 0 = none        */
+} gte_obs_view_t;
+int gte_obs_view(gte_env* env, gte_obs_view_t* out);
+int gte_bind_sliding_obs(gte_env* env, float* base, int32_t rows_per_env);
 /* Redirect ONLY the per-step returns (reward f32[N], terminated u8[N], truncated u8[N]) of
  * the steps enqueued AFTER this call; nothing is synchronised and nothing already
  * enqueued changes.  A sharded run rotates between two (or more) caller-owned return
