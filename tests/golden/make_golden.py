@@ -780,6 +780,143 @@ def numeric_traces():
     print(f"numeric: {len(NUMERIC)} traces, {total:.0f} KiB")
 
 
+# -- the slide family: the other families' hardest semantics at shapes whose window slides ----------
+SLIDE_SEED = 20261018
+SLIDE_KIB_PER_FIXTURE = 200
+SLIDE_KIB_TOTAL = 1536
+MIX3R = ["real_position", "last_position_taken", "real_position"]
+
+# (name, dataset, trace, config) as in NUMERIC, every trace at a shape that is granted a sliding
+# observation buffer (strata.slides).  trace["seed"]: added to the trace's own seeds (data, draws and
+# actions; no trace shares a generator with another), chosen so that the reference's trace has what
+# strata.slide_vacuous and the trace's strata ask for.
+SLIDE = [
+    ("multids_limit_orders_w8_f32", [dict(T=150, Fs=30, sigma=1.2e-2), dict(T=170, Fs=30, sigma=1.2e-2),
+                                     dict(T=190, Fs=30, sigma=1.2e-2)],
+     dict(E=4, K=140, p_none=0.3, p_order=0.3),
+     dict(positions=[-1, 0, 0.5, 1], windows=8, trading_fees=1e-3, borrow_interest_rate=1e-4,
+          max_episode_duration=25, episodes_between_dataset_switch=1)),
+    # (no dyn_persist: the generator asserts that no episode's first window holds rows an earlier
+    # episode on the same dataset object wrote)
+    ("multids_switch2_w16_f16_nd3", [dict(T=380, Fs=13, sigma=1e-2, special=True),
+                                     dict(T=400, Fs=13, sigma=1e-2, special=True)],
+     dict(E=4, K=200, seed=5),
+     dict(positions=P3, windows=16, trading_fees=1e-4, borrow_interest_rate=3e-6,
+          max_episode_duration=45, episodes_between_dataset_switch=2, dynamic_feature_functions=MIX3R)),
+    ("crash_w4_f64_nd4", dict(T=300, Fs=60, sigma=2e-2, jump=0.07), dict(E=4, K=140, p_none=0.3, seed=1),
+     dict(positions=CRASH, windows=4, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          portfolio_initial_value=3.0, dynamic_feature_functions=MIX4R)),
+    ("zero_close_special_w64_f4_nd1", dict(T=400, Fs=3, sigma=1e-2, zeros=8, special=True),
+     dict(E=4, K=200, seed=2),
+     dict(positions=[-1, 0, 1, 2], windows=64, trading_fees=1e-3, borrow_interest_rate=1e-4,
+          max_episode_duration=100, dynamic_feature_functions=["real_position"])),
+    ("short_episodes_w32_f8_nd1", dict(T=300, Fs=7, sigma=1e-2), dict(E=4, K=200),
+     dict(positions=LEV, windows=32, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          max_episode_duration=9, dynamic_feature_functions=["last_position_taken"],
+          reward_function=["scaled_log_return", 100.0])),
+    # (no auto-reset: K <= max_episode_duration + W keeps every env inside its data)
+    ("no_autoreset_w16_f16", dict(T=300, Fs=14, sigma=3e-2, drift=-6e-3),
+     dict(E=4, K=70, autoreset=False, p_none=0.4),
+     dict(positions=[-1, 0, 1, 2], windows=16, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          max_episode_duration=55)),
+    ("duration_max_w20_f16", dict(T=90, Fs=14, sigma=1e-2), dict(E=4, K=200),
+     dict(positions=P3, windows=20, trading_fees=1e-4, borrow_interest_rate=3e-6,
+          max_episode_duration="max")),
+    ("drawdown_clipped_special_w8_f32", dict(T=200, Fs=30, sigma=2.5e-2, drift=-4e-3, special=True),
+     dict(E=4, K=160, p_none=0.3, seed=1),
+     dict(positions=[-3, -1, 0, 1, 3], windows=8, trading_fees=1e-3, borrow_interest_rate=1e-3,
+          portfolio_initial_value=1e6, max_episode_duration=40,
+          reward_function=["clipped_log_return", 2.0, -0.004, 0.006])),
+    ("limit_orders_w64_f4_nd3", dict(T=400, Fs=1, sigma=1e-2), dict(E=4, K=200, p_none=0.2, p_order=0.35),
+     dict(positions=[-1, -0.5, 0, 1, 2], windows=64, trading_fees=1e-3, borrow_interest_rate=1e-4,
+          max_episode_duration=27, dynamic_feature_functions=MIX3R)),
+]
+
+
+def _assert_first_windows_are_fresh(name, sets, rec):
+    """Every reset returned a window whose earlier rows have zero dynamic columns: nothing an earlier
+    episode wrote on the same reference object is in the trace, so a batch without dyn_persist
+    replays it (episodes_between_dataset_switch > 1 keeps the object's table across episodes)."""
+    Fs = sets[0][0].shape[1]
+    first = rec["obs"][rec["op"] == 0]
+    assert not first[:, :-1, Fs:].any(), f"{name}: an episode starts inside rows an earlier one wrote"
+
+
+def slide_trace(n):
+    """The arrays of tests/golden/slide_<n>.npz and the loaded trace, from the reference."""
+    import replay
+    import strata
+    tag, dspec, tspec, over = SLIDE[n]
+    name = f"slide_{n:02d}"
+    cfg = base_cfg(**over)
+    kinds = cfg.get("dynamic_feature_functions", strata.DEFAULT_DYN)
+    kw = ref_kwargs(cfg)
+    kw.update(reward_function=_ref_reward(cfg["reward_function"]),
+              dynamic_feature_functions=_ref_dynamic(kinds))
+    tspec = dict(tspec)
+    E, K, pick = tspec.pop("E"), tspec.pop("K"), tspec.pop("seed", 0)
+    assert E <= 4 and K <= 200
+    high_low = tspec.get("p_order", 0) > 0
+    seed_base = 90000 + 1000 * n + 100 * pick
+    seed = SLIDE_SEED % 997 + 10 * n + 1000 * pick
+    rng = np.random.default_rng(SLIDE_SEED + 101 * n + pick)
+    if isinstance(dspec, list):
+        sets = [_numeric_dataset(seed + d, s, high_low) for d, s in enumerate(dspec)]
+        assert len({len(s[1]) for s in sets}) == len(sets), "datasets are identified by length"
+        with tempfile.TemporaryDirectory() as tmp:
+            names = []
+            for d, s in enumerate(sets):
+                names.append(f"sym{d}.pkl")
+                make_df(*s).to_pickle(os.path.join(tmp, names[-1]))
+            switch = cfg["episodes_between_dataset_switch"]
+
+            def mk(e):
+                np.random.seed(888 + 31 * n + e + 100 * pick)
+                return MultiDatasetTradingEnv(os.path.join(tmp, "*.pkl"),
+                                              episodes_between_dataset_switch=switch, **kw)
+            rec = run_trace(mk, cfg["positions"], n_envs=E, n_calls=K, action_rng=rng,
+                            ds_names=[len(s[1]) for s in sets], seed_base=seed_base, **tspec)
+            import glob as _glob
+            rec["glob_order"] = np.array([names.index(os.path.basename(q))
+                                          for q in _glob.glob(os.path.join(tmp, "*.pkl"))], np.int32)
+    else:
+        sets = [_numeric_dataset(seed, dspec, high_low)]
+        df = make_df(*sets[0])
+        rec = run_trace(lambda e: TradingEnv(df=df, **kw), cfg["positions"], n_envs=E, n_calls=K,
+                        action_rng=rng, seed_base=seed_base, fresh_env_each_episode=True, **tspec)
+    assert all(len(s[1]) <= 400 for s in sets)
+    _assert_static_columns_unaltered(name, sets, rec)
+    _assert_first_windows_are_fresh(name, sets, rec)
+    out = fixture_arrays(cfg, sets, rec, "")
+    g = replay.from_arrays(out)
+    assert strata.slides(strata.facts(g)), f"{name}: not a shape that slides"
+    assert not strata.slide_vacuous(g), f"{name}: {strata.slide_vacuous(g)}"
+    out["note"] = np.array(f"slide trace {tag}; strata: {', '.join(strata.slide_rows_of(g))}")
+    return out, g
+
+
+def slide_traces():
+    """tests/golden/slide_NN.npz: every row of SLIDE_STRATA (tests/strata.py) on traces whose window
+    slides, each generated by the reference from its own seeds.  The other fixtures are not touched."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import strata
+    assert 8 <= len(SLIDE) <= 10
+    loaded, total = [], 0
+    for n in range(len(SLIDE)):
+        name = f"slide_{n:02d}"
+        out, g = slide_trace(n)
+        write(name, out)
+        print("   ", str(out["note"]))
+        kib = os.path.getsize(os.path.join(HERE, name + ".npz")) / 1024
+        assert kib <= SLIDE_KIB_PER_FIXTURE, f"{name}: {kib:.0f} KiB"
+        total += kib
+        loaded.append(g)
+    assert total <= SLIDE_KIB_TOTAL, f"slide: {total:.0f} KiB"
+    gaps = strata.slide_missing(loaded)
+    assert not gaps, f"slide strata rows not covered: {gaps}"
+    print(f"slide: {len(SLIDE)} traces, {total:.0f} KiB")
+
+
 def portfolio_vectors():
     """Random known answers straight from the reference's Portfolio class
     (utils/portfolio.py:1-66, which imports nothing): every branch of trade_to_position
@@ -1038,6 +1175,10 @@ if __name__ == "__main__":
     if "--numeric" in sys.argv:
         with np.errstate(all="ignore"):  # the reference divides by zero prices on purpose here
             numeric_traces()
+        sys.exit(0)
+    if "--slide" in sys.argv:
+        with np.errstate(all="ignore"):  # zero closes again
+            slide_traces()
         sys.exit(0)
     if "--only-vector" in sys.argv:
         vector_example_fixture()

@@ -1,6 +1,6 @@
 """The strata tables of the reference-generated fixture families: STRATA for the configuration
 sweep (tests/golden/sweep_NN.npz), NUMERIC_STRATA further down for the numeric family
-(numeric_NN.npz).
+(numeric_NN.npz), SLIDE_STRATA at the end for the family at shapes whose window slides (slide_NN.npz).
 
 Every row names one corner of the configuration space the HIP kernels branch on and a
 predicate over a loaded trace (replay.load) that says whether the trace covers it.  The
@@ -315,3 +315,125 @@ def numeric_missing(traces):
     """Rows of NUMERIC_STRATA that none of the given loaded traces covers."""
     covered = {r for g in traces for r in numeric_rows_of(g)}
     return [name for name in NUMERIC_STRATA if name not in covered]
+
+
+# -- the slide family (tests/golden/slide_NN.npz, make_golden.py --slide) -------------------------
+# The sliding observation buffer (gte.h, gte_bind_sliding_obs) keeps W - 1 rows of every env that
+# merely advanced from earlier launches, dynamic columns included.  These rows put what the other
+# two families hold (datasets that switch, limit-order fills, drawdown ends, envs that step on after
+# their end, NaN valuations, special feature words) on shapes that are granted a slack, and sweep the
+# geometry of the slide loop itself (gte_step.h, phase_b_slide).
+def auto_slack(W):
+    """The automatic slack M of a window of W rows (gte_api.hip, plan_launches: 2 W / 5)."""
+    return 2 * W // 5
+
+
+def slides(f):
+    """plan_launches' grant of a sliding buffer, restated: 16-byte rows with dynamic columns staged
+    raw in LDS (F_obs % 4 == 0, nd > 0, no dyn_persist), a window of at least one wave instruction
+    of 16-byte vectors, and an automatic slack of at least one row.  (The traces have neither
+    final_obs nor a log; cooperative phase A holds at up to 16 envs per wave.)"""
+    return (f["W"] is not None and f["Fobs"] % 4 == 0 and f["nd"] > 0 and not f["persist"]
+            and f["W"] * f["Fobs"] // 4 >= 64 and auto_slack(f["W"]) >= 1)
+
+
+def slide_counts(g, M):
+    """What a replay of trace g exercises with a slack of M rows, from the trace alone: after the
+    reset() at call 0 the head at call k is k % (M + 1); a call with a head other than 0 slides, a
+    call k > 0 at head 0 is a wrap (full windows).  Counts the slide calls, the wraps, the per-env
+    resets (op == 0, k > 0) on slide calls, and the env-steps taken after the env's episode ended
+    (no auto-reset: its flags stay raised and it is stepped on, environments.py:233-272) on slide
+    calls."""
+    op = g["op"]
+    K = op.shape[0]
+    head = np.arange(K) % (M + 1)
+    slide = head != 0
+    ends = (g["done"] | g["truncated"]).astype(bool)
+    after_end = np.zeros_like(ends)
+    if not (op[1:] == 0).any():
+        after_end[1:] = np.maximum.accumulate(ends, axis=0)[:-1] & (op[1:] == 1)
+    return dict(slide_calls=int(slide.sum()), wraps=int((~slide[1:]).sum()),
+                resets_on_slide=int((op[slide] == 0).sum()),
+                after_end_on_slide=int(after_end[slide].sum()))
+
+
+def slacks_tested(f):
+    """The obs_slack_rows values the GPU test replays a trace with, as slack rows M."""
+    return sorted({1, 3, auto_slack(f["W"])})
+
+
+def _mixed_real_first(f, nd):
+    return f["nd"] == nd and len(set(f["kinds"])) == 2 and f["kinds"][0] == "real_position"
+
+
+def _nan_survives_the_window(g, f):
+    # a NaN real_position in the OLDEST row of a recorded window: written W - 1 calls earlier
+    return bool(f["W"] > 1 and np.isnan(_dyn_obs(g, f, "real_position")[:, :, 0]).any())
+
+
+def _leveraged_crash(g, f):
+    return bool(g["done"].any() and _negative_valuation(g, f) and f["nd"] > 0
+                and (_finite_abs(_dyn_obs(g, f, "real_position")) >= 10).any()
+                and (max(f["positions"]) > 1 or min(f["positions"]) < -1))
+
+
+SLIDE_STRATA = {
+    "multids_switch1": lambda g, f: f["D"] >= 2 and len(set(f["Ts"])) == f["D"] and f["switch"] == 1,
+    "multids_switch_ge2": lambda g, f: f["D"] >= 2 and len(set(f["Ts"])) == f["D"] and f["switch"] >= 2,
+    "limit_fill_with_market_action": _fill_with_market_action,
+    "limit_several_per_env": _several_orders,
+    "multids_limit_orders_high_low": lambda g, f: f["D"] >= 2 and f["limit"] and f["high_low"],
+    "leveraged_crash_done": _leveraged_crash,
+    "no_autoreset_steps_after_end": _steps_after_end,
+    "zero_close_nonfinite": lambda g, f: any((c == 0.0).any() for c in _closes(g)) and _nonfinite(g, f),
+    "nan_row_survives_the_window": _nan_survives_the_window,
+    "special_features": _special_features,
+    "fobs4_window_ge64": lambda g, f: f["Fobs"] == 4 and f["W"] >= 64,
+    "fobs_ge64_window4": lambda g, f: f["Fobs"] >= 64 and f["W"] == 4,
+    "window8_fobs32": lambda g, f: f["W"] == 8 and f["Fobs"] == 32,
+    "nd1": lambda g, f: f["nd"] == 1,
+    "nd3_mixed_real_position_first": lambda g, f: _mixed_real_first(f, 3),
+    "nd4_mixed_real_position_first": lambda g, f: _mixed_real_first(f, 4),
+    "duration_le_auto_slack": lambda g, f: f["dur"] != "max" and f["dur"] <= auto_slack(f["W"]),
+    "duration_max_truncated_end_of_data": lambda g, f: f["dur"] == "max" and f["trunc_end"],
+}
+
+#: rows that must hold in at least this many slide traces (all others: one)
+SLIDE_MIN_TRACES = {"drawdown_done": 2}
+#: per slack the GPU test uses, every slide trace has this many per-env resets on slide calls (the
+#: trace without auto-reset: env-steps after the end instead)
+SLIDE_MIN_EVENTS = 3
+
+
+def slide_rows_of(g):
+    """The SLIDE_STRATA rows trace g covers: none unless the trace slides."""
+    f = facts(g)
+    if not slides(f):
+        return []
+    rows = [name for name, pred in SLIDE_STRATA.items() if pred(g, f)]
+    if g["done"].any():
+        rows.append("drawdown_done")
+    return rows
+
+
+def slide_missing(traces):
+    """Rows of SLIDE_STRATA (and SLIDE_MIN_TRACES) the given loaded traces leave uncovered."""
+    count = {name: 0 for name in list(SLIDE_STRATA) + list(SLIDE_MIN_TRACES)}
+    for g in traces:
+        for r in slide_rows_of(g):
+            count[r] += 1
+    return {name: n for name, n in count.items() if n < SLIDE_MIN_TRACES.get(name, 1)}
+
+
+def slide_vacuous(g):
+    """Why a replay of slide trace g would prove too little at one of slacks_tested: a list of
+    reasons, empty when at every slack the trace has SLIDE_MIN_EVENTS resets (without auto-reset:
+    env-steps after the end) on slide calls and at least one wrap."""
+    f = facts(g)
+    what = "resets_on_slide" if f["autoreset"] else "after_end_on_slide"
+    out = []
+    for M in slacks_tested(f):
+        c = slide_counts(g, M)
+        if c[what] < SLIDE_MIN_EVENTS or c["wraps"] < 1:
+            out.append(f"M={M}: {c}")
+    return out

@@ -1,5 +1,6 @@
-"""Every sweep trace (tests/golden/sweep_NN.npz: the configurations the kernels branch on) and every
-numeric trace (numeric_NN.npz: the values the arithmetic and the copy loops run on), all generated
+"""Every sweep trace (tests/golden/sweep_NN.npz: the configurations the kernels branch on), every
+numeric trace (numeric_NN.npz: the values the arithmetic and the copy loops run on) and every slide
+trace (slide_NN.npz: their hardest semantics at shapes with lean, slidable windows), all generated
 by the reference itself (strata in tests/strata.py), through the HIP library on every step and
 rollout path, held to what the code claims: indices and flags exact, static observation columns
 bit for bit (NaN payloads, -0.0 and subnormals included), the fp64 portfolio state, the valuation
@@ -32,7 +33,10 @@ pytestmark = pytest.mark.gpu
 
 SWEEP = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(replay.GOLDEN_DIR, "sweep_*.npz")))
 NUMERIC = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(replay.GOLDEN_DIR, "numeric_*.npz")))
-TRACES = SWEEP + NUMERIC
+# (the slide family: multi-dataset, limit-order, crash and zero-close traces at lean shapes; its sliding
+# replays are in tests/test_gpu_sliding_reference.py)
+SLIDE = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(replay.GOLDEN_DIR, "slide_*.npz")))
+TRACES = SWEEP + NUMERIC + SLIDE
 WORST_ULPS = {}
 
 
