@@ -264,6 +264,8 @@ SYMBOLS = {
     "gte_bind_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64]),
     "gte_signal_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_backtest_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
+    "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_int64]),
     "gte_bind_returns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_comm_unique_id": (C.c_int, [C.c_void_p]),
     "gte_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),

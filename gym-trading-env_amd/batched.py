@@ -1240,11 +1240,7 @@ class BatchedTradingEnv(_VectorEnvBase):
             if T != self.datasets[d].T:
                 raise ValueError(f"signal table of dataset {d} has {T} columns, the dataset {self.datasets[d].T} rows")
             padded[d] = buf
-        # one S: over the tables of this call and those that stay bound
-        kept = {d: t for d, t in self._signals.items() if d not in tables}
-        sizes = {int(t.shape[0]) for t in list(padded.values()) + list(kept.values())}
-        if len(sizes) > 1:
-            raise ValueError(f"signal tables must have one number of strategies, got {sorted(sizes)}")
+        self._check_one_s(padded, tables)
         if padded:
             torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
         for d, t in tables.items():
@@ -1252,11 +1248,121 @@ class BatchedTradingEnv(_VectorEnvBase):
                 _abi.check(self._lib, self._lib.gte_bind_signals(self._h, d, None, 0, 0))
                 self._signals.pop(d, None)
             else:
-                buf = padded[d]
-                assert buf.data_ptr() % sig.PIECE == 0 and buf.is_contiguous()
-                _abi.check(self._lib, self._lib.gte_bind_signals(self._h, d, C.c_void_p(buf.data_ptr()),
-                                                                 int(buf.shape[0]), int(buf.shape[1])))
-                self._signals[d] = buf
+                self._bind_padded(d, padded[d])
+
+    def _check_one_s(self, padded, replaced):
+        """one S: over the padded tables of this call and those that stay bound"""
+        kept = {d: t for d, t in self._signals.items() if d not in replaced}
+        sizes = {int(t.shape[0]) for t in list(padded.values()) + list(kept.values())}
+        if len(sizes) > 1:
+            raise ValueError(f"signal tables must have one number of strategies, got {sorted(sizes)}")
+
+    def _bind_padded(self, d, buf):
+        """Bind the padded int8 [S, stride] device tensor `buf`, complete on the env's stream, to
+        dataset d and keep it alive (the bind step of bind_signals and build_signals)."""
+        from . import signals as sig
+        assert buf.data_ptr() % sig.PIECE == 0 and buf.is_contiguous()
+        _abi.check(self._lib, self._lib.gte_bind_signals(self._h, d, C.c_void_p(buf.data_ptr()),
+                                                         int(buf.shape[0]), int(buf.shape[1])))
+        self._signals[d] = buf
+
+    def build_signals(self, indicators, rules, dataset=None, bind=True):
+        """Build signal tables ON THE DEVICE from indicator rules (`gte_build_signals`): one rule per
+        strategy (`signals.rules`, `signals.RULE_DTYPE`; the rule is stated in include/gte.h) over a
+        bank of indicators f32 [C, T] of the dataset (`signals.sma_bank`, feature columns, anything).
+        Returns the table as a torch int8 [S, T] view of a padded device tensor — complete for torch
+        to read when the call returns — and, with ``bind=True``, binds that same tensor as
+        `bind_signals` would, without a second copy.  No [S, T] array exists on the host.
+
+        indicators: a NumPy array or a CUDA f32 tensor [C, T] for dataset `dataset` (default: the
+        only one); with ``dataset=None`` and D > 1 a list of D banks, one per resident dataset, and
+        the result is a list of D tables.  A CUDA bank whose rows are 16-byte aligned and padded to
+        `signals.bank_stride(T)` floats (a ``[:, :T]`` view of such a tensor) is read in place.
+        rules: a `RULE_DTYPE` array [S], whose `a` / `b` are checked against the bank here, or a
+        CUDA tensor uint8 [S, 32] / int32 [S, 8] of the same bytes, which is the caller's contract:
+        the kernel gives a rule that names no indicator a row of -1.  One rule array serves every
+        dataset.  The caller's rule order is kept (a row index is a strategy id).  One wavefront
+        builds one row, and the waves that run together share the bank through L2: rules sorted by
+        ``(a, b)`` built 65 536 rows x 33 259 columns over 256 indicators 36 % faster than the same
+        rules in random order (16 % at 4 096 rows; DESIGN.md §4, `tools/signal_build_bench.py`), so
+        sort a large sweep by indicator before it becomes the strategy numbering."""
+        torch = self._torch
+        if torch is None:
+            raise ValueError("build_signals needs output='torch'")
+        from . import signals as sig
+        D = len(self.datasets)
+        if dataset is None:
+            if D == 1 and not isinstance(indicators, (list, tuple)):
+                banks = {0: indicators}
+            elif isinstance(indicators, (list, tuple)) and len(indicators) == D:
+                banks = dict(enumerate(indicators))
+            else:
+                raise ValueError(f"expected a list of {D} indicator banks, one per dataset (or dataset=d)")
+        else:
+            if not 0 <= int(dataset) < D:
+                raise IndexError(f"dataset {dataset} out of range")
+            banks = {int(dataset): indicators}
+        dev = self._t["obs"].device
+        # the rules: 32 bytes each on the device
+        if isinstance(rules, torch.Tensor):
+            if not (rules.is_cuda and rules.dim() == 2 and rules.is_contiguous() and
+                    (rules.dtype, int(rules.shape[1])) in ((torch.uint8, 32), (torch.int32, 8))):
+                raise TypeError("rules: a RULE_DTYPE array, or a contiguous CUDA tensor uint8 [S, 32] / int32 [S, 8]")
+            d_rules, host_rules = rules.to(dev), None
+        else:
+            host_rules = np.ascontiguousarray(rules)
+            if host_rules.dtype != sig.RULE_DTYPE or host_rules.ndim != 1:
+                raise TypeError("rules: a one-dimensional array of signals.RULE_DTYPE (signals.rules)")
+            d_rules = torch.from_numpy(host_rules.view(np.uint8).reshape(-1, sig.RULE_DTYPE.itemsize)).to(dev)
+        S = int(d_rules.shape[0])
+        if S < 1:
+            raise ValueError("build_signals needs at least one rule")
+        d_banks = {}
+        for d, x in banks.items():
+            T = self.datasets[d].T
+            if isinstance(x, torch.Tensor) and x.is_cuda:
+                if x.dim() != 2 or x.dtype != torch.float32:
+                    raise TypeError("an indicator bank is a two-dimensional float32 tensor")
+                x = x.to(dev)
+                if not (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= sig.bank_stride(T)
+                        and x.data_ptr() % 16 == 0):
+                    with torch.cuda.device(dev):
+                        buf = torch.zeros((int(x.shape[0]), sig.bank_stride(int(x.shape[1]))), dtype=torch.float32,
+                                          device=dev)
+                    buf[:, :x.shape[1]] = x
+                    x = buf[:, :x.shape[1]]
+            else:
+                host = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x)
+                x = torch.from_numpy(sig.pad_bank(host)).to(dev)[:, :host.shape[-1]]
+            if int(x.shape[1]) != T:
+                raise ValueError(f"indicator bank of dataset {d} has {int(x.shape[1])} columns, the dataset {T} rows")
+            n_ind = int(x.shape[0])
+            if n_ind < 1:
+                raise ValueError("an indicator bank needs at least one row")
+            if host_rules is not None and ((host_rules["a"] < 0) | (host_rules["a"] >= n_ind) |
+                                           (host_rules["b"] < -1) | (host_rules["b"] >= n_ind)).any():
+                raise IndexError(f"rules name indicators outside the {n_ind} rows of dataset {d}'s bank "
+                                 "(a in [0, C), b in [-1, C))")
+            d_banks[d] = x
+        with torch.cuda.device(dev):
+            tables = {d: torch.empty((S, sig.row_stride(self.datasets[d].T)), dtype=torch.int8, device=dev)
+                      for d in d_banks}
+        if bind:
+            self._check_one_s(tables, tables)
+        torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
+        for d, x in d_banks.items():
+            buf = tables[d]
+            _abi.check(self._lib, self._lib.gte_build_signals(
+                self._h, d, C.c_void_p(x.data_ptr()), int(x.shape[0]), int(x.stride(0)),
+                C.c_void_p(d_rules.data_ptr()), S, C.c_void_p(buf.data_ptr()), int(buf.shape[1])))
+        self.synchronize()  # the tables are complete: for torch on any stream, and before the inputs go
+        out = {}
+        for d, buf in tables.items():
+            if bind:
+                self._bind_padded(d, buf)
+            out[d] = buf[:, :self.datasets[d].T]
+        return out[next(iter(out))] if (dataset is not None or not isinstance(indicators, (list, tuple))) \
+            else [out[d] for d in range(D)]
 
     @property
     def num_strategies(self) -> int:

@@ -1407,6 +1407,34 @@ int gte_backtest_signals(gte_env* E, const int32_t* strategy_device, int32_t n_s
   return backtest_entry(E, "gte_backtest_signals", nullptr, strategy_device, n_steps, clear, stats_device);
 }
 
+int gte_build_signals(gte_env* E, int32_t d, const float* indicators_device, int32_t n_indicators,
+                      int64_t ind_stride, const gte_signal_rule* rules_device, int32_t n_rules,
+                      int8_t* table_device, int64_t row_stride) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_build_signals inside a stream capture");
+  const int64_t T = E->h_ds[d].T;
+  if (T <= 0) return fail(GTE_ERR_STATE, "gte_build_signals: dataset %d was never uploaded", d);
+  const int64_t T16 = (T + 15) / 16 * 16;
+  if (!indicators_device || !rules_device || !table_device) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (((uintptr_t)indicators_device & 15) || ((uintptr_t)table_device & 15))
+    return fail(GTE_ERR_INVALID, "the indicator bank and the table must be 16-byte aligned");
+  if ((uintptr_t)rules_device & 3) return fail(GTE_ERR_INVALID, "rules must be 4-byte aligned");
+  if (row_stride % 16 != 0 || row_stride < T16)
+    return fail(GTE_ERR_INVALID, "row_stride %lld: a multiple of 16 and >= %lld (the %lld rows of dataset %d "
+                "rounded up to 16) required", (long long)row_stride, (long long)T16, (long long)T, d);
+  if (ind_stride % 4 != 0 || ind_stride < T16)
+    return fail(GTE_ERR_INVALID, "ind_stride %lld floats: a multiple of 4 and >= %lld required",
+                (long long)ind_stride, (long long)T16);
+  if (n_indicators < 1) return fail(GTE_ERR_INVALID, "n_indicators must be >= 1");
+  if (n_rules < 1) return fail(GTE_ERR_INVALID, "n_rules must be >= 1");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const hipError_t e = gte::launch_build_signals(indicators_device, n_indicators, ind_stride, rules_device, n_rules,
+                                                 T, table_device, row_stride, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal build launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
 int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backtest_stats* out) {
   if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
   if (!E->bt_stats) return fail(GTE_ERR_STATE, "gte_read_backtest_stats before gte_backtest");

@@ -98,6 +98,13 @@ hipError_t launch_signal_actions(const Params& p, const SignalTable* tables, int
 hipError_t launch_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
                                  gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream);
 
+// --- gte_signals.hip: signal tables written on the device from indicator rules (gte_build_signals,
+// include/gte.h): table rows 0 .. n_rules-1, bytes 0 .. round_up(T, 16)-1 of each; the caller has checked
+// alignments and strides
+hipError_t launch_build_signals(const float* indicators, int n_indicators, int64_t ind_stride,
+                                const gte_signal_rule* rules, int n_rules, int64_t T, int8_t* table,
+                                int64_t row_stride, hipStream_t stream);
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

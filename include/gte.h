@@ -509,6 +509,51 @@ int gte_signal_actions(gte_env* env, const int32_t* strategy_device, int32_t* ac
 int gte_backtest_signals(gte_env* env, const int32_t* strategy_device, int32_t n_steps, int32_t clear,
                          gte_backtest_stats** stats_device);
 
+/* ---- SIGNAL TABLES BUILT ON THE DEVICE from indicator rules: a parameter sweep passes a small bank of
+ * indicators and one 32-byte rule per strategy, and the device writes the int8 [n_rules][T] table that
+ * gte_bind_signals accepts — no host table, no host-to-device copy of it.
+ *
+ * An INDICATOR BANK of a dataset is caller-owned DEVICE memory float [n_indicators][ind_stride]: row c
+ * is indicator c over the dataset's rows t = 0 .. T-1 (an SMA, an EMA, an RSI, a feature column, a
+ * constant: the library does not care).  A RULE compares one indicator, or the difference of two,
+ * with two thresholds, optionally with a latch (hysteresis: enter above hi, leave below lo, keep the
+ * state in between).  This text is the specification; the reference has no counterpart. */
+typedef struct gte_signal_rule {
+  int32_t a, b;          /* indicator rows; b == -1: compare a alone            */
+  float   hi, lo;        /* thresholds on d                                     */
+  int32_t warmup;        /* rows t < warmup: output -1 (hold), state untouched  */
+  int8_t  pos_up, pos_down, pos_neutral;   /* table bytes written, not validated */
+  uint8_t latch;         /* non-zero: keep the last non-zero zone               */
+  int32_t reserved[2];   /* ignored                                             */
+} gte_signal_rule;
+/* Row s of the table is built from rule s for t = 0 .. T-1 in order, with state q = 0 before row 0
+ * (x = the bank):
+ *
+ *     if t < warmup: out[t] = -1; continue              (q unchanged)
+ *     d = x[a][t] - x[b][t]   (one IEEE f32 subtraction, subnormals kept)   or   x[a][t] when b == -1
+ *     z = +1 if d > hi, else -1 if d < lo, else 0       (NaN anywhere gives 0; hi < lo: "up" wins)
+ *     q = z if (z != 0 or not latch) else q
+ *     out[t] = pos_up if q > 0, pos_down if q < 0, else pos_neutral
+ *
+ * A rule with a outside [0, n_indicators) or b outside [-1, n_indicators) gives a row of -1: no rule
+ * content makes the kernel read outside the bank.  Bytes T .. round_up(T, 16) - 1 of every row are -1;
+ * bytes of a row beyond round_up(T, 16), and everything outside rows 0 .. n_rules - 1, are not
+ * touched.  What the bytes mean (hold outside [0, n_positions)) stays with the lookup.
+ *
+ * T is that of resident dataset `ds` (GTE_ERR_STATE if it was never uploaded).  The launch is ordered
+ * on the env's stream and binds nothing: pass the table to gte_bind_signals afterwards (which waits
+ * for the stream).  Refused inside a stream capture (GTE_ERR_STATE), like gte_bind_signals.
+ * GTE_ERR_INVALID, with nothing launched, unless: table_device and indicators_device are 16-byte
+ * aligned and rules_device 4-byte aligned; row_stride % 16 == 0 and row_stride >= round_up(T, 16)
+ * (bytes); ind_stride % 4 == 0 and ind_stride >= round_up(T, 16) (floats), so that a 16-byte load
+ * anywhere in the 16 rows of a piece is legal; n_indicators >= 1 and n_rules >= 1.  One wavefront
+ * builds one row in pieces of 1 024 rows (gte_signals.hip); rules that read the same indicator rows
+ * are best placed next to each other. */
+int gte_build_signals(gte_env* env, int32_t ds,
+                      const float* indicators_device, int32_t n_indicators, int64_t ind_stride,
+                      const gte_signal_rule* rules_device, int32_t n_rules,
+                      int8_t* table_device, int64_t row_stride);
+
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
 /* Same-step auto-reset with gte_config.final_obs: struct-of-arrays snapshot (device pointers,
