@@ -12,17 +12,20 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "gte_launch.h"
+#include "gte_ledger.h"
 
 using gte::DatasetDesc;
 using gte::EnvRec;
 using gte::Params;
+using gte_ledger::FLAGS;
+using gte_ledger::WINDOW;
+using gte_ledger::ledger;
 
 static thread_local std::string g_err = "";
 
@@ -54,7 +57,7 @@ struct LaunchPlan {
   int store = 0;           // observation store policy (store_out): 0 plain, 1 nt, 2 sc1 (never 3)
   bool hot_tu = false;     // the step may go to the isolated hot instantiations (hot_tu_covers permitting)
   bool fused_log = false;  // the step kernel writes the trajectory row itself
-  bool always_dense = false;     // every step stores all flags (flag ledger below)
+  bool always_dense = false;     // every step stores all flags (gte_ledger.h)
   int slide_rows = 0;            // M: spare rows a sliding observation buffer may have (0 = this env never slides)
   bool full_windows = false;     // a sliding buffer moves its head but every step writes full windows (A/B)
   bool fused_rollout = false;    // gte_rollout may use the fused kernels ...
@@ -133,126 +136,20 @@ struct gte_env {
   bool view_reads = false; // gte_read_envs_view has been used: the buffer is kept at full size
   void* h_logpack = nullptr;  // pinned host memory for gte_read_log_envs
   size_t h_logpack_bytes = 0;
-  // sparse flag stores (flag ledger below): the next step may store only the flags that change
-  bool flags_sparse_ok = false;
-  const uint8_t* flags_term = nullptr;   // ... into these two buffers, which this env's last step
-  const uint8_t* flags_trunc = nullptr;  //     wrote and nothing has written since
-  // sliding observation buffer (gte_bind_sliding_obs; window ledger below).  p.obs is its base, p.obs_rows
-  // = W + M and p.obs_head the head the last launch wrote at
+  // sliding observation buffer (gte_bind_sliding_obs).  p.obs is its base, p.obs_rows = W + M and p.obs_head
+  // the head the last launch wrote at.  Whether the next step may slide, or store its flags sparsely, is
+  // for the ledger to say (gte_ledger.h)
   bool sliding = false;
-  bool slide_valid = false;  // (g_flag_mu) the buffer holds every env's window at p.obs_head, written by this env
 };
 
-// Flag ledger.  A step stores an env's terminated / truncated bytes only where they change
-// (store_flags, gte_phase_a.h) when the two buffers hold exactly what this env's previous step
-// stored there.  That is true only while nothing else writes them, and the host keeps the proof
-// here, process-wide (several envs may share or rotate buffers):
-//   * an env's eager step records the ranges it wrote: its next step may be sparse if it writes the
-//     same two buffers again;
-//   * every launch that writes flag bytes (any env's step, reset or rollout) withdraws that right
-//     from every OTHER env whose recorded ranges it overlaps; a reset, a rollout and any rebinding
-//     of outputs or returns withdraw it from the env itself;
-//   * a range written by a step inside a graph capture is never sparse again: a replay writes it at
-//     times the host does not see.  Captured steps themselves store densely, so a replay is correct
-//     whatever ran before it.
-// A dense step stores every flag and brings each record's flags_out up to date, so one dense step
-// restores the invariant whatever happened before.
-namespace {
-struct FlagRange { gte_env* env; uintptr_t lo, hi; };
-std::mutex g_flag_mu;
-std::vector<FlagRange> g_flag_last;                         // ranges each env's last eager step wrote
-std::vector<std::pair<uintptr_t, uintptr_t>> g_flag_captured;  // ranges written inside a capture
-
-bool ranges_overlap(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) {
-  return a_lo < b_hi && b_lo < a_hi;
-}
-// (g_flag_mu held) env E's launch writes [ptr, ptr + n): other envs that rely on those bytes lose the right
-void flags_clobber_locked(const gte_env* E, const void* ptr, size_t n) {
-  if (!ptr || !n) return;
-  const uintptr_t lo = (uintptr_t)ptr, hi = lo + n;
-  for (const FlagRange& r : g_flag_last)
-    if (r.env != E && ranges_overlap(lo, hi, r.lo, r.hi)) r.env->flags_sparse_ok = false;
-}
-void flags_forget_locked(const gte_env* E) {
-  size_t k = 0;
-  for (size_t i = 0; i < g_flag_last.size(); ++i)
-    if (g_flag_last[i].env != E) g_flag_last[k++] = g_flag_last[i];
-  g_flag_last.resize(k);
-}
-}  // namespace
-
-// Window ledger, in the manner of the flag ledger.  A step of an env with a sliding observation buffer may
-// store only the newest row of the envs that advanced (Params.slide) when the buffer holds, at the current
-// head h < M, exactly the windows this env's previous reset or step wrote there:
-//   * an unmasked reset and every full step write all windows at head 0 and establish that;
-//   * a masked reset writes the masked envs' windows at the current head and changes nothing else;
-//   * a rebind, a rollout or backtest (their fused steps advance the envs without writing the buffer), a
-//     stream capture (a replay writes at times the host does not see: captured steps write in full at
-//     head 0), gte_set_schedule and any OTHER env's launch that writes into the buffer withdraw it.
-// One full step restores the invariant whatever came before.
-namespace {
-std::vector<FlagRange> g_slide_bufs;  // (g_flag_mu) the sliding buffers bound at the moment
-void slide_forget_locked(const gte_env* E) {
-  size_t k = 0;
-  for (size_t i = 0; i < g_slide_bufs.size(); ++i)
-    if (g_slide_bufs[i].env != E) g_slide_bufs[k++] = g_slide_bufs[i];
-  g_slide_bufs.resize(k);
-}
-}  // namespace
-// E's launch writes observations into [ptr, ptr + bytes): other envs sliding there write in full next
-static void obs_written(const gte_env* E, const void* ptr, size_t bytes) {
-  if (!ptr || !bytes) return;
-  std::lock_guard<std::mutex> lock(g_flag_mu);
-  const uintptr_t lo = (uintptr_t)ptr, hi = lo + bytes;
-  for (const FlagRange& r : g_slide_bufs)
-    if (r.env != E && ranges_overlap(lo, hi, r.lo, r.hi)) r.env->slide_valid = false;
-}
-static void slide_invalidate(gte_env* E) {
-  std::lock_guard<std::mutex> lock(g_flag_mu);
-  E->slide_valid = false;
-}
 // bytes of E's own observation buffer, whichever layout it has
 static size_t own_obs_bytes(const gte_env* E) {
   return sizeof(float) * (size_t)E->p.N * (size_t)obs_env_stride(E->p);
 }
 
-// A launch that is not a plain eager step writes (or may write) flag bytes: [ptr, ptr + n) for each
-// pair given; the env's own next step stores densely.
-static void flags_unsure(gte_env* E, std::initializer_list<std::pair<const void*, size_t>> written) {
-  std::lock_guard<std::mutex> lock(g_flag_mu);
-  E->flags_sparse_ok = false;
-  for (const auto& w : written) flags_clobber_locked(E, w.first, w.second);
-}
-
-// May this step of E store its flags sparsely into p's buffers?
-static bool flags_may_skip(gte_env* E, const Params& p, bool capturing) {
-  if (capturing || E->plan.always_dense) return false;
-  std::lock_guard<std::mutex> lock(g_flag_mu);
-  return E->flags_sparse_ok && E->flags_term == p.terminated && E->flags_trunc == p.truncated;
-}
-
-// E's step wrote every env's flags (densely or sparsely) into p's buffers
-static void flags_stepped(gte_env* E, const Params& p, bool capturing) {
-  const size_t N = (size_t)p.N;
-  const uintptr_t t = (uintptr_t)p.terminated, u = (uintptr_t)p.truncated;
-  std::lock_guard<std::mutex> lock(g_flag_mu);
-  flags_clobber_locked(E, p.terminated, N);
-  flags_clobber_locked(E, p.truncated, N);
-  flags_forget_locked(E);
-  E->flags_sparse_ok = false;
-  if (capturing) {
-    g_flag_captured.emplace_back(t, t + N);
-    g_flag_captured.emplace_back(u, u + N);
-    return;
-  }
-  for (const auto& c : g_flag_captured)
-    if (ranges_overlap(t, t + N, c.first, c.second) || ranges_overlap(u, u + N, c.first, c.second)) return;
-  g_flag_last.push_back({E, t, t + N});
-  g_flag_last.push_back({E, u, u + N});
-  E->flags_term = p.terminated;
-  E->flags_trunc = p.truncated;
-  E->flags_sparse_ok = true;
-}
+// what the ledger is told (gte_ledger.h): E's own observation buffer, a buffer of N flag bytes
+static gte_ledger::Span obs_span(const gte_env* E) { return {E->p.obs, own_obs_bytes(E)}; }
+static gte_ledger::Span flag_span(const gte_env* E, const uint8_t* flags) { return {flags, (size_t)E->p.N}; }
 
 template <typename T>
 static int dev_alloc(gte_env* E, T** out, size_t count, bool zero = true) {
@@ -877,13 +774,14 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   TRY(ensure_owned_obs(E));
   TRY(finalize(E));
   TRY(check_injection(E, (size_t)E->p.N, inj_idx, inj_pos_index, inj_dataset));
-  obs_written(E, E->p.obs, own_obs_bytes(E));
   Params p = E->p;  // (a masked reset writes the masked envs' windows at the current head)
   const bool fresh_run = E->sliding && !mask;  // every window is written: a fresh run of slides from head 0
-  if (fresh_run) {
-    p.obs_head = 0;
-    slide_invalidate(E);  // (until the launch below has gone out: a failed reset proves nothing)
-  }
+  if (fresh_run) p.obs_head = 0;
+  // masked envs get zero flags, flags_out untouched: the next step stores densely.  The window claim stands
+  // through a masked reset; a fresh run gives it up until the launch below has gone out (a failed reset
+  // proves nothing)
+  ledger().wrote(E, {obs_span(E), flag_span(E, p.terminated), flag_span(E, p.truncated)}, false,
+                 fresh_run ? FLAGS | WINDOW : FLAGS);
   const size_t N = (size_t)p.N;
   p.mask = nullptr; p.inj_idx = p.inj_pos = p.inj_ds = nullptr;
   if (mask) { TRY(stage(E, E->d_mask, mask, N)); p.mask = E->d_mask; }
@@ -895,13 +793,11 @@ int gte_reset(gte_env* E, const uint8_t* mask, const int32_t* inj_idx,
   E->term_slot = 0;
   p.term_count = E->term_base;
   p.term_count_next = E->term_base + 1;
-  flags_unsure(E, {{p.terminated, N}, {p.truncated, N}});  // (masked envs get zero flags, flags_out untouched)
   const LaunchPlan& L = E->plan;
   HIPCHK(gte::launch_reset(p, L.vec, L.store, L.coop, L.stage, L.blocks, L.threads, E->stream));
-  if (fresh_run) {  // window ledger: the buffer holds every env's window at head 0 now
-    std::lock_guard<std::mutex> lock(g_flag_mu);
+  if (fresh_run) {  // the buffer holds every env's window at head 0 now
     E->p.obs_head = 0;
-    E->slide_valid = true;
+    ledger().establish(E, WINDOW, {obs_span(E)}, false);
   }
   TRY(append_log(E, p, p.mask));
   if (L.affinity_period > 0) TRY(resort(E));  // new start rows: re-sort the processing order
@@ -976,7 +872,7 @@ struct StepTargets {
   float *obs, *reward;
   double* reward64;
   uint8_t *terminated, *truncated;
-  bool own_obs;  // obs is the env's own buffer (its layout and the window ledger apply), not a rollout's row
+  bool own_obs;  // obs is the env's own buffer (its layout and its window claim apply), not a rollout's row
 };
 
 static StepTargets own_targets(const gte_env* E, const int32_t* actions) {
@@ -1004,15 +900,15 @@ static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool captur
   if (terminal_rec) p.final_rec = terminal_rec;
   p.actions = t.actions; p.obs = t.obs; p.reward = t.reward; p.reward64 = t.reward64;
   p.terminated = t.terminated; p.truncated = t.truncated;
+  const bool slides_own = t.own_obs && E->sliding;
+  gte_ledger::Span obs = obs_span(E);
   if (!t.own_obs) {  // a rollout's per-step row: a classic [N, W, F_obs] block
     p.obs_rows = p.W; p.obs_head = 0;
-    obs_written(E, t.obs, sizeof(float) * (size_t)p.N * p.W * p.Fobs);
+    obs = {t.obs, sizeof(float) * (size_t)p.N * p.W * p.Fobs};
   } else if (E->sliding) {
-    // window ledger: slide while the buffer provably holds this env's windows at a head below M;
+    // slide while the buffer provably holds this env's windows (its window claim) at a head below M;
     // otherwise (and at head M: the wrap) every window in full at head 0, which makes it so again
-    obs_written(E, t.obs, own_obs_bytes(E));
-    std::lock_guard<std::mutex> lock(g_flag_mu);
-    if (!capturing && E->slide_valid && E->p.obs_head < L.slide_rows) {
+    if (!capturing && ledger().holds(E, WINDOW, {obs}) && E->p.obs_head < L.slide_rows) {
       E->p.obs_head += 1;
       // JOB_SLIDES shares bit 1 of the job record with dyn_persist's "zero the store" (gte_device.h):
       // plan_launches never grants slide_rows with dyn_persist, and only this launch ever sets p.slide
@@ -1021,20 +917,20 @@ static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool captur
       p.slide = L.full_windows ? 0 : 1;
     } else {
       E->p.obs_head = 0;
-      E->slide_valid = !capturing;
     }
     p.obs_head = E->p.obs_head;
-  } else {
-    obs_written(E, t.obs, own_obs_bytes(E));
   }
   advance_term_slot(E, p);
   if (L.fused_log) {
     p.log = E->log;
     p.log_cursor = E->log_cursor + (E->term_slot ^ 1);
   }
-  // terminated / truncated: only the changed ones, where the flag ledger proves the buffers hold the
+  // terminated / truncated: only the changed ones, where the env's flag claim proves the buffers hold the
   // previous step's flags (dense inside a capture: a replay cannot rely on what ran before it)
-  p.flags_sparse = flags_may_skip(E, p, capturing) ? 1 : 0;
+  const gte_ledger::Span term = flag_span(E, p.terminated), trunc = flag_span(E, p.truncated);
+  p.flags_sparse = !capturing && !L.always_dense && ledger().holds(E, FLAGS, {term, trunc}) ? 1 : 0;
+  // what this launch writes; its own claims hold again once it has gone out
+  ledger().wrote(E, {obs, term, trunc}, capturing, FLAGS | WINDOW);
   // (hot_tu_covers: the isolated instantiations have no terminal records and no trajectory row)
   const bool hot = L.hot_tu && gte::hot_tu_covers(p);
   if (hot && store == 2)
@@ -1043,7 +939,8 @@ static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool captur
     HIPCHK(gte::launch_step_hot_nt(p, L.blocks, L.threads, gte::lds_bytes(p, L.stage), E->stream));
   else
     HIPCHK(gte::launch_step(p, L.vec, store, L.coop, L.stage, L.blocks, L.threads, E->stream));
-  flags_stepped(E, p, capturing);
+  ledger().establish(E, FLAGS, {term, trunc}, capturing);
+  if (slides_own) ledger().establish(E, WINDOW, {obs}, capturing);
   if (L.fused_log) E->log_rows += 1;
   else TRY(append_log(E, p));
   return GTE_OK;
@@ -1081,8 +978,8 @@ int gte_set_schedule(gte_env* E, const gte_schedule* s) {
   E->log_rows = s->log_rows;
   E->term_slot = s->term_slot;
   E->steps_since_rebuild = s->steps_since_rebuild;
-  flags_unsure(E, {});  // the flag ledger may have recorded captured steps as run: the next step is dense
-  slide_invalidate(E);  // ... and the window ledger: the next step writes full windows at head 0
+  // captured steps may have been recorded as run: the next step stores densely, full windows at head 0
+  ledger().withdraw(E, FLAGS | WINDOW);
   return GTE_OK;
 }
 
@@ -1173,9 +1070,13 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
   // (non-temporal stores where the caller left the policy automatic)
   const int nt = (b->obs && E->cfg.nontemporal_obs == 3) ? 1 : L.store;
   const bool capturing = stream_capturing(E);
-  // the fused steps advance the envs without writing the env's own observation buffer (window ledger)
-  slide_invalidate(E);
-  if (b->obs) obs_written(E, b->obs, sizeof(float) * (size_t)n_steps * N * V);
+  // The fused kernels write the per-step rows and advance the envs without writing the env's own observation
+  // buffer: the window claim goes (a step that goes out as an ordinary launch into the own buffer below
+  // establishes it again).  They store the env's own flags densely, flags_out with them, so the flag claim
+  // stands for the ordinary step launches below; gte_rollout withdraws it after the copies that follow them.
+  const size_t rows = (size_t)n_steps * N;
+  ledger().wrote(E, {{b->obs, sizeof(float) * rows * V}, {b->terminated, rows}, {b->truncated, rows},
+                     flag_span(E, E->p.terminated), flag_span(E, E->p.truncated)}, capturing, WINDOW);
   // one step as its own launch, writing row k of every per-step buffer (what the unfused path
   // does for every step, and the backtest path for its last one)
   auto step_row = [&](int32_t k) -> int {
@@ -1265,9 +1166,7 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
   if (b->obs && ((uintptr_t)b->obs & 15)) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
   HIPCHK(hipSetDevice(E->cfg.device));
   const int rc = rollout(E, actions, n_steps, b);
-  // the fused kernels write flags into the env's buffers or the per-step rows (flag ledger)
-  const size_t N = (size_t)E->p.N, rows = (size_t)n_steps * N;
-  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}, {b->terminated, rows}, {b->truncated, rows}});
+  ledger().withdraw(E, FLAGS);  // (the copies into the env's own flags follow the last step's launch)
   return rc;
 }
 
@@ -1279,7 +1178,10 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   const size_t N = (size_t)E->p.N;
   const LaunchPlan& L = E->plan;
   const bool signals = actions == nullptr;
-  slide_invalidate(E);  // (window ledger: the summary kernels advance the envs without writing observations)
+  // the summary kernels advance the envs without writing observations: the window claim goes (the ordinary
+  // step launches below establish it again).  They store the env's own flags densely, so the flag claim
+  // stands for those launches; backtest_entry withdraws it afterwards
+  ledger().wrote(E, {flag_span(E, E->p.terminated), flag_span(E, E->p.truncated)}, false, WINDOW);
   if (signals && !E->d_sig_actions) TRY(dev_alloc_late(E, &E->d_sig_actions, N));
   if (!E->bt_stats) {
     if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->bt_final_rec, N));
@@ -1332,9 +1234,7 @@ static int backtest_entry(gte_env* E, const char* who, const int32_t* actions, c
     return fail(GTE_ERR_STATE, "%s inside a stream capture: a backtest is one launch already, run it eagerly", who);
   HIPCHK(hipSetDevice(E->cfg.device));
   const int rc = backtest(E, actions, strategy, n_steps, clear);
-  // the fused kernel writes flags into the env's buffers (flag ledger)
-  const size_t N = (size_t)E->p.N;
-  flags_unsure(E, {{E->p.terminated, N}, {E->p.truncated, N}});
+  ledger().withdraw(E, FLAGS);  // (as after a rollout: the next step stores densely)
   if (stats_device) *stats_device = E->bt_stats;
   return rc;
 }
@@ -1645,16 +1545,10 @@ int gte_bind_outputs(gte_env* E, const gte_outputs* b) {
   HIPCHK(hipStreamSynchronize(E->stream));
   Params& p = E->p;
   if (b->obs && ((uintptr_t)b->obs & 15)) return fail(GTE_ERR_INVALID, "obs must be 16-byte aligned");
-  flags_unsure(E, {});
-  {  // back to the classic layout, whatever was bound
-    std::lock_guard<std::mutex> lock(g_flag_mu);
-    slide_forget_locked(E);
-    E->sliding = false;
-    E->slide_valid = false;
-  }
+  E->sliding = false;  // back to the classic layout, whatever was bound
   p.obs_rows = p.W; p.obs_head = 0;
   p.obs = b->obs;  // NULL: back to the library's own buffers (allocated on first need)
-  if (b->obs) obs_written(E, b->obs, own_obs_bytes(E));
+  ledger().wrote(E, {obs_span(E)}, false, FLAGS | WINDOW);  // (other envs that slide in that buffer stop)
   if (E->cfg.final_obs) p.final_obs = b->final_obs;
   if (E->was_reset) TRY(ensure_owned_obs(E));
   p.reward = b->reward ? b->reward : E->owned.reward;
@@ -1694,14 +1588,9 @@ int gte_bind_sliding_obs(gte_env* E, float* base, int32_t rows_per_env) {
   p.obs = base;
   p.obs_rows = rows_per_env;
   p.obs_head = 0;
-  {
-    std::lock_guard<std::mutex> lock(g_flag_mu);
-    slide_forget_locked(E);
-    E->sliding = true;
-    E->slide_valid = false;  // the next step writes every window in full at head 0
-    g_slide_bufs.push_back({E, (uintptr_t)base, (uintptr_t)base + own_obs_bytes(E)});
-  }
-  obs_written(E, base, own_obs_bytes(E));
+  E->sliding = true;
+  // the next step writes every window in full at head 0 (and other envs that slide in that buffer stop)
+  ledger().wrote(E, {obs_span(E)}, false, WINDOW);
   return GTE_OK;
 }
 
@@ -1762,7 +1651,7 @@ int gte_bind_returns(gte_env* E, float* reward, uint8_t* terminated, uint8_t* tr
   if (!E || !reward || !terminated || !truncated) return fail(GTE_ERR_INVALID, "NULL argument");
   // Params travel by value with every launch: later launches see the new pointers,
   // launches already enqueued keep the old ones.
-  flags_unsure(E, {});  // (rotated buffers hold an older step's flags: the next step stores densely)
+  ledger().withdraw(E, FLAGS);  // (rotated buffers hold an older step's flags: the next step stores densely)
   E->p.reward = reward;
   E->p.terminated = terminated;
   E->p.truncated = truncated;
@@ -2036,11 +1925,7 @@ void gte_destroy(gte_env* E) {
   if (E->ev0) (void)hipEventDestroy(E->ev0);
   if (E->ev1) (void)hipEventDestroy(E->ev1);
   if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
-  {
-    std::lock_guard<std::mutex> lock(g_flag_mu);
-    flags_forget_locked(E);
-    slide_forget_locked(E);
-  }
+  ledger().forget(E);
   delete E;
 }
 

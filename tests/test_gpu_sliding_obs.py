@@ -337,6 +337,40 @@ def test_backtests_off_head_0_leave_the_current_observation():
     twin.close()
 
 
+@pytest.mark.parametrize("call", ["set_schedule", "reset"])
+def test_calls_that_withdraw_the_window_claim_off_head_0(call):
+    """gte_set_schedule outside a capture, and an unmasked reset in the middle of a run of slides (the table
+    in gte_ledger.h): the next observation is a full one at head 0, and the heads count up from there.  128
+    envs of the smallest shape that slides, beside a classic twin, past two wraps of the head."""
+    env = _env(8, 32, num_envs=128)
+    twin = _env(8, 32, num_envs=128, obs_slack_rows=-1)
+    assert env.sliding_obs and not twin.sliding_obs
+    acts = _actions(12, seed=9)[:, :128].contiguous()
+    env.reset(); twin.reset()
+    for i in range(2):
+        env.step(acts[i]); twin.step(acts[i])
+    assert int(env._obs_view.head) == 2
+    if call == "set_schedule":  # (what StepGraph does around a capture, with nothing captured)
+        for e in (env, twin):
+            s = _abi.GteSchedule()
+            _abi.check(e._lib, e._lib.gte_get_schedule(e._h, C.byref(s)))
+            _abi.check(e._lib, e._lib.gte_set_schedule(e._h, C.byref(s)))
+        expect = [0, 1, 2, 3, 0, 1, 2, 3, 0, 1]  # the first step after it writes every window
+    else:
+        env.reset(); twin.reset()
+        assert int(env._obs_view.head) == 0
+        _same(env, twin, "reset off head 0")
+        expect = [1, 2, 3, 0, 1, 2, 3, 0, 1, 2]  # the reset wrote every window
+    heads = []
+    for i in range(2, 12):
+        env.step(acts[i]); twin.step(acts[i])
+        heads.append(int(env._obs_view.head))
+        _same(env, twin, f"{call}, step {i}")
+    assert heads == expect, heads
+    env.close()
+    twin.close()
+
+
 def test_full_window_switch_keeps_the_layout_and_the_values(monkeypatch):
     """GTE_SLIDE_FULL_WINDOWS (gte.h): the moving head, full windows every step — the A/B twin."""
     import torch

@@ -1,4 +1,4 @@
-"""Sparse terminated / truncated stores (gte_phase_a.h store_flags, gte_api.hip "Flag ledger"): a
+"""Sparse terminated / truncated stores (gte_phase_a.h store_flags, the FLAGS claim of gte_ledger.h): a
 step stores only the flags that change when the host has proved that the buffers hold what the env's
 previous step stored there.  Every case below runs an env next to an untouched twin that always
 stores densely (kernel_variant KV_DENSE_FLAGS) and compares all four return arrays and the terminal list
@@ -168,6 +168,54 @@ def test_rollout_after_step_and_step_after_rollout():
         k += K
         ended += _steps(env, twin, 5, acts[k:])
         k += 5
+    assert ended > 0
+    env.close()
+    twin.close()
+
+
+@pytest.mark.parametrize("call", ["backtest", "backtest_signals", "reset", "masked_reset"])
+def test_step_after_a_call_that_writes_the_flags(call):
+    """The entry points that withdraw the flag claim without rebinding anything (the table in
+    gte_ledger.h): a backtest of either kind and a reset, masked or not, in the middle of a run of sparse
+    steps.  128 envs of the smallest shape that slides (windows 8 x 32 columns, 3 slack rows) beside a twin
+    that stores every flag and writes every window (KV_DENSE_FLAGS, obs_slack_rows=-1), compared after
+    every call, observations included, until the head has wrapped twice."""
+    from gym_trading_env_amd.batched import BatchedTradingEnv
+    N = 128
+    args = dict(num_envs=N, positions=[-1, 0, 1], windows=8, trading_fees=1e-3, borrow_interest_rate=1e-4,
+                max_episode_duration=9, seed=11, output="torch", verbose=0, envs_per_wave=16)
+    env = BatchedTradingEnv(_data(), obs_slack_rows=3, **args)
+    twin = BatchedTradingEnv(_data(), obs_slack_rows=-1, kernel_variant=DENSE, **args)
+    assert env.sliding_obs and not twin.sliding_obs
+
+    def same(what):
+        _same(env, twin, what)
+        assert env._torch.equal(env._t["obs"].view(env._torch.int32), twin._t["obs"].view(env._torch.int32)), what
+
+    def steps(acts, what):
+        ended = 0
+        for i in range(len(acts)):
+            env.step(acts[i])
+            twin.step(acts[i])
+            same(f"{what}, step {i}")
+            ended += len(twin.terminal_ids())
+        return ended
+
+    acts = _actions(env, 24)
+    table = np.random.default_rng(5).integers(-1, 3, (2, 900)).astype(np.int8)
+    for e in (env, twin):
+        e.reset()
+        e.bind_signals(table)
+    ended = steps(acts[:6], "before")  # (flags sparse from the second step on, one wrap of the head)
+    for e in (env, twin):
+        if call == "backtest":
+            e.backtest(acts[6:10])
+        elif call == "backtest_signals":
+            e.backtest_signals(4)
+        else:
+            e.reset(mask=(np.arange(N) % 3 == 0).astype(np.uint8) if call == "masked_reset" else None)
+    same(call)
+    ended += steps(acts[10:20], f"after {call}")
     assert ended > 0
     env.close()
     twin.close()

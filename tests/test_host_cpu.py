@@ -325,6 +325,15 @@ def test_gte_api_declares_no_gte_function_itself():
     assert _signatures(api) == {}
 
 
+def test_gte_api_keeps_no_ledger_of_its_own():
+    """What a sparse flag store and a slide step rely on is proved in gte_ledger.h, behind its mutex: the
+    host file keeps no lock and no validity bit of its own."""
+    api = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "gte_api.hip")).read()
+    assert '#include "gte_ledger.h"' in api
+    for gone in ("std::mutex", "lock_guard", "flags_sparse_ok", "slide_valid"):
+        assert gone not in api, gone
+
+
 def _makefile_srcs():
     makefile = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
     return re.search(r"^SRCS = (.*)$", makefile, re.M).group(1).split()
@@ -371,7 +380,8 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
     defined = {}
     for name in units + sorted(h for h in src if h.endswith(".h") and h != "gte_launch.h"):
         text = src[name]
-        assert name == "gte_device.h" or "gte_launch.h" in _included(src, name), name
+        # (gte_ledger.h: host bookkeeping only, no device code and no cross-file gte:: function)
+        assert name in ("gte_device.h", "gte_ledger.h") or "gte_launch.h" in _included(src, name), name
         for fn, (sig, is_def) in _signatures(text).items():
             assert is_def, f"{name} declares {fn} itself"
             assert fn not in defined, f"{fn} is defined in {name} and in {defined[fn]}"
@@ -390,6 +400,10 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
     makefile = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
     hdrs = re.search(r"^HDRS = (.*)$", makefile, re.M).group(1).split()
     assert sorted(h for h in src if h.endswith(".h")) == sorted(h for h in hdrs if "/" not in h)
+    # the ledger stands alone (tests/ledger_check.cpp compiles it with g++): nothing of csrc/, nothing of HIP
+    includes = re.findall(r'#\s*include\s*([<"][^>"]+[>"])', src["gte_ledger.h"])
+    assert includes and not any(i.startswith('"') or "hip" in i.lower() for i in includes), includes
+    assert "__global__" not in src["gte_ledger.h"] and "__device__" not in src["gte_ledger.h"]
 
 
 _HOLDS_VARIANT = re.compile(r"(?i:variant)|^kv$|^DENSE$|^ROLLOUT")  # names of things that hold kernel_variant bits
