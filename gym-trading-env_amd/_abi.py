@@ -134,6 +134,17 @@ class GteBacktestStats(C.Structure):
                [("reserved", C.c_int32 * 6)]
 
 
+#: struct gte_indicator_spec (include/gte.h), in declaration order: 16 bytes per bank row
+INDICATOR_FIELDS = [(n, "<i4") for n in ("kind", "source", "column", "n")]
+#: numpy view of an array of gte_indicator_spec (gte_build_indicators)
+INDICATOR_DTYPE = INDICATOR_FIELDS
+
+#: enum gte_indicator_kind / gte_indicator_source and GTE_IND_MAX_WINDOW (include/gte.h)
+IND_KINDS = ("value", "sma", "std", "zscore", "max", "min", "diff", "roc", "ema", "rsi")
+IND_SOURCES = ("close", "high", "low", "feature", "input")
+IND_MAX_WINDOW = 4096
+
+
 class GteOutputs(C.Structure):
     """struct gte_outputs: device pointers, kept as integers."""
 
@@ -266,6 +277,8 @@ SYMBOLS = {
     "gte_backtest_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
+    "gte_build_indicators": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
+                                       C.c_void_p, C.c_int64]),
     "gte_bind_returns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_comm_unique_id": (C.c_int, [C.c_void_p]),
     "gte_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),

@@ -1364,6 +1364,111 @@ class BatchedTradingEnv(_VectorEnvBase):
         return out[next(iter(out))] if (dataset is not None or not isinstance(indicators, (list, tuple))) \
             else [out[d] for d in range(D)]
 
+    def build_indicators(self, specs, dataset=None, inputs=None):
+        """Build indicator banks ON THE DEVICE from the resident market data (`gte_build_indicators`):
+        one row per spec (`signals.indicators`, `signals.INDICATOR_DTYPE`; what each kind computes is
+        stated in include/gte.h) over the dataset's close / high / low, a static feature column, or
+        a row of `inputs`.  Returns a torch f32 [C, T] view of a device tensor whose rows are padded to
+        `signals.bank_stride(T)` floats — complete for torch to read when the call returns, and exactly
+        the form `build_signals` reads in place: ``env.build_signals(env.build_indicators(specs),
+        rules)`` copies nothing.
+
+        specs: an `INDICATOR_DTYPE` array [C], checked here against the env (feature columns, input
+        rows, whether the dataset has high / low), or a CUDA tensor uint8 [C, 16] / int32 [C, 4] of
+        the same bytes, which is the caller's contract: the kernel gives a spec it cannot serve a row
+        of NaN.  With ``dataset=None`` and D > 1 one spec array serves every dataset and a list of D
+        banks comes back.  inputs: a NumPy array or a CUDA f32 tensor [C_in, T] (volume, or a bank an
+        earlier call returned: the signal line of a MACD is an EMA of such a row), or a list of D of
+        them; padded like a bank of `build_signals`, or read in place when it has that layout."""
+        torch = self._torch
+        if torch is None:
+            raise ValueError("build_indicators needs output='torch'")
+        from . import signals as sig
+        D = len(self.datasets)
+        if dataset is None:
+            which = list(range(D))
+        else:
+            if not 0 <= int(dataset) < D:
+                raise IndexError(f"dataset {dataset} out of range")
+            which = [int(dataset)]
+        if inputs is None:
+            banks = {d: None for d in which}
+        elif isinstance(inputs, (list, tuple)) and dataset is None and D > 1:
+            if len(inputs) != D:
+                raise ValueError(f"expected a list of {D} input banks, one per dataset (or dataset=d)")
+            banks = dict(enumerate(inputs))
+        elif len(which) == 1:
+            banks = {which[0]: inputs}
+        else:
+            raise ValueError(f"expected a list of {D} input banks, one per dataset (or dataset=d)")
+        dev = self._t["obs"].device
+        if isinstance(specs, torch.Tensor):
+            if not (specs.is_cuda and specs.dim() == 2 and specs.is_contiguous() and
+                    (specs.dtype, int(specs.shape[1])) in ((torch.uint8, 16), (torch.int32, 4))):
+                raise TypeError("specs: an INDICATOR_DTYPE array, or a contiguous CUDA tensor uint8 [C, 16] / "
+                                "int32 [C, 4]")
+            d_specs, host = specs.to(dev), None
+        else:
+            host = np.ascontiguousarray(specs)
+            if host.dtype != sig.INDICATOR_DTYPE or host.ndim != 1:
+                raise TypeError("specs: a one-dimensional array of signals.INDICATOR_DTYPE (signals.indicators)")
+            d_specs = torch.from_numpy(host.view(np.uint8).reshape(-1, sig.INDICATOR_DTYPE.itemsize).copy()).to(dev)
+        n_specs = int(d_specs.shape[0])
+        if n_specs < 1:
+            raise ValueError("build_indicators needs at least one spec")
+        d_in = {}
+        for d, x in banks.items():
+            T = self.datasets[d].T
+            if x is None:
+                d_in[d] = None
+            elif isinstance(x, torch.Tensor) and x.is_cuda:
+                if x.dim() != 2 or x.dtype != torch.float32:
+                    raise TypeError("an input bank is a two-dimensional float32 tensor")
+                x = x.to(dev)
+                if not (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= sig.bank_stride(T)
+                        and x.data_ptr() % 16 == 0):
+                    with torch.cuda.device(dev):
+                        buf = torch.zeros((int(x.shape[0]), sig.bank_stride(int(x.shape[1]))), dtype=torch.float32,
+                                          device=dev)
+                    buf[:, :x.shape[1]] = x
+                    x = buf[:, :x.shape[1]]
+                d_in[d] = x
+            else:
+                a = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x)
+                d_in[d] = torch.from_numpy(sig.pad_bank(a)).to(dev)[:, :a.shape[-1]]
+            x = d_in[d]
+            if x is not None and (int(x.shape[1]) != T or int(x.shape[0]) < 1):
+                raise ValueError(f"input bank of dataset {d} has {int(x.shape[1])} columns, the dataset {T} rows")
+            if host is not None:
+                n_in = 0 if x is None else int(x.shape[0])
+                kind, src, col, n = host["kind"], host["source"], host["column"], host["n"]
+                if ((kind < 0) | (kind >= len(sig.IND_KINDS)) | (src < 0) | (src >= len(sig.IND_SOURCES))).any():
+                    raise ValueError("specs hold an unknown kind or source")
+                if ((kind != sig.IND_VALUE) & ((n < 1) | (n > sig.IND_MAX_WINDOW))).any():
+                    raise ValueError(f"specs hold a window outside [1, {sig.IND_MAX_WINDOW}]")
+                n_static = self.datasets[d].n_static
+                if ((src == sig.SRC_FEATURE) & ((col < 0) | (col >= n_static))).any():
+                    raise ValueError(f"specs name feature columns outside the {n_static} static ones")
+                if ((src == sig.SRC_INPUT) & ((col < 0) | (col >= n_in))).any():
+                    raise ValueError(f"specs name input rows outside the {n_in} rows of dataset {d}'s input bank")
+                ds = self.datasets[d]
+                for name, code in (("high", sig.SRC_HIGH), ("low", sig.SRC_LOW)):
+                    if (src == code).any() and getattr(ds, name, None) is None:
+                        raise ValueError(f"specs read {name}, which dataset {d} does not have")
+        with torch.cuda.device(dev):
+            out = {d: torch.empty((n_specs, sig.bank_stride(self.datasets[d].T)), dtype=torch.float32, device=dev)
+                   for d in which}
+        torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
+        for d in which:
+            x, buf = d_in[d], out[d]
+            _abi.check(self._lib, self._lib.gte_build_indicators(
+                self._h, d, C.c_void_p(d_specs.data_ptr()), n_specs,
+                C.c_void_p(x.data_ptr()) if x is not None else None, int(x.shape[0]) if x is not None else 0,
+                int(x.stride(0)) if x is not None else 0, C.c_void_p(buf.data_ptr()), int(buf.shape[1])))
+        self.synchronize()  # the banks are complete: for torch on any stream, and before the inputs go
+        views = [out[d][:, :self.datasets[d].T] for d in which]
+        return views[0] if (dataset is not None or D == 1) else views
+
     @property
     def num_strategies(self) -> int:
         """S of the bound signal tables (0: none bound)."""

@@ -1335,6 +1335,45 @@ int gte_build_signals(gte_env* E, int32_t d, const float* indicators_device, int
   return GTE_OK;
 }
 
+int gte_build_indicators(gte_env* E, int32_t d, const gte_indicator_spec* specs_device, int32_t n_specs,
+                         const float* input_device, int32_t n_inputs, int64_t input_stride, float* bank_device,
+                         int64_t ind_stride) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_build_indicators inside a stream capture");
+  const int64_t T = E->h_ds[d].T;
+  if (T <= 0) return fail(GTE_ERR_STATE, "gte_build_indicators: dataset %d was never uploaded", d);
+  if (T > INT32_MAX - 2 * GTE_IND_MAX_WINDOW)  // (the kernel indexes rows with 32 bits, like EnvRec.idx)
+    return fail(GTE_ERR_INVALID, "gte_build_indicators: dataset %d has too many rows", d);
+  const int64_t T16 = (T + 15) / 16 * 16;
+  if (!specs_device || !bank_device) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (n_inputs < 0) return fail(GTE_ERR_INVALID, "n_inputs must be >= 0");
+  if ((input_device != nullptr) != (n_inputs > 0))
+    return fail(GTE_ERR_INVALID, "input_device must be non-NULL exactly when n_inputs > 0");
+  if (((uintptr_t)bank_device & 15) || ((uintptr_t)input_device & 15))
+    return fail(GTE_ERR_INVALID, "the indicator bank and the input bank must be 16-byte aligned");
+  if ((uintptr_t)specs_device & 3) return fail(GTE_ERR_INVALID, "specs must be 4-byte aligned");
+  if (ind_stride % 4 != 0 || ind_stride < T16)
+    return fail(GTE_ERR_INVALID, "ind_stride %lld floats: a multiple of 4 and >= %lld (the %lld rows of dataset %d "
+                "rounded up to 16) required", (long long)ind_stride, (long long)T16, (long long)T, d);
+  if (n_inputs > 0 && (input_stride % 4 != 0 || input_stride < T16))
+    return fail(GTE_ERR_INVALID, "input_stride %lld floats: a multiple of 4 and >= %lld required",
+                (long long)input_stride, (long long)T16);
+  if (n_specs < 1) return fail(GTE_ERR_INVALID, "n_specs must be >= 1");
+  if (n_inputs > 0) {  // what the kernel reads of the input and what it writes of the bank: disjoint
+    const uintptr_t in0 = (uintptr_t)input_device, out0 = (uintptr_t)bank_device;
+    const uintptr_t in1 = in0 + sizeof(float) * (size_t)((int64_t)(n_inputs - 1) * input_stride + T16);
+    const uintptr_t out1 = out0 + sizeof(float) * (size_t)((int64_t)(n_specs - 1) * ind_stride + T16);
+    if (in0 < out1 && out0 < in1) return fail(GTE_ERR_INVALID, "the input bank and the indicator bank overlap");
+  }
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const hipError_t e = gte::launch_build_indicators(E->h_ds[d], E->p.Fobs, E->p.Fobs - E->p.nd, specs_device, n_specs,
+                                                    input_device, n_inputs, input_stride, bank_device, ind_stride,
+                                                    E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "indicator build launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
 int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backtest_stats* out) {
   if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
   if (!E->bt_stats) return fail(GTE_ERR_STATE, "gte_read_backtest_stats before gte_backtest");

@@ -105,6 +105,13 @@ hipError_t launch_build_signals(const float* indicators, int n_indicators, int64
                                 const gte_signal_rule* rules, int n_rules, int64_t T, int8_t* table,
                                 int64_t row_stride, hipStream_t stream);
 
+// --- gte_indicators.hip: indicator banks written on the device from resident market data
+// (gte_build_indicators, include/gte.h): bank rows 0 .. n_specs-1, floats 0 .. round_up(T, 16)-1 of each;
+// the caller has checked alignments, strides and that input and bank are disjoint
+hipError_t launch_build_indicators(const DatasetDesc& ds, int Fobs, int n_static, const gte_indicator_spec* specs,
+                                   int n_specs, const float* input, int n_inputs, int64_t input_stride, float* bank,
+                                   int64_t ind_stride, hipStream_t stream);
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

@@ -110,3 +110,61 @@ def sma_bank(close, windows) -> np.ndarray:
         if n <= T:
             out[i, n - 1:] = ((csum[n:] - csum[:-n]) / n).astype(np.float32)
     return out
+
+
+# ---- indicator banks built on the device from the resident market data (gte_build_indicators) ----
+
+from ._abi import IND_KINDS, IND_MAX_WINDOW, IND_SOURCES  # noqa: E402
+from ._abi import INDICATOR_DTYPE as _INDICATOR_FIELDS  # noqa: E402
+
+#: `gte_indicator_spec` of include/gte.h, 16 bytes
+INDICATOR_DTYPE = np.dtype(_INDICATOR_FIELDS)
+
+#: enum gte_indicator_kind
+IND_VALUE, IND_SMA, IND_STD, IND_ZSCORE, IND_MAX, IND_MIN, IND_DIFF, IND_ROC, IND_EMA, IND_RSI = range(10)
+#: enum gte_indicator_source
+SRC_CLOSE, SRC_HIGH, SRC_LOW, SRC_FEATURE, SRC_INPUT = range(5)
+
+
+def _codes(values, names, what):
+    """names or constants of an enumeration -> an int array of the same shape"""
+    a = np.asarray(values)
+    if a.dtype.kind in "US":
+        flat = [str(v).lower() for v in a.reshape(-1)]
+        bad = sorted({v for v in flat if v not in names})
+        if bad:
+            raise ValueError(f"unknown {what} {bad[0]!r}: one of {', '.join(names)}")
+        return np.array([names.index(v) for v in flat], dtype=np.int64).reshape(a.shape)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{what} must be names or integers, not {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= len(names)):
+        raise ValueError(f"unknown {what}: expected 0 .. {len(names) - 1} ({', '.join(names)})")
+    return a.astype(np.int64)
+
+
+def indicators(kind, n=1, source="close", column=0) -> np.ndarray:
+    """One `INDICATOR_DTYPE` record per bank row, the arguments broadcast against each other (the
+    result is one-dimensional): `kind` over `n` rows of `source` — names (``"sma"``, ``"rsi"``, ...;
+    ``"close"``, ``"high"``, ``"low"``, ``"feature"``, ``"input"``) or the `IND_*` / `SRC_*`
+    constants; `column` is the static feature column of ``"feature"`` or the row of the input bank of
+    ``"input"``.  What each kind computes, to the rounding, is stated in include/gte.h.  `n` must lie
+    in ``[1, 4096]`` (``"value"`` ignores it)."""
+    k, s = _codes(kind, IND_KINDS, "indicator kind"), _codes(source, IND_SOURCES, "source")
+    arrays = {"kind": k, "source": s, "column": np.asarray(column), "n": np.asarray(n)}
+    for name in ("column", "n"):
+        v = arrays[name]
+        if v.dtype.kind not in "iub":
+            raise TypeError(f"{name} must be integers, not {v.dtype}")
+        if v.size and (v.min() < -2 ** 31 or v.max() > 2 ** 31 - 1):
+            raise ValueError(f"{name} does not fit its field")
+    shape = np.broadcast_shapes(*(v.shape for v in arrays.values()))
+    full = {name: np.broadcast_to(v, shape).reshape(-1) for name, v in arrays.items()}
+    windowed = full["kind"] != IND_VALUE
+    if ((full["n"][windowed] < 1) | (full["n"][windowed] > IND_MAX_WINDOW)).any():
+        raise ValueError(f"n must lie in [1, {IND_MAX_WINDOW}]")
+    if (full["column"] < 0).any():
+        raise ValueError("column must not be negative")
+    out = np.zeros(int(np.prod(shape, dtype=np.int64)) if shape else 1, dtype=INDICATOR_DTYPE)
+    for name, v in full.items():
+        out[name] = v
+    return out

@@ -554,6 +554,73 @@ int gte_build_signals(gte_env* env, int32_t ds,
                       const gte_signal_rule* rules_device, int32_t n_rules,
                       int8_t* table_device, int64_t row_stride);
 
+/* ---- INDICATOR BANKS BUILT ON THE DEVICE from the resident market data: the bank gte_build_signals
+ * reads is itself written by the device, one row per 16-byte spec, in the layout gte_build_signals
+ * reads in place — a sweep is specs, then rules, then table, then statistics, with no host array
+ * larger than the specs and the rules.  This text is the specification; the reference has no
+ * counterpart. */
+enum gte_indicator_kind {
+  GTE_IND_VALUE = 0, GTE_IND_SMA = 1, GTE_IND_STD = 2, GTE_IND_ZSCORE = 3, GTE_IND_MAX = 4,
+  GTE_IND_MIN = 5, GTE_IND_DIFF = 6, GTE_IND_ROC = 7, GTE_IND_EMA = 8, GTE_IND_RSI = 9
+};
+enum gte_indicator_source {
+  GTE_SRC_CLOSE = 0, GTE_SRC_HIGH = 1, GTE_SRC_LOW = 2, GTE_SRC_FEATURE = 3, GTE_SRC_INPUT = 4
+};
+#define GTE_IND_MAX_WINDOW 4096
+typedef struct gte_indicator_spec {   /* 16 bytes */
+  int32_t kind;     /* GTE_IND_* above                                              */
+  int32_t source;   /* GTE_SRC_CLOSE 0, _HIGH 1, _LOW 2, _FEATURE 3, _INPUT 4       */
+  int32_t column;   /* _FEATURE: static feature column; _INPUT: row of the input bank; else ignored */
+  int32_t n;        /* window / span, 1 .. GTE_IND_MAX_WINDOW (4096); ignored by VALUE */
+} gte_indicator_spec;
+/* SOURCE SERIES.  x[t], t = 0 .. T-1, is the source converted to f64 (exact): the dataset's close /
+ * high / low (f64); column `column` of its feature table (f32, stride F_obs, static columns
+ * [0, F_obs - n_dyn) only); or row `column` of a caller-owned f32 input bank
+ * float [n_inputs][input_stride] with the alignment and stride rules of the output, which must not
+ * overlap the output — volume or any series the env does not hold, and chaining: the signal line of a
+ * MACD is an EMA over a bank that an earlier call wrote.
+ *
+ * ARITHMETIC.  All of it is f64, each operation below rounded once, in the written order, with no
+ * contraction; the result is rounded once to f32 at the store.  "NaN" is a quiet NaN of unspecified
+ * payload.  Subnormals are kept.  Row s of the bank is y[t] of spec s:
+ *
+ *   kind      NaN for     y[t] otherwise
+ *   VALUE     -           x[t]
+ *   SMA       t < n-1     s = 0; for k = 0..n-1: s += x[t-n+1+k]; y = s / n               (oldest first)
+ *   STD       t < n-1     m = the SMA above; q = 0; for k: d = x[t-n+1+k] - m; q += d*d; y = sqrt(q / n)
+ *   ZSCORE    t < n-1     (x[t] - m) / sd, m and sd as above          (IEEE gives NaN for a flat window)
+ *   MAX, MIN  t < n-1     NaN if any window value is NaN; otherwise m = x[t-n+1]; for later k:
+ *                         if (v > m) m = v   (< for MIN).  Of equal values the oldest stays, which fixes
+ *                         the sign of a zero.
+ *   DIFF      t < n       x[t] - x[t-n]
+ *   ROC       t < n       x[t] / x[t-n] - 1
+ *   EMA       -           a = 2.0 / (n + 1.0); y[0] = x[0]; y[t] = y[t-1] + a * (x[t] - y[t-1])
+ *                         (sub, mul, add).  Warm-up is the rule's `warmup`.
+ *   RSI       t < n       (Wilder) change c[j] = x[j] - x[j-1], gain g = c > 0 ? c : 0, loss
+ *                         l = c < 0 ? -c : 0; a NaN change counts as neither.  At t = n:
+ *                         au = (sum of g[j], j = 1..n) / n, ad likewise, sums from 0 in order.  For
+ *                         t > n: au = (au*(n-1) + g[t]) / n, ad likewise.  y = 100 - 100 / (1 + au / ad).
+ *
+ * INVALID SPECS.  A spec whose kind is unknown, whose n is outside [1, 4096] (VALUE excepted), whose
+ * source is unknown, that asks for high / low of a dataset without them, or whose column is out of
+ * range gives a row of NaN and reads nothing: no spec content makes the kernel read outside its
+ * sources.  A window longer than T is legal: every row is NaN.
+ *
+ * PADDING.  Floats T .. round_up(T, 16) - 1 of every row are written 0 (the padding of a host-made
+ * bank); nothing beyond that and nothing outside rows 0 .. n_specs - 1 is touched.
+ *
+ * T is that of resident dataset `ds` (GTE_ERR_STATE if it was never uploaded).  The launch is ordered
+ * on the env's stream; refused inside a stream capture (GTE_ERR_STATE).  GTE_ERR_INVALID, with nothing
+ * launched, unless: bank_device and input_device are 16-byte aligned and specs_device 4-byte aligned;
+ * ind_stride and (with an input) input_stride are multiples of 4 floats and >= round_up(T, 16);
+ * n_specs >= 1; n_inputs >= 0 and input_device non-NULL exactly when n_inputs > 0 (NULL, 0, 0: none);
+ * the input and the output ranges are disjoint.  One wavefront builds one row in pieces of 256 rows
+ * (gte_indicators.hip). */
+int gte_build_indicators(gte_env* env, int32_t ds,
+                         const gte_indicator_spec* specs_device, int32_t n_specs,
+                         const float* input_device, int32_t n_inputs, int64_t input_stride, /* NULL, 0, 0: none */
+                         float* bank_device, int64_t ind_stride);
+
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
 /* Same-step auto-reset with gte_config.final_obs: struct-of-arrays snapshot (device pointers,
