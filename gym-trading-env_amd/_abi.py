@@ -46,6 +46,18 @@ KV_GENERIC_COPY = 4096
 KV_RECORD_DIRECT = 8192
 KV_DENSE_FLAGS = 16384
 
+# enum gte_strategy_metric: the score gte_rank_strategies orders strategies by
+METRIC_MEAN_REWARD = 0
+METRIC_SHARPE = 1
+METRIC_MEAN_EPISODE_RETURN = 2
+METRIC_EPISODE_SHARPE = 3
+METRIC_NEG_MAX_DRAWDOWN = 4
+METRIC_WORST_REWARD_SUM = 5
+#: the same by name, in enum order (StrategyStats.score / .top take either)
+STRATEGY_METRICS = ("mean_reward", "sharpe", "mean_episode_return", "episode_sharpe", "neg_max_drawdown",
+                    "worst_reward_sum")
+GTE_RANK_MAX = 256
+
 
 class GteError(RuntimeError):
     """A libgte call failed (status code + the library's message)."""
@@ -132,6 +144,22 @@ class GteBacktestStats(C.Structure):
     """struct gte_backtest_stats (include/gte.h)."""
     _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in BACKTEST_FIELDS] + \
                [("reserved", C.c_int32 * 6)]
+
+
+#: struct gte_strategy_stats (include/gte.h), in declaration order: one 128-byte record per strategy
+STRATEGY_FIELDS = [("steps", "<i8")] + \
+    [(n, "<f8") for n in ("reward_sum", "reward_sq_sum", "ep_return_sum", "ep_return_sq_sum", "max_drawdown",
+                          "best_reward_sum", "worst_reward_sum")] + \
+    [(n, "<i8") for n in ("trades", "episodes", "terminations")] + \
+    [(n, "<i4") for n in ("envs", "envs_stepped")]
+#: numpy view of an array of gte_strategy_stats (gte_reduce_backtest_stats)
+STRATEGY_DTYPE = STRATEGY_FIELDS + [("reserved", "<i4", (8,))]
+
+
+class GteStrategyStats(C.Structure):
+    """struct gte_strategy_stats (include/gte.h)."""
+    _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in STRATEGY_FIELDS] + \
+               [("reserved", C.c_int32 * 8)]
 
 
 #: struct gte_indicator_spec (include/gte.h), in declaration order: 16 bytes per bank row
@@ -279,6 +307,9 @@ SYMBOLS = {
                                     C.c_void_p, C.c_int64]),
     "gte_build_indicators": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
                                        C.c_void_p, C.c_int64]),
+    "gte_reduce_backtest_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gte_rank_strategies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "gte_bind_returns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_comm_unique_id": (C.c_int, [C.c_void_p]),
     "gte_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),

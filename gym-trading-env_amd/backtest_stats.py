@@ -3,6 +3,8 @@ libgte (struct gte_backtest_stats, include/gte.h) as torch views of device memor
 figures a backtest is read for, derived from them on the device when first asked for."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 from . import _abi
@@ -24,6 +26,7 @@ class BacktestStats:
         from .batched import _device_view
         self._env = env
         self._derived = {}
+        self._map = getattr(env, "_backtest_map", None)  # what the call that made these records ran with
         dev = env._t["obs"].device
         stride = np.dtype(_abi.BACKTEST_DTYPE).itemsize
         offsets = np.dtype(_abi.BACKTEST_DTYPE).fields
@@ -77,3 +80,225 @@ class BacktestStats:
         out = np.empty(e.num_envs, dtype=np.dtype(_abi.BACKTEST_DTYPE))
         _abi.check(e._lib, e._lib.gte_read_backtest_stats(e._h, 0, e.num_envs, out.ctypes.data))
         return out
+
+    def by_strategy(self, strategy=None, n_strategies=None) -> "StrategyStats":
+        """These records folded into one record per strategy, on the device (`gte_reduce_backtest_stats`):
+        a `StrategyStats`.  The defaults are the map and the S of the `backtest_signals()` call that
+        produced this object; for the result of `backtest()` pass `n_strategies` (env e then belongs to
+        strategy ``(env_id_base + e) % S``) or `strategy` (int32 [N], host or CUDA) with `n_strategies`.
+        The sums are taken in the fixed order include/gte.h states: the same records give the same bits.
+
+        This object is a live VIEW of the env's records: what is folded is what they hold when `by_strategy()`
+        runs, so after a later `backtest()` / `backtest_signals()` it folds that call's records — while the
+        default map and S stay those captured when this object was made.  Fold first, or pass the later
+        call's `strategy` / `n_strategies`.  The launch is enqueued on the env's stream (see `StrategyStats`)."""
+        if strategy is None and n_strategies is None:
+            if self._map is None:
+                raise ValueError("by_strategy() of a backtest() result needs n_strategies (and strategy=, unless "
+                                 "env e follows strategy (env_id_base + e) % S)")
+            strategy, n_strategies = self._map
+        elif n_strategies is None:
+            if self._map is None:
+                raise ValueError("by_strategy(strategy=...) needs n_strategies")
+            n_strategies = self._map[1]
+        return StrategyStats._reduce(self._env, None, strategy, n_strategies)
+
+
+def _metric_code(metric) -> int:
+    if isinstance(metric, str):
+        if metric.lower() not in _abi.STRATEGY_METRICS:
+            raise ValueError(f"unknown metric {metric!r}: one of {', '.join(_abi.STRATEGY_METRICS)}")
+        return _abi.STRATEGY_METRICS.index(metric.lower())
+    if isinstance(metric, (bool, float)) or int(metric) != metric:
+        raise TypeError("metric must be a name or a METRIC_* constant")
+    if not 0 <= int(metric) < len(_abi.STRATEGY_METRICS):
+        raise ValueError(f"unknown metric {metric}: 0 .. {len(_abi.STRATEGY_METRICS) - 1}")
+    return int(metric)
+
+
+class StrategyStats:
+    """Per-strategy statistics of a backtest: the env records of a `BacktestStats` folded over the
+    members of each strategy by one device launch (struct gte_strategy_stats, include/gte.h), and the
+    ranking of the strategies by a score, also on the device (`gte_rank_strategies`).
+
+    Every field of the record is an attribute (``steps``, ``reward_sum``, ``reward_sq_sum``,
+    ``ep_return_sum``, ``ep_return_sq_sum``, ``max_drawdown``, ``best_reward_sum``,
+    ``worst_reward_sum``, ``trades``, ``episodes``, ``terminations``, ``envs``, ``envs_stepped``): a
+    torch tensor [S] that is a strided view of the result records, which this object owns.
+
+    Like `signal_actions()`, every call here enqueues its launches on the env's stream — torch's current
+    stream when the env was made — and returns without waiting for the device: torch work on that stream is
+    ordered with them, and the object keeps the records, the member lists and the result alive meanwhile.  An
+    env moved to another stream (`gte_set_stream`) is the caller's to order.  `top()` alone waits: it trims
+    its result to the number of ranked strategies, which it reads back (`numpy()` is a transfer)."""
+
+    FIELDS = tuple(n for n, _ in _abi.STRATEGY_FIELDS)
+    METRICS = _abi.STRATEGY_METRICS
+
+    def __init__(self, env, records, inputs=()):
+        from .batched import _device_view
+        self._env = env
+        self._records = records  # uint8 [S, 128], CUDA
+        self._keep = inputs      # what the reduction reads: alive while the launch may be in flight
+        self._derived = {}
+        self.num_strategies = int(records.shape[0])
+        dt = np.dtype(_abi.STRATEGY_DTYPE)
+        for name, typestr in _abi.STRATEGY_FIELDS:
+            setattr(self, name, _device_view(records.data_ptr() + dt.fields[name][1], (self.num_strategies,), typestr,
+                                             records.device, (dt.itemsize,)))
+
+    # -- construction ---------------------------------------------------------------------------
+    @staticmethod
+    def _groups(env, strategy, S):
+        """An explicit map int32 [N] -> the CSR lists of gte_reduce_backtest_stats, built on the device:
+        members by increasing env id (a stable sort of the map), offsets by searchsorted."""
+        torch = env._torch
+        dev = env._t["obs"].device
+        if isinstance(strategy, torch.Tensor) and strategy.is_cuda:
+            if strategy.dtype not in (torch.int32, torch.int64):
+                raise TypeError("strategy must be integers")
+            m = strategy
+        else:
+            a = np.asarray(strategy.numpy() if isinstance(strategy, torch.Tensor) else strategy)
+            if a.dtype.kind not in "iu":
+                raise TypeError("strategy must be integers")
+            if a.size and (a.min() < 0 or a.max() >= S):
+                raise IndexError(f"strategy outside [0, {S})")
+            m = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64))).to(dev)
+        if tuple(m.shape) != (env.num_envs,):
+            raise ValueError(f"expected strategy of shape ({env.num_envs},)")
+        m = m.to(torch.int64)
+        order = torch.sort(m, stable=True).indices
+        sorted_map = m[order]
+        # envs whose strategy lies outside [0, S) belong to nobody: offsets[0] skips the negative ones,
+        # offsets[S] stops before those >= S
+        bounds = torch.arange(S + 1, dtype=torch.int64, device=dev)
+        offsets = torch.searchsorted(sorted_map, bounds).to(torch.int32).contiguous()
+        return offsets, order.to(torch.int32).contiguous()
+
+    @classmethod
+    def _reduce(cls, env, records, strategy, n_strategies):
+        torch = env._torch
+        if torch is None:
+            raise ValueError("strategy statistics need output='torch'")
+        if isinstance(n_strategies, bool) or int(n_strategies) != n_strategies:
+            raise TypeError("n_strategies must be an integer")
+        S = int(n_strategies)
+        if S < 1:
+            raise ValueError("n_strategies must be >= 1")
+        dev = env._t["obs"].device
+        offsets = members = None
+        if strategy is not None:
+            offsets, members = cls._groups(env, strategy, S)
+        with torch.cuda.device(dev):
+            out = torch.empty((S, 128), dtype=torch.uint8, device=dev)
+        _abi.check(env._lib, env._lib.gte_reduce_backtest_stats(
+            env._h, None if records is None else C.c_void_p(records.data_ptr()), S,
+            None if offsets is None else C.c_void_p(offsets.data_ptr()),
+            None if members is None else C.c_void_p(members.data_ptr()), C.c_void_p(out.data_ptr())))
+        return cls(env, out, (records, offsets, members))
+
+    @classmethod
+    def from_records(cls, env, records, strategy=None, n_strategies=None) -> "StrategyStats":
+        """Fold caller-held env records — a `BACKTEST_DTYPE` array [N] (e.g. `BacktestStats.numpy()` saved
+        from an earlier chunk) or a contiguous CUDA uint8 [N, 128] tensor — over the strategies of `env`'s
+        N envs.  `strategy` / `n_strategies` as in `BacktestStats.by_strategy`; `n_strategies` is required."""
+        torch = env._torch
+        if torch is None:
+            raise ValueError("strategy statistics need output='torch'")
+        if n_strategies is None:
+            raise ValueError("from_records needs n_strategies")
+        N = env.num_envs
+        if isinstance(records, torch.Tensor):
+            if not records.is_cuda:
+                raise ValueError("a records tensor must live on the device (pass a BACKTEST_DTYPE array from the host)")
+            if records.dtype != torch.uint8:
+                raise TypeError(f"a records tensor is uint8 [N, 128], not {records.dtype}")
+            if tuple(records.shape) != (N, 128) or not records.is_contiguous():
+                raise ValueError(f"expected a contiguous records tensor of shape ({N}, 128)")
+            if records.data_ptr() % 16:
+                raise ValueError("records must be 16-byte aligned")
+            dev_records = records
+        else:
+            a = np.asarray(records)
+            if a.dtype != np.dtype(_abi.BACKTEST_DTYPE):
+                raise TypeError("records must be a BACKTEST_DTYPE array (BacktestStats.numpy()) or a CUDA uint8 tensor")
+            if a.shape != (N,):
+                raise ValueError(f"expected records of shape ({N},)")
+            raw = np.ascontiguousarray(a).view(np.uint8).reshape(N, 128)
+            dev_records = torch.from_numpy(raw.copy()).to(env._t["obs"].device)
+        return cls._reduce(env, dev_records, strategy, n_strategies)
+
+    # -- figures ---------------------------------------------------------------------------------
+    def _lazy(self, key, make):
+        if key not in self._derived:
+            self._derived[key] = make()
+        return self._derived[key]
+
+    @property
+    def mean_reward(self):
+        """Mean step reward over all transitions of the strategy's envs."""
+        return self._lazy("mean_reward", lambda: self.reward_sum / self.steps)
+
+    @property
+    def reward_std(self):
+        """Population standard deviation of the pooled step rewards."""
+        def make():
+            var = self.reward_sq_sum / self.steps - self.mean_reward ** 2
+            return var.clamp_min(0.0).sqrt()
+        return self._lazy("reward_std", make)
+
+    def sharpe(self, periods_per_year=None):
+        """mean_reward / reward_std of the pooled step rewards, annualised by sqrt(periods_per_year)."""
+        s = self.score("sharpe")
+        return s if periods_per_year is None else s * float(periods_per_year) ** 0.5
+
+    @property
+    def mean_episode_return(self):
+        """Mean return of the finished episodes of the strategy's envs (NaN where none finished)."""
+        return self._lazy("mean_episode_return", lambda: self.ep_return_sum / self.episodes)
+
+    @property
+    def episode_return_std(self):
+        """Population standard deviation of the finished episodes' returns."""
+        def make():
+            var = self.ep_return_sq_sum / self.episodes - self.mean_episode_return ** 2
+            return var.clamp_min(0.0).sqrt()
+        return self._lazy("episode_return_std", make)
+
+    def _rank(self, metric, min_episodes, k, want_scores):
+        env, torch = self._env, self._env._torch
+        code = _metric_code(metric)
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.GTE_RANK_MAX:
+            raise ValueError(f"k must lie in [1, {_abi.GTE_RANK_MAX}]")
+        dev = self._records.device
+        with torch.cuda.device(dev):
+            index = torch.empty((int(k),), dtype=torch.int32, device=dev)
+            top = torch.empty((int(k),), dtype=torch.float64, device=dev)
+            scores = torch.empty((self.num_strategies,), dtype=torch.float64, device=dev) if want_scores else None
+        _abi.check(env._lib, env._lib.gte_rank_strategies(
+            env._h, C.c_void_p(self._records.data_ptr()), self.num_strategies, code, int(min_episodes), int(k),
+            C.c_void_p(index.data_ptr()), C.c_void_p(top.data_ptr()),
+            None if scores is None else C.c_void_p(scores.data_ptr())))
+        return index, top, scores
+
+    def score(self, metric):
+        """The score of every strategy under `metric` (a name of `METRICS` or a `METRIC_*` constant), f64
+        [S] on the device, as `gte_rank_strategies` computes it — NaN included."""
+        code = _metric_code(metric)
+        return self._lazy(("score", code), lambda: self._rank(code, 0, 1, True)[2])
+
+    def top(self, k, metric="mean_episode_return", min_episodes=1):
+        """The k best strategies: ``(index int32 [r], score f64 [r])`` on the device, best first, r = min(k,
+        ranked strategies).  Ranked are those with at least one transition, at least `min_episodes`
+        finished episodes and a score that is not NaN; equal scores order by index.  Waits for the device: the
+        ranked count is read back to trim the result (`gte_rank_strategies` itself does not wait and pads with
+        -1 / NaN)."""
+        index, top, _ = self._rank(metric, min_episodes, k, False)
+        r = int((index >= 0).sum().item())
+        return index[:r], top[:r]
+
+    def numpy(self) -> np.ndarray:
+        """The records on the host, one transfer: a structured array [S] of `STRATEGY_DTYPE`."""
+        raw = self._records.cpu().numpy()
+        return raw.view(np.dtype(_abi.STRATEGY_DTYPE)).reshape(self.num_strategies).copy()

@@ -244,6 +244,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         self.observation_space = spaces.Box(-np.inf, np.inf,
                                             shape=(self.num_envs,) + self.obs_shape)
         self._signals = {}  # dataset -> the padded int8 [S, stride] device tensor bound to it (bind_signals)
+        self._backtest_map = None  # (strategy tensor or None, S) of the last backtest_signals(); None after backtest()
         for d, s in enumerate(self.datasets):
             self.upload_dataset(d, s)
 
@@ -1184,6 +1185,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._epoch += 1
         if self._obs_views is not None:
             self._follow_head()
+        self._backtest_map = None  # (no strategies: by_strategy() needs its arguments)
         return BacktestStats(self, ptr.value)
 
     # -- signal tables: the action looked up on the device by the row an env stands on -----
@@ -1535,6 +1537,8 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._epoch += 1
         if self._obs_views is not None:
             self._follow_head()
+        # what this call ran with, for BacktestStats.by_strategy(): the map (None = the default one) and S
+        self._backtest_map = (strategy, self.num_strategies)
         return BacktestStats(self, ptr.value)
 
     # -- misc ---------------------------------------------------------------------------

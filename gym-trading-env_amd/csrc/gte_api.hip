@@ -122,6 +122,11 @@ struct gte_env {
   gte::SignalTable* d_sig = nullptr;
   int32_t sig_S = 0;  // strategies of every bound table (0 = none bound)
   int32_t* d_sig_actions = nullptr;
+  // gte_rank_strategies: the two candidate lists (gte_strategy.hip), allocated by the first call and
+  // again when S outgrows them (the old ones stay until gte_destroy: launches in flight may read them)
+  double* rank_score[2] = {nullptr, nullptr};
+  int32_t* rank_index[2] = {nullptr, nullptr};
+  int64_t rank_entries[2] = {0, 0};
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -1371,6 +1376,58 @@ int gte_build_indicators(gte_env* E, int32_t d, const gte_indicator_spec* specs_
                                                     input_device, n_inputs, input_stride, bank_device, ind_stride,
                                                     E->stream);
   if (e != hipSuccess) return fail(GTE_ERR_HIP, "indicator build launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_reduce_backtest_stats(gte_env* E, const gte_backtest_stats* records_device, int32_t n_strategies,
+                              const int32_t* group_offsets_device, const int32_t* group_envs_device,
+                              gte_strategy_stats* out_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  if (!out_device || ((uintptr_t)out_device & 15))
+    return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
+  if ((uintptr_t)records_device & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
+  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
+    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
+  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
+    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reduce_backtest_stats inside a stream capture");
+  const gte_backtest_stats* const records = records_device ? records_device : E->bt_stats;
+  if (!records) return fail(GTE_ERR_STATE, "gte_reduce_backtest_stats before gte_backtest: the env has no records yet");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const hipError_t e = gte::launch_reduce_strategies(records, E->p.N, n_strategies, E->cfg.env_id_base,
+                                                     group_offsets_device, group_envs_device, out_device, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "strategy reduction launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_rank_strategies(gte_env* E, const gte_strategy_stats* stats_device, int32_t n_strategies, int32_t metric,
+                        int64_t min_episodes, int32_t k, int32_t* top_index_device, double* top_score_device,
+                        double* scores_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
+  if (metric < GTE_METRIC_MEAN_REWARD || metric > GTE_METRIC_WORST_REWARD_SUM)
+    return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
+  if (!stats_device || ((uintptr_t)stats_device & 15))
+    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  if (!top_index_device || ((uintptr_t)top_index_device & 3) || !top_score_device || ((uintptr_t)top_score_device & 7))
+    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
+  if ((uintptr_t)scores_device & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_rank_strategies inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  for (int w = 0; w < 2; ++w) {
+    const int64_t need = gte::rank_scratch_entries(n_strategies, w);
+    if (E->rank_entries[w] >= need) continue;
+    const int64_t entries = need > 2 * E->rank_entries[w] ? need : 2 * E->rank_entries[w];
+    TRY(dev_alloc(E, &E->rank_score[w], (size_t)entries, false));
+    TRY(dev_alloc(E, &E->rank_index[w], (size_t)entries, false));
+    E->rank_entries[w] = entries;
+  }
+  const hipError_t e = gte::launch_rank_strategies(stats_device, n_strategies, metric, min_episodes, k,
+                                                   top_index_device, top_score_device, scores_device, E->rank_score,
+                                                   E->rank_index, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "strategy ranking launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
 

@@ -112,6 +112,18 @@ hipError_t launch_build_indicators(const DatasetDesc& ds, int Fobs, int n_static
                                    int n_specs, const float* input, int n_inputs, int64_t input_stride, float* bank,
                                    int64_t ind_stride, hipStream_t stream);
 
+// --- gte_strategy.hip: strategy records from env records, and their ranking (gte_reduce_backtest_stats,
+// gte_rank_strategies, include/gte.h); the caller has checked alignments and that the group pointers are
+// both null (the default map over env_id_base) or both set
+hipError_t launch_reduce_strategies(const gte_backtest_stats* records, int n_envs, int n_strategies,
+                                    int64_t env_id_base, const int32_t* group_offsets, const int32_t* group_envs,
+                                    gte_strategy_stats* out, hipStream_t stream);
+// entries (a score and an index each) of candidate list `which` (0, 1) that ranking S strategies needs
+int64_t rank_scratch_entries(int n_strategies, int which);
+hipError_t launch_rank_strategies(const gte_strategy_stats* stats, int n_strategies, int metric, int64_t min_episodes,
+                                  int k, int32_t* top_index, double* top_score, double* scores, double* const* cand_score,
+                                  int32_t* const* cand_index, hipStream_t stream);
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

@@ -621,6 +621,95 @@ int gte_build_indicators(gte_env* env, int32_t ds,
                          const float* input_device, int32_t n_inputs, int64_t input_stride, /* NULL, 0, 0: none */
                          float* bank_device, int64_t ind_stride);
 
+/* ---- STRATEGY STATISTICS AND RANKING ON THE DEVICE: the N env records of a backtest folded into one
+ * record per strategy, and the best k strategies by a stated score — the last stage of a sweep (specs,
+ * rules, table, statistics, leaders) with no record copied to the host.  This text is the
+ * specification; the reference has no counterpart.
+ *
+ * MEMBERS.  Strategy s, 0 <= s < n_strategies = S, has an ordered list of member envs:
+ *   - group_offsets_device == group_envs_device == NULL, the library's map (the one gte_backtest_signals
+ *     uses with strategy == NULL): e = ((s - env_id_base) mod S) + j * S for j = 0, 1, ... while e < N;
+ *   - both non-NULL, a CSR list of DEVICE int32 arrays: group_offsets[S + 1] non-decreasing with
+ *     0 <= offsets[s] <= offsets[S] <= N, and the members of s are group_envs[offsets[s] ..
+ *     offsets[s + 1]) in that order.  An entry outside [0, N) holds its place in the list (see the sums)
+ *     and is otherwise skipped: no list content makes the kernel read outside the records.  (Offsets are
+ *     clamped into [0, N] and made non-decreasing before use.)
+ * Member number j = 0, 1, ... of a list is x_j below; a skipped entry contributes to nothing.
+ *
+ * THE RECORD of strategy s over its members:
+ *   steps, trades, episodes, terminations   exact 64-bit sums of the members' counters;
+ *   envs            members that are not skipped;      envs_stepped   those of them with steps > 0;
+ *   max_drawdown    m = 0.0; in member order: if (x > m) m = x;
+ *   best_reward_sum   m = -inf; over the members with steps > 0, in member order: if (x > m) m = x;
+ *   worst_reward_sum  m = +inf; likewise with  if (x < m) m = x
+ *                   (plain comparisons: a NaN never wins, of equal values the first stays);
+ *   reward_sum, reward_sq_sum, ep_return_sum, ep_return_sq_sum   f64 sums in ONE FIXED ORDER that
+ *     depends on nothing but the member list: eight interleaved accumulators a_0 .. a_7, each starting
+ *     from 0.0; a_i adds x_i, x_(i+8), x_(i+16), ... one after the other (a skipped entry adds nothing);
+ *     the sum is ((((((a_0 + a_1) + a_2) + a_3) + a_4) + a_5) + a_6) + a_7.  Every + is one IEEE f64
+ *     addition; the result is the same bit for bit for any launch geometry and either kernel.
+ *     A NaN that a sum produces is a quiet NaN of unspecified payload.
+ * A strategy without members gets zero sums and counters, max_drawdown 0.0, best -inf, worst +inf.
+ * reserved is written as zero. */
+typedef struct gte_strategy_stats {     /* 128 bytes, eight 16-byte pieces like gte_backtest_stats */
+  int64_t steps;
+  double  reward_sum, reward_sq_sum, ep_return_sum, ep_return_sq_sum;   /* sums over the members  */
+  double  max_drawdown;                 /* largest member max_drawdown                            */
+  double  best_reward_sum, worst_reward_sum;  /* over members with steps > 0                      */
+  int64_t trades, episodes, terminations;     /* 64-bit: member counters are int32, sums are not   */
+  int32_t envs, envs_stepped;           /* members; members with steps > 0                        */
+  int32_t reserved[8];                  /* written as zero                                        */
+} gte_strategy_stats;
+/* records_device == NULL: the env's own N records (GTE_ERR_STATE before the first gte_backtest /
+ * gte_backtest_signals); else a caller-owned DEVICE array of N gte_backtest_stats, 16-byte aligned —
+ * records saved from earlier chunks or other runs.  out_device: DEVICE array of S records, 16-byte
+ * aligned, all 128 bytes of each written.  One launch, ordered on the env's stream, no host
+ * synchronisation; changes neither the env's records nor its state.  GTE_ERR_INVALID, with nothing
+ * launched, for n_strategies < 1, a NULL or misaligned out_device, misaligned records, or exactly one
+ * of the two group pointers NULL.  Refused inside a stream capture (GTE_ERR_STATE). */
+int gte_reduce_backtest_stats(gte_env* env, const gte_backtest_stats* records_device,
+                              int32_t n_strategies, const int32_t* group_offsets_device,
+                              const int32_t* group_envs_device, gte_strategy_stats* out_device);
+
+/* The score a strategy is ranked by, from its gte_strategy_stats; every operation one IEEE f64 operation
+ * as written (an int64 converts to f64 first), sqrt correctly rounded:
+ *   MEAN_REWARD          m = reward_sum / steps
+ *   SHARPE               q = reward_sq_sum / steps;  v = q - m * m;  if (!(v > 0.0)) v = 0.0;  m / sqrt(v)
+ *                        (mean / population standard deviation of the pooled step rewards; NaN when
+ *                        both are 0, +-inf for a constant non-zero reward)
+ *   MEAN_EPISODE_RETURN  ep_return_sum / episodes
+ *   EPISODE_SHARPE       the SHARPE formulas over ep_return_sum, ep_return_sq_sum and episodes
+ *   NEG_MAX_DRAWDOWN     -max_drawdown
+ *   WORST_REWARD_SUM     worst_reward_sum */
+typedef enum gte_strategy_metric {
+  GTE_METRIC_MEAN_REWARD = 0,
+  GTE_METRIC_SHARPE = 1,
+  GTE_METRIC_MEAN_EPISODE_RETURN = 2,
+  GTE_METRIC_EPISODE_SHARPE = 3,
+  GTE_METRIC_NEG_MAX_DRAWDOWN = 4,
+  GTE_METRIC_WORST_REWARD_SUM = 5
+} gte_strategy_metric;
+#define GTE_RANK_MAX 256
+/* The k best of S strategies.  Strategy s is RANKED iff steps >= 1, episodes >= min_episodes and its
+ * score is not NaN.  Ranked strategies are ordered by score, highest first (+-inf like any value;
+ * -0.0 == 0.0, by comparison); equal scores by strategy index, lowest first.  top_index_device
+ * (int32 [k]) and top_score_device (f64 [k]) receive the first k of that order; places beyond the
+ * number of ranked strategies hold -1 and NaN.  1 <= k <= GTE_RANK_MAX; k may exceed S.
+ * scores_device (f64 [S]) or NULL: every strategy's score as computed, ranked or not, NaN included.
+ * stats_device: DEVICE array of S records, 16-byte aligned.  A score launch and a few selection launches
+ * (the best 256 of every 1 024 candidates, repeated until one workgroup holds them all), ordered on the
+ * env's stream, no host synchronisation; the candidate lists are library-owned scratch, allocated by
+ * the first call (and again only when S grows: to at least twice the old size, and the old lists are freed
+ * by gte_destroy, not before — launches in flight may read them — so an env ranked over ever larger S holds
+ * up to about twice what its largest S needs).  GTE_ERR_INVALID, with nothing launched, for
+ * n_strategies < 1, k outside [1, GTE_RANK_MAX], an unknown metric, a NULL or misaligned stats_device
+ * (16 bytes), top_index_device (4), top_score_device (8) or a misaligned scores_device (8).  Refused
+ * inside a stream capture (GTE_ERR_STATE). */
+int gte_rank_strategies(gte_env* env, const gte_strategy_stats* stats_device, int32_t n_strategies,
+                        int32_t metric, int64_t min_episodes, int32_t k,
+                        int32_t* top_index_device, double* top_score_device,
+                        double* scores_device /* [n_strategies] or NULL */);
+
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
 /* Same-step auto-reset with gte_config.final_obs: struct-of-arrays snapshot (device pointers,
