@@ -167,6 +167,14 @@ INDICATOR_FIELDS = [(n, "<i4") for n in ("kind", "source", "column", "n")]
 #: numpy view of an array of gte_indicator_spec (gte_build_indicators)
 INDICATOR_DTYPE = INDICATOR_FIELDS
 
+#: struct gte_signal_compose (include/gte.h), in declaration order: 128 bytes per composed strategy
+COMPOSE_FIELDS = [("in", "<i4", (4,)), ("n_in", "i1"), ("initial", "i1"), ("pos_invalid", "i1"), ("reserved0", "i1"),
+                  ("lut", "i1", (81,)), ("reserved", "i1", (27,))]
+#: numpy view of an array of gte_signal_compose (gte_compose_signals)
+COMPOSE_DTYPE = COMPOSE_FIELDS
+#: GTE_COMPOSE_KEEP
+COMPOSE_KEEP = -128
+
 #: enum gte_indicator_kind / gte_indicator_source and GTE_IND_MAX_WINDOW (include/gte.h)
 IND_KINDS = ("value", "sma", "std", "zscore", "max", "min", "diff", "roc", "ema", "rsi")
 IND_SOURCES = ("close", "high", "low", "feature", "input")
@@ -305,6 +313,8 @@ SYMBOLS = {
     "gte_backtest_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
+    "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_int64]),
     "gte_build_indicators": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
                                        C.c_void_p, C.c_int64]),
     "gte_reduce_backtest_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

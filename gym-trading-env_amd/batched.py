@@ -1366,6 +1366,105 @@ class BatchedTradingEnv(_VectorEnvBase):
         return out[next(iter(out))] if (dataset is not None or not isinstance(indicators, (list, tuple))) \
             else [out[d] for d in range(D)]
 
+    def compose_signals(self, clauses, specs, dataset=None, bind=True):
+        """Compose signal tables ON THE DEVICE from clause rows (`gte_compose_signals`): one spec per
+        strategy (`signals.compose`, `signals.COMPOSE_DTYPE`; the rule is stated in include/gte.h) over
+        a table of clause rows int8 [R, T] of zone codes 0 / 1 / 2 — what
+        ``build_signals(bank, signals.clauses(...), bind=False)`` returns, or an earlier composed table.
+        Returns the table as a torch int8 [S, T] view of a padded device tensor — complete for torch to
+        read when the call returns — and, with ``bind=True``, binds that same tensor as `bind_signals`
+        would, without a second copy.  No [S, T] array exists on the host.
+
+        clauses: a NumPy array or a CUDA int8 tensor [R, T] for dataset `dataset` (default: the only
+        one); with ``dataset=None`` and D > 1 a list of D clause tables, one per resident dataset, and
+        the result is a list of D tables.  A CUDA table whose rows are 16-byte aligned and padded to
+        `signals.row_stride(T)` bytes (the ``[:, :T]`` view `build_signals` returns) is read in place.
+        specs: a `COMPOSE_DTYPE` array [S], whose `n_in` and `in` are checked against R here, or a
+        CUDA tensor uint8 [S, 128] of the same bytes, which is the caller's contract: the kernel gives
+        a spec that names no clause row a row of -1.  One spec array serves every dataset; the
+        caller's order is kept (a row index is a strategy id).  Specs that read the same clause rows
+        are best placed next to each other, as the rules of `build_signals` are."""
+        torch = self._torch
+        if torch is None:
+            raise ValueError("compose_signals needs output='torch'")
+        from . import signals as sig
+        D = len(self.datasets)
+        if dataset is None:
+            if D == 1 and not isinstance(clauses, (list, tuple)):
+                rows = {0: clauses}
+            elif isinstance(clauses, (list, tuple)) and len(clauses) == D:
+                rows = dict(enumerate(clauses))
+            else:
+                raise ValueError(f"expected a list of {D} clause tables, one per dataset (or dataset=d)")
+        else:
+            if not 0 <= int(dataset) < D:
+                raise IndexError(f"dataset {dataset} out of range")
+            rows = {int(dataset): clauses}
+        dev = self._t["obs"].device
+        # the specs: 128 bytes each on the device
+        if isinstance(specs, torch.Tensor):
+            if not (specs.is_cuda and specs.dim() == 2 and specs.is_contiguous() and
+                    (specs.dtype, int(specs.shape[1])) == (torch.uint8, sig.COMPOSE_DTYPE.itemsize)):
+                raise TypeError("specs: a COMPOSE_DTYPE array, or a contiguous CUDA tensor uint8 [S, 128]")
+            d_specs, host_specs = specs.to(dev), None
+        else:
+            host_specs = np.ascontiguousarray(specs)
+            if host_specs.dtype != sig.COMPOSE_DTYPE or host_specs.ndim != 1:
+                raise TypeError("specs: a one-dimensional array of signals.COMPOSE_DTYPE (signals.compose)")
+            d_specs = torch.from_numpy(host_specs.view(np.uint8).reshape(-1, sig.COMPOSE_DTYPE.itemsize).copy()).to(dev)
+        S = int(d_specs.shape[0])
+        if S < 1:
+            raise ValueError("compose_signals needs at least one spec")
+        d_rows = {}
+        for d, x in rows.items():
+            T = self.datasets[d].T
+            if isinstance(x, torch.Tensor) and x.is_cuda:
+                if x.dim() != 2 or x.dtype != torch.int8:
+                    raise TypeError("a clause table is a two-dimensional int8 tensor")
+                x = x.to(dev)
+                if not (x.stride(1) == 1 and x.stride(0) % sig.PIECE == 0 and x.stride(0) >= sig.row_stride(T)
+                        and x.data_ptr() % sig.PIECE == 0):
+                    with torch.cuda.device(dev):
+                        buf = torch.full((int(x.shape[0]), sig.row_stride(int(x.shape[1]))), -1, dtype=torch.int8,
+                                         device=dev)
+                    buf[:, :x.shape[1]] = x
+                    x = buf[:, :x.shape[1]]
+            else:
+                host = sig.as_int8_table(x.numpy() if isinstance(x, torch.Tensor) else x)
+                x = torch.from_numpy(sig.pad_rows(host)).to(dev)[:, :host.shape[1]]
+            if int(x.shape[1]) != T:
+                raise ValueError(f"clause table of dataset {d} has {int(x.shape[1])} columns, the dataset {T} rows")
+            R = int(x.shape[0])
+            if R < 1:
+                raise ValueError("a clause table needs at least one row")
+            if host_specs is not None:
+                n_in = host_specs["n_in"].astype(np.int64)
+                if ((n_in < 1) | (n_in > 4)).any():
+                    raise ValueError("specs hold an n_in outside [1, 4]")
+                used = np.arange(4)[None, :] < n_in[:, None]
+                if (used & ((host_specs["in"] < 0) | (host_specs["in"] >= R))).any():
+                    raise IndexError(f"specs name clause rows outside the {R} rows of dataset {d}'s clause table")
+            d_rows[d] = x
+        with torch.cuda.device(dev):
+            tables = {d: torch.empty((S, sig.row_stride(self.datasets[d].T)), dtype=torch.int8, device=dev)
+                      for d in d_rows}
+        if bind:
+            self._check_one_s(tables, tables)
+        torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
+        for d, x in d_rows.items():
+            buf = tables[d]
+            _abi.check(self._lib, self._lib.gte_compose_signals(
+                self._h, d, C.c_void_p(x.data_ptr()), int(x.shape[0]), int(x.stride(0)),
+                C.c_void_p(d_specs.data_ptr()), S, C.c_void_p(buf.data_ptr()), int(buf.shape[1])))
+        self.synchronize()  # the tables are complete: for torch on any stream, and before the inputs go
+        out = {}
+        for d, buf in tables.items():
+            if bind:
+                self._bind_padded(d, buf)
+            out[d] = buf[:, :self.datasets[d].T]
+        return out[next(iter(out))] if (dataset is not None or not isinstance(clauses, (list, tuple))) \
+            else [out[d] for d in range(D)]
+
     def build_indicators(self, specs, dataset=None, inputs=None):
         """Build indicator banks ON THE DEVICE from the resident market data (`gte_build_indicators`):
         one row per spec (`signals.indicators`, `signals.INDICATOR_DTYPE`; what each kind computes is

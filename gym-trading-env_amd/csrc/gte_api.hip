@@ -1340,6 +1340,40 @@ int gte_build_signals(gte_env* E, int32_t d, const float* indicators_device, int
   return GTE_OK;
 }
 
+int gte_compose_signals(gte_env* E, int32_t d, const int8_t* clauses_device, int32_t n_clause_rows,
+                        int64_t clause_stride, const gte_signal_compose* specs_device, int32_t n_specs,
+                        int8_t* table_device, int64_t row_stride) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_compose_signals inside a stream capture");
+  const int64_t T = E->h_ds[d].T;
+  if (T <= 0) return fail(GTE_ERR_STATE, "gte_compose_signals: dataset %d was never uploaded", d);
+  const int64_t T16 = (T + 15) / 16 * 16;
+  if (!clauses_device || !specs_device || !table_device) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (((uintptr_t)clauses_device & 15) || ((uintptr_t)table_device & 15))
+    return fail(GTE_ERR_INVALID, "the clause table and the table must be 16-byte aligned");
+  if ((uintptr_t)specs_device & 3) return fail(GTE_ERR_INVALID, "specs must be 4-byte aligned");
+  if (row_stride % 16 != 0 || row_stride < T16)
+    return fail(GTE_ERR_INVALID, "row_stride %lld: a multiple of 16 and >= %lld (the %lld rows of dataset %d "
+                "rounded up to 16) required", (long long)row_stride, (long long)T16, (long long)T, d);
+  if (clause_stride % 16 != 0 || clause_stride < T16)
+    return fail(GTE_ERR_INVALID, "clause_stride %lld: a multiple of 16 and >= %lld required",
+                (long long)clause_stride, (long long)T16);
+  if (n_clause_rows < 1) return fail(GTE_ERR_INVALID, "n_clause_rows must be >= 1");
+  if (n_specs < 1) return fail(GTE_ERR_INVALID, "n_specs must be >= 1");
+  {  // what the kernel may read of the clause table and what it writes of the table: disjoint
+    const uintptr_t in0 = (uintptr_t)clauses_device, out0 = (uintptr_t)table_device;
+    const uintptr_t in1 = in0 + (size_t)((int64_t)(n_clause_rows - 1) * clause_stride + T16);
+    const uintptr_t out1 = out0 + (size_t)((int64_t)(n_specs - 1) * row_stride + T16);
+    if (in0 < out1 && out0 < in1) return fail(GTE_ERR_INVALID, "the clause table and the table overlap");
+  }
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const hipError_t e = gte::launch_compose_signals(clauses_device, n_clause_rows, clause_stride, specs_device, n_specs,
+                                                   T, table_device, row_stride, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal compose launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
 int gte_build_indicators(gte_env* E, int32_t d, const gte_indicator_spec* specs_device, int32_t n_specs,
                          const float* input_device, int32_t n_inputs, int64_t input_stride, float* bank_device,
                          int64_t ind_stride) {

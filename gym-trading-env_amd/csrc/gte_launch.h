@@ -105,6 +105,13 @@ hipError_t launch_build_signals(const float* indicators, int n_indicators, int64
                                 const gte_signal_rule* rules, int n_rules, int64_t T, int8_t* table,
                                 int64_t row_stride, hipStream_t stream);
 
+// --- gte_compose.hip: signal tables composed on the device from clause rows and a truth table per strategy
+// (gte_compose_signals, include/gte.h): table rows 0 .. n_specs-1, bytes 0 .. round_up(T, 16)-1 of each;
+// the caller has checked alignments, strides and that the clause table and the output are disjoint
+hipError_t launch_compose_signals(const int8_t* clauses, int n_clause_rows, int64_t clause_stride,
+                                  const gte_signal_compose* specs, int n_specs, int64_t T, int8_t* table,
+                                  int64_t row_stride, hipStream_t stream);
+
 // --- gte_indicators.hip: indicator banks written on the device from resident market data
 // (gte_build_indicators, include/gte.h): bank rows 0 .. n_specs-1, floats 0 .. round_up(T, 16)-1 of each;
 // the caller has checked alignments, strides and that input and bank are disjoint

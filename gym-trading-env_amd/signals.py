@@ -77,6 +77,81 @@ def rules(a, b=-1, hi=0.0, lo=0.0, warmup=0, pos_up=1, pos_down=0, pos_neutral=-
     return out
 
 
+# ---- signal tables composed on the device from clause rows and a truth table (gte_compose_signals) ----
+
+from ._abi import COMPOSE_DTYPE as _COMPOSE_FIELDS  # noqa: E402
+from ._abi import COMPOSE_KEEP as KEEP  # noqa: E402
+
+#: `gte_signal_compose` of include/gte.h, 128 bytes
+COMPOSE_DTYPE = np.dtype(_COMPOSE_FIELDS)
+#: the zone codes of a clause row: what `clauses(...)` makes `build_signals` write
+DOWN, NEUTRAL, UP = 0, 1, 2
+
+
+def clauses(a, b=-1, hi=0.0, lo=0.0, warmup=0, latch=False) -> np.ndarray:
+    """`rules(...)` whose table bytes are the zone codes: `DOWN` (0) below `lo`, `NEUTRAL` (1) in
+    between, `UP` (2) above `hi`, and -1 inside the warm-up — the rows `compose` specs read."""
+    return rules(a, b, hi, lo, warmup, pos_up=UP, pos_down=DOWN, pos_neutral=NEUTRAL, latch=latch)
+
+
+def compose(inputs, lut, initial=-1, invalid=-1) -> np.ndarray:
+    """One `COMPOSE_DTYPE` record per strategy: row t of strategy s is ``lut[c0, c1, ...]`` with
+    ``c_k`` the code (0 / 1 / 2) that clause row ``inputs[s, k]`` holds at t — or, where that entry is
+    `KEEP`, what the row before gave (`initial` before the first decision) — and `invalid` where some
+    input holds no code (a clause's warm-up), which leaves the state alone.  The rule itself is
+    stated in include/gte.h.
+
+    inputs: integers ``[S, n]``, or ``[n]`` for every strategy, ``1 <= n <= 4``.  lut: an array of
+    shape ``(3,) * n`` indexed ``[c0, c1, ...]``; one per strategy as ``[S, 3, ...]``; or a callable
+    ``f(c0, ..., c_{n-1}) -> byte | KEEP``, evaluated here over the 3**n tuples.  `initial` and
+    `invalid` are bytes, or one per strategy.  The entries of the 81 that only a fifth, sixth ...
+    code could reach repeat the others, so that missing inputs count as code 0."""
+    idx = np.asarray(inputs)
+    if idx.dtype.kind not in "iu":
+        raise TypeError(f"inputs must be integers (clause rows), not {idx.dtype}")
+    if idx.ndim not in (1, 2) or not 1 <= idx.shape[-1] <= 4:
+        raise ValueError(f"inputs: [S, n] or [n] with 1 <= n <= 4, got shape {idx.shape}")
+    if idx.size and (idx.min() < -2 ** 31 or idx.max() > 2 ** 31 - 1):
+        raise ValueError("inputs do not fit their field")
+    n = idx.shape[-1]
+    if callable(lut):
+        codes = np.indices((3,) * n).reshape(n, -1)
+        small = np.array([lut(*(int(c) for c in tup)) for tup in codes.T]).reshape((3,) * n)
+    else:
+        small = np.asarray(lut)
+    if small.dtype == np.bool_:
+        small = small.astype(np.int64)
+    if small.dtype.kind not in "iu":
+        raise TypeError(f"truth-table entries must be integers (table bytes or KEEP), not {small.dtype}")
+    if small.shape == (3,) * n:
+        small = small[None]
+    elif small.ndim != n + 1 or small.shape[1:] != (3,) * n or small.shape[0] < 1:
+        raise ValueError(f"lut: shape {(3,) * n} or (S,) + {(3,) * n} for {n} inputs, got {small.shape}")
+    extra = {"initial": np.asarray(initial), "invalid": np.asarray(invalid)}
+    for name, v in list(extra.items()) + [("lut", small)]:
+        if v.dtype.kind not in "iub":
+            raise TypeError(f"{name} must be integers, not {v.dtype}")
+        if v.size and (v.min() < -128 or v.max() > 127):
+            raise ValueError(f"{name} does not fit a byte")
+        if name != "lut" and v.ndim > 1:
+            raise ValueError(f"{name}: a byte, or one per strategy")
+    sizes = {int(v.shape[0]) for v in (idx[None] if idx.ndim == 1 else idx, small, *(v.reshape(-1) for v in extra.values()))}
+    sizes.discard(1)
+    if len(sizes) > 1:
+        raise ValueError(f"inputs, lut, initial and invalid disagree about the number of strategies: {sorted(sizes)}")
+    S = sizes.pop() if sizes else 1
+    out = np.zeros(S, dtype=COMPOSE_DTYPE)
+    out["in"][:, :n] = np.broadcast_to(idx if idx.ndim == 2 else idx[None], (S, n))
+    out["n_in"] = n
+    out["initial"] = np.broadcast_to(extra["initial"].reshape(-1), (S,))
+    out["pos_invalid"] = np.broadcast_to(extra["invalid"].reshape(-1), (S,))
+    # entry c0 + 3 c1 + ...: c0 runs fastest, so the axes are reversed before flattening; codes of missing
+    # inputs are 0, and the entries a non-zero one would reach repeat those
+    flat = small.transpose((0,) + tuple(range(n, 0, -1))).reshape(small.shape[0], 3 ** n)
+    out["lut"] = np.broadcast_to(np.tile(flat, (1, 81 // 3 ** n)), (S, 81))
+    return out
+
+
 def bank_stride(T: int) -> int:
     """Floats from one indicator row to the next: T rounded up to a multiple of 16."""
     return row_stride(T)

@@ -554,6 +554,56 @@ int gte_build_signals(gte_env* env, int32_t ds,
                       const gte_signal_rule* rules_device, int32_t n_rules,
                       int8_t* table_device, int64_t row_stride);
 
+/* ---- SIGNAL TABLES COMPOSED ON THE DEVICE from clause rows and a truth table: a gte_signal_rule is one
+ * comparison; a strategy is usually several ("long while SMA(fast) > SMA(slow) AND RSI < 70", "enter on
+ * a breakout, leave on a slower condition", "two of three filters agree").  A CLAUSE TABLE of a dataset
+ * is caller-owned DEVICE memory int8 [n_clause_rows][clause_stride] of ZONE CODES 0 / 1 / 2 — what
+ * gte_build_signals writes with pos_down / pos_neutral / pos_up = 0 / 1 / 2 — and one 128-byte spec per
+ * strategy names up to four clause rows and gives the table byte for each of the 3^4 code tuples, or
+ * KEEP: the state stays what it was.  The device writes the int8 [n_specs][T] table that
+ * gte_bind_signals accepts.  This text is the specification; the reference has no counterpart. */
+#define GTE_COMPOSE_KEEP (-128)
+typedef struct gte_signal_compose {   /* 128 bytes, 4-byte aligned */
+  int32_t in[4];        /* clause rows read; only in[0 .. n_in-1] are looked at        */
+  int8_t  n_in;         /* 1 .. 4                                                      */
+  int8_t  initial;      /* the state q before row 0 (a table byte, not validated)      */
+  int8_t  pos_invalid;  /* byte written where some input is no code                    */
+  int8_t  reserved0;    /* ignored                                                     */
+  int8_t  lut[81];      /* entry c0 + 3 c1 + 9 c2 + 27 c3; a table byte, or KEEP       */
+  int8_t  reserved[27]; /* ignored                                                     */
+} gte_signal_compose;
+/* Row s of the table is composed from spec s for t = 0 .. T-1 in order, with state q = initial before
+ * row 0 (clauses = the clause table):
+ *
+ *     c_k = clauses[in[k]][t] for k < n_in;  c_k = 0 for k >= n_in
+ *     if any c_k (k < n_in) is outside {0, 1, 2}:   out[t] = pos_invalid; continue     (q unchanged)
+ *     e = lut[c_0 + 3 c_1 + 9 c_2 + 27 c_3]
+ *     if e != GTE_COMPOSE_KEEP:  q = e
+ *     out[t] = q
+ *
+ * So a clause's warm-up byte (-1), or any stray byte, makes the composed row pos_invalid there and leaves
+ * the state alone; KEEP is what makes asymmetric entry / exit expressible; initial == KEEP is written as
+ * the byte -128 until an entry decides.  A spec with n_in outside [1, 4], or with an in[k], k < n_in,
+ * outside [0, n_clause_rows), gives a row of -1 and reads nothing: no spec content makes the kernel read
+ * outside the clause table.  Bytes T .. round_up(T, 16) - 1 of every row are -1; bytes of a row beyond
+ * round_up(T, 16), and everything outside rows 0 .. n_specs - 1, are not touched.  Output bytes are not
+ * validated: what they mean (hold outside [0, n_positions)) stays with the lookup.  Because 0 / 1 / 2
+ * are codes, a composed table is a legal clause table for a second call: trees deeper than four inputs.
+ *
+ * T is that of resident dataset `ds` (GTE_ERR_STATE if it was never uploaded).  The launch is ordered
+ * on the env's stream and binds nothing: pass the table to gte_bind_signals afterwards (which waits
+ * for the stream).  Refused inside a stream capture (GTE_ERR_STATE).  GTE_ERR_INVALID, with nothing
+ * launched, unless: clauses_device and table_device are 16-byte aligned and specs_device 4-byte aligned;
+ * clause_stride and row_stride (bytes) are multiples of 16 and >= round_up(T, 16), so that a 16-byte
+ * load or store anywhere in the 16 bytes of a piece is legal; n_clause_rows >= 1 and n_specs >= 1; the
+ * bytes read (rows 0 .. n_clause_rows - 1, round_up(T, 16) bytes of each) and the bytes written are
+ * disjoint.  One wavefront composes one row in pieces of 1 024 bytes (gte_compose.hip); specs that read
+ * the same clause rows are best placed next to each other. */
+int gte_compose_signals(gte_env* env, int32_t ds,
+                        const int8_t* clauses_device, int32_t n_clause_rows, int64_t clause_stride,
+                        const gte_signal_compose* specs_device, int32_t n_specs,
+                        int8_t* table_device, int64_t row_stride);
+
 /* ---- INDICATOR BANKS BUILT ON THE DEVICE from the resident market data: the bank gte_build_signals
  * reads is itself written by the device, one row per 16-byte spec, in the layout gte_build_signals
  * reads in place — a sweep is specs, then rules, then table, then statistics, with no host array
