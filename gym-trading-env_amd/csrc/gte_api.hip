@@ -47,6 +47,9 @@ static int fail(int code, const char* fmt, ...) {
                   "%s failed: %s", #expr, hipGetErrorString(e_));                 \
   } while (0)
 
+// GTE_SLIDE_AB (include/gte.h): what a set bit keeps as the sliding window's first version had it
+enum { SLIDE_AB_ORDER = 1 };
+
 // Which kernels an env launches, with what geometry: decided by plan_launches (gte_create) and changed
 // later only where noted.  p.epw, p.lean_rows and p.hot_lds are set there too.
 struct LaunchPlan {
@@ -60,6 +63,7 @@ struct LaunchPlan {
   bool always_dense = false;     // every step stores all flags (gte_ledger.h)
   int slide_rows = 0;            // M: spare rows a sliding observation buffer may have (0 = this env never slides)
   bool full_windows = false;     // a sliding buffer moves its head but every step writes full windows (A/B)
+  int slide_ab = 0;              // GTE_SLIDE_AB (include/gte.h): bits that keep the earlier slide launch (A/B)
   bool fused_rollout = false;    // gte_rollout may use the fused kernels ...
   bool resident_rollout = false; // ... and among them the window-resident one
   // L2-affinity processing order (gte_kernels.hip, "L2-affinity permutation")
@@ -450,6 +454,8 @@ static int plan_launches(gte_env* E) {
   // A/B: the head still moves, every step writes full windows (an environment variable like
   // GTE_AFFINITY_BINS, not a GTE_KV_* bit: results and layout are the sliding ones)
   L.full_windows = getenv("GTE_SLIDE_FULL_WINDOWS") != nullptr;  // (read here, at gte_create, once per env)
+  // A/B: bit 1 keeps slide launches in the L2-affinity order (read the same way; include/gte.h)
+  if (const char* o = getenv("GTE_SLIDE_AB")) L.slide_ab = atoi(o);
   L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & GTE_KV_ROLLOUT_PER_STEP);
   L.resident_rollout = p.W >= 2 && !(kv & GTE_KV_ROLLOUT_GATHER);
   // envs per wavefront from registers: full waves once every SIMD has one (65 536 envs: 5.8 us per step
@@ -900,20 +906,31 @@ static int age_order(gte_env* E, int32_t steps) {
 static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool capturing,
                         EnvRec* terminal_rec = nullptr) {
   const LaunchPlan& L = E->plan;
-  TRY(age_order(E, 1));
+  const bool slides_own = t.own_obs && E->sliding;
+  gte_ledger::Span obs = obs_span(E);
+  // slide while the buffer provably holds this env's windows (its window claim) at a head below M;
+  // otherwise (and at head M: the wrap) every window in full at head 0, which makes it so again
+  const bool slide = slides_own && !capturing && ledger().holds(E, WINDOW, {obs}) && E->p.obs_head < L.slide_rows;
+  // A launch that stores one row per env runs in env order: the L2-affinity order exists so that the
+  // full-window gathers of one XCD hit its L2, and a slide reads one 128-byte table row per env; what the
+  // order costs it is the hop perm[slot] -> rec[env] at the head of phase A and 64 scattered addresses per
+  // wave instruction for every per-env store (reward, ring, flags).  Results do not depend on the order
+  // (resort()); term_ids has no order contract (its users sort or scatter by id: terminal_ids() sorts).
+  // A re-sort that falls due in a run of such launches waits for the next launch that writes full
+  // windows — the wrap, or a full step after a withdrawn claim; steps_since_rebuild keeps counting.
+  const bool env_order = slide && !L.full_windows && !(L.slide_ab & SLIDE_AB_ORDER);
+  if (env_order) { if (L.affinity_period > 0) E->steps_since_rebuild += 1; }
+  else TRY(age_order(E, 1));
   Params p = E->p;  // (after the re-sort: it sets p.perm)
+  if (env_order) p.perm = nullptr;
   if (terminal_rec) p.final_rec = terminal_rec;
   p.actions = t.actions; p.obs = t.obs; p.reward = t.reward; p.reward64 = t.reward64;
   p.terminated = t.terminated; p.truncated = t.truncated;
-  const bool slides_own = t.own_obs && E->sliding;
-  gte_ledger::Span obs = obs_span(E);
   if (!t.own_obs) {  // a rollout's per-step row: a classic [N, W, F_obs] block
     p.obs_rows = p.W; p.obs_head = 0;
     obs = {t.obs, sizeof(float) * (size_t)p.N * p.W * p.Fobs};
   } else if (E->sliding) {
-    // slide while the buffer provably holds this env's windows (its window claim) at a head below M;
-    // otherwise (and at head M: the wrap) every window in full at head 0, which makes it so again
-    if (!capturing && ledger().holds(E, WINDOW, {obs}) && E->p.obs_head < L.slide_rows) {
+    if (slide) {
       E->p.obs_head += 1;
       // JOB_SLIDES shares bit 1 of the job record with dyn_persist's "zero the store" (gte_device.h):
       // plan_launches never grants slide_rows with dyn_persist, and only this launch ever sets p.slide

@@ -835,7 +835,12 @@ int gte_bind_outputs(gte_env* env, const gte_outputs* bufs);
  * A/B and twin runs: with GTE_SLIDE_FULL_WINDOWS set in the environment when gte_create runs, the env
  * keeps the sliding layout and the moving head, but every step writes every window in full (the
  * enum gte_kernel_variant keeps its values: tests pin them; this is a tuning switch like
- * GTE_AFFINITY_BINS). */
+ * GTE_AFFINITY_BINS).
+ *
+ * GTE_SLIDE_AB, read the same way, is a bit mask.  Bit 1 keeps slide launches (steps that store one row per
+ * env) in the L2-affinity order, with a due re-sort run at once, as the sliding window's first version did;
+ * by default they run in env order and a re-sort that falls due waits for the next launch that writes full
+ * windows.  Results never depend on it.  The other bits are reserved and ignored. */
 typedef struct gte_obs_view_t {
   float*  base;          /* the bound observation buffer (NULL before one exists)            */
   int32_t rows_per_env;  /* W + M while sliding, else W                                      */
