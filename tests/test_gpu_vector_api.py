@@ -140,8 +140,9 @@ def test_batch_custom_callables_replay_the_reference_fixture():
         ref = np.tile(g["obs"][k], (tile, 1, 1))
         got = obs.cpu().numpy()
         np.testing.assert_array_equal(got[..., :4], ref[..., :4], err_msg=f"call {k} static + device column")
-        # the custom columns: f32 of an f64 formula evaluated by torch instead of CPython
-        np.testing.assert_allclose(got[..., 4:], ref[..., 4:], rtol=1e-6, atol=1e-9, err_msg=f"call {k}")
+        # the custom columns: both formulas are exact-class (tests/device_array_cases.py) and both casts
+        # to f32 round to nearest even, so the reference's bits
+        np.testing.assert_array_equal(got[..., 4:], ref[..., 4:], err_msg=f"call {k}")
     env.close()
 
 
