@@ -397,6 +397,13 @@ class BatchedTradingEnv(_VectorEnvBase):
                                           self._t["obs"].device)
             self._obs_views = None
 
+    def _stepped(self):
+        """After a reset or a launch that stepped the envs (step, rollout, backtest): what was read of
+        the state before is stale, and a sliding window has moved."""
+        self._epoch += 1
+        if self._obs_views is not None:
+            self._follow_head()
+
     def _leave_sliding(self):
         """Back to a contiguous [N, W, F_obs] observation buffer for good: the current window is
         copied once and bound the classic way (a HIP graph reads `_t["obs"]` at capture time and
@@ -943,9 +950,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         c, cp = arr(inject_dataset, np.int32)
         _abi.check(self._lib, self._lib.gte_reset(self._h, mp, ap, bp, cp))
         self._was_reset = True
-        self._epoch += 1
-        if self._obs_views is not None:
-            self._follow_head()
+        self._stepped()
         self._apply_callables(after_reset=True)
         return self._results()[0], LazyInfo(self)
 
@@ -1042,9 +1047,7 @@ class BatchedTradingEnv(_VectorEnvBase):
             _abi.check(self._lib, self._lib.gte_step(self._h, C.c_void_p(actions.data_ptr()), 1))
         else:
             _abi.check(self._lib, self._lib.gte_step(self._h, a.ctypes.data, 0))
-        self._epoch += 1
-        if self._obs_views is not None:
-            self._follow_head()
+        self._stepped()
 
     def capture_steps(self, body, n_steps: int):
         """Record `body(i)` for i in range(n_steps) — each call taking ONE `step()` with a CUDA
@@ -1155,9 +1158,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._keep = (actions, out)  # alive until the launch has consumed them
         _abi.check(self._lib, self._lib.gte_rollout(self._h, C.c_void_p(actions.data_ptr()), K,
                                                     C.byref(b)))
-        self._epoch += 1
-        if self._obs_views is not None:
-            self._follow_head()
+        self._stepped()
         if not keep_obs:
             out["obs"] = self._t["obs"]
         return out
@@ -1182,9 +1183,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._keep = (actions,)  # alive until the launch has consumed them
         _abi.check(self._lib, self._lib.gte_backtest(self._h, C.c_void_p(actions.data_ptr()),
                                                      int(actions.shape[0]), 0 if resume else 1, C.byref(ptr)))
-        self._epoch += 1
-        if self._obs_views is not None:
-            self._follow_head()
+        self._stepped()
         self._backtest_map = None  # (no strategies: by_strategy() needs its arguments)
         return BacktestStats(self, ptr.value)
 
@@ -1291,80 +1290,23 @@ class BatchedTradingEnv(_VectorEnvBase):
         torch = self._torch
         if torch is None:
             raise ValueError("build_signals needs output='torch'")
-        from . import signals as sig
-        D = len(self.datasets)
-        if dataset is None:
-            if D == 1 and not isinstance(indicators, (list, tuple)):
-                banks = {0: indicators}
-            elif isinstance(indicators, (list, tuple)) and len(indicators) == D:
-                banks = dict(enumerate(indicators))
-            else:
-                raise ValueError(f"expected a list of {D} indicator banks, one per dataset (or dataset=d)")
-        else:
-            if not 0 <= int(dataset) < D:
-                raise IndexError(f"dataset {dataset} out of range")
-            banks = {int(dataset): indicators}
+        from . import signal_device as sd, signals as sig
         dev = self._t["obs"].device
-        # the rules: 32 bytes each on the device
-        if isinstance(rules, torch.Tensor):
-            if not (rules.is_cuda and rules.dim() == 2 and rules.is_contiguous() and
-                    (rules.dtype, int(rules.shape[1])) in ((torch.uint8, 32), (torch.int32, 8))):
-                raise TypeError("rules: a RULE_DTYPE array, or a contiguous CUDA tensor uint8 [S, 32] / int32 [S, 8]")
-            d_rules, host_rules = rules.to(dev), None
-        else:
-            host_rules = np.ascontiguousarray(rules)
-            if host_rules.dtype != sig.RULE_DTYPE or host_rules.ndim != 1:
-                raise TypeError("rules: a one-dimensional array of signals.RULE_DTYPE (signals.rules)")
-            d_rules = torch.from_numpy(host_rules.view(np.uint8).reshape(-1, sig.RULE_DTYPE.itemsize)).to(dev)
-        S = int(d_rules.shape[0])
-        if S < 1:
-            raise ValueError("build_signals needs at least one rule")
-        d_banks = {}
+        banks, wants_list = sd.per_dataset(indicators, len(self.datasets), dataset, "indicator banks")
+        d_rules, host_rules = sd.records(rules, sig.RULE_DTYPE, "RULE_DTYPE", ((torch.uint8, 32), (torch.int32, 8)),
+                                         dev, "rules")
         for d, x in banks.items():
-            T = self.datasets[d].T
-            if isinstance(x, torch.Tensor) and x.is_cuda:
-                if x.dim() != 2 or x.dtype != torch.float32:
-                    raise TypeError("an indicator bank is a two-dimensional float32 tensor")
-                x = x.to(dev)
-                if not (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= sig.bank_stride(T)
-                        and x.data_ptr() % 16 == 0):
-                    with torch.cuda.device(dev):
-                        buf = torch.zeros((int(x.shape[0]), sig.bank_stride(int(x.shape[1]))), dtype=torch.float32,
-                                          device=dev)
-                    buf[:, :x.shape[1]] = x
-                    x = buf[:, :x.shape[1]]
-            else:
-                host = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x)
-                x = torch.from_numpy(sig.pad_bank(host)).to(dev)[:, :host.shape[-1]]
-            if int(x.shape[1]) != T:
-                raise ValueError(f"indicator bank of dataset {d} has {int(x.shape[1])} columns, the dataset {T} rows")
-            n_ind = int(x.shape[0])
-            if n_ind < 1:
-                raise ValueError("an indicator bank needs at least one row")
-            if host_rules is not None and ((host_rules["a"] < 0) | (host_rules["a"] >= n_ind) |
-                                           (host_rules["b"] < -1) | (host_rules["b"] >= n_ind)).any():
-                raise IndexError(f"rules name indicators outside the {n_ind} rows of dataset {d}'s bank "
-                                 "(a in [0, C), b in [-1, C))")
-            d_banks[d] = x
-        with torch.cuda.device(dev):
-            tables = {d: torch.empty((S, sig.row_stride(self.datasets[d].T)), dtype=torch.int8, device=dev)
-                      for d in d_banks}
-        if bind:
-            self._check_one_s(tables, tables)
-        torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
-        for d, x in d_banks.items():
-            buf = tables[d]
+            banks[d] = x = sd.bank_rows(x, self.datasets[d].T, dev, "indicator bank", d)
+            if host_rules is not None:
+                sig.check_rules(host_rules, int(x.shape[0]), d)
+
+        def launch(d, table):
+            x = banks[d]
             _abi.check(self._lib, self._lib.gte_build_signals(
                 self._h, d, C.c_void_p(x.data_ptr()), int(x.shape[0]), int(x.stride(0)),
-                C.c_void_p(d_rules.data_ptr()), S, C.c_void_p(buf.data_ptr()), int(buf.shape[1])))
-        self.synchronize()  # the tables are complete: for torch on any stream, and before the inputs go
-        out = {}
-        for d, buf in tables.items():
-            if bind:
-                self._bind_padded(d, buf)
-            out[d] = buf[:, :self.datasets[d].T]
-        return out[next(iter(out))] if (dataset is not None or not isinstance(indicators, (list, tuple))) \
-            else [out[d] for d in range(D)]
+                C.c_void_p(d_rules.data_ptr()), int(d_rules.shape[0]), C.c_void_p(table.data_ptr()),
+                int(table.shape[1])))
+        return sd.run_builder(self, banks, int(d_rules.shape[0]), torch.int8, sig.row_stride, launch, bind, wants_list)
 
     def compose_signals(self, clauses, specs, dataset=None, bind=True):
         """Compose signal tables ON THE DEVICE from clause rows (`gte_compose_signals`): one spec per
@@ -1387,83 +1329,23 @@ class BatchedTradingEnv(_VectorEnvBase):
         torch = self._torch
         if torch is None:
             raise ValueError("compose_signals needs output='torch'")
-        from . import signals as sig
-        D = len(self.datasets)
-        if dataset is None:
-            if D == 1 and not isinstance(clauses, (list, tuple)):
-                rows = {0: clauses}
-            elif isinstance(clauses, (list, tuple)) and len(clauses) == D:
-                rows = dict(enumerate(clauses))
-            else:
-                raise ValueError(f"expected a list of {D} clause tables, one per dataset (or dataset=d)")
-        else:
-            if not 0 <= int(dataset) < D:
-                raise IndexError(f"dataset {dataset} out of range")
-            rows = {int(dataset): clauses}
+        from . import signal_device as sd, signals as sig
         dev = self._t["obs"].device
-        # the specs: 128 bytes each on the device
-        if isinstance(specs, torch.Tensor):
-            if not (specs.is_cuda and specs.dim() == 2 and specs.is_contiguous() and
-                    (specs.dtype, int(specs.shape[1])) == (torch.uint8, sig.COMPOSE_DTYPE.itemsize)):
-                raise TypeError("specs: a COMPOSE_DTYPE array, or a contiguous CUDA tensor uint8 [S, 128]")
-            d_specs, host_specs = specs.to(dev), None
-        else:
-            host_specs = np.ascontiguousarray(specs)
-            if host_specs.dtype != sig.COMPOSE_DTYPE or host_specs.ndim != 1:
-                raise TypeError("specs: a one-dimensional array of signals.COMPOSE_DTYPE (signals.compose)")
-            d_specs = torch.from_numpy(host_specs.view(np.uint8).reshape(-1, sig.COMPOSE_DTYPE.itemsize).copy()).to(dev)
-        S = int(d_specs.shape[0])
-        if S < 1:
-            raise ValueError("compose_signals needs at least one spec")
-        d_rows = {}
+        rows, wants_list = sd.per_dataset(clauses, len(self.datasets), dataset, "clause tables")
+        d_specs, host_specs = sd.records(specs, sig.COMPOSE_DTYPE, "COMPOSE_DTYPE", ((torch.uint8, 128),),
+                                         dev, "specs")
         for d, x in rows.items():
-            T = self.datasets[d].T
-            if isinstance(x, torch.Tensor) and x.is_cuda:
-                if x.dim() != 2 or x.dtype != torch.int8:
-                    raise TypeError("a clause table is a two-dimensional int8 tensor")
-                x = x.to(dev)
-                if not (x.stride(1) == 1 and x.stride(0) % sig.PIECE == 0 and x.stride(0) >= sig.row_stride(T)
-                        and x.data_ptr() % sig.PIECE == 0):
-                    with torch.cuda.device(dev):
-                        buf = torch.full((int(x.shape[0]), sig.row_stride(int(x.shape[1]))), -1, dtype=torch.int8,
-                                         device=dev)
-                    buf[:, :x.shape[1]] = x
-                    x = buf[:, :x.shape[1]]
-            else:
-                host = sig.as_int8_table(x.numpy() if isinstance(x, torch.Tensor) else x)
-                x = torch.from_numpy(sig.pad_rows(host)).to(dev)[:, :host.shape[1]]
-            if int(x.shape[1]) != T:
-                raise ValueError(f"clause table of dataset {d} has {int(x.shape[1])} columns, the dataset {T} rows")
-            R = int(x.shape[0])
-            if R < 1:
-                raise ValueError("a clause table needs at least one row")
+            rows[d] = x = sd.table_rows(x, self.datasets[d].T, dev, "clause table", d)
             if host_specs is not None:
-                n_in = host_specs["n_in"].astype(np.int64)
-                if ((n_in < 1) | (n_in > 4)).any():
-                    raise ValueError("specs hold an n_in outside [1, 4]")
-                used = np.arange(4)[None, :] < n_in[:, None]
-                if (used & ((host_specs["in"] < 0) | (host_specs["in"] >= R))).any():
-                    raise IndexError(f"specs name clause rows outside the {R} rows of dataset {d}'s clause table")
-            d_rows[d] = x
-        with torch.cuda.device(dev):
-            tables = {d: torch.empty((S, sig.row_stride(self.datasets[d].T)), dtype=torch.int8, device=dev)
-                      for d in d_rows}
-        if bind:
-            self._check_one_s(tables, tables)
-        torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
-        for d, x in d_rows.items():
-            buf = tables[d]
+                sig.check_compose(host_specs, int(x.shape[0]), d)
+
+        def launch(d, table):
+            x = rows[d]
             _abi.check(self._lib, self._lib.gte_compose_signals(
                 self._h, d, C.c_void_p(x.data_ptr()), int(x.shape[0]), int(x.stride(0)),
-                C.c_void_p(d_specs.data_ptr()), S, C.c_void_p(buf.data_ptr()), int(buf.shape[1])))
-        self.synchronize()  # the tables are complete: for torch on any stream, and before the inputs go
-        out = {}
-        for d, buf in tables.items():
-            if bind:
-                self._bind_padded(d, buf)
-            out[d] = buf[:, :self.datasets[d].T]
-        return out[next(iter(out))] if (dataset is not None or not isinstance(clauses, (list, tuple))) \
-            else [out[d] for d in range(D)]
+                C.c_void_p(d_specs.data_ptr()), int(d_specs.shape[0]), C.c_void_p(table.data_ptr()),
+                int(table.shape[1])))
+        return sd.run_builder(self, rows, int(d_specs.shape[0]), torch.int8, sig.row_stride, launch, bind, wants_list)
 
     def build_indicators(self, specs, dataset=None, inputs=None):
         """Build indicator banks ON THE DEVICE from the resident market data (`gte_build_indicators`):
@@ -1484,91 +1366,29 @@ class BatchedTradingEnv(_VectorEnvBase):
         torch = self._torch
         if torch is None:
             raise ValueError("build_indicators needs output='torch'")
-        from . import signals as sig
-        D = len(self.datasets)
-        if dataset is None:
-            which = list(range(D))
-        else:
-            if not 0 <= int(dataset) < D:
-                raise IndexError(f"dataset {dataset} out of range")
-            which = [int(dataset)]
-        if inputs is None:
-            banks = {d: None for d in which}
-        elif isinstance(inputs, (list, tuple)) and dataset is None and D > 1:
-            if len(inputs) != D:
-                raise ValueError(f"expected a list of {D} input banks, one per dataset (or dataset=d)")
-            banks = dict(enumerate(inputs))
-        elif len(which) == 1:
-            banks = {which[0]: inputs}
-        else:
-            raise ValueError(f"expected a list of {D} input banks, one per dataset (or dataset=d)")
+        from . import signal_device as sd, signals as sig
         dev = self._t["obs"].device
-        if isinstance(specs, torch.Tensor):
-            if not (specs.is_cuda and specs.dim() == 2 and specs.is_contiguous() and
-                    (specs.dtype, int(specs.shape[1])) in ((torch.uint8, 16), (torch.int32, 4))):
-                raise TypeError("specs: an INDICATOR_DTYPE array, or a contiguous CUDA tensor uint8 [C, 16] / "
-                                "int32 [C, 4]")
-            d_specs, host = specs.to(dev), None
-        else:
-            host = np.ascontiguousarray(specs)
-            if host.dtype != sig.INDICATOR_DTYPE or host.ndim != 1:
-                raise TypeError("specs: a one-dimensional array of signals.INDICATOR_DTYPE (signals.indicators)")
-            d_specs = torch.from_numpy(host.view(np.uint8).reshape(-1, sig.INDICATOR_DTYPE.itemsize).copy()).to(dev)
-        n_specs = int(d_specs.shape[0])
-        if n_specs < 1:
-            raise ValueError("build_indicators needs at least one spec")
-        d_in = {}
+        D = len(self.datasets)
+        # (the only dataset needs no list: a list is then one input bank, as nested rows)
+        banks, wants_list = sd.per_dataset(inputs, D, 0 if D == 1 and dataset is None else dataset, "input banks",
+                                           optional=True)
+        d_specs, host_specs = sd.records(specs, sig.INDICATOR_DTYPE, "INDICATOR_DTYPE",
+                                         ((torch.uint8, 16), (torch.int32, 4)), dev, "specs")
         for d, x in banks.items():
-            T = self.datasets[d].T
-            if x is None:
-                d_in[d] = None
-            elif isinstance(x, torch.Tensor) and x.is_cuda:
-                if x.dim() != 2 or x.dtype != torch.float32:
-                    raise TypeError("an input bank is a two-dimensional float32 tensor")
-                x = x.to(dev)
-                if not (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= sig.bank_stride(T)
-                        and x.data_ptr() % 16 == 0):
-                    with torch.cuda.device(dev):
-                        buf = torch.zeros((int(x.shape[0]), sig.bank_stride(int(x.shape[1]))), dtype=torch.float32,
-                                          device=dev)
-                    buf[:, :x.shape[1]] = x
-                    x = buf[:, :x.shape[1]]
-                d_in[d] = x
-            else:
-                a = np.asarray(x.numpy() if isinstance(x, torch.Tensor) else x)
-                d_in[d] = torch.from_numpy(sig.pad_bank(a)).to(dev)[:, :a.shape[-1]]
-            x = d_in[d]
-            if x is not None and (int(x.shape[1]) != T or int(x.shape[0]) < 1):
-                raise ValueError(f"input bank of dataset {d} has {int(x.shape[1])} columns, the dataset {T} rows")
-            if host is not None:
-                n_in = 0 if x is None else int(x.shape[0])
-                kind, src, col, n = host["kind"], host["source"], host["column"], host["n"]
-                if ((kind < 0) | (kind >= len(sig.IND_KINDS)) | (src < 0) | (src >= len(sig.IND_SOURCES))).any():
-                    raise ValueError("specs hold an unknown kind or source")
-                if ((kind != sig.IND_VALUE) & ((n < 1) | (n > sig.IND_MAX_WINDOW))).any():
-                    raise ValueError(f"specs hold a window outside [1, {sig.IND_MAX_WINDOW}]")
-                n_static = self.datasets[d].n_static
-                if ((src == sig.SRC_FEATURE) & ((col < 0) | (col >= n_static))).any():
-                    raise ValueError(f"specs name feature columns outside the {n_static} static ones")
-                if ((src == sig.SRC_INPUT) & ((col < 0) | (col >= n_in))).any():
-                    raise ValueError(f"specs name input rows outside the {n_in} rows of dataset {d}'s input bank")
-                ds = self.datasets[d]
-                for name, code in (("high", sig.SRC_HIGH), ("low", sig.SRC_LOW)):
-                    if (src == code).any() and getattr(ds, name, None) is None:
-                        raise ValueError(f"specs read {name}, which dataset {d} does not have")
-        with torch.cuda.device(dev):
-            out = {d: torch.empty((n_specs, sig.bank_stride(self.datasets[d].T)), dtype=torch.float32, device=dev)
-                   for d in which}
-        torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
-        for d in which:
-            x, buf = d_in[d], out[d]
+            ds = self.datasets[d]
+            if x is not None:
+                banks[d] = x = sd.bank_rows(x, ds.T, dev, "input bank", d)
+            if host_specs is not None:
+                sig.check_indicators(host_specs, ds.n_static, 0 if x is None else int(x.shape[0]),
+                                     getattr(ds, "high", None) is not None, getattr(ds, "low", None) is not None, d)
+
+        def launch(d, bank):
+            x = banks[d]
             _abi.check(self._lib, self._lib.gte_build_indicators(
-                self._h, d, C.c_void_p(d_specs.data_ptr()), n_specs,
+                self._h, d, C.c_void_p(d_specs.data_ptr()), int(d_specs.shape[0]),
                 C.c_void_p(x.data_ptr()) if x is not None else None, int(x.shape[0]) if x is not None else 0,
-                int(x.stride(0)) if x is not None else 0, C.c_void_p(buf.data_ptr()), int(buf.shape[1])))
-        self.synchronize()  # the banks are complete: for torch on any stream, and before the inputs go
-        views = [out[d][:, :self.datasets[d].T] for d in which]
-        return views[0] if (dataset is not None or D == 1) else views
+                int(x.stride(0)) if x is not None else 0, C.c_void_p(bank.data_ptr()), int(bank.shape[1])))
+        return sd.run_builder(self, banks, int(d_specs.shape[0]), torch.float32, sig.bank_stride, launch, False, wants_list)
 
     @property
     def num_strategies(self) -> int:
@@ -1633,9 +1453,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         _abi.check(self._lib, self._lib.gte_backtest_signals(
             self._h, None if strategy is None else C.c_void_p(strategy.data_ptr()), int(K),
             0 if resume else 1, C.byref(ptr)))
-        self._epoch += 1
-        if self._obs_views is not None:
-            self._follow_head()
+        self._stepped()
         # what this call ran with, for BacktestStats.by_strategy(): the map (None = the default one) and S
         self._backtest_map = (strategy, self.num_strategies)
         return BacktestStats(self, ptr.value)

@@ -1269,6 +1269,38 @@ int gte_backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t cl
   return backtest_entry(E, "gte_backtest", actions, nullptr, n_steps, clear, stats_device);
 }
 
+// ---- a per-dataset table of rows on the device: the checks gte_bind_signals and the builders share ----
+// A row holds T elements and is padded: the stride is a whole number of 16-byte pieces and at least T
+// rounded up to 16 elements, so that an aligned 16-byte access anywhere in a row stays inside it.
+static int64_t round_up_16(int64_t T) { return (T + 15) / 16 * 16; }
+
+// dataset d of a builder call -> its T: a builder runs outside a capture, on a dataset that was uploaded
+static int builder_dataset(gte_env* E, const char* who, int32_t d, int64_t* T) {
+  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "%s inside a stream capture", who);
+  *T = E->h_ds[d].T;
+  if (*T <= 0) return fail(GTE_ERR_STATE, "%s: dataset %d was never uploaded", who, d);
+  return GTE_OK;
+}
+
+// `stride`, in elements of `elem` bytes, of a table over the T rows of dataset d
+static int check_stride(const char* name, int64_t stride, size_t elem, int64_t T, int32_t d) {
+  const int64_t k = 16 / (int64_t)elem;
+  if (stride % k == 0 && stride >= round_up_16(T)) return GTE_OK;
+  return fail(GTE_ERR_INVALID, "%s %lld%s: a multiple of %lld and >= %lld (the %lld rows of dataset %d rounded up "
+              "to 16) required", name, (long long)stride, elem == sizeof(float) ? " floats" : "", (long long)k,
+              (long long)round_up_16(T), (long long)T, d);
+}
+
+// what a kernel touches of a table: T16 elements of each of its rows
+struct RowSpan { const void* base; int64_t rows, stride; size_t elem; };
+static bool spans_overlap(const RowSpan& r, const RowSpan& w, int64_t T16) {
+  const uintptr_t r0 = (uintptr_t)r.base, w0 = (uintptr_t)w.base;
+  const uintptr_t r1 = r0 + r.elem * (size_t)((r.rows - 1) * r.stride + T16);
+  const uintptr_t w1 = w0 + w.elem * (size_t)((w.rows - 1) * w.stride + T16);
+  return r0 < w1 && w0 < r1;
+}
+
 int gte_bind_signals(gte_env* E, int32_t d, const int8_t* signals_device, int32_t n_strategies,
                      int64_t row_stride) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
@@ -1279,10 +1311,7 @@ int gte_bind_signals(gte_env* E, int32_t d, const int8_t* signals_device, int32_
     const int64_t T = E->h_ds[d].T;
     if (T <= 0) return fail(GTE_ERR_STATE, "gte_bind_signals: dataset %d was never uploaded", d);
     if ((uintptr_t)signals_device & 15) return fail(GTE_ERR_INVALID, "signals must be 16-byte aligned");
-    if (row_stride % 16 != 0 || row_stride < (T + 15) / 16 * 16)
-      return fail(GTE_ERR_INVALID, "row_stride %lld: a multiple of 16 and >= %lld (the %lld rows of dataset %d "
-                  "rounded up to 16) required", (long long)row_stride, (long long)((T + 15) / 16 * 16),
-                  (long long)T, d);
+    TRY(check_stride("row_stride", row_stride, sizeof(int8_t), T, d));
     if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
     for (int o = 0; o < (int)E->h_sig.size(); ++o)
       if (o != d && E->h_sig[o].base && E->sig_S != n_strategies)
@@ -1333,21 +1362,14 @@ int gte_build_signals(gte_env* E, int32_t d, const float* indicators_device, int
                       int64_t ind_stride, const gte_signal_rule* rules_device, int32_t n_rules,
                       int8_t* table_device, int64_t row_stride) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_build_signals inside a stream capture");
-  const int64_t T = E->h_ds[d].T;
-  if (T <= 0) return fail(GTE_ERR_STATE, "gte_build_signals: dataset %d was never uploaded", d);
-  const int64_t T16 = (T + 15) / 16 * 16;
+  int64_t T;
+  TRY(builder_dataset(E, "gte_build_signals", d, &T));
   if (!indicators_device || !rules_device || !table_device) return fail(GTE_ERR_INVALID, "NULL argument");
   if (((uintptr_t)indicators_device & 15) || ((uintptr_t)table_device & 15))
     return fail(GTE_ERR_INVALID, "the indicator bank and the table must be 16-byte aligned");
   if ((uintptr_t)rules_device & 3) return fail(GTE_ERR_INVALID, "rules must be 4-byte aligned");
-  if (row_stride % 16 != 0 || row_stride < T16)
-    return fail(GTE_ERR_INVALID, "row_stride %lld: a multiple of 16 and >= %lld (the %lld rows of dataset %d "
-                "rounded up to 16) required", (long long)row_stride, (long long)T16, (long long)T, d);
-  if (ind_stride % 4 != 0 || ind_stride < T16)
-    return fail(GTE_ERR_INVALID, "ind_stride %lld floats: a multiple of 4 and >= %lld required",
-                (long long)ind_stride, (long long)T16);
+  TRY(check_stride("row_stride", row_stride, sizeof(int8_t), T, d));
+  TRY(check_stride("ind_stride", ind_stride, sizeof(float), T, d));
   if (n_indicators < 1) return fail(GTE_ERR_INVALID, "n_indicators must be >= 1");
   if (n_rules < 1) return fail(GTE_ERR_INVALID, "n_rules must be >= 1");
   HIPCHK(hipSetDevice(E->cfg.device));
@@ -1361,29 +1383,20 @@ int gte_compose_signals(gte_env* E, int32_t d, const int8_t* clauses_device, int
                         int64_t clause_stride, const gte_signal_compose* specs_device, int32_t n_specs,
                         int8_t* table_device, int64_t row_stride) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_compose_signals inside a stream capture");
-  const int64_t T = E->h_ds[d].T;
-  if (T <= 0) return fail(GTE_ERR_STATE, "gte_compose_signals: dataset %d was never uploaded", d);
-  const int64_t T16 = (T + 15) / 16 * 16;
+  int64_t T;
+  TRY(builder_dataset(E, "gte_compose_signals", d, &T));
   if (!clauses_device || !specs_device || !table_device) return fail(GTE_ERR_INVALID, "NULL argument");
   if (((uintptr_t)clauses_device & 15) || ((uintptr_t)table_device & 15))
     return fail(GTE_ERR_INVALID, "the clause table and the table must be 16-byte aligned");
   if ((uintptr_t)specs_device & 3) return fail(GTE_ERR_INVALID, "specs must be 4-byte aligned");
-  if (row_stride % 16 != 0 || row_stride < T16)
-    return fail(GTE_ERR_INVALID, "row_stride %lld: a multiple of 16 and >= %lld (the %lld rows of dataset %d "
-                "rounded up to 16) required", (long long)row_stride, (long long)T16, (long long)T, d);
-  if (clause_stride % 16 != 0 || clause_stride < T16)
-    return fail(GTE_ERR_INVALID, "clause_stride %lld: a multiple of 16 and >= %lld required",
-                (long long)clause_stride, (long long)T16);
+  TRY(check_stride("row_stride", row_stride, sizeof(int8_t), T, d));
+  TRY(check_stride("clause_stride", clause_stride, sizeof(int8_t), T, d));
   if (n_clause_rows < 1) return fail(GTE_ERR_INVALID, "n_clause_rows must be >= 1");
   if (n_specs < 1) return fail(GTE_ERR_INVALID, "n_specs must be >= 1");
-  {  // what the kernel may read of the clause table and what it writes of the table: disjoint
-    const uintptr_t in0 = (uintptr_t)clauses_device, out0 = (uintptr_t)table_device;
-    const uintptr_t in1 = in0 + (size_t)((int64_t)(n_clause_rows - 1) * clause_stride + T16);
-    const uintptr_t out1 = out0 + (size_t)((int64_t)(n_specs - 1) * row_stride + T16);
-    if (in0 < out1 && out0 < in1) return fail(GTE_ERR_INVALID, "the clause table and the table overlap");
-  }
+  // what the kernel may read of the clause table and what it writes of the table: disjoint
+  if (spans_overlap({clauses_device, n_clause_rows, clause_stride, sizeof(int8_t)},
+                    {table_device, n_specs, row_stride, sizeof(int8_t)}, round_up_16(T)))
+    return fail(GTE_ERR_INVALID, "the clause table and the table overlap");
   HIPCHK(hipSetDevice(E->cfg.device));
   const hipError_t e = gte::launch_compose_signals(clauses_device, n_clause_rows, clause_stride, specs_device, n_specs,
                                                    T, table_device, row_stride, E->stream);
@@ -1395,13 +1408,10 @@ int gte_build_indicators(gte_env* E, int32_t d, const gte_indicator_spec* specs_
                          const float* input_device, int32_t n_inputs, int64_t input_stride, float* bank_device,
                          int64_t ind_stride) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_build_indicators inside a stream capture");
-  const int64_t T = E->h_ds[d].T;
-  if (T <= 0) return fail(GTE_ERR_STATE, "gte_build_indicators: dataset %d was never uploaded", d);
+  int64_t T;
+  TRY(builder_dataset(E, "gte_build_indicators", d, &T));
   if (T > INT32_MAX - 2 * GTE_IND_MAX_WINDOW)  // (the kernel indexes rows with 32 bits, like EnvRec.idx)
     return fail(GTE_ERR_INVALID, "gte_build_indicators: dataset %d has too many rows", d);
-  const int64_t T16 = (T + 15) / 16 * 16;
   if (!specs_device || !bank_device) return fail(GTE_ERR_INVALID, "NULL argument");
   if (n_inputs < 0) return fail(GTE_ERR_INVALID, "n_inputs must be >= 0");
   if ((input_device != nullptr) != (n_inputs > 0))
@@ -1409,19 +1419,13 @@ int gte_build_indicators(gte_env* E, int32_t d, const gte_indicator_spec* specs_
   if (((uintptr_t)bank_device & 15) || ((uintptr_t)input_device & 15))
     return fail(GTE_ERR_INVALID, "the indicator bank and the input bank must be 16-byte aligned");
   if ((uintptr_t)specs_device & 3) return fail(GTE_ERR_INVALID, "specs must be 4-byte aligned");
-  if (ind_stride % 4 != 0 || ind_stride < T16)
-    return fail(GTE_ERR_INVALID, "ind_stride %lld floats: a multiple of 4 and >= %lld (the %lld rows of dataset %d "
-                "rounded up to 16) required", (long long)ind_stride, (long long)T16, (long long)T, d);
-  if (n_inputs > 0 && (input_stride % 4 != 0 || input_stride < T16))
-    return fail(GTE_ERR_INVALID, "input_stride %lld floats: a multiple of 4 and >= %lld required",
-                (long long)input_stride, (long long)T16);
+  TRY(check_stride("ind_stride", ind_stride, sizeof(float), T, d));
+  if (n_inputs > 0) TRY(check_stride("input_stride", input_stride, sizeof(float), T, d));
   if (n_specs < 1) return fail(GTE_ERR_INVALID, "n_specs must be >= 1");
-  if (n_inputs > 0) {  // what the kernel reads of the input and what it writes of the bank: disjoint
-    const uintptr_t in0 = (uintptr_t)input_device, out0 = (uintptr_t)bank_device;
-    const uintptr_t in1 = in0 + sizeof(float) * (size_t)((int64_t)(n_inputs - 1) * input_stride + T16);
-    const uintptr_t out1 = out0 + sizeof(float) * (size_t)((int64_t)(n_specs - 1) * ind_stride + T16);
-    if (in0 < out1 && out0 < in1) return fail(GTE_ERR_INVALID, "the input bank and the indicator bank overlap");
-  }
+  // what the kernel reads of the input and what it writes of the bank: disjoint
+  if (n_inputs > 0 && spans_overlap({input_device, n_inputs, input_stride, sizeof(float)},
+                                    {bank_device, n_specs, ind_stride, sizeof(float)}, round_up_16(T)))
+    return fail(GTE_ERR_INVALID, "the input bank and the indicator bank overlap");
   HIPCHK(hipSetDevice(E->cfg.device));
   const hipError_t e = gte::launch_build_indicators(E->h_ds[d], E->p.Fobs, E->p.Fobs - E->p.nd, specs_device, n_specs,
                                                     input_device, n_inputs, input_stride, bank_device, ind_stride,

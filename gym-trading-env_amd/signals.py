@@ -77,6 +77,15 @@ def rules(a, b=-1, hi=0.0, lo=0.0, warmup=0, pos_up=1, pos_down=0, pos_neutral=-
     return out
 
 
+def check_rules(rules: np.ndarray, n_indicators: int, d: int) -> None:
+    """`RULE_DTYPE` records against the bank of dataset d they read: `a` names one of its rows, `b` one
+    or none (-1)."""
+    C = int(n_indicators)
+    if ((rules["a"] < 0) | (rules["a"] >= C) | (rules["b"] < -1) | (rules["b"] >= C)).any():
+        raise IndexError(f"rules name indicators outside the {C} rows of dataset {d}'s bank "
+                         "(a in [0, C), b in [-1, C))")
+
+
 # ---- signal tables composed on the device from clause rows and a truth table (gte_compose_signals) ----
 
 from ._abi import COMPOSE_DTYPE as _COMPOSE_FIELDS  # noqa: E402
@@ -150,6 +159,18 @@ def compose(inputs, lut, initial=-1, invalid=-1) -> np.ndarray:
     flat = small.transpose((0,) + tuple(range(n, 0, -1))).reshape(small.shape[0], 3 ** n)
     out["lut"] = np.broadcast_to(np.tile(flat, (1, 81 // 3 ** n)), (S, 81))
     return out
+
+
+def check_compose(specs: np.ndarray, n_clause_rows: int, d: int) -> None:
+    """`COMPOSE_DTYPE` records against the clause table of dataset d they read: one to four inputs,
+    each of those one of its rows."""
+    R = int(n_clause_rows)
+    n_in = specs["n_in"].astype(np.int64)
+    if ((n_in < 1) | (n_in > 4)).any():
+        raise ValueError("specs hold an n_in outside [1, 4]")
+    used = np.arange(4)[None, :] < n_in[:, None]
+    if (used & ((specs["in"] < 0) | (specs["in"] >= R))).any():
+        raise IndexError(f"specs name clause rows outside the {R} rows of dataset {d}'s clause table")
 
 
 def bank_stride(T: int) -> int:
@@ -243,3 +264,21 @@ def indicators(kind, n=1, source="close", column=0) -> np.ndarray:
     for name, v in full.items():
         out[name] = v
     return out
+
+
+def check_indicators(specs: np.ndarray, n_static: int, n_inputs: int, has_high: bool, has_low: bool, d: int) -> None:
+    """`INDICATOR_DTYPE` records against what dataset d can serve: known kinds and sources, windows in
+    range, feature columns among its `n_static` static ones, input rows among the `n_inputs` of its
+    input bank, and high / low only where the dataset has them."""
+    kind, src, col, n = specs["kind"], specs["source"], specs["column"], specs["n"]
+    if ((kind < 0) | (kind >= len(IND_KINDS)) | (src < 0) | (src >= len(IND_SOURCES))).any():
+        raise ValueError("specs hold an unknown kind or source")
+    if ((kind != IND_VALUE) & ((n < 1) | (n > IND_MAX_WINDOW))).any():
+        raise ValueError(f"specs hold a window outside [1, {IND_MAX_WINDOW}]")
+    if ((src == SRC_FEATURE) & ((col < 0) | (col >= n_static))).any():
+        raise ValueError(f"specs name feature columns outside the {n_static} static ones")
+    if ((src == SRC_INPUT) & ((col < 0) | (col >= n_inputs))).any():
+        raise ValueError(f"specs name input rows outside the {n_inputs} rows of dataset {d}'s input bank")
+    for name, code, has in (("high", SRC_HIGH, has_high), ("low", SRC_LOW, has_low)):
+        if (src == code).any() and not has:
+            raise ValueError(f"specs read {name}, which dataset {d} does not have")
