@@ -175,6 +175,34 @@ COMPOSE_DTYPE = COMPOSE_FIELDS
 #: GTE_COMPOSE_KEEP
 COMPOSE_KEEP = -128
 
+#: struct gte_exit_rule (include/gte.h), in declaration order: 32 bytes per exit rule
+EXIT_RULE_FIELDS = [("stop_loss", "<f4"), ("take_profit", "<f4"), ("trailing", "<f4"), ("max_hold", "<i4"),
+                    ("exit_position", "i1"), ("reserved0", "i1", (3,)), ("reserved", "<i4", (3,))]
+#: numpy view of an array of gte_exit_rule (gte_bind_exit_rules)
+EXIT_RULE_DTYPE = EXIT_RULE_FIELDS
+#: struct gte_exit_state (include/gte.h), in declaration order: 80 bytes per env
+EXIT_STATE_FIELDS = [("entry", "<f8"), ("peak", "<f8"), ("v_seen", "<f8")] + \
+    [(n, "<i4") for n in ("held", "latched", "latched_raw", "i_seen", "episode_seen", "step_seen", "decided",
+                          "decided_action")]
+#: numpy view of an array of gte_exit_state (gte_read_exit_state)
+EXIT_STATE_DTYPE = EXIT_STATE_FIELDS + [("reserved", "<i4", (2,)), ("exits", "<i4", (4,))]
+#: index of each exit kind in gte_exit_state.exits (GTE_EXIT_*)
+EXIT_KINDS = ("stop", "trail", "target", "time")
+
+
+class GteExitRule(C.Structure):
+    """struct gte_exit_rule (include/gte.h)."""
+    _fields_ = [("stop_loss", C.c_float), ("take_profit", C.c_float), ("trailing", C.c_float),
+                ("max_hold", C.c_int32), ("exit_position", C.c_int8), ("reserved0", C.c_int8 * 3),
+                ("reserved", C.c_int32 * 3)]
+
+
+class GteExitState(C.Structure):
+    """struct gte_exit_state (include/gte.h)."""
+    _fields_ = [(n, {"<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in EXIT_STATE_FIELDS] + \
+               [("reserved", C.c_int32 * 2), ("exits", C.c_int32 * 4)]
+
+
 #: enum gte_indicator_kind / gte_indicator_source and GTE_IND_MAX_WINDOW (include/gte.h)
 IND_KINDS = ("value", "sma", "std", "zscore", "max", "min", "diff", "roc", "ema", "rsi")
 IND_SOURCES = ("close", "high", "low", "feature", "input")
@@ -311,6 +339,8 @@ SYMBOLS = {
     "gte_bind_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64]),
     "gte_signal_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_backtest_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
+    "gte_bind_exit_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, _P(C.c_void_p)]),
+    "gte_read_exit_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
     "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,

@@ -245,6 +245,8 @@ class BatchedTradingEnv(_VectorEnvBase):
                                             shape=(self.num_envs,) + self.obs_shape)
         self._signals = {}  # dataset -> the padded int8 [S, stride] device tensor bound to it (bind_signals)
         self._backtest_map = None  # (strategy tensor or None, S) of the last backtest_signals(); None after backtest()
+        self._exits = None  # (rules tensor, rule_of_env tensor or None) bound by bind_exits, kept alive
+        self._exit_state_ptr = 0  # device address of the exit states (0 before the first bind_exits)
         for d, s in enumerate(self.datasets):
             self.upload_dataset(d, s)
 
@@ -1457,6 +1459,70 @@ class BatchedTradingEnv(_VectorEnvBase):
         # what this call ran with, for BacktestStats.by_strategy(): the map (None = the default one) and S
         self._backtest_map = (strategy, self.num_strategies)
         return BacktestStats(self, ptr.value)
+
+    # -- exit rules: stop-loss, trailing stop, take-profit and time exits per strategy --------
+    def bind_exits(self, rules, rule_of_env=None):
+        """Bind exit rules (`gte_bind_exit_rules`): while they are bound, `signal_actions()` and
+        `backtest_signals()` let every env leave for its rule's `exit_position` when its OWN path
+        trips a stop-loss, a trailing stop, a take-profit or a time limit, and hold until the signal
+        moves; otherwise the table decides as before (the rule is stated in include/gte.h).  The fused
+        backtest keeps each env's exit state in registers through all its steps.
+
+        rules: an `EXIT_DTYPE` array [R] (`signals.exit_rules`), whose `exit_position` is checked
+        against `positions` here, or a CUDA tensor uint8 [R, 32] / int32 [R, 8] of the same bytes,
+        which is the caller's contract: a rule whose exit_position names no position is off.
+        rule_of_env: int32 [N] with values in [0, R) — a host array is checked, a CUDA tensor is the
+        caller's contract — or None: env e follows rule ``strategy_of(e) % R``.  Every call starts
+        the exit state afresh (the next decision sees a reset row).  ``rules=None`` unbinds."""
+        torch = self._torch
+        if torch is None:
+            raise ValueError("bind_exits needs output='torch'")
+        ptr = C.c_void_p()
+        if rules is None:
+            if rule_of_env is not None:
+                raise ValueError("rule_of_env without rules")
+            _abi.check(self._lib, self._lib.gte_bind_exit_rules(self._h, None, 0, None, C.byref(ptr)))
+            self._exits = None
+            return
+        from . import signal_device as sd, signals as sig
+        dev = self._t["obs"].device
+        d_rules, host = sd.records(rules, sig.EXIT_DTYPE, "EXIT_DTYPE", ((torch.uint8, 32), (torch.int32, 8)),
+                                   dev, "rules")
+        if host is not None:
+            sig.check_exit_rules(host, len(self.positions))
+        R = int(d_rules.shape[0])
+        d_map = None
+        if rule_of_env is not None:
+            if isinstance(rule_of_env, torch.Tensor) and rule_of_env.is_cuda:
+                d_map = rule_of_env.to(device=dev, dtype=torch.int32).contiguous()
+            else:
+                a = np.asarray(rule_of_env.numpy() if isinstance(rule_of_env, torch.Tensor) else rule_of_env)
+                if a.dtype.kind not in "iu":
+                    raise TypeError("rule_of_env must be integers")
+                if a.size and (a.min() < 0 or a.max() >= R):
+                    raise IndexError(f"rule_of_env outside [0, {R})")
+                d_map = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(dev)
+            if tuple(d_map.shape) != (self.num_envs,):
+                raise ValueError(f"expected rule_of_env of shape ({self.num_envs},)")
+        torch.cuda.current_stream(dev).synchronize()  # the copies above: the env may launch on another stream
+        _abi.check(self._lib, self._lib.gte_bind_exit_rules(
+            self._h, C.c_void_p(d_rules.data_ptr()), R, None if d_map is None else C.c_void_p(d_map.data_ptr()),
+            C.byref(ptr)))
+        self._exits = (d_rules, d_map)
+        self._exit_state_ptr = int(ptr.value or 0)
+
+    @property
+    def num_exit_rules(self) -> int:
+        """R of the bound exit rules (0: none bound)."""
+        return int(self._exits[0].shape[0]) if self._exits else 0
+
+    def exit_state(self):
+        """The per-env exit state (`gte_exit_state`, include/gte.h) as an `ExitState` of device views;
+        needs a `bind_exits` before it."""
+        from .exit_state import ExitState
+        if not self._exit_state_ptr:
+            raise ValueError("exit_state() before bind_exits(): the env has no exit state yet")
+        return ExitState(self, self._exit_state_ptr)
 
     # -- misc ---------------------------------------------------------------------------
     def synchronize(self):

@@ -126,6 +126,9 @@ struct gte_env {
   gte::SignalTable* d_sig = nullptr;
   int32_t sig_S = 0;  // strategies of every bound table (0 = none bound)
   int32_t* d_sig_actions = nullptr;
+  // exit rules (gte_bind_exit_rules): the caller's rules and map (rules null = none bound) and the per-env
+  // state, allocated by the first bind
+  gte::ExitRules exits = {nullptr, nullptr, nullptr, 0};
   // gte_rank_strategies: the two candidate lists (gte_strategy.hip), allocated by the first call and
   // again when S outgrows them (the old ones stay until gte_destroy: launches in flight may read them)
   double* rank_score[2] = {nullptr, nullptr};
@@ -1196,6 +1199,13 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
 // folded into the statistics records
 // With actions == NULL (gte_backtest_signals) each step's actions are looked up in the bound signal tables
 // for `strategy` instead.
+// the lookup of gte_signal_actions, with the exits decided as well while rules are bound
+static hipError_t launch_lookup(gte_env* E, const int32_t* strategy, int32_t* actions) {
+  if (E->exits.rules)
+    return gte::launch_exit_actions(E->p, E->d_sig, E->sig_S, strategy, E->exits, actions, E->stream);
+  return gte::launch_signal_actions(E->p, E->d_sig, E->sig_S, strategy, actions, E->stream);
+}
+
 static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy, int32_t n_steps, int32_t clear) {
   const size_t N = (size_t)E->p.N;
   const LaunchPlan& L = E->plan;
@@ -1221,8 +1231,7 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   // its results into the records
   auto step_and_fold = [&](int32_t k) -> int {
     if (signals) {
-      const hipError_t se = gte::launch_signal_actions(E->p, E->d_sig, E->sig_S, strategy, E->d_sig_actions,
-                                                       E->stream);
+      const hipError_t se = launch_lookup(E, strategy, E->d_sig_actions);
       if (se != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(se));
     }
     const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
@@ -1240,8 +1249,11 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   else report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
   if (n_steps > 1) {
     TRY(age_order(E, n_steps - 1));
-    le = signals ? gte::launch_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, n_steps - 1,
-                                              L.state_epw, E->stream)
+    le = signals && E->exits.rules
+             ? gte::launch_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, n_steps - 1,
+                                        L.state_epw, E->stream)
+         : signals ? gte::launch_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, n_steps - 1,
+                                                L.state_epw, E->stream)
                  : gte::launch_backtest_summary(ps, actions, E->bt_stats, n_steps - 1, L.state_epw, E->stream);
     if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   }
@@ -1345,8 +1357,7 @@ int gte_signal_actions(gte_env* E, const int32_t* strategy_device, int32_t* acti
   if (!actions_device) return fail(GTE_ERR_INVALID, "actions is NULL");
   TRY(signals_ready(E, "gte_signal_actions"));
   if (!stream_capturing(E)) HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::launch_signal_actions(E->p, E->d_sig, E->sig_S, strategy_device, actions_device,
-                                                  E->stream);
+  const hipError_t e = launch_lookup(E, strategy_device, actions_device);
   if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal lookup launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
@@ -1356,6 +1367,41 @@ int gte_backtest_signals(gte_env* E, const int32_t* strategy_device, int32_t n_s
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   TRY(signals_ready(E, "gte_backtest_signals"));
   return backtest_entry(E, "gte_backtest_signals", nullptr, strategy_device, n_steps, clear, stats_device);
+}
+
+int gte_bind_exit_rules(gte_env* E, const gte_exit_rule* rules_device, int32_t n_rules,
+                        const int32_t* rule_of_env_device, gte_exit_state** state_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bind_exit_rules inside a stream capture");
+  if (rules_device) {
+    if ((uintptr_t)rules_device & 3) return fail(GTE_ERR_INVALID, "exit rules must be 4-byte aligned");
+    if ((uintptr_t)rule_of_env_device & 3) return fail(GTE_ERR_INVALID, "rule_of_env must be 4-byte aligned");
+    if (n_rules < 1) return fail(GTE_ERR_INVALID, "n_rules must be >= 1");
+  }
+  HIPCHK(hipSetDevice(E->cfg.device));
+  if (rules_device && !E->exits.state) TRY(dev_alloc_late(E, &E->exits.state, (size_t)E->p.N));
+  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight read the rules and the state
+  if (E->exits.state) {
+    const hipError_t e = gte::launch_exit_init(E->exits.state, E->p.N, E->stream);
+    if (e != hipSuccess) return fail(GTE_ERR_HIP, "exit state launch: %s", hipGetErrorString(e));
+  }
+  E->exits.rules = rules_device;
+  E->exits.rule_of_env = rules_device ? rule_of_env_device : nullptr;
+  E->exits.n_rules = rules_device ? n_rules : 0;
+  if (state_device) *state_device = E->exits.state;
+  return GTE_OK;
+}
+
+int gte_read_exit_state(gte_env* E, int32_t first, int32_t count, gte_exit_state* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (!E->exits.state) return fail(GTE_ERR_STATE, "gte_read_exit_state before gte_bind_exit_rules");
+  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
+    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(hipStreamSynchronize(E->stream));
+  if (count > 0)
+    HIPCHK(hipMemcpy(out, E->exits.state + first, sizeof(gte_exit_state) * (size_t)count, hipMemcpyDeviceToHost));
+  return GTE_OK;
 }
 
 int gte_build_signals(gte_env* E, int32_t d, const float* indicators_device, int32_t n_indicators,

@@ -1,0 +1,281 @@
+// gte_exits.hip — exit rules (gte_bind_exit_rules, include/gte.h): stop-loss, trailing stop, take-profit
+// and time exits decided from the env's own path, next to the signal-table lookup.  Own translation
+// unit: nothing here can perturb the code generated for the kernels of gte_backtest.hip.
+//
+//   gte_backtest_exit_kernel    gte_backtest_signal_kernel (same geometry, same piece-in-registers lookup,
+//                               same record handling) with the env's exit state in registers as well: the
+//                               state is loaded once and stored once per launch, the rule is loaded once,
+//                               and a step issues no memory request the signal kernel does not issue.
+//   gte_exit_actions_kernel     gte_signal_actions_kernel with rules bound: brings the state up to date
+//                               from the env record, decides, and keeps the decision as a memo so that a
+//                               second call before the env has stepped changes nothing.
+//   gte_exit_init_kernel        the state a bind leaves: the next decision sees a reset row.
+//
+// Both paths run exit_sync() / exit_decide() on the same values, so they give the same exit state and
+// actions bit for bit (tests/test_gpu_exits.py).  Compiled WITHOUT GTE_HOT_ONLY like gte_backtest.hip.
+#include "gte_backtest_regs.h"
+
+namespace gte {
+
+static_assert(sizeof(gte_exit_state) == 80 && offsetof(gte_exit_state, v_seen) == 16 &&
+              offsetof(gte_exit_state, latched_raw) == 32 && offsetof(gte_exit_state, decided) == 48 &&
+              offsetof(gte_exit_state, exits) == 64,
+              "gte_exit_state: five 16-byte pieces");
+static_assert(sizeof(gte_exit_rule) == 32 && offsetof(gte_exit_rule, max_hold) == 12 &&
+              offsetof(gte_exit_rule, exit_position) == 16, "gte_exit_rule: 32 bytes");
+
+__device__ __forceinline__ void load_exit_state(const gte_exit_state* src, gte_exit_state& x) {
+  const double2_t d0 = reinterpret_cast<const double2_t*>(src)[0];
+  const int4_t c1 = reinterpret_cast<const int4_t*>(src)[1], c2 = reinterpret_cast<const int4_t*>(src)[2],
+               c3 = reinterpret_cast<const int4_t*>(src)[3], c4 = reinterpret_cast<const int4_t*>(src)[4];
+  x.entry = d0[0]; x.peak = d0[1];
+  x.v_seen = __longlong_as_double(((int64_t)c1[1] << 32) | (uint32_t)c1[0]);
+  x.held = c1[2]; x.latched = c1[3];
+  x.latched_raw = c2[0]; x.i_seen = c2[1]; x.episode_seen = c2[2]; x.step_seen = c2[3];
+  x.decided = c3[0]; x.decided_action = c3[1];
+  x.exits[0] = c4[0]; x.exits[1] = c4[1]; x.exits[2] = c4[2]; x.exits[3] = c4[3];
+}
+
+__device__ __forceinline__ void store_exit_state(gte_exit_state* dst, const gte_exit_state& x) {
+  const double2_t d0 = {x.entry, x.peak};
+  const int64_t vb = __double_as_longlong(x.v_seen);
+  const int4_t c1 = {(int32_t)(uint32_t)vb, (int32_t)(vb >> 32), x.held, x.latched};
+  const int4_t c2 = {x.latched_raw, x.i_seen, x.episode_seen, x.step_seen};
+  const int4_t c3 = {x.decided, x.decided_action, 0, 0};
+  const int4_t c4 = {x.exits[0], x.exits[1], x.exits[2], x.exits[3]};
+  reinterpret_cast<double2_t*>(dst)[0] = d0;
+  reinterpret_cast<int4_t*>(dst)[1] = c1;
+  reinterpret_cast<int4_t*>(dst)[2] = c2;
+  reinterpret_cast<int4_t*>(dst)[3] = c3;
+  reinterpret_cast<int4_t*>(dst)[4] = c4;
+}
+
+// rule of env e (include/gte.h): the caller's map, or the env's strategy modulo the number of rules.
+// The rules are caller-owned memory of which the ABI asks 4-byte alignment only: five 4-byte loads, no vector
+__device__ __forceinline__ gte_exit_rule load_exit_rule(const gte_exit_rule* rules, int n_rules,
+                                                        const int32_t* rule_of_env, int64_t strat, int e, int P) {
+  const int64_t r = rule_of_env ? (int64_t)rule_of_env[e] : strat % n_rules;
+  const int32_t* q = reinterpret_cast<const int32_t*>(rules + r);
+  const int32_t a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], b = q[4];
+  gte_exit_rule R = {};
+  R.stop_loss = __int_as_float(a0); R.take_profit = __int_as_float(a1); R.trailing = __int_as_float(a2);
+  R.max_hold = a3;
+  const int32_t xp = (int32_t)(int8_t)(b & 0xFF);
+  R.exit_position = (uint32_t)xp < (uint32_t)P ? (int8_t)xp : (int8_t)-1;  // outside [0, P): the rule is off
+  return R;
+}
+
+// a reset row of any kind (valuation v0)
+__device__ __forceinline__ void exit_reset_row(gte_exit_state& x, double v0) {
+  x.entry = v0;
+  x.peak = v0;
+  x.held = 0;
+  x.latched = 0;
+}
+
+// d >= 1 steps seen as one transition from (v_prev, i_prev) to (v, i)
+__device__ __forceinline__ void exit_transition(gte_exit_state& x, double v_prev, int32_t i_prev, double v,
+                                                int32_t i, int32_t d) {
+  if (i != i_prev) {
+    x.entry = v_prev;
+    x.peak = v_prev;
+    x.held = d;
+  } else {
+    x.held = x.held > 0x7FFFFFFF - d ? 0x7FFFFFFF : x.held + d;
+  }
+  if (v > x.peak) x.peak = v;
+}
+
+// the state brought up to date with the row the env stands on: its reset count, _step, valuation, position
+__device__ __forceinline__ void exit_sync(gte_exit_state& x, int32_t episode, int32_t step, double pv, int32_t pos) {
+  if (episode != x.episode_seen) {
+    exit_reset_row(x, pv);
+  } else if (step != x.step_seen) {
+    const int32_t d = step - x.step_seen;
+    exit_transition(x, x.v_seen, x.i_seen, pv, pos, d < 1 ? 1 : d);
+  }
+  x.v_seen = pv;
+  x.i_seen = pos;
+  x.episode_seen = episode;
+  x.step_seen = step;
+}
+
+// the action of the next step for an env on valuation v, position index i, with table byte raw
+__device__ __forceinline__ int32_t exit_decide(gte_exit_state& x, const gte_exit_rule& R, int32_t raw, double v,
+                                               int32_t i, bool needs_reset, int32_t P) {
+  if (needs_reset) return -1;
+  if (x.latched && raw != x.latched_raw) x.latched = 0;
+  if (x.latched) return -1;
+  const int32_t xp = R.exit_position;
+  if (xp >= 0 && i != xp) {
+    int k = -1;
+    if (R.stop_loss > 0.0f && v <= x.entry * (1.0 - (double)R.stop_loss)) k = GTE_EXIT_STOP;
+    else if (R.trailing > 0.0f && v <= x.peak * (1.0 - (double)R.trailing)) k = GTE_EXIT_TRAIL;
+    else if (R.take_profit > 0.0f && v >= x.entry * (1.0 + (double)R.take_profit)) k = GTE_EXIT_TARGET;
+    else if (R.max_hold > 0 && x.held >= R.max_hold) k = GTE_EXIT_TIME;
+    if (k >= 0) {
+      x.latched = 1;
+      x.latched_raw = raw;
+      x.exits[0] += k == GTE_EXIT_STOP;  // (no indexing by k: the counters stay in registers)
+      x.exits[1] += k == GTE_EXIT_TRAIL;
+      x.exits[2] += k == GTE_EXIT_TARGET;
+      x.exits[3] += k == GTE_EXIT_TIME;
+      return xp;
+    }
+  }
+  return signal_action(raw, P);
+}
+
+__global__ __launch_bounds__(256) void gte_exit_init_kernel(gte_exit_state* state, const int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  gte_exit_state x = {};
+  x.episode_seen = -1;  // no env has this reset count: the first decision sees a reset row
+  store_exit_state(state + e, x);
+}
+
+__global__ __launch_bounds__(256) void gte_exit_actions_kernel(const Params p, const SignalTable* tables,
+                                                               const int S, const int32_t* strategy,
+                                                               const ExitRules rules, int32_t* actions) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= p.N) return;
+  const EnvRec* r = &p.rec[e];
+  const int4_t a = reinterpret_cast<const int4_t*>(r)[0];  // idx, step, pos, dsi
+  const int4_t b = reinterpret_cast<const int4_t*>(r)[4];  // start, episode, needs_reset, eps_on_ds
+  const double pv = r->pv;
+  gte_exit_state x;
+  load_exit_state(rules.state + e, x);
+  if (x.decided && b[1] == x.episode_seen && a[1] == x.step_seen) {
+    actions[e] = x.decided_action;  // decided already for this row: nothing changes
+    return;
+  }
+  const int64_t strat = signal_strategy(p, strategy, S, e);
+  const SignalTable t = tables[a[3]];
+  const int32_t raw = t.base[strat * t.stride + a[0]];
+  const gte_exit_rule R = load_exit_rule(rules.rules, rules.n_rules, rules.rule_of_env, strat, e, p.P);
+  exit_sync(x, b[1], a[1], pv, a[2]);
+  const int32_t act = exit_decide(x, R, raw, pv, a[2], b[2] != 0, p.P);
+  x.decided = 1;
+  x.decided_action = act;
+  store_exit_state(rules.state + e, x);
+  actions[e] = act;
+}
+
+// gte_backtest_signal_kernel (gte_backtest.hip: geometry, piece fetch, record handling — see there) with the
+// exit state x and the rule R of the lane's env in registers.  Before a step the lane decides from x, the
+// table byte and the env's registers; after it, it updates x from what the step left in them, recognising
+// resets the way backtest_step does (a same-step reset by the step's flags, a next-step one by needs_reset
+// before the step, a frozen step by a _step that did not move).  v_seen / i_seen / step_seen are the env's own
+// registers during the launch and are written out with the state at the end.
+__global__ __launch_bounds__(256) void gte_backtest_exit_kernel(const Params p, const SignalTable* tables,
+                                                                const int S, const int32_t* strategy,
+                                                                const ExitRules rules, gte_backtest_stats* stats,
+                                                                const int n_steps, const int epw) {
+  const int lane = threadIdx.x & 63;
+  const int slot = (blockIdx.x * 4 + (threadIdx.x >> 6)) * epw + lane;
+  const bool active = lane < epw && slot < p.N;
+  const int e = active ? slot : 0;
+  EnvRegs s = {};
+  if (active) load_state(p, e, s);
+  gte_backtest_stats a = {};
+  if (active) load_stats(stats + e, a);
+  const int64_t strat = active ? signal_strategy(p, strategy, S, e) : 0;
+  gte_exit_state x = {};
+  gte_exit_rule R = {};
+  R.exit_position = -1;
+  // the row the env stands on may have its decision already (a gte_signal_actions call before this one): the
+  // first step then takes that memo and decides nothing, as a second lookup would
+  constexpr int32_t NO_MEMO = -2;
+  int32_t memo = NO_MEMO;
+  if (active) {
+    load_exit_state(rules.state + e, x);
+    R = load_exit_rule(rules.rules, rules.n_rules, rules.rule_of_env, strat, e, p.P);
+    const int32_t episode = p.rec[e].episode;
+    if (x.decided && episode == x.episode_seen && s.step == x.step_seen) memo = x.decided_action;
+    else exit_sync(x, episode, s.step, s.pv, s.pos);  // steps and resets since the last decision
+  }
+  const int8_t* row = nullptr;  // this env's row of the table of dataset pdsi
+  int32_t pdsi = -1;
+  int32_t lim = 0, pbase = 0;
+  int4_t w = {0, 0, 0, 0};
+  auto fetch = [&](int32_t idx) {
+    if (s.dsi != pdsi) {
+      const SignalTable t = tables[s.dsi];
+      row = t.base + strat * t.stride;
+      pdsi = s.dsi;
+      lim = t.stride > 0x7FFFFFFFll ? 0x7FFFFFFF : (int32_t)t.stride;
+    }
+    pbase = idx & ~15;
+    w = *reinterpret_cast<const int4_t*>(row + pbase);
+  };
+  if (active) fetch(s.idx);
+  PriceCarry pc = {0.0, 0.0, -1, 0};
+  ObsJob job;
+  // (a lambda like gte_backtest_kernel's step, for the same reason)
+  auto run_a = [&](int k) {
+    const double v_before = s.pv;
+    const int32_t i_before = s.pos, step_before = s.step;
+    const bool nr = s.needs_reset != 0;
+    int32_t now = memo;
+    if (k != 0 || memo == NO_MEMO) now = exit_decide(x, R, signal_byte(w, s.idx), v_before, i_before, nr, p.P);
+    if (active && k + 1 < n_steps && (s.idx & 15) == 15 && s.idx + 1 < lim) fetch(s.idx + 1);
+    double pv = 0.0;
+    StepOut so = {};
+    phase_a<MODE_STEP>(p, e, active, lane, job, nullptr, /*compact=*/false, &pv, &s, &now,
+                       /*write_record=*/k == n_steps - 1, &pc, &so);
+    if (active) {
+      const bool stepped = !(nr && (p.autoreset == GTE_AUTORESET_NEXT_STEP || s.step == step_before));
+      if (stepped) {
+        // (a transition into a same-step reset is overwritten by the reset row: only that is written)
+        if (so.flags != 0 && p.autoreset == GTE_AUTORESET_SAME_STEP) exit_reset_row(x, pv);
+        else exit_transition(x, v_before, i_before, pv, s.pos, 1);
+      } else if (p.autoreset == GTE_AUTORESET_NEXT_STEP) {
+        exit_reset_row(x, pv);
+      }
+      backtest_step(a, p, e, s.step, pv, s.pos, so.reward, so.flags);
+    }
+    if (active && k + 1 < n_steps && (s.dsi != pdsi || (s.idx & ~15) != pbase)) fetch(s.idx);
+  };
+  for (int k = 0; k < n_steps; ++k) run_a(k);
+  if (active) {
+    const int32_t episode = p.rec[e].episode;  // (this lane's own resets wrote it)
+    a.episode_seen = episode;
+    store_stats(stats + e, a);
+    x.v_seen = s.pv;
+    x.i_seen = s.pos;
+    x.episode_seen = episode;
+    x.step_seen = s.step;
+    x.decided = 0;  // the row the env stands on now has no decision yet
+    store_exit_state(rules.state + e, x);
+  }
+}
+
+static bool exit_rules_usable(const ExitRules& r) { return r.rules && r.n_rules >= 1 && r.state; }
+
+hipError_t launch_exit_init(gte_exit_state* state, int n, hipStream_t stream) {
+  if (!state || n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gte_exit_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, state, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_exit_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                               const ExitRules& rules, int32_t* actions, hipStream_t stream) {
+  if (!tables || S < 1 || !actions || !exit_rules_usable(rules)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gte_exit_actions_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, tables, S,
+                     strategy, rules, actions);
+  return hipGetLastError();
+}
+
+hipError_t launch_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                               const ExitRules& rules, gte_backtest_stats* stats, int n_steps, int epw,
+                               hipStream_t stream) {
+  // (what launch_signal_summary refuses: trajectory rows; same-step mode without terminal records)
+  if (p.log.rows != nullptr || (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) || epw < 1 ||
+      epw > 64 || !tables || S < 1 || !exit_rules_usable(rules))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gte_backtest_exit_kernel, dim3(rollout_blocks(p.N, epw)), dim3(64 * ROLLOUT_WAVES), 0, stream,
+                     p, tables, S, strategy, rules, stats, n_steps, epw);
+  return hipGetLastError();
+}
+
+}  // namespace gte

@@ -98,6 +98,23 @@ hipError_t launch_signal_actions(const Params& p, const SignalTable* tables, int
 hipError_t launch_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
                                  gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream);
 
+// --- gte_exits.hip: the two lookups above with exit rules bound (gte_bind_exit_rules, include/gte.h)
+struct ExitRules {  // what a bind left: the caller's rules and map, the library's per-env state
+  const gte_exit_rule* rules;  // device [n_rules]
+  const int32_t* rule_of_env;  // device i32 [N], or null = strategy of the env % n_rules
+  gte_exit_state* state;       // device [N]
+  int32_t n_rules;
+};
+// every state as a bind leaves it: the next decision sees a reset row
+hipError_t launch_exit_init(gte_exit_state* state, int n, hipStream_t stream);
+// launch_signal_actions that also brings the exit states up to date, decides the exits and keeps the memo
+hipError_t launch_exit_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                               const ExitRules& rules, int32_t* actions, hipStream_t stream);
+// launch_signal_summary with the exit state of every env in registers next to its statistics
+hipError_t launch_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                               const ExitRules& rules, gte_backtest_stats* stats, int n_steps, int epw,
+                               hipStream_t stream);
+
 // --- gte_signals.hip: signal tables written on the device from indicator rules (gte_build_signals,
 // include/gte.h): table rows 0 .. n_rules-1, bytes 0 .. round_up(T, 16)-1 of each; the caller has checked
 // alignments and strides

@@ -282,3 +282,46 @@ def check_indicators(specs: np.ndarray, n_static: int, n_inputs: int, has_high: 
     for name, code, has in (("high", SRC_HIGH, has_high), ("low", SRC_LOW, has_low)):
         if (src == code).any() and not has:
             raise ValueError(f"specs read {name}, which dataset {d} does not have")
+
+
+# ---- exit rules: stop-loss, trailing stop, take-profit and time exits (gte_bind_exit_rules) ----
+
+from ._abi import EXIT_KINDS  # noqa: E402,F401
+from ._abi import EXIT_RULE_DTYPE as _EXIT_FIELDS  # noqa: E402
+
+#: `gte_exit_rule` of include/gte.h, 32 bytes
+EXIT_DTYPE = np.dtype(_EXIT_FIELDS)
+
+
+def exit_rules(stop_loss=0.0, take_profit=0.0, trailing=0.0, max_hold=0, exit_position=0) -> np.ndarray:
+    """One `EXIT_DTYPE` record per exit rule, the arguments broadcast against each other (the result is
+    one-dimensional): leave for position index `exit_position` when the env's valuation has fallen
+    `stop_loss` (a fraction) under the valuation it entered at, `trailing` under its best valuation
+    since, has risen `take_profit` over the entry valuation, or when the position has been held
+    `max_hold` transitions.  0 (or a NaN fraction) switches that exit off; the rule itself, with the
+    order of the four and the latch that follows an exit, is stated in include/gte.h.  `exit_position`
+    is checked against the env's `positions` by `bind_exits`; the kernels take one outside them as
+    "this rule is off"."""
+    arrays = {"stop_loss": np.asarray(stop_loss), "take_profit": np.asarray(take_profit),
+              "trailing": np.asarray(trailing), "max_hold": np.asarray(max_hold),
+              "exit_position": np.asarray(exit_position)}
+    for k in ("stop_loss", "take_profit", "trailing"):
+        if arrays[k].dtype.kind not in "fiu":
+            raise TypeError(f"{k} must be numbers, not {arrays[k].dtype}")
+    for k, (lo_, hi_) in (("max_hold", (-2 ** 31, 2 ** 31 - 1)), ("exit_position", (-128, 127))):
+        if arrays[k].dtype.kind not in "iu":
+            raise TypeError(f"{k} must be integers, not {arrays[k].dtype}")
+        if arrays[k].size and (arrays[k].min() < lo_ or arrays[k].max() > hi_):
+            raise ValueError(f"{k} does not fit its field")
+    shape = np.broadcast_shapes(*(v.shape for v in arrays.values()))
+    out = np.zeros(int(np.prod(shape, dtype=np.int64)) if shape else 1, dtype=EXIT_DTYPE)
+    for k, v in arrays.items():
+        out[k] = np.broadcast_to(v, shape).reshape(-1)
+    return out
+
+
+def check_exit_rules(rules: np.ndarray, n_positions: int) -> None:
+    """`EXIT_DTYPE` records against the env they are bound to: `exit_position` names one of its positions."""
+    P = int(n_positions)
+    if ((rules["exit_position"] < 0) | (rules["exit_position"] >= P)).any():
+        raise IndexError(f"exit rules name an exit_position outside the env's {P} positions")

@@ -492,7 +492,8 @@ int gte_bind_signals(gte_env* env, int32_t ds, const int8_t* signals_device, int
  * dataset_index if it lies in [0, n_positions), else -1 (hold) — the argument of the next
  * TradingEnv.step (environments.py:233-234).  Stream-ordered and capturable: the building block of
  * the step-by-step path, and what a caller uses to drive gte_step closed-loop.  GTE_ERR_STATE
- * before gte_reset or while a resident dataset has no table bound. */
+ * before gte_reset or while a resident dataset has no table bound.  While exit rules are bound
+ * (gte_bind_exit_rules, below) the launch decides the exits as well and updates the exit states. */
 int gte_signal_actions(gte_env* env, const int32_t* strategy_device, int32_t* actions_device);
 /* gte_backtest with that lookup in place of `actions`: n_steps TradingEnv.step calls
  * (environments.py:233-272), each with the action its table gives the env on the row it stands on
@@ -505,9 +506,116 @@ int gte_signal_actions(gte_env* env, const int32_t* strategy_device, int32_t* ac
  * the last one as gte_signal_actions + a step launch + the fold; elsewhere every step is that
  * triple, with the same records bit for bit.  The lookup writes a library-owned int32 [N] buffer
  * allocated by the first call.  GTE_ERR_STATE while a resident dataset has no table bound, before
- * gte_reset and inside a stream capture. */
+ * gte_reset and inside a stream capture.  While exit rules are bound (gte_bind_exit_rules, below) the fused
+ * launch is gte_backtest_exit_kernel (gte_exits.hip) and the lookup the exit-aware one. */
 int gte_backtest_signals(gte_env* env, const int32_t* strategy_device, int32_t n_steps, int32_t clear,
                          gte_backtest_stats** stats_device);
+
+/* ---- EXIT RULES: stop-loss, trailing stop, take-profit and time exits per strategy.  A signal table
+ * decides by MARKET ROW; an exit decides by the ENV'S OWN PATH (the valuation it entered at, its best
+ * valuation since, the steps it has held), so the same table row gives different answers to envs that
+ * entered at different valuations.  An exit rule only chooses the argument of TradingEnv.step
+ * (environments.py:233-234); trading arithmetic is untouched.  This text is the specification; the
+ * reference has no counterpart.
+ *
+ * RULE.  32 bytes, 4-byte aligned.  No rule content makes a kernel read or index outside anything. */
+typedef struct gte_exit_rule {
+  float   stop_loss, take_profit, trailing;   /* fractions; <= 0 or NaN: that exit is off          */
+  int32_t max_hold;                           /* transitions; <= 0: off                            */
+  int8_t  exit_position;                      /* position INDEX to go to; outside [0, P): rule off */
+  int8_t  reserved0[3];
+  int32_t reserved[3];                        /* ignored                                           */
+} gte_exit_rule;
+/* EXIT STATE of one env: 80 bytes, five 16-byte pieces, owned by the library on the device. */
+typedef struct gte_exit_state {
+  double  entry;          /* valuation the env had when it decided the trade it is in (or v_0)        */
+  double  peak;           /* highest valuation since then                                             */
+  double  v_seen;         /* bookkeeping: valuation and ...                                           */
+  int32_t held;           /* transitions since the position last changed (0 on a reset row; saturates) */
+  int32_t latched;        /* 1 after an exit fired, until the table byte moves or the env is reset    */
+  int32_t latched_raw;    /* the table byte the latch waits to see change                             */
+  int32_t i_seen;         /* ... position index of the row the state is up to date with               */
+  int32_t episode_seen;   /* bookkeeping: the env's reset count and ...                               */
+  int32_t step_seen;      /* ... _step of that row                                                    */
+  int32_t decided;        /* 1: decided_action is the decision for (episode_seen, step_seen)          */
+  int32_t decided_action; /* that decision: a position index or -1 (hold)                             */
+  int32_t reserved[2];
+  int32_t exits[4];       /* exits fired so far: STOP, TRAIL, TARGET, TIME                            */
+} gte_exit_state;
+#define GTE_EXIT_STOP 0
+#define GTE_EXIT_TRAIL 1
+#define GTE_EXIT_TARGET 2
+#define GTE_EXIT_TIME 3
+#ifdef __cplusplus
+static_assert(sizeof(gte_exit_rule) == 32 && sizeof(gte_exit_state) == 80, "exit rule: 32 bytes; exit state: five 16-byte pieces");
+#endif
+/* TIMELINE.  It is the one of gte_backtest_stats: a reset row has valuation v_0 and position index
+ * i_0; transitions t = 1, 2, ... follow with v_t and i_t, the index after the step, limit-order fills
+ * included.  A next-step auto-reset step and a frozen step are not transitions: their action is hold
+ * and they change no exit state (the reset row a next-step reset produces is a reset row).
+ *
+ * AT A RESET ROW of any kind:  entry = peak = v_0;  held = 0;  latched = 0.  The counters exits[] go on.
+ *
+ * BEFORE TRANSITION t+1 the env stands on row _idx with v_t, i_t and its rule R; P = n_positions:
+ *
+ *     raw = the sign-extended table byte at (dataset, strategy, _idx)
+ *     if needs_reset:                      action = hold                      (nothing below runs)
+ *     if latched and raw != latched_raw:   latched = 0                        (the signal moved: re-armed)
+ *     if latched:                          action = hold
+ *     elif 0 <= R.exit_position < P and i_t != R.exit_position and some exit holds:
+ *         k = the first in the order STOP, TRAIL, TARGET, TIME that holds
+ *         latched = 1;  latched_raw = raw;  exits[k] += 1;  action = R.exit_position
+ *     else:                                action = raw if 0 <= raw < P else hold
+ *
+ *     STOP    stop_loss   > 0 and v_t <= entry * (1.0 - (double)stop_loss)
+ *     TRAIL   trailing    > 0 and v_t <= peak  * (1.0 - (double)trailing)
+ *     TARGET  take_profit > 0 and v_t >= entry * (1.0 + (double)take_profit)
+ *     TIME    max_hold    > 0 and held >= max_hold
+ *
+ * Every floating operation is one IEEE f64 operation as written; the comparisons are plain, so a NaN
+ * valuation trips nothing.
+ *
+ * AFTER TRANSITION t+1:
+ *
+ *     if i_{t+1} != i_t:  entry = peak = v_t;  held = 1        (any change of position, fills included)
+ *     else:               held += 1                            (saturating at INT32_MAX)
+ *     if v_{t+1} > peak:  peak = v_{t+1}
+ *
+ * entry is the valuation the env had when it DECIDED the trade, so the trade's own fees count against
+ * it.  A transition into a same-step reset is followed at once by that reset row, which overwrites all
+ * the transition wrote.  An env that goes on stepping after its episode ended (auto-reset off, rows
+ * left) keeps making transitions and, having needs_reset, keeps getting hold.
+ *
+ * STEP-BY-STEP PATH.  gte_signal_actions with rules bound first brings the state up to date from the
+ * env record (episode, _step, pv, pos), then decides:
+ *     decided and episode == episode_seen and _step == step_seen:  return decided_action, change nothing
+ *       (a second call before the env has stepped: the call stays safe to repeat and to capture);
+ *     episode != episode_seen:   a reset row with v_0 = pv;
+ *     else _step != step_seen:   ONE transition from (v_seen, i_seen) to (pv, pos) over d = _step -
+ *       step_seen steps: held = d where the position changed, else held += d (saturating);
+ *     then (v_seen, i_seen, episode_seen, step_seen) = (pv, pos, episode, _step), the decision above, and
+ *     decided = 1, decided_action = action (for an env with needs_reset too: hold).
+ * The fused kernel keeps the same state in registers and runs the same update after every step; where the row
+ * it starts on already has its decision (a gte_signal_actions call before it), its first step takes that memo
+ * and decides nothing.  So both paths give the same records, env state and exit state bit for bit.
+ *
+ * RULE OF ENV e: rule_of_env[e] if that array was given — DEVICE int32 [N] with values in
+ * [0, n_rules), the caller's contract like `strategy` — else strategy_of(e) % n_rules, strategy_of(e)
+ * being what the lookup uses (strategy[e], or (env_id_base + e) % n_strategies).
+ *
+ * gte_bind_exit_rules borrows caller-owned DEVICE memory like gte_bind_signals (nothing is copied; the
+ * caller keeps it alive while launches that read it are in flight); rules_device == NULL unbinds, and
+ * gte_signal_actions / gte_backtest_signals then launch exactly the kernels they launch without this
+ * feature.  The state is allocated by the first call; EVERY call re-initialises it (all zero,
+ * episode_seen = -1), so the next decision sees a reset row.  *state_device (may be NULL) receives the
+ * DEVICE address of the N states (NULL before one exists), which stays the same until gte_destroy.  The call
+ * waits for the env's stream and is refused inside a stream capture (GTE_ERR_STATE).  GTE_ERR_INVALID
+ * for rules_device or rule_of_env_device not 4-byte aligned and for n_rules < 1. */
+int gte_bind_exit_rules(gte_env* env, const gte_exit_rule* rules_device, int32_t n_rules,
+                        const int32_t* rule_of_env_device, gte_exit_state** state_device);
+/* States first .. first+count-1 into HOST memory: waits for the env's stream, one transfer.
+ * GTE_ERR_STATE before the first gte_bind_exit_rules. */
+int gte_read_exit_state(gte_env* env, int32_t first, int32_t count, gte_exit_state* out);
 
 /* ---- SIGNAL TABLES BUILT ON THE DEVICE from indicator rules: a parameter sweep passes a small bank of
  * indicators and one 32-byte rule per strategy, and the device writes the int8 [n_rules][T] table that
