@@ -1539,6 +1539,8 @@ class BatchedTradingEnv(_VectorEnvBase):
         d["structure"] = "phase A, LDS barrier, gather"
         d["obs_stores"] = ("plain", "non-temporal", "sc1", "?")[(flags >> 4) & 3]
         d["resident_workgroups_per_cu"] = (flags >> 6) & 15
+        # the launches that store one row per env (gte.h, GTE_SLIDE_STORE); obs_stores while the env does not slide
+        d["slide_obs_stores"] = ("plain", "non-temporal", "sc1", "?")[(flags >> 10) & 3]
         return d
 
     def timer_start(self):

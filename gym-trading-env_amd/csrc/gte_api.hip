@@ -48,7 +48,7 @@ static int fail(int code, const char* fmt, ...) {
   } while (0)
 
 // GTE_SLIDE_AB (include/gte.h): what a set bit keeps as the sliding window's first version had it
-enum { SLIDE_AB_ORDER = 1 };
+enum { SLIDE_AB_ORDER = 1, SLIDE_AB_STORE = 2 };
 
 // Which kernels an env launches, with what geometry: decided by plan_launches (gte_create) and changed
 // later only where noted.  p.epw, p.lean_rows and p.hot_lds are set there too.
@@ -58,6 +58,7 @@ struct LaunchPlan {
   int stage = 0;           // dynamic columns: 0 global, 1 raw rings in LDS, 2 resolved in LDS
   int hot_per_cu = 0;      // resident workgroups per CU the geometry was sized for (0 = n/a)
   int store = 0;           // observation store policy (store_out): 0 plain, 1 nt, 2 sc1 (never 3)
+  int slide_store = 0;     // the same for launches that store one row per env (p.slide); == store where none slide
   bool hot_tu = false;     // the step may go to the isolated hot instantiations (hot_tu_covers permitting)
   bool fused_log = false;  // the step kernel writes the trajectory row itself
   bool always_dense = false;     // every step stores all flags (gte_ledger.h)
@@ -411,6 +412,32 @@ static int setup_affinity(gte_env* E) {
   return GTE_OK;
 }
 
+// Store policy of the launches that store one row per env (LaunchPlan::slide_store; plan_launches has the
+// rule and its evidence next to L.store's).  Called once store, the geometry, hot_tu, slide_rows and slide_ab
+// are set.
+static int slide_store_policy(const gte_env* E) {
+  const LaunchPlan& L = E->plan;
+  const Params& p = E->p;
+  // (full_windows: the head moves, but no launch ever stores one row per env)
+  if (L.slide_rows == 0 || L.full_windows || (L.slide_ab & SLIDE_AB_STORE)) return L.store;
+  int s = E->cfg.nontemporal_obs;  // the caller's explicit word governs both kinds of launch
+  if (s == 3) s = ((size_t)p.N * (p.W + L.slide_rows) * p.Fobs * sizeof(float) > ((size_t)190 << 20)) ? 1 : L.store;
+  // step_geometry sized the workgroups by the occupancy of store's instantiation: the other isolated
+  // instantiation must hold them all at once too, or slides keep store's
+  if (s != L.store && L.hot_tu && s != 0) {
+    hipDeviceProp_t prop;
+    const size_t smem = gte::lds_bytes(p, L.stage);
+    const int per_cu = s == 1 ? gte::hot_blocks_per_cu_nt(smem) : gte::hot_blocks_per_cu(smem);
+    if (hipGetDeviceProperties(&prop, E->cfg.device) != hipSuccess || prop.multiProcessorCount <= 0 ||
+        per_cu < (L.blocks + prop.multiProcessorCount - 1) / prop.multiProcessorCount)
+      s = L.store;
+  }
+  // tuning / tests: force it, whatever the rule and the residency check said (include/gte.h)
+  if (const char* o = getenv("GTE_SLIDE_STORE"))
+    if (o[0] >= '0' && o[0] <= '2' && o[1] == '\0') s = o[0] - '0';
+  return s;
+}
+
 // Every launch choice of the env (LaunchPlan).  The only reader of cfg.kernel_variant, whose bits select
 // reference structures for A/B timing and the tests' twins (GTE_KV_*, include/gte.h).
 static int plan_launches(gte_env* E) {
@@ -421,7 +448,17 @@ static int plan_launches(gte_env* E) {
   // observation store policy (gte_step.h, store_out): while the observation buffer fits
   // the 256 MB Infinity Cache next to the feature table, sc1 stores keep it there (65 536 envs,
   // 168 MB: 42.5 us vs 45.8 us with nt); beyond that the stores are a pure stream and
-  // non-temporal ones win (81 920 envs, 210 MB: 48 us vs 58 us; 262 144 envs: 162 us vs 261 us)
+  // non-temporal ones win (81 920 envs, 210 MB: 48 us vs 58 us; 262 144 envs: 162 us vs 261 us;
+  // profiles/r01_tune_store_policy.log).  That is the rule of every launch that writes full windows:
+  // wraps, resets, full steps after a withdrawn claim, rollout rows, captured steps, envs that do not
+  // slide.  At c3 the wrap alone, kernel trace: sc1 40.2 / 37.5 us, non-temporal 43.4 us (r06, r07).
+  // Launches that store one row per env have a policy of their own, slide_store (slide_store_policy):
+  // they are a latency chain far from any memory limit, and what counts is the SLAB the rows are
+  // scattered over, N x (W + M) rows: non-temporal once it exceeds the same 190 MB.  c3 (235 MB slab),
+  // us per step, three interleaved passes (profiles/r07_slide_store_ab.log): slides sc1 17.57-17.79,
+  // non-temporal 16.26-16.48, plain 17.93; kernel trace of the slide launch 14.36 -> 12.72 us.  Below
+  // the threshold they keep `store`: at the 117 MB slabs (32 768 envs) non-temporal slides gain 0.25 us
+  // on c4 without its gather (12.41 vs 12.67) but nothing outside the spread of the passes on c5.
   L.store = cfg.nontemporal_obs;
   if (L.store == 3) L.store = ((size_t)p.N * p.W * p.Fobs * sizeof(float) > ((size_t)190 << 20)) ? 1 : 2;
   step_geometry(E, !(kv & (GTE_KV_PER_WAVE_PHASE_A | GTE_KV_NO_LDS_STAGING)), !(kv & GTE_KV_GENERIC_COPY));
@@ -459,6 +496,7 @@ static int plan_launches(gte_env* E) {
   L.full_windows = getenv("GTE_SLIDE_FULL_WINDOWS") != nullptr;  // (read here, at gte_create, once per env)
   // A/B: bit 1 keeps slide launches in the L2-affinity order (read the same way; include/gte.h)
   if (const char* o = getenv("GTE_SLIDE_AB")) L.slide_ab = atoi(o);
+  L.slide_store = slide_store_policy(E);
   L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & GTE_KV_ROLLOUT_PER_STEP);
   L.resident_rollout = p.W >= 2 && !(kv & GTE_KV_ROLLOUT_GATHER);
   // envs per wavefront from registers: full waves once every SIMD has one (65 536 envs: 5.8 us per step
@@ -904,7 +942,7 @@ static int age_order(gte_env* E, int32_t steps) {
 }
 
 // The one place a step is launched (gte_step; gte_rollout and gte_backtest one launch per step), with
-// store policy `store`.  terminal_rec: terminal records for this launch where the env keeps none
+// store policy `store`, or the plan's slide_store where the launch stores one row per env.  terminal_rec: terminal records for this launch where the env keeps none
 // (gte_backtest in same-step mode).
 static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool capturing,
                         EnvRec* terminal_rec = nullptr) {
@@ -958,6 +996,7 @@ static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool captur
   ledger().wrote(E, {obs, term, trunc}, capturing, FLAGS | WINDOW);
   // (hot_tu_covers: the isolated instantiations have no terminal records and no trajectory row)
   const bool hot = L.hot_tu && gte::hot_tu_covers(p);
+  if (p.slide) store = L.slide_store;  // one row per env: the policy of its own (plan_launches)
   if (hot && store == 2)
     HIPCHK(gte::launch_step_hot(p, L.blocks, L.threads, gte::lds_bytes(p, L.stage), E->stream));
   else if (hot && store == 1)
@@ -2092,7 +2131,8 @@ int gte_get_launch_info(gte_env* E, int32_t* envs_per_wave, int32_t* threads_per
   if (threads_per_block) *threads_per_block = L.threads;
   if (n_blocks) *n_blocks = L.blocks;
   if (vector_bytes)
-    *vector_bytes = L.vec * 4 + 1000 * ((L.coop ? 1 : 0) + 2 * L.stage + 16 * L.store + 64 * (L.hot_per_cu & 15));
+    *vector_bytes = L.vec * 4 + 1000 * ((L.coop ? 1 : 0) + 2 * L.stage + 16 * L.store + 64 * (L.hot_per_cu & 15) +
+                                        1024 * (E->sliding ? L.slide_store : L.store));
   return GTE_OK;
 }
 

@@ -948,7 +948,19 @@ int gte_bind_outputs(gte_env* env, const gte_outputs* bufs);
  * GTE_SLIDE_AB, read the same way, is a bit mask.  Bit 1 keeps slide launches (steps that store one row per
  * env) in the L2-affinity order, with a due re-sort run at once, as the sliding window's first version did;
  * by default they run in env order and a re-sort that falls due waits for the next launch that writes full
- * windows.  Results never depend on it.  The other bits are reserved and ignored. */
+ * windows.  Bit 2 makes slide launches store with the policy of the launches that write full windows (below),
+ * as they did before they had one of their own; it outranks GTE_SLIDE_STORE.  Results never depend on either.
+ * The other bits are reserved and ignored.
+ *
+ * Store policy per launch kind.  nontemporal_obs (gte_config) names the observation store policy; left
+ * automatic (3), the launches that write full windows — wraps, resets, full steps after a withdrawn claim,
+ * GTE_SLIDE_FULL_WINDOWS, rollout rows, captured steps, every env that does not slide — take sc1 while the
+ * classic N x W x F_obs x 4 bytes stay below 190 MB and non-temporal stores beyond, and slide launches take
+ * non-temporal stores once the slab, N x (W + M) x F_obs x 4 bytes, exceeds 190 MB (else the same policy).
+ * An explicit 0, 1 or 2 governs both kinds.  Where the two differ, slide launches keep their own only if its
+ * kernel instantiation holds the plan's workgroups resident at once as the other does.
+ * GTE_SLIDE_STORE=0|1|2 in the environment when gte_create runs forces the slide launches' policy (a tuning
+ * switch like GTE_AFFINITY_BINS; no effect on an env that never slides).  gte_get_launch_info reports both. */
 typedef struct gte_obs_view_t {
   float*  base;          /* the bound observation buffer (NULL before one exists)            */
   int32_t rows_per_env;  /* W + M while sliding, else W                                      */
@@ -1028,7 +1040,8 @@ int gte_copy_to_host(gte_env* env, const void* device_src, void* host_dst,
  * copy vector + 1000 * flags: bit 0 cooperative phase A, bits 1-2 staging of the dynamic
  * columns (0 none, 1 raw rings in LDS, 2 resolved in LDS), bit 3 unused, bits 4-5
  * the observation store policy in use (0 plain, 1 nt, 2 sc1; never 3), bits 6-9 the resident
- * workgroups per CU the automatic geometry was sized for (0 = not applicable). */
+ * workgroups per CU the automatic geometry was sized for (0 = not applicable), bits 10-11 the
+ * store policy of slide launches (same values; equal to bits 4-5 while no sliding buffer is bound). */
 int gte_get_launch_info(gte_env* env, int32_t* envs_per_wave,
                         int32_t* threads_per_block, int32_t* n_blocks,
                         int32_t* vector_bytes);
