@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import backtest_model as bm
+import backtest_trace
 import replay
 from gym_trading_env_amd import _abi
 
@@ -304,7 +305,9 @@ def test_backtest_against_the_reference_trace(name):
     and the fields are comparisons and one division of them); the three reward sums within a bound
     derived here: each reward lies within B = replay.reward_ulp_bound ulp of the trace's, and each
     addition rounds once on either side (half an ulp each, of a partial sum no larger than the
-    largest one) -> sum_t B ulp(|r_t|) + (additions) ulp(largest partial sum)."""
+    largest one) -> sum_t B ulp(|r_t|) + (additions) ulp(largest partial sum).  The two sums of squares
+    within the bounds backtest_trace.run_with_bounds derives for them by the same rule: a square r'^2 lies
+    within (2 |r| + e) e of r^2 for a reward within e, and is rounded once more on either side."""
     import torch
     from gym_trading_env_amd.batched import BatchedTradingEnv
     g = replay.load(name)
@@ -330,7 +333,13 @@ def test_backtest_against_the_reference_trace(name):
     np.testing.assert_array_equal(env.state("idx"), g["idx"][K - 1])
     B = replay.reward_ulp_bound(g)
     worst = 0.0
+    whole, sq_bounds, _ = backtest_trace.chunk_records(g, 1, K)
     for e in range(E):
+        for f in ("reward_sq_sum", "ep_return_sq_sum"):
+            d, b = abs(got[f][e] - whole[e][f]), sq_bounds[e][f]
+            print(f"{name} env {e} {f}: |difference| {d:.3e}, bound {b:.3e}, ratio {d / b:.4f}")
+            assert np.isfinite(whole[e][f]) and d <= b, (name, e, f, got[f][e], whole[e][f], b)
+            worst = max(worst, d / b)
         rec = bm.new_record(g["portfolio_valuation"][0, e], g["position"][0, e])
         bound, largest, adds = 0.0, 0.0, 0
         for s in bm.trace_steps(g, e):

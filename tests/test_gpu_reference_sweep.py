@@ -24,6 +24,7 @@ import re
 import numpy as np
 import pytest
 
+import backtest_trace
 import replay
 import strata
 from gym_trading_env_amd import _abi
@@ -134,21 +135,9 @@ PATH_LINE = re.compile(r"\[gte\] rollout path: ([a-z-]+), (\d+) steps")
 
 
 def _chunks(g, rng):
-    """[start, stop) call ranges covering calls 1..K-1: random lengths, and a new chunk at every
-    call that adds limit orders (they are added before that call's step)."""
-    K = g["op"].shape[0]
-    forced = set()
-    if "lo_pos" in g:
-        forced = {int(k) for k in np.nonzero((g["lo_pos"] >= 0).any(axis=1))[0] if k > 0}
-    out, start = [], 1
-    while start < K:
-        stop = min(K, start + int(rng.integers(1, 40)))
-        nxt = [k for k in forced if start < k < stop]
-        if nxt:
-            stop = min(nxt)
-        out.append((start, stop))
-        start = stop
-    return out
+    """[start, stop) call ranges covering calls 1..K-1: random lengths up to 39, and a new chunk at every
+    call that adds limit orders (backtest_trace.chunks, which the backtest replays share)."""
+    return backtest_trace.chunks(g, rng, 39)
 
 
 @pytest.mark.parametrize("mode", sorted(strata.ROLLOUT_MODES))
