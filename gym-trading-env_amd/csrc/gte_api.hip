@@ -19,10 +19,13 @@
 
 #include "gte_launch.h"
 #include "gte_ledger.h"
+#include "gte_plan.h"
 
 using gte::DatasetDesc;
 using gte::EnvRec;
 using gte::Params;
+using gte_plan::LaunchPlan;
+using gte_plan::SLIDE_AB_ORDER;
 using gte_ledger::FLAGS;
 using gte_ledger::WINDOW;
 using gte_ledger::ledger;
@@ -47,40 +50,10 @@ static int fail(int code, const char* fmt, ...) {
                   "%s failed: %s", #expr, hipGetErrorString(e_));                 \
   } while (0)
 
-// GTE_SLIDE_AB (include/gte.h): what a set bit keeps as the sliding window's first version had it
-enum { SLIDE_AB_ORDER = 1, SLIDE_AB_STORE = 2 };
-
-// Which kernels an env launches, with what geometry: decided by plan_launches (gte_create) and changed
-// later only where noted.  p.epw, p.lean_rows and p.hot_lds are set there too.
-struct LaunchPlan {
-  int vec = 1, blocks = 0, threads = 256;
-  bool coop = false;       // wave 0 of a workgroup runs phase A for the whole workgroup
-  int stage = 0;           // dynamic columns: 0 global, 1 raw rings in LDS, 2 resolved in LDS
-  int hot_per_cu = 0;      // resident workgroups per CU the geometry was sized for (0 = n/a)
-  int store = 0;           // observation store policy (store_out): 0 plain, 1 nt, 2 sc1 (never 3)
-  int slide_store = 0;     // the same for launches that store one row per env (p.slide); == store where none slide
-  bool hot_tu = false;     // the step may go to the isolated hot instantiations (hot_tu_covers permitting)
-  bool fused_log = false;  // the step kernel writes the trajectory row itself
-  bool always_dense = false;     // every step stores all flags (gte_ledger.h)
-  int slide_rows = 0;            // M: spare rows a sliding observation buffer may have (0 = this env never slides)
-  bool full_windows = false;     // a sliding buffer moves its head but every step writes full windows (A/B)
-  int slide_ab = 0;              // GTE_SLIDE_AB (include/gte.h): bits that keep the earlier slide launch (A/B)
-  bool fused_rollout = false;    // gte_rollout may use the fused kernels ...
-  bool resident_rollout = false; // ... and among them the window-resident one
-  // L2-affinity processing order (gte_kernels.hip, "L2-affinity permutation")
-  int affinity_period = 0;       // 0 = off (also set by finalize and by a failed re-sort)
-  int n_bins_per_ds = 0;
-  int state_epw = 0;       // envs per wavefront of the from-registers kernels (state-only rollout, backtest)
-  // rollout geometries, chosen by the first rollout that needs them
-  int rollout_epw = 0;     // envs per wavefront of the fused rollout kernel (0 = not chosen yet)
-  int resident_slots[3] = {0, 0, 0};  // workgroups of that geometry the chip holds at once
-  int resident_epb[3] = {0, 0, 0};  // envs per workgroup of the window-resident rollout kernel per
-                                    // store policy (0 = not chosen yet, -1 = shape not covered)
-};
-
 struct gte_env {
   gte_config cfg;
   Params p;
+  int n_cu = 0;  // compute units of cfg.device (require_device)
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -98,7 +71,7 @@ struct gte_env {
   uint8_t* d_lo_persist_in = nullptr;
   bool finalized = false;
   bool was_reset = false;
-  LaunchPlan plan;
+  LaunchPlan plan;  // every launch choice, decided by the rules of gte_plan.h (plan_launches, finalize, rollout)
   int32_t* term_base = nullptr;  // the two-slot terminal counter in use (owned or bound)
   int term_slot = 0;       // slot the last launch added to
   // L2-affinity processing order (plan.affinity_period)
@@ -239,7 +212,8 @@ static int validate(const gte_config* c) {
   return GTE_OK;
 }
 
-static int require_device(int device) {
+// *n_cu: the device's compute units, which the launch planner sizes by
+static int require_device(int device, int* n_cu) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n <= 0)
@@ -253,6 +227,9 @@ static int require_device(int device) {
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(GTE_ERR_NO_DEVICE, "device %d is %s; libgte is built for gfx950 (MI355X) only",
                 device, prop.gcnArchName);
+  if (prop.multiProcessorCount <= 0)
+    return fail(GTE_ERR_NO_DEVICE, "device %d reports no compute units", device);
+  *n_cu = prop.multiProcessorCount;
   return GTE_OK;
 }
 
@@ -271,240 +248,106 @@ static int create_failed(gte_env* E, int rc) {
   return rc;
 }
 
-// Step launch geometry: EPW environments per wavefront, 4 wavefronts per workgroup.  hot_ok: the
-// config leaves the hot kernel's cooperative, LDS-staged shape on; lean_ok: the lean copy loop.
-static void step_geometry(gte_env* E, bool hot_ok, bool lean_ok) {
-  LaunchPlan& L = E->plan;
-  Params& p = E->p;
-  L.vec = (p.Fobs % 4 == 0) ? 4 : 1;
-  const int64_t vpe = (int64_t)p.W * p.Fobs / L.vec;  // vectors per env
-  int epw = E->cfg.envs_per_wave;
-  if (epw == 0) {
-    // windows of at least one wave instruction: 16 envs per wave (64 per workgroup, cooperative
-    // phase A) measured best at every size tried; tiny windows may pack up to 64 per wave
-    epw = (vpe >= 64) ? 16 : 64;
-    // enough wavefronts to fill 256 CUs x 16 waves ...
-    while (epw > 1 && ((int64_t)p.N + epw - 1) / epw < 4096) epw >>= 1;
-    // ... but at least one full wave instruction (64 vectors) of copy work per wavefront
-    // (small windows are latency-bound: 16 envs/wave with cooperative phase A measured
-    // 5.4 us vs 7.5 us at 64 envs/wave on config 2, profiles/r01_tune_c2.log)
-    while (epw < 64 && (int64_t)epw * vpe < 64) epw <<= 1;
-    // Windowed shapes on the hot kernel.  Two regimes, both measured:
-    //  * every workgroup resident at once, at least 16 waves on every CU: the launch ends when the
-    //    BUSIEST CU is done (workgroups are dealt evenly: ceil(wgs / CUs) per CU), so take the
-    //    envs-per-wave with the fewest envs on that CU; ties go to the bigger workgroup (fewer
-    //    phase-A waves).  Config 3, us per step by envs on the busiest CU: 256 (16 per wave) 39.5,
-    //    260 (13) 40.4, 264 (11) 40.5, 280 (14) 40.7, 288 (12) 42.0, 300 (15) 42.0; config 5:
-    //    128 (8 per wave, 4 workgroups per CU) 36.3, 16 per wave on 2 per CU 43.5
-    //    (profiles/r02_tune_epw.log, r02_waves_ab.log, r02_c5_sweep.log).
-    //  * more workgroups than the chip holds (the observations stream to HBM): small workgroups —
-    //    the phase A of those that start later hides behind the copies of those already running
-    //    and the tail is one small workgroup.  Config 3 (profiles/r02_tune_epw_repeat.log, 3 passes
-    //    each): 262 144 envs 16 per wave 156.4, 12: 154.7, 8: 149.2, 6: 143.8, 4: 142.6, 3: 145.5,
-    //    2: 169.0; 131 072 envs 16: 86.7, 11: 83.3, 8: 80.1, 6: 79.0, 4: 78.2, 3: 79.8; 100 003 envs
-    //    16: 74.5, 9: 62.1, 6: 60.0, 4: 61.6 -> about 640 vectors of copy work per wave (4 envs
-    //    of 20x32), 960 below 120 000 envs.
-    const bool hot_shape = L.vec == 4 && vpe >= 64 && p.nd > 0 && !p.persist && !E->cfg.final_obs &&
-                           (L.store == 1 || L.store == 2) && hot_ok;
-    if (hot_shape) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, E->cfg.device) == hipSuccess) {
-        const int64_t n_cu = prop.multiProcessorCount;
-        int some_per_cu = 0;  // (residency of any candidate: the occupancy queries work)
-        int64_t fewest = 0;
-        int one_round_epw = 0, one_round_per_cu = 0;
-        for (int e = 64 / GTE_WAVES; e >= 1; --e) {
-          if ((int64_t)e * vpe < 64) break;
-          Params q = p;
-          q.epw = e;  // registers AND the workgroup's LDS (which shrinks with e) bound residency
-          const size_t smem = gte::lds_bytes(q, 1);
-          const int per_cu = L.store == 1 ? gte::hot_blocks_per_cu_nt(smem) : gte::hot_blocks_per_cu(smem);
-          if (per_cu <= 0) break;
-          if (e <= 8 || !some_per_cu) some_per_cu = per_cu;
-          const int64_t wgs = ((int64_t)p.N + GTE_WAVES * e - 1) / (GTE_WAVES * e);
-          const int64_t busiest = (wgs + n_cu - 1) / n_cu;  // workgroups on the busiest CU
-          if (getenv("GTE_DEBUG_GEOMETRY"))
-            fprintf(stderr, "[gte] envs/wave %2d: LDS %5zu B, %d workgroups/CU resident, %lld workgroups, "
-                            "%lld on the busiest CU\n", e, smem, per_cu, (long long)wgs, (long long)busiest);
-          if (busiest <= per_cu && busiest * GTE_WAVES >= 16 && (fewest == 0 || busiest * e < fewest)) {
-            fewest = busiest * e;
-            one_round_epw = e;
-            one_round_per_cu = per_cu;
-          }
-        }
-        if (one_round_epw) {
-          epw = one_round_epw;
-          L.hot_per_cu = one_round_per_cu;
-        } else if (some_per_cu) {
-          L.hot_per_cu = some_per_cu;
-          const int64_t target = (int64_t)p.N >= 120000 ? 640 : 960;
-          int e = (int)((target + vpe / 2) / vpe);
-          e = e < 1 ? 1 : (e > 64 / GTE_WAVES ? 64 / GTE_WAVES : e);
-          while (e < 64 / GTE_WAVES && (int64_t)e * vpe < 64) ++e;
-          epw = e;
-          // Round 3: where the lean copy loop applies (whole passes of 4 wave instructions per wave,
-          // gte_step.h) it beats the small workgroups above — 262 144 envs: 4 per wave 149 us,
-          // 8: 139.8, 16: 137.8; 131 072: 4: 80, 8: 74, 16: 71-78; 100 003: 6: 62, 8: 58.7, 16: 60-67
-          // (profiles/r03_epw_hbm.log) — so take the smallest envs-per-wave the lean loop accepts, twice
-          // that from 200 000 envs on.
-          if (lean_ok) {
-            int lean_e = 0;
-            for (int c = 1; c <= 64 / GTE_WAVES; ++c)
-              if (((int64_t)c * vpe) % (64 * GTE_LEAN_U) == 0 && (int64_t)c * p.W <= gte::LEAN_MAX_ROWS) { lean_e = c; break; }
-            if (lean_e) {
-              int c = lean_e;
-              while (c * 2 <= 64 / GTE_WAVES && (int64_t)c * vpe < 1280 && (int64_t)c * 2 * p.W <= gte::LEAN_MAX_ROWS) c *= 2;
-              if ((int64_t)p.N >= 200000 && c * 2 <= 64 / GTE_WAVES && (int64_t)c * 2 * p.W <= gte::LEAN_MAX_ROWS) c *= 2;
-              epw = c;
-            }
-          }
-        }
-      }
-    }
-  }
-  while (epw > 1 && (int64_t)epw * vpe > (1 << 20)) epw >>= 1;  // keeps the index math in range
-  // the LDS-staged dynamic columns must fit comfortably: shrink the workgroup's envs
-  while (epw > 1 && (int64_t)epw * GTE_WAVES * p.W * (p.nd ? p.nd : 1) * 4 > 32 * 1024) epw >>= 1;
-  p.epw = epw;
-  const int64_t waves = ((int64_t)p.N + epw - 1) / epw;
-  L.threads = 64 * GTE_WAVES;
-  L.blocks = (int)((waves + GTE_WAVES - 1) / GTE_WAVES);
-}
+// --- launch planning: the rules are in gte_plan.h; here are what they are given and what is done with the result
 
-// L2-affinity order: only worth it when every XCD gets several workgroups and the
-// windows are big enough to be bandwidth-bound
-static int setup_affinity(gte_env* E) {
-  LaunchPlan& L = E->plan;
+static gte_plan::Shape plan_shape(const gte_env* E) {
   const Params& p = E->p;
-  const size_t N = (size_t)p.N;
-  // Default re-sort period: the order decays as envs jump to new start rows, i.e. with the
-  // reset rate, about 1 / max_episode_duration of the envs per step once the episodes are out
-  // of phase.  Measured at duration 500, episodes staggered (profiles/r02_tune_affinity_period.log):
-  // every 128 steps 42.4 us per step, 64: 41.3, 32: 40.6, 16: 40.5, 8: 41.6 (a re-sort was four
-  // small launches then, ~25 us) -> re-sort after ~6 % of the envs have moved; 128 when episodes
-  // only end by the drawdown rule or at the end of the data.
-  int auto_period = 128;
-  if (p.max_dur > 0) {
-    auto_period = p.max_dur / 16;
-    auto_period = auto_period < 8 ? 8 : (auto_period > 128 ? 128 : auto_period);
-  }
-  const int period = E->cfg.affinity_period == 0 ? auto_period : E->cfg.affinity_period;
-  const int EPB = p.epw * GTE_WAVES;
-  const int n_wg = (p.N + EPB - 1) / EPB;
-  if (!(period > 0 && n_wg >= 64 && (int64_t)p.W * p.Fobs * 4 >= 512)) return GTE_OK;
-  // slots in XCD-major order: workgroup b runs on XCD b % 8 (round-robin dispatch)
-  std::vector<int32_t> slot_of_rank;
-  slot_of_rank.reserve(N);
-  for (int x = 0; x < 8; ++x)
-    for (int b = x; b < n_wg; b += 8)
-      for (int sl = b * EPB; sl < (b + 1) * EPB && sl < p.N; ++sl) slot_of_rank.push_back(sl);
-  int nb = 8192 / p.D;
-  if (const char* o = getenv("GTE_AFFINITY_BINS")) nb = atoi(o) / p.D;  // tuning: total bins of the counting sort
-  nb = nb < 1 ? 1 : (nb > 4096 ? 4096 : nb);
-  L.n_bins_per_ds = nb;
-  TRY(dev_alloc(E, &E->d_perm, N, false));
-  TRY(dev_alloc(E, &E->d_slot_of_rank, N, false));
-  TRY(dev_alloc(E, &E->d_bins, (size_t)2 * p.D * nb));  // histogram (zero-filled) + cursors
-  if (hipMemcpy(E->d_slot_of_rank, slot_of_rank.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice) !=
-      hipSuccess)
-    return fail(GTE_ERR_HIP, "copying slot_of_rank failed");
-  L.affinity_period = period;
-  return GTE_OK;
-}
-
-// Store policy of the launches that store one row per env (LaunchPlan::slide_store; plan_launches has the
-// rule and its evidence next to L.store's).  Called once store, the geometry, hot_tu, slide_rows and slide_ab
-// are set.
-static int slide_store_policy(const gte_env* E) {
-  const LaunchPlan& L = E->plan;
-  const Params& p = E->p;
-  // (full_windows: the head moves, but no launch ever stores one row per env)
-  if (L.slide_rows == 0 || L.full_windows || (L.slide_ab & SLIDE_AB_STORE)) return L.store;
-  int s = E->cfg.nontemporal_obs;  // the caller's explicit word governs both kinds of launch
-  if (s == 3) s = ((size_t)p.N * (p.W + L.slide_rows) * p.Fobs * sizeof(float) > ((size_t)190 << 20)) ? 1 : L.store;
-  // step_geometry sized the workgroups by the occupancy of store's instantiation: the other isolated
-  // instantiation must hold them all at once too, or slides keep store's
-  if (s != L.store && L.hot_tu && s != 0) {
-    hipDeviceProp_t prop;
-    const size_t smem = gte::lds_bytes(p, L.stage);
-    const int per_cu = s == 1 ? gte::hot_blocks_per_cu_nt(smem) : gte::hot_blocks_per_cu(smem);
-    if (hipGetDeviceProperties(&prop, E->cfg.device) != hipSuccess || prop.multiProcessorCount <= 0 ||
-        per_cu < (L.blocks + prop.multiProcessorCount - 1) / prop.multiProcessorCount)
-      s = L.store;
-  }
-  // tuning / tests: force it, whatever the rule and the residency check said (include/gte.h)
-  if (const char* o = getenv("GTE_SLIDE_STORE"))
-    if (o[0] >= '0' && o[0] <= '2' && o[1] == '\0') s = o[0] - '0';
+  const gte_config& c = E->cfg;
+  gte_plan::Shape s;
+  s.N = p.N; s.D = p.D; s.W = p.W; s.has_window = p.has_window != 0; s.Fobs = p.Fobs; s.nd = p.nd;
+  s.persist = p.persist != 0; s.max_dur = p.max_dur; s.final_obs = c.final_obs != 0; s.log_steps = c.log_steps;
+  s.envs_per_wave = c.envs_per_wave; s.nontemporal_obs = c.nontemporal_obs; s.obs_slack_rows = c.obs_slack_rows;
+  s.affinity_period = c.affinity_period; s.kernel_variant = c.kernel_variant; s.debug_flags = c.debug_flags;
   return s;
 }
 
-// Every launch choice of the env (LaunchPlan).  The only reader of cfg.kernel_variant, whose bits select
-// reference structures for A/B timing and the tests' twins (GTE_KV_*, include/gte.h).
+static bool debug_geometry() { return getenv("GTE_DEBUG_GEOMETRY") != nullptr; }
+
+// The environment switches, read at the moments include/gte.h promises (tests set them between two gte_create
+// calls of one process): the slide switches and the bins at gte_create, GTE_RESIDENT_EPB at the first rollout
+// that chooses a resident geometry for a store policy, GTE_DEBUG_GEOMETRY whenever a line would be printed.
+enum KnobsMoment { KNOBS_CREATE, KNOBS_ROLLOUT };
+static gte_plan::Knobs read_knobs(KnobsMoment when) {
+  gte_plan::Knobs k;
+  k.debug_geometry = debug_geometry();
+  if (when == KNOBS_CREATE) {
+    k.slide_full_windows = getenv("GTE_SLIDE_FULL_WINDOWS") != nullptr;
+    if (const char* o = getenv("GTE_SLIDE_AB")) k.slide_ab = atoi(o);
+    if (const char* o = getenv("GTE_SLIDE_STORE"))
+      if (o[0] >= '0' && o[0] <= '2' && o[1] == '\0') k.slide_store = o[0] - '0';
+    if (const char* o = getenv("GTE_AFFINITY_BINS")) { k.has_affinity_bins = true; k.affinity_bins = atoi(o); }
+  } else if (const char* o = getenv("GTE_RESIDENT_EPB")) {
+    k.has_resident_epb = true;
+    k.resident_epb = atoi(o);
+  }
+  return k;
+}
+
+// The chip as the planner sees it: the kernels' LDS images and what the HIP runtime says of their residency.
+// Every answer is asked afresh (the resident query opts its kernel into large LDS as a side effect).
+// GTE_DEBUG_GEOMETRY: each question prints its arguments and its answer.
+struct DeviceChip final : gte_plan::Chip {
+  const gte_env* E;
+  explicit DeviceChip(const gte_env* env) : E(env) { n_cu = said(env->n_cu, "n_cu device=%d", env->cfg.device); }
+  template <typename T>
+  static T said(T answer, const char* fmt, ...) {
+    if (debug_geometry()) {
+      char q[128];
+      va_list ap;
+      va_start(ap, fmt);
+      vsnprintf(q, sizeof q, fmt, ap);
+      va_end(ap);
+      fprintf(stderr, "[gte] chip: %s -> %lld\n", q, (long long)answer);
+    }
+    return answer;
+  }
+  size_t step_lds_bytes(int epw, int stage) override {
+    // (no trajectory row: planning has always run before a launch sets p.log)
+    return said(gte::lds_image_bytes(epw, E->p.W, E->p.nd, E->cfg.final_obs != 0, false, stage),
+                "step_lds_bytes epw=%d stage=%d", epw, stage);
+  }
+  int hot_per_cu(int store, size_t smem) override {
+    return said(store == 1 ? gte::hot_blocks_per_cu_nt(smem) : gte::hot_blocks_per_cu(smem),
+                "hot_per_cu store=%d smem=%zu", store, smem);
+  }
+  size_t resident_lds_bytes(int epb) override {
+    return said(gte::resident_lds_bytes(E->p, epb), "resident_lds_bytes epb=%d", epb);
+  }
+  int resident_per_cu(int epb, int store) override {
+    return said(gte::resident_blocks_per_cu(E->p, epb, store), "resident_per_cu epb=%d store=%d", epb, store);
+  }
+  int gather_per_cu(int epw, int store) override {
+    Params q = E->p;
+    q.epw = epw;
+    return said(gte::rollout_blocks_per_cu(q, store), "gather_per_cu epw=%d store=%d", epw, store);
+  }
+};
+
+// GTE_DEBUG_GEOMETRY: the whole plan on one line, after every moment that decides some of it
+static void report_plan(const gte_env* E, const char* when) {
+  if (debug_geometry()) gte_plan::print_plan(stderr, when, E->plan);
+}
+
+// gte_create: plan every launch, copy what the plan decides of Params, allocate what it asks for
 static int plan_launches(gte_env* E) {
   LaunchPlan& L = E->plan;
   Params& p = E->p;
-  const gte_config& cfg = E->cfg;
-  const int kv = cfg.kernel_variant;
-  // observation store policy (gte_step.h, store_out): while the observation buffer fits
-  // the 256 MB Infinity Cache next to the feature table, sc1 stores keep it there (65 536 envs,
-  // 168 MB: 42.5 us vs 45.8 us with nt); beyond that the stores are a pure stream and
-  // non-temporal ones win (81 920 envs, 210 MB: 48 us vs 58 us; 262 144 envs: 162 us vs 261 us;
-  // profiles/r01_tune_store_policy.log).  That is the rule of every launch that writes full windows:
-  // wraps, resets, full steps after a withdrawn claim, rollout rows, captured steps, envs that do not
-  // slide.  At c3 the wrap alone, kernel trace: sc1 40.2 / 37.5 us, non-temporal 43.4 us (r06, r07).
-  // Launches that store one row per env have a policy of their own, slide_store (slide_store_policy):
-  // they are a latency chain far from any memory limit, and what counts is the SLAB the rows are
-  // scattered over, N x (W + M) rows: non-temporal once it exceeds the same 190 MB.  c3 (235 MB slab),
-  // us per step, three interleaved passes (profiles/r07_slide_store_ab.log): slides sc1 17.57-17.79,
-  // non-temporal 16.26-16.48, plain 17.93; kernel trace of the slide launch 14.36 -> 12.72 us.  Below
-  // the threshold they keep `store`: at the 117 MB slabs (32 768 envs) non-temporal slides gain 0.25 us
-  // on c4 without its gather (12.41 vs 12.67) but nothing outside the spread of the passes on c5.
-  L.store = cfg.nontemporal_obs;
-  if (L.store == 3) L.store = ((size_t)p.N * p.W * p.Fobs * sizeof(float) > ((size_t)190 << 20)) ? 1 : 2;
-  step_geometry(E, !(kv & (GTE_KV_PER_WAVE_PHASE_A | GTE_KV_NO_LDS_STAGING)), !(kv & GTE_KV_GENERIC_COPY));
-  p.debug = cfg.debug_flags;
-  L.coop = (p.epw * GTE_WAVES <= 64) && !(kv & GTE_KV_PER_WAVE_PHASE_A);
-  L.stage = (p.nd > 0 && gte::lds_bytes(p, 1) <= 48 * 1024 && !(kv & GTE_KV_NO_LDS_STAGING)) ? (p.persist ? 2 : 1) : 0;
-  // the lean copy loop (gte_step.h): 16-byte vectors with the raw rings staged in LDS (stage 1;
-  // dyn_persist takes stage 2)
-  p.lean_rows = (L.vec == 4 && L.stage == 1 && !(kv & GTE_KV_GENERIC_COPY)) ? 1 : 0;
-  p.hot_lds = (kv & GTE_KV_RECORD_DIRECT) ? 0 : 1;  // (A/B: the stepping lane stores its record itself)
-  // the shape the isolated hot instantiations (gte_hot.hip) and the fused rollouts are written for
-  const bool hot_shape = L.vec == 4 && L.coop && L.stage == 1;
-  L.hot_tu = hot_shape && !(kv & GTE_KV_SHARED_TU);  // (A/B: the shared-TU instantiation instead)
-  // With a trajectory log the step kernel writes the row itself (shared-TU instantiation): the lane
-  // that stepped the env puts its 80-byte record into LDS and the copy waves write it out, five
-  // lanes per env.  At the config-3 shape, us per step: 38.5 against 43.2 with the separate
-  // gte_log_kernel launch (and 37.5 without a log; profiles/r03_log_ab.log).  (Rounds 1-2 kept the
-  // log as twelve [L, N] columns: twelve scattered stores per env from the stepping lane, which
-  // beyond 16 384 envs lost to the separate launch.)
-  // GTE_KV_LOG_SEPARATE keeps the separate launch (A/B); GTE_KV_LOG_FUSED is the default now.
-  L.fused_log = cfg.log_steps > 0 && !(kv & GTE_KV_LOG_SEPARATE);
-  L.always_dense = (kv & GTE_KV_DENSE_FLAGS) != 0;  // (A/B of the sparse flag stores)
-  // Sliding observation buffer (gte.h, gte_bind_sliding_obs): where the hot instantiation's shape runs —
-  // 16-byte vectors, windows of at least one wave instruction, cooperative phase A, raw rings in LDS —
-  // and nothing hot_tu_covers() excludes or that needs whole windows elsewhere (terminal observations, a
-  // trajectory log and with it Python callables, T-deep dynamic columns, no window at all).
-  // Automatic M = 2 W / 5: a period of M + 1 steps has one full write, and the buffer is (W + M) / W =
-  // 1.4 x the classic one (8 spare rows at W = 20).
-  L.slide_rows = 0;
-  if (hot_shape && (int64_t)p.W * p.Fobs / 4 >= 64 && p.has_window && !p.persist && !cfg.final_obs &&
-      cfg.log_steps == 0 && cfg.obs_slack_rows >= 0)
-    L.slide_rows = cfg.obs_slack_rows > 0 ? cfg.obs_slack_rows : 2 * p.W / 5;
-  // A/B: the head still moves, every step writes full windows (an environment variable like
-  // GTE_AFFINITY_BINS, not a GTE_KV_* bit: results and layout are the sliding ones)
-  L.full_windows = getenv("GTE_SLIDE_FULL_WINDOWS") != nullptr;  // (read here, at gte_create, once per env)
-  // A/B: bit 1 keeps slide launches in the L2-affinity order (read the same way; include/gte.h)
-  if (const char* o = getenv("GTE_SLIDE_AB")) L.slide_ab = atoi(o);
-  L.slide_store = slide_store_policy(E);
-  L.fused_rollout = hot_shape && !cfg.final_obs && cfg.log_steps == 0 && !(kv & GTE_KV_ROLLOUT_PER_STEP);
-  L.resident_rollout = p.W >= 2 && !(kv & GTE_KV_ROLLOUT_GATHER);
-  // envs per wavefront from registers: full waves once every SIMD has one (65 536 envs: 5.8 us per step
-  // with 64, 6.0 with 32, 9.2 with 16 — throughput of the scattered record / ring stores);
-  // small batches are a latency chain and two half-filled waves overlap better (4 096 envs:
-  // 3.5 us with 32, 3.9 with 64) — profiles/r02_state_epw.log
-  L.state_epw = (p.N >= 64 * 1024) ? 64 : 32;
-  return setup_affinity(E);
+  const gte_plan::Shape shape = plan_shape(E);
+  DeviceChip chip(E);
+  L = gte_plan::plan_create(shape, read_knobs(KNOBS_CREATE), chip);
+  p.epw = L.epw; p.lean_rows = L.lean_rows; p.hot_lds = L.hot_lds; p.debug = L.debug;
+  if (L.affinity_period > 0) {
+    const size_t N = (size_t)p.N;
+    std::vector<int32_t> slot_of_rank(N);
+    gte_plan::fill_slot_of_rank(shape, L.epw, slot_of_rank.data());
+    TRY(dev_alloc(E, &E->d_perm, N, false));
+    TRY(dev_alloc(E, &E->d_slot_of_rank, N, false));
+    TRY(dev_alloc(E, &E->d_bins, (size_t)2 * p.D * L.n_bins_per_ds));  // histogram (zero-filled) + cursors
+    if (hipMemcpy(E->d_slot_of_rank, slot_of_rank.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice) !=
+        hipSuccess)
+      return fail(GTE_ERR_HIP, "copying slot_of_rank failed");
+  }
+  return GTE_OK;
 }
 
 extern "C" {
@@ -523,11 +366,13 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
   *out = nullptr;
   TRY(validate(cfg));
-  TRY(require_device(cfg->device));
+  int n_cu = 0;
+  TRY(require_device(cfg->device, &n_cu));
   HIPCHK(hipSetDevice(cfg->device));
   gte_env* E = new (std::nothrow) gte_env();
   if (!E) return fail(GTE_ERR_OOM, "host allocation failed");
   E->cfg = *cfg;
+  E->n_cu = n_cu;
   memset(&E->p, 0, sizeof(Params));
   memset(&E->owned, 0, sizeof(gte_outputs));
   Params& p = E->p;
@@ -606,10 +451,8 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   p.positions = d_pos;
   p.ds = E->d_ds;
   E->owned.obs_elems_per_env = (int64_t)p.W * p.Fobs;
-  // the observation buffers come later (ensure_owned_obs / gte_bind_outputs); while the launch
-  // geometry is worked out below, a placeholder stands for "terminal observations are kept"
-  // (the LDS image has a FinalJob per env then, lds_bytes)
-  p.final_obs = cfg->final_obs ? (float*)(uintptr_t)16 : nullptr;
+  // the observation buffers come later (ensure_owned_obs / gte_bind_outputs)
+  p.final_obs = nullptr;
   p.obs = nullptr; p.reward = E->owned.reward; p.reward64 = E->owned.reward64;
   p.obs_rows = p.W; p.obs_head = 0; p.slide = 0;  // classic layout until gte_bind_sliding_obs
   p.terminated = E->owned.terminated; p.truncated = E->owned.truncated;
@@ -622,7 +465,7 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   // the zero-fills above ran on the null stream; the env's stream is non-blocking
   if (hipDeviceSynchronize() != hipSuccess)
     return create_failed(E, fail(GTE_ERR_HIP, "hipDeviceSynchronize failed after allocation"));
-  p.final_obs = nullptr;  // (placeholder above)
+  report_plan(E, "create");
   *out = E;
   return GTE_OK;
 }
@@ -715,18 +558,12 @@ static int finalize(gte_env* E) {
     if (E->h_ds[d].T > maxT) maxT = E->h_ds[d].T;
   }
   p.depth = p.persist ? maxT : p.W;
-  // The L2-affinity order pays when each XCD's 4 MiB L2 can hold its 1/8 share of the feature
-  // tables (config 3: 12.8 MB).  Tables far beyond the 32 MiB of aggregate L2 (config 5: 1.6 GB
-  // per GPU, L2 hit rate 0.16 either way) only pay for the re-sorts and for scattered
-  // observation stores: 39.4 us per step with the order, 36.8 without
-  // (profiles/r02_c5_sweep.log).  Automatic (affinity_period = 0) turns it off there.
-  if (E->plan.affinity_period > 0 && E->cfg.affinity_period == 0) {
-    size_t table_bytes = 0;
-    for (int d = 0; d < p.D; ++d) table_bytes += (size_t)E->h_ds[d].T * p.Fobs * sizeof(float);
-    if (table_bytes > ((size_t)64 << 20)) E->plan.affinity_period = 0;
-  }
+  size_t table_bytes = 0;
+  for (int d = 0; d < p.D; ++d) table_bytes += (size_t)E->h_ds[d].T * p.Fobs * sizeof(float);
+  gte_plan::affinity_after_upload(E->plan, plan_shape(E), table_bytes);
   TRY(dev_alloc(E, &p.ring, (size_t)p.N * p.depth * (p.nd ? p.nd : 1)));
   HIPCHK(hipDeviceSynchronize());
+  report_plan(E, "finalize");
   E->finalized = true;
   return GTE_OK;
 }
@@ -974,9 +811,9 @@ static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool captur
     if (slide) {
       E->p.obs_head += 1;
       // JOB_SLIDES shares bit 1 of the job record with dyn_persist's "zero the store" (gte_device.h):
-      // plan_launches never grants slide_rows with dyn_persist, and only this launch ever sets p.slide
+      // plan_create (gte_plan.h) never grants slide_rows with dyn_persist, and only this launch ever sets p.slide
       if (p.persist || p.final_obs)
-        return fail(GTE_ERR_STATE, "internal: a sliding step with dyn_persist or final_obs (plan_launches grants neither)");
+        return fail(GTE_ERR_STATE, "internal: a sliding step with dyn_persist or final_obs (the planner grants neither)");
       p.slide = L.full_windows ? 0 : 1;
     } else {
       E->p.obs_head = 0;
@@ -996,7 +833,7 @@ static int enqueue_step(gte_env* E, const StepTargets& t, int store, bool captur
   ledger().wrote(E, {obs, term, trunc}, capturing, FLAGS | WINDOW);
   // (hot_tu_covers: the isolated instantiations have no terminal records and no trajectory row)
   const bool hot = L.hot_tu && gte::hot_tu_covers(p);
-  if (p.slide) store = L.slide_store;  // one row per env: the policy of its own (plan_launches)
+  if (p.slide) store = L.slide_store;  // one row per env: the policy of its own (gte_plan.h)
   if (hot && store == 2)
     HIPCHK(gte::launch_step_hot(p, L.blocks, L.threads, gte::lds_bytes(p, L.stage), E->stream));
   else if (hot && store == 1)
@@ -1055,74 +892,9 @@ int gte_advance_log(gte_env* E, int64_t rows) {
   return GTE_OK;
 }
 
-// Window-resident kernel (gte_rollout.hip): each env's W-1 older rows stay in LDS for the
-// whole launch.  Geometry: E envs per workgroup such that (a) the newest rows fit the owner
-// threads, (b) as many envs as possible are resident per CU and (c) the workgroups fill a
-// whole number of rounds (each workgroup runs all K steps, so a part-filled last round costs
-// a full one): minimise rounds x max(phase A chain, the CU's observation bytes per step).
-static void choose_resident_epb(gte_env* E, const Params& p, int nt) {
-  LaunchPlan& L = E->plan;
-  L.resident_epb[nt] = -1;
-  hipDeviceProp_t prop;
-  const int64_t FV = p.Fobs / 4;
-  if (!L.resident_rollout || hipGetDeviceProperties(&prop, E->cfg.device) != hipSuccess) return;
-  double best = 0.0;
-  const char* force = getenv("GTE_RESIDENT_EPB");  // tuning: envs per group, no search
-  for (int e = 64; e >= 1; --e) {
-    if (force && atoi(force) != e) continue;
-    if ((int64_t)e * FV > gte::RES_NEW * gte::RES_OWNERS) continue;  // newest-row vectors the owner threads carry
-    if (gte::resident_lds_bytes(p, e) > gte::RES_LDS_MAX) continue;
-    const int per_cu = gte::resident_blocks_per_cu(p, e, nt);
-    if (per_cu <= 0) continue;
-    const int64_t slots = (int64_t)per_cu * prop.multiProcessorCount;
-    const int64_t wgs = ((int64_t)p.N + e - 1) / e;
-    // the launch is a work queue over the groups: "rounds" is a real number, at least one
-    const double rounds = wgs > slots ? (double)wgs / (double)slots : 1.0;
-    const double live = (double)(wgs < slots ? (wgs + prop.multiProcessorCount - 1) / prop.multiProcessorCount
-                                             : per_cu);  // workgroups sharing a CU
-    const double us_bw = live * e * (double)p.W * p.Fobs * 4.0 / 22.0e3;  // ~5.6 TB/s over 256 CUs
-    // a workgroup's barriers and its state wave's latency are hidden by the OTHER workgroups
-    // of its CU: prefer four of them
-    // (measured at config 3, profiles/r02_resident_epb.log: 4 per CU 27.7 us per step, 3: 28.9,
-    // 2: 30.3, 1: 47.2)
-    static const double kAlone[5] = {1.7, 1.7, 1.10, 1.05, 1.0};
-    const double alone = kAlone[per_cu < 4 ? per_cu : 4];
-    const double cost = rounds * (us_bw > 3.0 ? us_bw : 3.0) * alone;
-    if (getenv("GTE_DEBUG_GEOMETRY"))
-      fprintf(stderr, "[gte] resident rollout, %2d envs/workgroup: LDS %6zu B, %d workgroups/CU, "
-                      "%lld groups, %.2f round(s), cost %.1f\n", e, gte::resident_lds_bytes(p, e),
-              per_cu, (long long)wgs, rounds, cost);
-    if (best == 0.0 || cost < best * 0.999) {
-      best = cost;
-      L.resident_epb[nt] = e;
-      L.resident_slots[nt] = (int)slots;
-    }
-  }
-}
-
-// The gather-per-step rollout kernel is a long-running loop: a workgroup that is not
-// resident from the start runs all K steps after the others have finished.  It needs more
-// registers than the step kernel, so it gets its own workgroup size, the smallest that
-// keeps every workgroup resident.
-static void choose_rollout_epw(gte_env* E, const Params& p, int nt) {
-  LaunchPlan& L = E->plan;
-  L.rollout_epw = p.epw;
-  hipDeviceProp_t prop;
-  if (E->cfg.envs_per_wave != 0 || hipGetDeviceProperties(&prop, E->cfg.device) != hipSuccess) return;
-  for (int e = 1; e <= 16; ++e) {
-    Params q = p;
-    q.epw = e;
-    if ((int64_t)e * p.W * p.Fobs / 4 < 64) continue;
-    const int per_cu = gte::rollout_blocks_per_cu(q, nt);
-    const int64_t wgs = ((int64_t)p.N + gte::ROLLOUT_WAVES * e - 1) / (gte::ROLLOUT_WAVES * e);
-    if (per_cu > 0 && wgs <= (int64_t)per_cu * prop.multiProcessorCount) { L.rollout_epw = e; break; }
-    if (e == 16) L.rollout_epw = 16;  // more envs than one round holds: biggest workgroups
-  }
-}
-
 // GTE_DEBUG_GEOMETRY: name the path each gte_rollout call takes (the tests assert it)
 static void report_rollout_path(const char* path, int32_t n_steps) {
-  if (getenv("GTE_DEBUG_GEOMETRY")) fprintf(stderr, "[gte] rollout path: %s, %d steps\n", path, n_steps);
+  if (debug_geometry()) fprintf(stderr, "[gte] rollout path: %s, %d steps\n", path, n_steps);
 }
 
 // gte_rollout's launches, after its checks
@@ -1184,7 +956,11 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
   } else {
     TRY(age_order(E, n_steps));
     Params p = E->p;
-    if (L.resident_epb[nt] == 0) choose_resident_epb(E, p, nt);
+    if (L.resident_epb[nt] == 0) {
+      DeviceChip chip(E);
+      gte_plan::choose_resident_epb(E->plan, plan_shape(E), read_knobs(KNOBS_ROLLOUT), chip, nt);
+      report_plan(E, "resident");
+    }
     advance_term_slot(E, p);
     report_rollout_path(L.resident_epb[nt] > 0 ? "resident" : "gather", n_steps);
     if (L.resident_epb[nt] > 0) {
@@ -1202,7 +978,11 @@ static int rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gt
       const hipError_t le = gte::launch_rollout_resident(p, r, nt, blocks, E->stream);
       if (le != hipSuccess) return fail(GTE_ERR_HIP, "rollout launch: %s", hipGetErrorString(le));
     } else {
-      if (L.rollout_epw == 0) choose_rollout_epw(E, p, nt);
+      if (L.rollout_epw == 0) {
+        DeviceChip chip(E);
+        gte_plan::choose_rollout_epw(E->plan, plan_shape(E), chip, nt);
+        report_plan(E, "gather");
+      }
       p.epw = L.rollout_epw;
       const int r_blocks = gte::rollout_blocks(p.N, p.epw);
       gte::RolloutArgs r = {actions, n_steps, b->obs, b->reward, b->reward64, b->terminated,

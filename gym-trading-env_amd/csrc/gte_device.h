@@ -13,13 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/gte.h"
-
-// Wavefronts per workgroup of the step kernel (wave 0 runs phase A for the whole workgroup,
-// every wave gathers its own p.epw envs).  4 is the product; other values are for A/B builds
-// only (tools/waves_ab.sh): the rollout kernels assume 4.
-#ifndef GTE_WAVES
-#define GTE_WAVES 4
-#endif
+#include "gte_plan.h"  // GTE_WAVES, wavefronts per workgroup of the step kernel: the host's planner sizes launches by it
 
 namespace gte {
 

@@ -18,7 +18,7 @@ hipError_t GTE_HOT_NAME(launch_step_hot)(const Params& p, int blocks, int thread
 }
 
 // Workgroups of this kernel one CU holds at once (registers, LDS): the launch geometry sizes
-// the workgroups so that all of them are resident together (gte_api.hip, step_geometry).
+// the workgroups so that all of them are resident together (gte_plan.h, step_geometry).
 int GTE_HOT_NAME(hot_blocks_per_cu)(size_t smem) {
   int n = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(

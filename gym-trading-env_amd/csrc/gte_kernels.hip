@@ -159,12 +159,16 @@ hipError_t launch_rewind_queue(EnvRec* rec, int n, hipStream_t stream) {
 // ---------------------------------------------------------------------------
 // launchers (called from gte_api.hip)
 
-size_t lds_bytes(const Params& p, int stage) {
-  const size_t EPB = (size_t)p.epw * GTE_WAVES;
-  size_t b = EPB * (16 + 64 + 4 * GTE_MAX_DYN + 4) + (p.final_obs ? EPB * sizeof(FinalJob) : 0) +
-             (p.log.rows ? EPB * sizeof(LogRow) : 0);
-  if (stage) b += EPB * (size_t)p.W * (size_t)(p.nd ? p.nd : 1) * 4;
+size_t lds_image_bytes(int epw, int W, int nd, bool final_obs, bool log_row, int stage) {
+  const size_t EPB = (size_t)epw * GTE_WAVES;
+  size_t b = EPB * (16 + 64 + 4 * GTE_MAX_DYN + 4) + (final_obs ? EPB * sizeof(FinalJob) : 0) +
+             (log_row ? EPB * sizeof(LogRow) : 0);
+  if (stage) b += EPB * (size_t)W * (size_t)(nd ? nd : 1) * 4;
   return b;
+}
+
+size_t lds_bytes(const Params& p, int stage) {
+  return lds_image_bytes(p.epw, p.W, p.nd, p.final_obs != nullptr, p.log.rows != nullptr, stage);
 }
 
 template <int MODE>

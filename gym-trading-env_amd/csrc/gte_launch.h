@@ -9,23 +9,16 @@
 
 namespace gte {
 
-// lean copy loop (gte_step.h): window rows of one wave's envs the in-place resolve holds in registers,
-// and the vectors in flight per lane (a wave copies whole passes of 64 * GTE_LEAN_U)
-constexpr int LEAN_MAX_ROWS = 512;
-#ifndef GTE_LEAN_U
-#define GTE_LEAN_U 4
-#endif
-// rollout kernels (gte_rollout.hip): workgroups of four wavefronts, whatever GTE_WAVES is
-constexpr int ROLLOUT_WAVES = 4;
-// ... and how many of them give every env a lane at epw envs per wavefront
+// the limits the kernels share with the host's planner are defined there (gte_plan.h, with GTE_WAVES and GTE_LEAN_U)
+using gte_plan::LEAN_MAX_ROWS;
+using gte_plan::RES_LDS_MAX;
+using gte_plan::RES_NEW;
+using gte_plan::RES_OWNERS;
+using gte_plan::ROLLOUT_WAVES;
+// how many workgroups of the rollout kernels give every env a lane at epw envs per wavefront
 inline int rollout_blocks(int n_envs, int epw) {
   return (int)((((int64_t)n_envs + epw - 1) / epw + ROLLOUT_WAVES - 1) / ROLLOUT_WAVES);
 }
-// window-resident kernel: waves 1..3 (RES_OWNERS threads) carry the newest window rows of the workgroup's envs,
-// at most RES_NEW vectors each; a geometry with more of them than RES_NEW * RES_OWNERS would drop some
-constexpr int RES_NEW = 2;
-constexpr int RES_OWNERS = 192;
-constexpr size_t RES_LDS_MAX = 160 * 1024;  // LDS of a gfx950 CU: the most a workgroup's image may take
 constexpr size_t LDS_OPT_IN = 64 * 1024;    // dynamic LDS beyond this is opted into, per instantiation
 
 // 40-bit magic of the kernels' divisions by a launch constant (fastdiv40, gte_step.h)
@@ -37,6 +30,8 @@ hipError_t launch_step(const Params& p, int vec, int nt, bool coop, int stage, i
 hipError_t launch_reset(const Params& p, int vec, int nt, bool coop, int stage, int blocks, int threads,
                         hipStream_t stream);
 size_t lds_bytes(const Params& p, int stage);
+// the same from the fields it depends on (the planner asks before any of the buffers exists)
+size_t lds_image_bytes(int epw, int W, int nd, bool final_obs, bool log_row, int stage);
 hipError_t launch_add_orders(const Params& p, const int32_t* pos_index, const double* limit,
                              const uint8_t* persistent, hipStream_t stream);
 hipError_t launch_affinity_rebuild(const Params& p, int32_t* bins, int n_bins_per_ds, const int32_t* slot_of_rank,

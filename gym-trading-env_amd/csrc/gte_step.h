@@ -304,7 +304,7 @@ __device__ inline void phase_b(const Params& p, const WgLds& L, int s_first,
 //     counters instead of dividing;
 //   * no per-vector validity branches (the caller checks the whole wave once).
 // Results are the generic loop's, bit for bit (the parity suite runs through it).
-// (LEAN_MAX_ROWS and GTE_LEAN_U, the vectors in flight per lane, are in gte_launch.h: the host's geometry search uses them)
+// (LEAN_MAX_ROWS and GTE_LEAN_U, the vectors in flight per lane, are in gte_plan.h: the host's geometry search uses them)
 template <int ND>
 __device__ inline void resolve_dynamic_rows(const Params& p, const WgLds& L, int s_first, int n_env,
                                             int lane, uint64_t wnd_magic) {

@@ -96,7 +96,7 @@ ROLLOUT_MODES = {"resident": (0, True), "gather": (_abi.KV_ROLLOUT_GATHER, True)
 
 
 def hot_shape(f):
-    """The shape the fused rollout kernels are written for (gte_api.hip, plan_launches): 16-byte
+    """The shape the fused rollout kernels are written for (gte_plan.h, plan_create): 16-byte
     rows and dynamic columns staged raw in LDS (nd > 0, not dyn_persist), given a cooperative
     phase A (envs_per_wave <= 16)."""
     return f["Fobs"] % 4 == 0 and f["nd"] > 0 and not f["persist"]
@@ -324,12 +324,12 @@ def numeric_missing(traces):
 # their end, NaN valuations, special feature words) on shapes that are granted a slack, and sweep the
 # geometry of the slide loop itself (gte_step.h, phase_b_slide).
 def auto_slack(W):
-    """The automatic slack M of a window of W rows (gte_api.hip, plan_launches: 2 W / 5)."""
+    """The automatic slack M of a window of W rows (gte_plan.h, plan_create: 2 W / 5)."""
     return 2 * W // 5
 
 
 def slides(f):
-    """plan_launches' grant of a sliding buffer, restated: 16-byte rows with dynamic columns staged
+    """plan_create's grant of a sliding buffer (gte_plan.h), restated: 16-byte rows with dynamic columns staged
     raw in LDS (F_obs % 4 == 0, nd > 0, no dyn_persist), a window of at least one wave instruction
     of 16-byte vectors, and an automatic slack of at least one row.  (The traces have neither
     final_obs nor a log; cooperative phase A holds at up to 16 envs per wave.)"""

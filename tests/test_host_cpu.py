@@ -309,10 +309,12 @@ def test_every_struct_under_csrc_is_defined_in_exactly_one_file():
     for name, src in _csrc_sources().items():
         for s in re.findall(r"^\s*struct\s+(?:alignas\(\d+\)\s+)?(\w+)\s*\{", src, re.M):
             seen.setdefault(s, []).append(name)
-    assert {"RolloutArgs", "StateSoA", "LogPack", "Params", "EnvRec"} <= set(seen)
+    assert {"RolloutArgs", "StateSoA", "LogPack", "Params", "EnvRec", "LaunchPlan"} <= set(seen)
     assert {s: f for s, f in seen.items() if len(f) != 1} == {}
     for s in ("RolloutArgs", "StateSoA", "LogPack"):
         assert seen[s] == ["gte_launch.h"]
+    for s in ("LaunchPlan", "Shape", "Knobs", "Chip"):  # the planner's (tests/plan_check.cpp compiles them with g++)
+        assert seen[s] == ["gte_plan.h"]
 
 
 def test_gte_api_declares_no_gte_function_itself():
@@ -332,6 +334,28 @@ def test_gte_api_keeps_no_ledger_of_its_own():
     assert '#include "gte_ledger.h"' in api
     for gone in ("std::mutex", "lock_guard", "flags_sparse_ok", "slide_valid"):
         assert gone not in api, gone
+
+
+def test_gte_api_plans_nothing_itself():
+    """The launch rules are in gte_plan.h, fed with values: the host file asks the device for its properties once,
+    in require_device (whose CU count the planner's Chip hands on), reads the planner's environment switches only
+    where it fills Knobs (debug_geometry / read_knobs), and stands no placeholder pointer in for a Shape bool."""
+    api = _csrc_sources()["gte_api.hip"]
+    once = api.split("static int require_device(")[1].split("\n}\n")[0]
+    assert once.count("hipGetDeviceProperties") == 1 and api.count("hipGetDeviceProperties") == 1
+    assert "multiProcessorCount <= 0" in once  # gte_create refuses a device without compute units
+    knobs = api.split("static bool debug_geometry()")[1].split("static gte_plan::Knobs read_knobs(")[1].split("\n}\n")[0]
+    names = ("GTE_SLIDE_FULL_WINDOWS", "GTE_SLIDE_AB", "GTE_SLIDE_STORE", "GTE_AFFINITY_BINS", "GTE_RESIDENT_EPB")
+    for name in names:
+        assert knobs.count(f'getenv("{name}")') == 1 and api.count(f'"{name}"') == 1, name
+    assert api.count('"GTE_DEBUG_GEOMETRY"') == 1
+    assert 'static bool debug_geometry() { return getenv("GTE_DEBUG_GEOMETRY") != nullptr; }' in api
+    assert "(float*)(uintptr_t)16" not in api and "uintptr_t)16" not in api
+    for rule in ("step_geometry", "slide_store_policy", "setup_affinity", "choose_resident_epb(gte_env",
+                 "choose_rollout_epw(gte_env"):
+        assert f"static void {rule}" not in api and f"static int {rule}" not in api, rule
+    plan = _csrc_sources()["gte_plan.h"]  # (comments removed)
+    assert "getenv" not in plan and "hipGetDeviceProperties" not in plan
 
 
 def _makefile_srcs():
@@ -381,7 +405,7 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
     for name in units + sorted(h for h in src if h.endswith(".h") and h != "gte_launch.h"):
         text = src[name]
         # (gte_ledger.h: host bookkeeping only, no device code and no cross-file gte:: function)
-        assert name in ("gte_device.h", "gte_ledger.h") or "gte_launch.h" in _included(src, name), name
+        assert name in ("gte_device.h", "gte_ledger.h", "gte_plan.h") or "gte_launch.h" in _included(src, name), name
         for fn, (sig, is_def) in _signatures(text).items():
             assert is_def, f"{name} declares {fn} itself"
             assert fn not in defined, f"{fn} is defined in {name} and in {defined[fn]}"
@@ -400,10 +424,18 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
     makefile = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
     hdrs = re.search(r"^HDRS = (.*)$", makefile, re.M).group(1).split()
     assert sorted(h for h in src if h.endswith(".h")) == sorted(h for h in hdrs if "/" not in h)
-    # the ledger stands alone (tests/ledger_check.cpp compiles it with g++): nothing of csrc/, nothing of HIP
-    includes = re.findall(r'#\s*include\s*([<"][^>"]+[>"])', src["gte_ledger.h"])
-    assert includes and not any(i.startswith('"') or "hip" in i.lower() for i in includes), includes
-    assert "__global__" not in src["gte_ledger.h"] and "__device__" not in src["gte_ledger.h"]
+    # the ledger and the planner stand alone (tests/ledger_check.cpp, tests/plan_check.cpp compile them with g++):
+    # nothing of csrc/, nothing of HIP; the planner takes include/gte.h for the GTE_KV_* names
+    for alone, own in (("gte_ledger.h", ()), ("gte_plan.h", ('"../../include/gte.h"',))):
+        includes = re.findall(r'#\s*include\s*([<"][^>"]+[>"])', src[alone])
+        assert includes and not any((i.startswith('"') and i not in own) or "hip" in i.lower() for i in includes), includes
+        assert "__global__" not in src[alone] and "__device__" not in src[alone]
+        assert alone in hdrs
+    # the limits the kernels share with the planner have one definition each, in gte_plan.h
+    for const in ("LEAN_MAX_ROWS", "ROLLOUT_WAVES", "RES_NEW", "RES_OWNERS", "RES_LDS_MAX"):
+        assert [n for n, t in src.items() if re.search(rf"constexpr \w+ {const}\b", t)] == ["gte_plan.h"], const
+    for macro in ("GTE_WAVES", "GTE_LEAN_U"):
+        assert [n for n, t in src.items() if re.search(rf"#\s*define {macro}\b", t)] == ["gte_plan.h"], macro
 
 
 _HOLDS_VARIANT = re.compile(r"(?i:variant)|^kv$|^DENSE$|^ROLLOUT")  # names of things that hold kernel_variant bits
@@ -448,7 +480,7 @@ def _bare_variant_literals(text):
 
 def test_kernel_variant_bits_have_one_set_of_names():
     """`_abi.KV_*` mirror `enum gte_kernel_variant` of include/gte.h, and nobody passes or tests a
-    bit as a bare number: not plan_launches, not a test, not a Python tool (see
+    bit as a bare number: not plan_create (gte_plan.h), not a test, not a Python tool (see
     _bare_variant_literals for what counts; the forms this project used to write are tried first)."""
     hdr = open(os.path.join(ROOT, "include", "gte.h")).read()
     body = re.search(r"typedef enum gte_kernel_variant \{(.*?)\} gte_kernel_variant;", hdr, re.S).group(1)
@@ -457,10 +489,11 @@ def test_kernel_variant_bits_have_one_set_of_names():
     mirror = {k: v for k, v in vars(_abi).items() if k.startswith("KV_")}
     assert enum == mirror
     assert sorted(enum.values()) == [1, 2, 4, 64, 128, 256, 1024, 2048, 4096, 8192, 16384]
-    api = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "gte_api.hip")).read()
-    plan = api.split("static int plan_launches(gte_env* E) {")[1].split("\n}\n")[0]
+    planner = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "gte_plan.h")).read()
+    assert planner.count("kernel_variant;") == 1  # (besides the Shape member's declaration, which ends `= 0,`)
+    plan = planner.split("inline LaunchPlan plan_create(const Shape& p, const Knobs& k, Chip& chip) {")[1].split("\n}\n")[0]
     assert plan.count("kernel_variant") == 1  # read once, into `kv`; every use of `kv` tests named bits
-    uses = re.findall(r"\bkv\b\s*([^\n]{0,10})", re.sub(r"//[^\n]*", "", plan).split("kv = cfg.kernel_variant;")[1])
+    uses = re.findall(r"\bkv\b\s*([^\n]{0,10})", re.sub(r"//[^\n]*", "", plan).split("kv = p.kernel_variant;")[1])
     assert len(uses) >= 10 and all(re.match(r"&\s*\(?GTE_KV_", u) for u in uses), uses
 
     head = "import pytest\n"
