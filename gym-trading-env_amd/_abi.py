@@ -58,6 +58,16 @@ STRATEGY_METRICS = ("mean_reward", "sharpe", "mean_episode_return", "episode_sha
                     "worst_reward_sum")
 GTE_RANK_MAX = 256
 
+# enum gte_trade_metric: the score gte_rank_trade_stats orders strategies by
+TRADE_METRIC_WIN_RATE = 0
+TRADE_METRIC_PROFIT_FACTOR = 1
+TRADE_METRIC_EXPECTANCY = 2
+TRADE_METRIC_TRADE_SHARPE = 3
+TRADE_METRIC_WORST_TRADE = 4
+TRADE_METRIC_NEG_MAX_LOSS_STREAK = 5
+#: the same by name, in enum order (StrategyTradeStats.score / .top take either)
+TRADE_METRICS = ("win_rate", "profit_factor", "expectancy", "trade_sharpe", "worst_trade", "neg_max_loss_streak")
+
 
 class GteError(RuntimeError):
     """A libgte call failed (status code + the library's message)."""
@@ -144,6 +154,37 @@ class GteBacktestStats(C.Structure):
     """struct gte_backtest_stats (include/gte.h)."""
     _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in BACKTEST_FIELDS] + \
                [("reserved", C.c_int32 * 6)]
+
+
+#: struct gte_trade_stats (include/gte.h), in declaration order: one 128-byte record per env
+TRADE_FIELDS = [(n, "<f8") for n in ("open_value", "open_position", "last_valuation", "gross_profit", "gross_loss",
+                                     "ret_sq_sum", "best_trade", "worst_trade")] + \
+    [(n, "<i8") for n in ("exposure", "hold_sum")] + \
+    [(n, "<i4") for n in ("closed", "wins", "losses", "forced", "reversals", "dropped", "open_len", "max_len",
+                          "loss_streak", "max_loss_streak")]
+#: numpy view of an array of gte_trade_stats (gte_read_trade_stats)
+TRADE_DTYPE = TRADE_FIELDS + [("reserved", "<i4", (2,))]
+
+
+class GteTradeStats(C.Structure):
+    """struct gte_trade_stats (include/gte.h)."""
+    _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in TRADE_FIELDS] + \
+               [("reserved", C.c_int32 * 2)]
+
+
+#: struct gte_strategy_trade_stats (include/gte.h), in declaration order: one 128-byte record per strategy
+STRATEGY_TRADE_FIELDS = [(n, "<i8") for n in ("closed", "wins", "losses", "forced", "reversals", "exposure",
+                                              "hold_sum")] + \
+    [(n, "<f8") for n in ("gross_profit", "gross_loss", "ret_sq_sum", "best_trade", "worst_trade")] + \
+    [(n, "<i4") for n in ("max_len", "max_loss_streak", "envs", "envs_traded")]
+#: numpy view of an array of gte_strategy_trade_stats (gte_reduce_trade_stats)
+STRATEGY_TRADE_DTYPE = STRATEGY_TRADE_FIELDS + [("reserved", "<i4", (4,))]
+
+
+class GteStrategyTradeStats(C.Structure):
+    """struct gte_strategy_trade_stats (include/gte.h)."""
+    _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in STRATEGY_TRADE_FIELDS] + \
+               [("reserved", C.c_int32 * 4)]
 
 
 #: struct gte_strategy_stats (include/gte.h), in declaration order: one 128-byte record per strategy
@@ -341,6 +382,11 @@ SYMBOLS = {
     "gte_backtest_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
     "gte_bind_exit_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, _P(C.c_void_p)]),
     "gte_read_exit_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gte_track_trades": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
+    "gte_read_trade_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gte_reduce_trade_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gte_rank_trade_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
     "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,

@@ -27,6 +27,7 @@ class BacktestStats:
         self._env = env
         self._derived = {}
         self._map = getattr(env, "_backtest_map", None)  # what the call that made these records ran with
+        self._trades_ptr = getattr(env, "_trades_ptr", 0)  # the trade records, if that call kept them
         dev = env._t["obs"].device
         stride = np.dtype(_abi.BACKTEST_DTYPE).itemsize
         offsets = np.dtype(_abi.BACKTEST_DTYPE).fields
@@ -72,6 +73,15 @@ class BacktestStats:
             return self._lazy("total_return", lambda: (self.reward_sum / self._env.cfg.reward_param0).exp())
         raise ValueError("total_return = exp(reward_sum) needs a log-return reward (basic_reward_function or "
                          "scaled_log_return): the sum of clipped rewards is not the log of a return")
+
+    @property
+    def trade_stats(self):
+        """The round-trip trade statistics of the same transitions, a `TradeStats` — or None when the call
+        that made these records ran with trade tracking off (`BatchedTradingEnv.track_trades`)."""
+        if not self._trades_ptr:
+            return None
+        from .trade_stats import TradeStats
+        return self._lazy("trade_stats", lambda: TradeStats(self._env, self._trades_ptr, self.steps, self._map))
 
     def numpy(self) -> np.ndarray:
         """The whole record array on the host, one transfer: a structured array [N] with the

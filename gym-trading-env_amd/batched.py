@@ -247,6 +247,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._backtest_map = None  # (strategy tensor or None, S) of the last backtest_signals(); None after backtest()
         self._exits = None  # (rules tensor, rule_of_env tensor or None) bound by bind_exits, kept alive
         self._exit_state_ptr = 0  # device address of the exit states (0 before the first bind_exits)
+        self._trades_ptr = 0  # device address of the trade records while track_trades() is on, else 0
         for d, s in enumerate(self.datasets):
             self.upload_dataset(d, s)
 
@@ -1188,6 +1189,18 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._stepped()
         self._backtest_map = None  # (no strategies: by_strategy() needs its arguments)
         return BacktestStats(self, ptr.value)
+
+    def track_trades(self, on=True):
+        """Keep round-trip TRADE statistics next to the backtest statistics (`gte_track_trades`): while on,
+        `backtest()` and `backtest_signals()` maintain a second 128-byte record per env — closed trades, wins and
+        losses, gross profit and loss, best and worst trade, holding times, time in the market, losing streaks
+        (the rule is stated in include/gte.h) — reduced in registers while they step, and the `BacktestStats`
+        they return has them as `.trade_stats`.  Off (the default) every call launches exactly the kernels it
+        launches without this feature.  The first backtest call after a change clears both records whatever
+        its `resume` says.  Needs a `reset()` before it; waits for the env's stream."""
+        ptr = C.c_void_p()
+        _abi.check(self._lib, self._lib.gte_track_trades(self._h, 1 if on else 0, C.byref(ptr)))
+        self._trades_ptr = int(ptr.value or 0) if on else 0
 
     # -- signal tables: the action looked up on the device by the row an env stands on -----
     def bind_signals(self, signals, dataset=None):

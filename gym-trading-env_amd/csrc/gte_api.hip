@@ -94,6 +94,10 @@ struct gte_env {
   // of its own (the terminal valuation is read from them); allocated by the first call
   gte_backtest_stats* bt_stats = nullptr;
   EnvRec* bt_final_rec = nullptr;
+  // gte_track_trades: the trade records (allocated by the first call that turns tracking on), whether the
+  // backtest calls maintain them, and whether that changed since the last backtest call (which then clears)
+  gte_trade_stats* tr_stats = nullptr;
+  bool tr_on = false, tr_changed = false;
   // signal tables (gte_bind_signals): one descriptor per dataset (base null = none bound), the host
   // copy and the device array the kernels read; the lookup's output for gte_backtest_signals
   std::vector<gte::SignalTable> h_sig;
@@ -1039,12 +1043,17 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
     TRY(dev_alloc_late(E, &E->bt_stats, N));  // (its wait covers the fill before it too)
     clear = 1;
   }
+  // tracking was switched since the last call: both records start afresh, so that they cover the same transitions
+  if (E->tr_changed) clear = 1;
+  E->tr_changed = false;
+  gte_trade_stats* const trades = E->tr_on ? E->tr_stats : nullptr;
   // same-step mode: the terminal valuation comes from the terminal records, the env's or our own
   EnvRec* const terminal = E->p.final_rec ? E->p.final_rec : E->bt_final_rec;
   Params ps = E->p;
   ps.perm = nullptr;  // identity order, as in the state-only rollout: per-env loads and stores coalesce
   ps.final_rec = terminal;
-  hipError_t le = gte::launch_backtest_begin(ps, E->bt_stats, clear, E->stream);
+  hipError_t le = trades ? gte::launch_trade_begin(ps, E->bt_stats, trades, clear, E->stream)
+                         : gte::launch_backtest_begin(ps, E->bt_stats, clear, E->stream);
   if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   // one step as an ordinary launch (it also produces the observation and the terminal list), then
   // its results into the records
@@ -1055,7 +1064,8 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
     }
     const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
     TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->bt_final_rec));
-    const hipError_t fe = gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
+    const hipError_t fe = trades ? gte::launch_trade_fold(ps, E->bt_stats, trades, E->stream)
+                                 : gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
     if (fe != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(fe));
     return GTE_OK;
   };
@@ -1068,12 +1078,20 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   else report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
   if (n_steps > 1) {
     TRY(age_order(E, n_steps - 1));
-    le = signals && E->exits.rules
-             ? gte::launch_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, n_steps - 1,
-                                        L.state_epw, E->stream)
-         : signals ? gte::launch_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, n_steps - 1,
-                                                L.state_epw, E->stream)
-                 : gte::launch_backtest_summary(ps, actions, E->bt_stats, n_steps - 1, L.state_epw, E->stream);
+    if (trades)  // the same three launches with the trade record in registers as well (gte_trades.hip)
+      le = signals && E->exits.rules
+               ? gte::launch_trade_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, trades,
+                                                n_steps - 1, L.state_epw, E->stream)
+           : signals ? gte::launch_trade_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, trades,
+                                                        n_steps - 1, L.state_epw, E->stream)
+                     : gte::launch_trade_summary(ps, actions, E->bt_stats, trades, n_steps - 1, L.state_epw, E->stream);
+    else
+      le = signals && E->exits.rules
+               ? gte::launch_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, n_steps - 1,
+                                          L.state_epw, E->stream)
+           : signals ? gte::launch_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, n_steps - 1,
+                                                  L.state_epw, E->stream)
+                   : gte::launch_backtest_summary(ps, actions, E->bt_stats, n_steps - 1, L.state_epw, E->stream);
     if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   }
   return step_and_fold(n_steps - 1);
@@ -1321,6 +1339,19 @@ int gte_reduce_backtest_stats(gte_env* E, const gte_backtest_stats* records_devi
   return GTE_OK;
 }
 
+// the two candidate lists of the selection launches, grown to what S strategies need (gte_strategy.hip)
+static int rank_scratch(gte_env* E, int32_t n_strategies) {
+  for (int w = 0; w < 2; ++w) {
+    const int64_t need = gte::rank_scratch_entries(n_strategies, w);
+    if (E->rank_entries[w] >= need) continue;
+    const int64_t entries = need > 2 * E->rank_entries[w] ? need : 2 * E->rank_entries[w];
+    TRY(dev_alloc(E, &E->rank_score[w], (size_t)entries, false));
+    TRY(dev_alloc(E, &E->rank_index[w], (size_t)entries, false));
+    E->rank_entries[w] = entries;
+  }
+  return GTE_OK;
+}
+
 int gte_rank_strategies(gte_env* E, const gte_strategy_stats* stats_device, int32_t n_strategies, int32_t metric,
                         int64_t min_episodes, int32_t k, int32_t* top_index_device, double* top_score_device,
                         double* scores_device) {
@@ -1336,18 +1367,58 @@ int gte_rank_strategies(gte_env* E, const gte_strategy_stats* stats_device, int3
   if ((uintptr_t)scores_device & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
   if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_rank_strategies inside a stream capture");
   HIPCHK(hipSetDevice(E->cfg.device));
-  for (int w = 0; w < 2; ++w) {
-    const int64_t need = gte::rank_scratch_entries(n_strategies, w);
-    if (E->rank_entries[w] >= need) continue;
-    const int64_t entries = need > 2 * E->rank_entries[w] ? need : 2 * E->rank_entries[w];
-    TRY(dev_alloc(E, &E->rank_score[w], (size_t)entries, false));
-    TRY(dev_alloc(E, &E->rank_index[w], (size_t)entries, false));
-    E->rank_entries[w] = entries;
-  }
+  TRY(rank_scratch(E, n_strategies));
   const hipError_t e = gte::launch_rank_strategies(stats_device, n_strategies, metric, min_episodes, k,
                                                    top_index_device, top_score_device, scores_device, E->rank_score,
                                                    E->rank_index, E->stream);
   if (e != hipSuccess) return fail(GTE_ERR_HIP, "strategy ranking launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_reduce_trade_stats(gte_env* E, const gte_trade_stats* records_device, int32_t n_strategies,
+                           const int32_t* group_offsets_device, const int32_t* group_envs_device,
+                           gte_strategy_trade_stats* out_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  if (!out_device || ((uintptr_t)out_device & 15))
+    return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
+  if ((uintptr_t)records_device & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
+  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
+    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
+  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
+    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reduce_trade_stats inside a stream capture");
+  const gte_trade_stats* const records = records_device ? records_device : E->tr_stats;
+  if (!records) return fail(GTE_ERR_STATE, "gte_reduce_trade_stats before gte_track_trades: the env has no trade records yet");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const hipError_t e = gte::launch_reduce_trade_stats(records, E->p.N, n_strategies, E->cfg.env_id_base,
+                                                      group_offsets_device, group_envs_device, out_device, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "trade reduction launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_rank_trade_stats(gte_env* E, const gte_strategy_trade_stats* stats_device, int32_t n_strategies, int32_t metric,
+                         int64_t min_trades, int32_t k, int32_t* top_index_device, double* top_score_device,
+                         double* scores_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
+  if (metric < GTE_TRADE_METRIC_WIN_RATE || metric > GTE_TRADE_METRIC_NEG_MAX_LOSS_STREAK)
+    return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
+  if (!stats_device || ((uintptr_t)stats_device & 15))
+    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  if (!top_index_device || ((uintptr_t)top_index_device & 3) || !top_score_device || ((uintptr_t)top_score_device & 7))
+    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
+  if ((uintptr_t)scores_device & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_rank_trade_stats inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  TRY(rank_scratch(E, n_strategies));
+  hipError_t e = gte::launch_trade_scores(stats_device, n_strategies, metric, min_trades, scores_device,
+                                          E->rank_score[0], E->rank_index[0], E->stream);
+  if (e == hipSuccess)
+    e = gte::launch_rank_select(n_strategies, k, top_index_device, top_score_device, E->rank_score, E->rank_index,
+                                E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "trade ranking launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
 
@@ -1360,6 +1431,31 @@ int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backte
   HIPCHK(hipStreamSynchronize(E->stream));
   if (count > 0)
     HIPCHK(hipMemcpy(out, E->bt_stats + first, sizeof(gte_backtest_stats) * (size_t)count, hipMemcpyDeviceToHost));
+  return GTE_OK;
+}
+
+int gte_track_trades(gte_env* E, int32_t on, gte_trade_stats** records_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_trades before gte_reset");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_trades inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  if (on && !E->tr_stats) TRY(dev_alloc_late(E, &E->tr_stats, (size_t)E->p.N));
+  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the records
+  if ((on != 0) != E->tr_on) E->tr_changed = true;
+  E->tr_on = on != 0;
+  if (records_device) *records_device = E->tr_stats;
+  return GTE_OK;
+}
+
+int gte_read_trade_stats(gte_env* E, int32_t first, int32_t count, gte_trade_stats* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (!E->tr_stats) return fail(GTE_ERR_STATE, "gte_read_trade_stats before gte_track_trades");
+  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
+    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(hipStreamSynchronize(E->stream));
+  if (count > 0)
+    HIPCHK(hipMemcpy(out, E->tr_stats + first, sizeof(gte_trade_stats) * (size_t)count, hipMemcpyDeviceToHost));
   return GTE_OK;
 }
 

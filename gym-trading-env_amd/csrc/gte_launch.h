@@ -110,6 +110,24 @@ hipError_t launch_exit_summary(const Params& p, const SignalTable* tables, int S
                                const ExitRules& rules, gte_backtest_stats* stats, int n_steps, int epw,
                                hipStream_t stream);
 
+// --- gte_trades.hip: the backtest launches above with the trade statistics (gte_track_trades, include/gte.h)
+// kept as well: `trades` is the device array of the N trade records, next to `stats`
+// launch_backtest_begin for both records
+hipError_t launch_trade_begin(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades, int clear,
+                              hipStream_t stream);
+// launch_backtest_summary / launch_signal_summary / launch_exit_summary with the trade record in registers too
+hipError_t launch_trade_summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats,
+                                gte_trade_stats* trades, int n_steps, int epw, hipStream_t stream);
+hipError_t launch_trade_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                       gte_backtest_stats* stats, gte_trade_stats* trades, int n_steps, int epw,
+                                       hipStream_t stream);
+hipError_t launch_trade_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                     const ExitRules& rules, gte_backtest_stats* stats, gte_trade_stats* trades,
+                                     int n_steps, int epw, hipStream_t stream);
+// launch_backtest_fold for both records
+hipError_t launch_trade_fold(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades,
+                             hipStream_t stream);
+
 // --- gte_signals.hip: signal tables written on the device from indicator rules (gte_build_signals,
 // include/gte.h): table rows 0 .. n_rules-1, bytes 0 .. round_up(T, 16)-1 of each; the caller has checked
 // alignments and strides
@@ -142,6 +160,18 @@ int64_t rank_scratch_entries(int n_strategies, int which);
 hipError_t launch_rank_strategies(const gte_strategy_stats* stats, int n_strategies, int metric, int64_t min_episodes,
                                   int k, int32_t* top_index, double* top_score, double* scores, double* const* cand_score,
                                   int32_t* const* cand_index, hipStream_t stream);
+// its selection launches alone: the k best of the S candidates a score kernel left in list 0
+hipError_t launch_rank_select(int n_strategies, int k, int32_t* top_index, double* top_score, double* const* cand_score,
+                              int32_t* const* cand_index, hipStream_t stream);
+
+// --- gte_trade_strategy.hip: the same for trade records (gte_reduce_trade_stats, gte_rank_trade_stats,
+// include/gte.h); the caller has checked what it checks for the two launches above
+hipError_t launch_reduce_trade_stats(const gte_trade_stats* records, int n_envs, int n_strategies, int64_t env_id_base,
+                                     const int32_t* group_offsets, const int32_t* group_envs,
+                                     gte_strategy_trade_stats* out, hipStream_t stream);
+// the score kernel alone: candidate list 0 (cand_score, cand_index: S entries), launch_rank_select follows
+hipError_t launch_trade_scores(const gte_strategy_trade_stats* stats, int n_strategies, int metric, int64_t min_trades,
+                               double* scores, double* cand_score, int32_t* cand_index, hipStream_t stream);
 
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,

@@ -374,7 +374,17 @@ hipError_t launch_rank_strategies(const gte_strategy_stats* stats, int n_strateg
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(gte_strategy_score_kernel, dim3((unsigned)(((int64_t)n_strategies + 255) / 256)), dim3(256), 0, stream,
                      stats, n_strategies, metric, (long long)min_episodes, scores, cand_score[0], cand_index[0]);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : launch_rank_select(n_strategies, k, top_index, top_score, cand_score, cand_index, stream);
+}
+
+// the k best of the S candidates a score kernel left in list 0 (a score and an index each; NaN, -1: not ranked)
+hipError_t launch_rank_select(int n_strategies, int k, int32_t* top_index, double* top_score, double* const* cand_score,
+                              int32_t* const* cand_index, hipStream_t stream) {
+  if (!top_index || !top_score || n_strategies < 1 || k < 1 || k > GTE_RANK_MAX || k > SEL_TILE || !cand_score[0] ||
+      !cand_score[1] || !cand_index[0] || !cand_index[1])
+    return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
   // list 0 holds S candidates and list 1 what a pass over S leaves (rank_scratch_entries); every pass
   // keeps SEL_KEEP of each SEL_TILE, so a later pass fits whichever list it writes
   int64_t n = n_strategies;

@@ -617,6 +617,83 @@ int gte_bind_exit_rules(gte_env* env, const gte_exit_rule* rules_device, int32_t
  * GTE_ERR_STATE before the first gte_bind_exit_rules. */
 int gte_read_exit_state(gte_env* env, int32_t first, int32_t count, gte_exit_state* out);
 
+/* ---- TRADE STATISTICS: round-trip figures per env (closed trades, wins and losses, gross profit and loss,
+ * best and worst trade, holding time, time in the market, losing streaks), kept next to gte_backtest_stats
+ * while a backtest steps.  Opt-in (gte_track_trades); with tracking off every call launches exactly the
+ * kernels it launches without this feature.  This text is the specification; the reference has no counterpart.
+ *
+ * TIMELINE.  It is the one of gte_backtest_stats: reset rows (v_0, p_0) and transitions with v_t, the
+ * position VALUE p_t after the step (fills included) and the step's flags; what is and what is not a
+ * transition is stated there.  A TRADE is a maximal run of transitions of one episode with one constant
+ * non-zero position value.
+ *
+ * PER TRANSITION.  `ended` below is the `ended` of the env's gte_backtest_stats BEFORE the transition (the
+ * trade record has no bookkeeping fields of its own): a transition of an episode that has already ended
+ * changes nothing.  Otherwise, every floating operation one IEEE f64 operation as written, comparisons plain:
+ *
+ *     if (p_t != open_position) {
+ *         if (open_position != 0.0) {
+ *             if (p_t == 0.0) close(v_t);                      left to flat: v_t is v_{t-1} less the fees of leaving
+ *             else { close(last_valuation); reversals += 1; }  reversal / resize: the flip's fees count against the new trade
+ *         }
+ *         open_position = p_t;  open_value = last_valuation;  open_len = 0;
+ *     }
+ *     if (open_position != 0.0) { open_len += 1;  exposure += 1; }
+ *     if (flags != 0 && open_position != 0.0) { close(v_t);  forced += 1;  open_position = 0.0; }
+ *     last_valuation = v_t;
+ *
+ *     close(vc):  ret = vc / open_value - 1.0;  closed += 1;  hold_sum += open_len;
+ *                 if (open_len > max_len) max_len = open_len;
+ *                 if (ret > 0.0)      { wins += 1;  gross_profit += ret;  ret_sq_sum += ret * ret;  loss_streak = 0; }
+ *                 else if (ret < 0.0) { losses += 1;  gross_loss += ret;  ret_sq_sum += ret * ret;  loss_streak += 1;
+ *                                       if (loss_streak > max_loss_streak) max_loss_streak = loss_streak; }
+ *                 if (ret > best_trade) best_trade = ret;  if (ret < worst_trade) worst_trade = ret;
+ *
+ * A zero or NaN ret counts in `closed` only and touches neither a sum nor the streak; an infinite ret is a
+ * value like any other.  open_value is the valuation the trade was DECIDED at (like gte_exit_state.entry), so
+ * the fees of entering count against the trade.
+ *
+ * AT A RESET ROW of any kind (next-step, same-step inside a launch, gte_reset between calls):
+ *     if (open_position != 0.0) dropped += 1;      only a gte_reset in mid-episode: an episode's end closed its trade
+ *     open_position = p_0;  open_value = last_valuation = v_0;  open_len = 0;        loss_streak carries on
+ *
+ * CLEARING: all fields zero, best_trade = -inf, worst_trade = +inf, open_position = the env's current position
+ * value, open_value = last_valuation = its current portfolio_valuation.
+ *
+ * The record is defined by valuations, not rewards: it does not depend on the reward kind, and every f64
+ * field is a function of state the kernels reproduce by value. */
+typedef struct gte_trade_stats {     /* 128 bytes, eight 16-byte pieces */
+  double  open_value;       /* valuation the open trade was decided at                      */
+  double  open_position;    /* position value of the open trade; 0.0: none open             */
+  double  last_valuation;   /* valuation of the last row folded in, reset rows included     */
+  double  gross_profit;     /* sum of ret over closes with ret > 0, in close order          */
+  double  gross_loss;       /* sum of ret over closes with ret < 0  (<= 0)                  */
+  double  ret_sq_sum;       /* sum of ret * ret over those same closes                      */
+  double  best_trade;       /* largest ret  (-inf while none)                               */
+  double  worst_trade;      /* smallest ret (+inf while none)                               */
+  int64_t exposure;         /* transitions spent inside a trade                             */
+  int64_t hold_sum;         /* sum of open_len over closed trades                           */
+  int32_t closed, wins, losses, forced, reversals, dropped;
+  int32_t open_len, max_len, loss_streak, max_loss_streak;
+  int32_t reserved[2];      /* written as zero                                              */
+} gte_trade_stats;
+#ifdef __cplusplus
+static_assert(sizeof(gte_trade_stats) == 128, "trade statistics: eight 16-byte pieces");
+#endif
+/* on != 0: gte_backtest and gte_backtest_signals maintain BOTH records of every env from now on — with or
+ * without exit rules bound, on the fused path (gte_trades.hip: the from-registers kernels with the trade
+ * record in registers as well) and on the step-by-step path, in all three auto-reset modes — and the
+ * gte_backtest_stats records, the env state and the exit state come out bit for bit as with tracking off.
+ * on == 0: tracking stops; the trade records keep what they hold.  The FIRST backtest call after a change of
+ * `on` clears both records whatever its `clear` says, so the two records always cover the same transitions.
+ * The N trade records are allocated by the first call with on != 0; *records_device (may be NULL) receives
+ * their DEVICE address (NULL before they exist), which stays the same until gte_destroy.  The call waits for
+ * the env's stream and is refused before gte_reset and inside a stream capture (GTE_ERR_STATE). */
+int gte_track_trades(gte_env* env, int32_t on, gte_trade_stats** records_device);
+/* Trade records first .. first+count-1 into HOST memory: waits for the env's stream, one transfer.
+ * GTE_ERR_STATE before the first gte_track_trades(env, 1, ...). */
+int gte_read_trade_stats(gte_env* env, int32_t first, int32_t count, gte_trade_stats* out);
+
 /* ---- SIGNAL TABLES BUILT ON THE DEVICE from indicator rules: a parameter sweep passes a small bank of
  * indicators and one 32-byte rule per strategy, and the device writes the int8 [n_rules][T] table that
  * gte_bind_signals accepts — no host table, no host-to-device copy of it.
@@ -867,6 +944,62 @@ int gte_rank_strategies(gte_env* env, const gte_strategy_stats* stats_device, in
                         int32_t metric, int64_t min_episodes, int32_t k,
                         int32_t* top_index_device, double* top_score_device,
                         double* scores_device /* [n_strategies] or NULL */);
+
+/* ---- TRADE STATISTICS PER STRATEGY, AND THEIR RANKING: the N gte_trade_stats folded into one record per
+ * strategy and the best k by a per-trade score, as above for gte_backtest_stats.  MEMBERS, the skipping rule
+ * and the ONE FIXED ORDER of the f64 sums (eight interleaved accumulators) are those of
+ * gte_reduce_backtest_stats.  THE RECORD of strategy s over its members:
+ *   closed, wins, losses, forced, reversals, exposure, hold_sum   exact 64-bit sums of the members' counters;
+ *   gross_profit, gross_loss, ret_sq_sum   f64 sums in the fixed order;
+ *   best_trade    m = -inf; in member order: if (x > m) m = x;     worst_trade   m = +inf; if (x < m) m = x
+ *                 (plain comparisons, of equal values the first stays; a member without a closed trade holds
+ *                 -inf / +inf and never wins);
+ *   max_len, max_loss_streak   the largest of the members';
+ *   envs          members that are not skipped;      envs_traded   those of them with closed > 0.
+ * A strategy without members gets zero sums and counters, best -inf, worst +inf.  reserved is written as zero.
+ * The bits are the same for either launch geometry. */
+typedef struct gte_strategy_trade_stats {     /* 128 bytes, eight 16-byte pieces */
+  int64_t closed, wins, losses, forced, reversals, exposure, hold_sum;
+  double  gross_profit, gross_loss, ret_sq_sum;
+  double  best_trade, worst_trade;
+  int32_t max_len, max_loss_streak, envs, envs_traded;
+  int32_t reserved[4];
+} gte_strategy_trade_stats;
+#ifdef __cplusplus
+static_assert(sizeof(gte_strategy_trade_stats) == 128, "strategy trade statistics: eight 16-byte pieces");
+#endif
+/* records_device == NULL: the env's own N trade records (GTE_ERR_STATE before gte_track_trades allocated
+ * them); else a caller-owned DEVICE array of N gte_trade_stats, 16-byte aligned.  out_device, the group lists,
+ * the launch (one, on the env's stream, no host synchronisation) and the error codes are those of
+ * gte_reduce_backtest_stats. */
+int gte_reduce_trade_stats(gte_env* env, const gte_trade_stats* records_device, int32_t n_strategies,
+                           const int32_t* group_offsets_device, const int32_t* group_envs_device,
+                           gte_strategy_trade_stats* out_device);
+/* The score a strategy is ranked by, from its gte_strategy_trade_stats; every operation one IEEE f64
+ * operation as written (an int64 converts to f64 first), sqrt correctly rounded:
+ *   WIN_RATE             wins / closed
+ *   PROFIT_FACTOR        gross_profit / (0.0 - gross_loss)
+ *   EXPECTANCY           (gross_profit + gross_loss) / closed
+ *   TRADE_SHARPE         the SHARPE formulas of gte_strategy_metric over gross_profit + gross_loss, ret_sq_sum
+ *                        and closed:  m = (gross_profit + gross_loss) / closed;  q = ret_sq_sum / closed;
+ *                        v = q - m * m;  if (!(v > 0.0)) v = 0.0;  m / sqrt(v)
+ *   WORST_TRADE          worst_trade
+ *   NEG_MAX_LOSS_STREAK  -(double)max_loss_streak */
+typedef enum gte_trade_metric {
+  GTE_TRADE_METRIC_WIN_RATE = 0,
+  GTE_TRADE_METRIC_PROFIT_FACTOR = 1,
+  GTE_TRADE_METRIC_EXPECTANCY = 2,
+  GTE_TRADE_METRIC_TRADE_SHARPE = 3,
+  GTE_TRADE_METRIC_WORST_TRADE = 4,
+  GTE_TRADE_METRIC_NEG_MAX_LOSS_STREAK = 5
+} gte_trade_metric;
+/* gte_rank_strategies over trade records: strategy s is RANKED iff closed >= max(1, min_trades) and its score
+ * is not NaN.  One score launch, then the selection launches of gte_rank_strategies on the same library-owned
+ * scratch; order, ties, NaN, padding (-1 / NaN), k (1 <= k <= GTE_RANK_MAX, may exceed S), scores_device,
+ * alignments and error codes are those of gte_rank_strategies. */
+int gte_rank_trade_stats(gte_env* env, const gte_strategy_trade_stats* stats_device, int32_t n_strategies,
+                         int32_t metric, int64_t min_trades, int32_t k, int32_t* top_index_device,
+                         double* top_score_device, double* scores_device /* [n_strategies] or NULL */);
 
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);

@@ -1,0 +1,536 @@
+"""Trade statistics on the GPU (gte_track_trades, csrc/gte_trades.hip, csrc/gte_trade_strategy.hip) against
+tests/trade_model.py.  Needs an MI355X.
+
+On twelve traces the reference itself generated (each env tiled x16 at 4 envs per wave) the trade records are held
+to the model run over the REFERENCE's own columns — integer fields exactly, f64 fields by value, no tolerance:
+a trade record is a function of valuations and position values, which the kernels reproduce by value — on every
+path that maintains them: backtest(actions) resumed over the whole trace and cleared per random chunk,
+backtest_signals() with and without never-firing exit rules, all of it step by step, and same-step auto-reset.
+The 16 copies of an env give identical bytes, and the gte_backtest_stats records are byte for byte those of a
+twin env with tracking off.  Then: firing exit rules (fused == step by step == the model over a single-stepped
+twin's rows), a reset() in mid-trade, switching tracking on and off, the refusals, the fold per strategy and the
+ranking, and the example."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import backtest_trace as bt
+import replay
+import strategy_model as sm
+import test_gpu_backtest as tb
+import test_gpu_backtest_reference as ref
+import test_gpu_exits as tx
+import trade_model as tm
+from gym_trading_env_amd import _abi
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+TILE = ref.TILE
+NAMES = ("c1_btc_example", "drawdown_done", "limit_orders", "multidataset_k3", "no_autoreset", "numeric_03",
+         "numeric_07", "numeric_09", "slide_03", "sweep_15", "sweep_17", "reward_clipped_nodyn")
+traces = ref.traces
+
+
+def _assert_trades(got, want, tag):
+    """TRADE_DTYPE [E] against model records: integers exactly, f64 by value."""
+    assert got.dtype == tm.TRADE and not got["reserved"].any(), tag
+    bad = tm.same_records(got, tm.as_array(want))
+    assert not bad, (tag, {f: [(e, got[f][e], want[e][f]) for e in envs[:3]] for f, envs in bad.items()})
+
+
+class Pair:
+    """A tracked env and its untracked twin, both driven through trace g like ref.Replayed drives one."""
+
+    def __init__(self, g, monkeypatch, capfd, kernel_variant=0, autoreset="trace"):
+        self.on = ref.Replayed(g, monkeypatch, capfd, kernel_variant, autoreset)
+        self.off = ref.Replayed(g, monkeypatch, capfd, kernel_variant, autoreset)
+        self.on.env.track_trades()
+        self.g, self.E = g, self.on.E
+
+    def both(self, f):
+        f(self.on)
+        f(self.off)
+
+    def _records(self, run, what, n, tag):
+        """run(env) -> BacktestStats on both; the statistics records byte for byte -> the trade records [E]"""
+        stats = run(self.on.env)
+        self.on._path(what, n, tag)
+        plain = run(self.off.env)
+        self.off._path(what, n, tag + " untracked")
+        assert plain.trade_stats is None
+        a, b = ref._one(stats.numpy(), tag + " records"), ref._one(plain.numpy(), tag + " untracked records")
+        assert a.tobytes() == b.tobytes(), f"{tag}: tracking changed the statistics records"
+        trades = stats.trade_stats
+        host = trades.numpy()
+        np.testing.assert_array_equal(trades.closed.cpu().numpy(), host["closed"])
+        np.testing.assert_array_equal(trades.exposure.cpu().numpy(), host["exposure"])
+        return ref._one(host, tag + " trade records")
+
+    def backtest(self, actions, resume, tag):
+        import torch
+        acts = torch.from_numpy(np.ascontiguousarray(np.tile(actions, (1, TILE)).astype(np.int32))).cuda()
+        return self._records(lambda env: env.backtest(acts, resume=resume), "", acts.shape[0], tag)
+
+    def backtest_signals(self, n, resume, tag):
+        return self._records(lambda env: env.backtest_signals(n, resume=resume), "signals ", n, tag)
+
+    def assert_same_env(self, tag):
+        for f in tb.STATE:
+            np.testing.assert_array_equal(self.on.env.state(f), self.off.env.state(f), err_msg=f"{tag}: {f}")
+
+    def close(self):
+        self.both(lambda x: x.close())
+
+
+def _chunk_model(g, start, stop):
+    """Per env: the trade record of calls [start, stop), cleared at the row of call start - 1."""
+    ended = bt.ended_at(g, start - 1)
+    steps = bt._trace_steps(g)
+    return [tm.run(tm.new_record(g["portfolio_valuation"][start - 1, e], g["position"][start - 1, e], ended=bool(ended[e])),
+                   steps[e][start - 1:stop - 1]) for e in range(g["op"].shape[1])]
+
+
+def _run_actions(g, name, monkeypatch, capfd, kernel_variant, path):
+    K = g["op"].shape[0]
+    x = Pair(g, monkeypatch, capfd, kernel_variant)   # cleared per chunk
+    y = Pair(g, monkeypatch, capfd, kernel_variant)   # one record continued through the same chunks
+    got_y = None
+    for start, stop in bt.chunks(g, np.random.default_rng(ref._seed(name)), bt.longest(name)):
+        tag = f"{name} {path} calls [{start}, {stop})"
+        x.both(lambda r: r.orders(start))
+        y.both(lambda r: r.orders(start))
+        _assert_trades(x.backtest(g["action"][start:stop], False, tag), _chunk_model(g, start, stop), tag)
+        got_y = y.backtest(g["action"][start:stop], start > 1, tag + " resumed")
+    tag = f"{name} {path} resumed over the whole trace"
+    whole = _chunk_model(g, 1, K)
+    _assert_trades(got_y, whole, tag)
+    x.assert_same_env(tag)
+    x.close()
+    y.close()
+    return whole
+
+
+def _run_signals(g, name, monkeypatch, capfd, kernel_variant, path, exits=False):
+    import torch
+    K, E = g["op"].shape
+    P = len(g["cfg"]["positions"])
+    end = ref._exit_replay_end(g) if exits else K
+    assert end > 1
+    x = Pair(g, monkeypatch, capfd, kernel_variant)
+    rng = np.random.default_rng(ref._seed(name))
+    spans = bt.table_spans(g, rng, 1, end)
+    if exits:
+        rules = torch.from_numpy(ref._never_firing_rules(P).view(np.uint8).reshape(-1, 32).copy()).cuda()
+        x.both(lambda r: r.env.bind_exits(rules))
+    cuts = sorted({c for c in [s for s, _ in bt.chunks(g, rng, bt.longest(name))] + [s[1] for s in spans] if c < end})
+    first_of = {s[1]: s[0] for s in spans}
+    closed = 0
+    for start, stop in zip(cuts, cuts[1:] + [end]):
+        tag = f"{name} {path} calls [{start}, {stop})"
+        if start in first_of:
+            x.both(lambda r: r.env.bind_signals(first_of[start]))
+        x.both(lambda r: r.orders(start))
+        want = _chunk_model(g, start, stop)
+        _assert_trades(x.backtest_signals(stop - start, False, tag), want, tag)
+        closed += sum(r["closed"] for r in want)
+    if exits:
+        a, b = x.on.env.exit_state().numpy(), x.off.env.exit_state().numpy()
+        assert a.tobytes() == b.tobytes(), f"{name} {path}: tracking changed the exit state"
+    x.assert_same_env(f"{name} {path}")
+    assert closed > 0
+    x.close()
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_trades_actions(name, traces, monkeypatch, capfd):
+    whole = _run_actions(traces(name), name, monkeypatch, capfd, 0, "actions")
+    assert sum(r["closed"] for r in whole) >= 100 and sum(r["forced"] for r in whole) >= 3
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_trades_signals(name, traces, monkeypatch, capfd):
+    _run_signals(traces(name), name, monkeypatch, capfd, 0, "signals")
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_trades_signals_with_exit_rules_that_never_fire(name, traces, monkeypatch, capfd):
+    _run_signals(traces(name), name, monkeypatch, capfd, 0, "signals+exits", exits=True)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_trades_actions_per_step(name, traces, monkeypatch, capfd):
+    _run_actions(traces(name), name, monkeypatch, capfd, _abi.KV_ROLLOUT_PER_STEP, "actions per-step")
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_trades_signals_per_step(name, traces, monkeypatch, capfd):
+    _run_signals(traces(name), name, monkeypatch, capfd, _abi.KV_ROLLOUT_PER_STEP, "signals per-step")
+
+
+SAME_STEP = [n for n in NAMES if ref._same_step(n)]
+
+
+@pytest.mark.parametrize("name", SAME_STEP)
+def test_trades_same_step(name, traces, monkeypatch, capfd):
+    """The same-step branch of trade_step: the terminal valuation and position from the terminal record, then the
+    reset row, inside one step."""
+    g = traces(name)
+    steps, actions, step_call, state_call = bt.same_step_timeline(g)
+    n, E = actions.shape
+    x = Pair(g, monkeypatch, capfd, autoreset="same_step")
+    whole = Pair(g, monkeypatch, capfd, autoreset="same_step")
+    rng = np.random.default_rng(ref._seed(name))
+
+    def records(j0, j1):
+        at = state_call[j0 - 1] if j0 else np.zeros(E, np.int64)
+        return [tm.run(tm.new_record(g["portfolio_valuation"][at[e], e], g["position"][at[e], e]), steps[e][j0:j1])
+                for e in range(E)]
+
+    j0 = 0
+    while j0 < n:
+        j1 = min(n, j0 + int(rng.integers(1, bt.longest(name) + 1)))
+        tag = f"{name} same-step steps [{j0}, {j1})"
+        _assert_trades(x.backtest(actions[j0:j1], False, tag), records(j0, j1), tag)
+        j0 = j1
+    tag = f"{name} same-step, one call of {n} steps"
+    want = records(0, n)
+    _assert_trades(whole.backtest(actions, False, tag), want, tag)
+    assert sum(r["forced"] for r in want) >= 1 and all(r["dropped"] == 0 for r in want)
+    x.close()
+    whole.close()
+
+
+# ---- firing exit rules: fused == step by step == the model over a single-stepped twin's rows ------------------
+
+class _DeviceLookup:
+    """The [K, N] actions of the single-stepped twin: its own signal_actions() (exits decided on the device)
+    when step k is about to run (what tb._single_step_columns asks for)."""
+
+    def __init__(self, env, strategy, steps):
+        self.env, self.strategy, self.shape = env, strategy, (steps,)
+
+    def __getitem__(self, k):
+        return self.env.signal_actions(strategy=self.strategy).clone()
+
+
+def _start_records(env):
+    positions = np.asarray(env.positions, np.float64)
+    return [tm.new_record(v, positions[p], ended=bool(nr)) for v, p, nr in
+            zip(env.state("portfolio_valuation"), env.state("position_index"), env.state("needs_reset"))]
+
+
+@pytest.mark.parametrize("mode", tb.MODES, ids=lambda m: str(m))
+@pytest.mark.parametrize("explicit", [False, True])
+def test_trades_with_firing_exit_rules(mode, explicit):
+    import torch
+    N, K, n_rules = tx.N, tx.K, 7
+    data, tables = tx._data(31), tx._table(21)
+    kw = dict(tx.BASE, windows=5)
+    rules = tx._rules(n_rules)
+    strategy, rule_of_env = tx._maps(explicit, n_rules)
+    envs = dict(single=tb._env(data, N, mode, final_obs=(mode == "same_step"), **kw), fused=tb._env(data, N, mode, **kw),
+                stepwise=tb._env(data, N, mode, kernel_variant=_abi.KV_ROLLOUT_PER_STEP, **kw),
+                untracked=tb._env(data, N, mode, **kw))
+    gen = torch.Generator(device="cuda")
+    for name, e in envs.items():
+        e.bind_signals(tables)
+        e.reset()
+        gen.manual_seed(17)
+        tx._phase_one(e, gen)
+        e.bind_exits(tx._bindable(rules), rule_of_env=rule_of_env)
+        if name not in ("single", "untracked"):
+            e.track_trades()
+    recs = _start_records(envs["single"])
+    _, steps = tb._single_step_columns(envs["single"], _DeviceLookup(envs["single"], strategy, K))
+    want = [tm.run(r, s) for r, s in zip(recs, steps)]
+    tag = f"firing exits {mode} explicit={explicit}"
+    got = {k: envs[k].backtest_signals(K, strategy=strategy) for k in ("fused", "stepwise", "untracked")}
+    fused, stepwise = got["fused"].trade_stats.numpy(), got["stepwise"].trade_stats.numpy()
+    assert fused.tobytes() == stepwise.tobytes(), f"{tag}: fused and step-by-step trade records differ"
+    _assert_trades(fused, want, tag)
+    assert got["fused"].numpy().tobytes() == got["untracked"].numpy().tobytes() == got["stepwise"].numpy().tobytes()
+    assert envs["fused"].exit_state().numpy().tobytes() == envs["untracked"].exit_state().numpy().tobytes()
+    tb._assert_same_env(envs["single"], envs["fused"], tag)
+    assert envs["fused"].exit_state().numpy()["exits"].sum() > 0
+    tot = {f: sum(r[f] for r in want) for f in ("closed", "wins", "losses", "forced", "reversals")}
+    assert tot["closed"] > N and tot["wins"] > 0 and tot["losses"] > 0 and tot["reversals"] > 0, tot
+    assert tot["forced"] > (0 if mode is None else N // 2), tot
+    # the derived figures are the records'
+    t, h = got["fused"].trade_stats, fused
+    with np.errstate(all="ignore"):
+        assert replay.same_value(t.win_rate.cpu().numpy(), h["wins"] / h["closed"]).all()
+        assert replay.same_value(t.profit_factor.cpu().numpy(), h["gross_profit"] / (0.0 - h["gross_loss"])).all()
+        assert replay.same_value(t.expectancy.cpu().numpy(), (h["gross_profit"] + h["gross_loss"]) / h["closed"]).all()
+        assert replay.same_value(t.mean_hold.cpu().numpy(), h["hold_sum"] / h["closed"]).all()
+        assert replay.same_value(t.exposure_share.cpu().numpy(), h["exposure"] / got["fused"].numpy()["steps"]).all()
+    for e in envs.values():
+        e.close()
+
+
+# ---- resets between calls, switching, refusals ------------------------------------------------------------------
+
+def _plain_twins(mode, N=129, **over):
+    import torch
+    kw = dict(tb.BASE, max_episode_duration=12, **over)
+    a, b = tb._twins(tb._data(1, 60, 6)[:2], N, mode, **kw)
+    tb._both(a, b, lambda e: e.reset())
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(17)
+    tb._phase(a, b, N, 3, gen)
+    return a, b, gen
+
+
+@pytest.mark.parametrize("mode", tb.MODES, ids=lambda m: str(m))
+def test_reset_between_resumed_chunks_drops_the_open_trade(mode):
+    import torch
+    N, K = 129, 4   # (12-step episodes: after the 6 steps of _plain_twins and 4 more, most envs are in mid-episode)
+    a, b, gen = _plain_twins(mode)
+    b.track_trades()
+    acts = torch.randint(-1, 3, (2, K, N), dtype=torch.int32, device="cuda", generator=gen)
+    recs = _start_records(a)
+    _, steps = tb._single_step_columns(a, acts[0])
+    first = b.backtest(acts[0]).trade_stats.numpy()
+    mask = (np.arange(N) % 2 == 0).astype(np.uint8)
+    tb._both(a, b, lambda e: e.reset(mask=mask))
+    positions = np.asarray(a.positions, np.float64)
+    for e in np.flatnonzero(mask):
+        steps[e].append(dict(stepped=False, reset=True, v0=a.state("portfolio_valuation")[e],
+                             p0=positions[a.state("position_index")[e]]))
+    _, more = tb._single_step_columns(a, acts[1])
+    want = [tm.run(r, s + m) for r, s, m in zip(recs, steps, more)]
+    stats = b.backtest(acts[1], resume=True)
+    tag = f"reset between chunks {mode}"
+    _assert_trades(stats.trade_stats.numpy(), want, tag)
+    dropped = stats.trade_stats.numpy()["dropped"]
+    np.testing.assert_array_equal(dropped, ((first["open_position"] != 0) & (mask != 0)).astype(np.int32))
+    assert dropped.sum() > 10
+    tb._assert_same_env(a, b, tag)
+    a.close()
+    b.close()
+
+
+def test_switching_tracking_clears_both_records():
+    import torch
+    N, K = 129, 5
+    a, b, gen = _plain_twins("next_step")
+    acts = torch.randint(-1, 3, (3, K, N), dtype=torch.int32, device="cuda", generator=gen)
+    assert a.backtest(acts[0]).trade_stats is None and b.backtest(acts[0]).trade_stats is None
+    tb._both(a, b, lambda e: e.track_trades())
+    on_a, on_b = a.backtest(acts[1], resume=True), b.backtest(acts[1], resume=False)   # the switch clears either way
+    assert on_a.numpy().tobytes() == on_b.numpy().tobytes()
+    assert on_a.trade_stats.numpy().tobytes() == on_b.trade_stats.numpy().tobytes()
+    assert (on_a.steps <= K).all() and (on_a.trade_stats.exposure <= K).all() and int(on_a.trade_stats.exposure.sum()) > 0
+    before = on_a.steps.clone()
+    more, same = a.backtest(acts[2], resume=True), b.backtest(acts[2], resume=True)     # no switch: the records go on
+    assert (more.steps >= before).all() and (more.steps > before).any() and more.trade_stats is not None
+    assert more.numpy().tobytes() == same.numpy().tobytes()
+    assert more.trade_stats.numpy().tobytes() == same.trade_stats.numpy().tobytes()
+    a.track_trades(False)
+    off, cleared = a.backtest(acts[2], resume=True), b.backtest(acts[2], resume=False)  # switched off: cleared again
+    assert off.trade_stats is None and off.numpy().tobytes() == cleared.numpy().tobytes()
+    a.close()
+    b.close()
+
+
+def test_refusals():
+    import torch
+    from gym_trading_env_amd.batched import BatchedTradingEnv
+    feat, close = tb._data(1, 60, 6)[:2]
+    env = BatchedTradingEnv((feat, close), num_envs=64, positions=[-1, 0, 1], windows=3, initial_position=0)
+    lib, h = env._lib, env._h
+    err = lambda: lib.gte_last_error().decode()
+    ptr = C.c_void_p()
+    with pytest.raises(_abi.GteError, match="before gte_reset"):
+        env.track_trades()
+    env.reset()
+    rec = np.empty(64, dtype=tm.TRADE)
+    assert lib.gte_read_trade_stats(h, 0, 64, rec.ctypes.data) == _abi.GTE_ERR_STATE
+    assert "before gte_track_trades" in err()
+    out = torch.empty((3, 128), dtype=torch.uint8, device="cuda")
+    assert lib.gte_reduce_trade_stats(h, None, 3, None, None, C.c_void_p(out.data_ptr())) == _abi.GTE_ERR_STATE
+    assert "before gte_track_trades" in err()
+    assert lib.gte_track_trades(None, 1, C.byref(ptr)) == _abi.GTE_ERR_INVALID
+    seen = []
+
+    def body(i):
+        try:
+            env.track_trades()
+        except _abi.GteError as e:
+            seen.append(e)
+            raise
+    with pytest.raises(Exception):
+        env.capture_steps(body, 2)
+    torch.cuda.synchronize()
+    assert len(seen) == 1 and seen[0].status == _abi.GTE_ERR_STATE and "stream capture" in str(seen[0])
+    env.track_trades()
+    stats = env.backtest([[2] * 64, [None] * 64, [1] * 64])   # flat -> long, hold, -> flat
+    t = stats.trade_stats
+    assert (t.closed == 1).all() and (t.exposure == 2).all() and (t.hold_sum == 2).all()
+    assert lib.gte_read_trade_stats(h, 60, 5, rec.ctypes.data) == _abi.GTE_ERR_INVALID and "outside" in err()
+    idx = torch.empty(4, dtype=torch.int32, device="cuda")
+    top = torch.empty(4, dtype=torch.float64, device="cuda")
+    args = (C.c_void_p(idx.data_ptr()), C.c_void_p(top.data_ptr()), None)
+    assert lib.gte_rank_trade_stats(h, C.c_void_p(out.data_ptr()), 3, 6, 1, 4, *args) == _abi.GTE_ERR_INVALID
+    assert "metric 6 unknown" in err()
+    assert lib.gte_rank_trade_stats(h, C.c_void_p(out.data_ptr()), 3, 0, 1, 0, *args) == _abi.GTE_ERR_INVALID
+    assert lib.gte_reduce_trade_stats(h, None, 0, None, None, C.c_void_p(out.data_ptr())) == _abi.GTE_ERR_INVALID
+    assert lib.gte_reduce_trade_stats(h, None, 3, C.c_void_p(idx.data_ptr()), None, C.c_void_p(out.data_ptr())) == _abi.GTE_ERR_INVALID
+    with pytest.raises(ValueError, match="n_strategies"):
+        t.by_strategy()
+    with pytest.raises(ValueError, match="unknown metric"):
+        t.by_strategy(n_strategies=3).top(2, metric="sharpe")
+    env.close()
+
+
+# ---- per strategy, and the ranking ------------------------------------------------------------------------------
+
+N_FOLD = 1000
+
+
+@pytest.fixture(scope="module")
+def fold_env():
+    from gym_trading_env_amd.batched import BatchedTradingEnv
+    feat, close = tb._data(1, 60, 6)[:2]
+    env = BatchedTradingEnv((feat, close), num_envs=N_FOLD, positions=[-1, 0, 1], windows=None)
+    yield env
+    env.close()
+
+
+def _reduce(env, rec, S, groups=None):
+    """gte_reduce_trade_stats over caller-held records: the default map, or the CSR lists of `groups`"""
+    import torch
+    dev = env._t["obs"].device
+    d_rec = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), 128).copy()).to(dev)
+    out = torch.full((S, 128), 0xAB, dtype=torch.uint8, device=dev)
+    lists = (None, None)
+    if groups is not None:
+        offsets, members = sm.csr(groups)
+        keep = torch.from_numpy(offsets).to(dev), torch.from_numpy(np.append(members, 0).astype(np.int32)).to(dev)
+        lists = tuple(C.c_void_p(t.data_ptr()) for t in keep)
+    torch.cuda.synchronize()
+    _abi.check(env._lib, env._lib.gte_reduce_trade_stats(env._h, C.c_void_p(d_rec.data_ptr()), S, *lists,
+                                                         C.c_void_p(out.data_ptr())))
+    env.synchronize()
+    return out.cpu().numpy().view(tm.STRATEGY_TRADE).reshape(S).copy()
+
+
+def _check_fold(got, want, what):
+    if not tm.same_bytes(got, want):
+        bad = [(s, n) for s in range(len(want)) for n in want.dtype.names
+               if tm.canonical(got[s:s + 1])[n].tobytes() != tm.canonical(want[s:s + 1])[n].tobytes()]
+        pytest.fail(f"{what}: {len(bad)} fields differ, first {bad[:5]}: {[(got[n][s], want[n][s]) for s, n in bad[:5]]}")
+
+
+@pytest.mark.parametrize("S", [7, 40])
+def test_fold_equals_the_model(fold_env, S):
+    """N = 1 000: S = 7 runs a workgroup per strategy (N >= 32 S), S = 40 a lane per strategy; N % S != 0 for
+    S = 7.  The default map (the env's own), then an explicit one with an empty strategy and ids outside [0, N)
+    that keep their place — lists of 0 .. 600 members through the same kernel (600: 75 places per accumulator, a
+    second pass of the 64 lanes of its wavefront)."""
+    rec = tm.craft_records(N_FOLD, seed=S)
+    got = _reduce(fold_env, rec, S)
+    _check_fold(got, tm.reduce_loop(rec, sm.default_groups(N_FOLD, S)), f"default map S={S}")
+    assert not got["reserved"].any() and int(got["envs"].sum()) == N_FOLD
+    # explicit lists: sizes around the 8 accumulators and the 64 lanes, an empty one, ids outside [0, N)
+    rng = np.random.default_rng(S)
+    sizes = ([0, 1, 7, 8, 9, 63, 600] if S == 7 else [0, 1, 7, 8, 9, 15, 16, 17, 63, 64, 65] + [12] * 29)
+    assert len(sizes) == S and (N_FOLD >= 32 * S) == (S == 7)
+    groups = [rng.choice(N_FOLD, n, replace=False).tolist() for n in sizes]
+    groups[-1][3], groups[-1][9], groups[-2][0] = -1, N_FOLD, 2 ** 31 - 1
+    got = _reduce(fold_env, rec, S, groups)
+    want = tm.reduce_loop(rec, groups)
+    _check_fold(got, want, f"explicit lists S={S}")
+    assert got["envs"][0] == 0 and got["best_trade"][0] == -np.inf and got["worst_trade"][0] == np.inf
+    assert got["envs"][-1] == sizes[-1] - 2 and (got["envs_traded"] <= got["envs"]).all()
+
+
+@pytest.mark.parametrize("S,k,min_trades", [(1, 1, 0), (16, 5, 1), (300, 256, 0), (300, 7, 40), (3000, 256, 2), (3, 9, 1)])
+def test_scores_and_ranking_equal_the_model(fold_env, S, k, min_trades):
+    """Crafted strategy records (duplicates, +-0.0, +-inf, NaN scores, strategies below min_trades): every score bit
+    for bit, and the k best given those scores; k > S pads with -1 / NaN."""
+    import torch
+    t = tm.craft_stats(S, seed=S)
+    dev = fold_env._t["obs"].device
+    d = torch.from_numpy(t.view(np.uint8).reshape(S, 128).copy()).to(dev)
+    for code, metric in enumerate(tm.METRICS):
+        scores = torch.empty(S, dtype=torch.float64, device=dev)
+        index = torch.empty(k, dtype=torch.int32, device=dev)
+        top = torch.empty(k, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        _abi.check(fold_env._lib, fold_env._lib.gte_rank_trade_stats(
+            fold_env._h, C.c_void_p(d.data_ptr()), S, code, min_trades, k, C.c_void_p(index.data_ptr()),
+            C.c_void_p(top.data_ptr()), C.c_void_p(scores.data_ptr())))
+        fold_env.synchronize()
+        want = tm.scores_loop(t, metric)
+        got = scores.cpu().numpy()
+        assert sm.same_f64(got, want), (metric, [(s, got[s], want[s]) for s in range(S) if not sm.same_f64(got[s:s + 1], want[s:s + 1])][:5])
+        w_index, w_top = tm.rank_loop(t, want, min_trades, k)
+        np.testing.assert_array_equal(index.cpu().numpy(), w_index, err_msg=metric)
+        assert sm.same_f64(top.cpu().numpy(), w_top), metric
+
+
+def test_pipeline_by_strategy_and_top():
+    """backtest_signals() with tracking on -> trade_stats.by_strategy() -> top(): the records of the env's own
+    trade records under the default and an explicit map, and the leaders."""
+    import gym_trading_env_amd as gte
+    N, S, T = 100, 12, 300
+    rng = np.random.default_rng(11)
+    close = 100.0 * np.exp(np.cumsum(rng.normal(0, 1e-2, T)))
+    feat = rng.normal(0, 1, (T, 3)).astype(np.float32)
+    env = gte.BatchedTradingEnv((feat, close), num_envs=N, positions=[-1, 0, 1], windows=None, trading_fees=1e-4,
+                                max_episode_duration=40, autoreset="next_step", seed=4)
+    env.bind_signals(np.repeat(rng.integers(0, 3, (S, T // 4)), 4, axis=1).astype(np.int8))
+    env.reset()
+    env.track_trades()
+    stats = env.backtest_signals(120)
+    trades = stats.trade_stats
+    rec = trades.numpy()
+    assert rec["closed"].sum() > N
+    by = trades.by_strategy()
+    assert isinstance(by, gte.StrategyTradeStats) and by.num_strategies == S
+    _check_fold(by.numpy(), tm.reduce_loop(rec, sm.default_groups(N, S)), "by_strategy()")
+    m = rng.integers(-1, 6, N).astype(np.int32)   # strategies -1 .. 5 with S = 5: -1 and 5 belong to nobody
+    with pytest.raises(IndexError):
+        trades.by_strategy(strategy=m, n_strategies=5)
+    import torch
+    explicit = trades.by_strategy(strategy=torch.from_numpy(m).cuda(), n_strategies=5)
+    _check_fold(explicit.numpy(), tm.reduce_loop(rec, sm.map_groups(m, 5)), "by_strategy(map)")
+    host = by.numpy()
+    for metric in tm.METRICS:
+        want = tm.scores_loop(host, metric)
+        assert sm.same_f64(by.score(metric).cpu().numpy(), want), metric
+        index, top = by.top(5, metric=metric, min_trades=3)
+        w_index, w_top = tm.rank_loop(host, want, 3, 5)
+        r = int((w_index >= 0).sum())
+        np.testing.assert_array_equal(index.cpu().numpy(), w_index[:r])
+        assert sm.same_f64(top.cpu().numpy(), w_top[:r])
+    index, top = by.top(3)
+    assert sm.same_f64(top.cpu().numpy(), tm.rank_loop(host, tm.scores_loop(host, "profit_factor"), 1, 3)[1][:len(top)])
+    assert rec.tobytes() == trades.numpy().tobytes()   # folding and ranking change no record
+    env.close()
+
+
+def test_trade_report_example(capsys):
+    """examples/backtest_trade_report.py runs, and the table it prints is numpy() of the records."""
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    try:
+        import backtest_trade_report as ex
+    finally:
+        sys.path.pop(0)
+    out = ex.main(rows=3, stops=2, targets=2, replicas=2, K=600, T=1500)
+    text = capsys.readouterr().out
+    rows = [l.split() for l in text.splitlines() if len(l.split()) == 10 and l.split()[0].isdigit()]
+    host = out["by_strategy"].numpy()
+    assert 1 <= len(rows) <= 10 and len(rows) == len(out["index"])
+    with np.errstate(all="ignore"):
+        for row, s in zip(rows, out["index"].cpu().numpy().tolist()):
+            r = host[s]
+            assert int(row[1]) == s and int(row[-2]) == int(r["closed"])
+            assert abs(float(row[-3]) - 100.0 * r["wins"] / r["closed"]) < 0.051
+            assert abs(float(row[-1]) - r["hold_sum"] / r["closed"]) < 0.051
+    want = tm.rank_loop(host, tm.scores_loop(host, "profit_factor"), out["min_trades"], 10)[0]
+    np.testing.assert_array_equal(out["index"].cpu().numpy(), want[:len(out["index"])])
