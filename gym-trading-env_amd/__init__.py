@@ -11,6 +11,7 @@ from ._abi import GteError  # noqa: F401
 
 __all__ = ["TradingEnv", "MultiDatasetTradingEnv", "BatchedTradingEnv", "SB3TradingVecEnv", "GteError",
            "BacktestStats", "StrategyStats", "ExitState", "TradeStats", "StrategyTradeStats",
+           "PeriodStats", "StrategyPeriodStats", "periods",
            "basic_reward_function", "dynamic_feature_last_position_taken",
            "dynamic_feature_real_position"]
 
@@ -22,10 +23,14 @@ _LAZY = {
     "SB3TradingVecEnv": "sb3", "BatchedHistory": "batched_history", "DeviceArray": "device_array",
     "BacktestStats": "backtest_stats", "StrategyStats": "backtest_stats", "ExitState": "exit_state",
     "TradeStats": "trade_stats", "StrategyTradeStats": "trade_stats",
+    "PeriodStats": "period_stats", "StrategyPeriodStats": "period_stats",
 }
 
 
 def __getattr__(name):
+    if name == "periods":  # (a plain NumPy module: period rows for BatchedTradingEnv.track_periods)
+        import importlib
+        return importlib.import_module(f"{__name__}.periods")
     if name in _LAZY:
         import importlib
         mod = importlib.import_module(f"{__name__}.{_LAZY[name]}")

@@ -68,6 +68,17 @@ TRADE_METRIC_NEG_MAX_LOSS_STREAK = 5
 #: the same by name, in enum order (StrategyTradeStats.score / .top take either)
 TRADE_METRICS = ("win_rate", "profit_factor", "expectancy", "trade_sharpe", "worst_trade", "neg_max_loss_streak")
 
+# enum gte_period_metric: the score gte_rank_period_stats orders strategies by, over a set of periods
+PERIOD_METRIC_MEAN_REWARD = 0
+PERIOD_METRIC_SHARPE = 1
+PERIOD_METRIC_REWARD_SUM = 2
+PERIOD_METRIC_PERIOD_SHARPE = 3
+PERIOD_METRIC_WORST_PERIOD = 4
+PERIOD_METRIC_POSITIVE_SHARE = 5
+#: the same by name, in enum order (StrategyPeriodStats.score / .top take either)
+PERIOD_METRICS = ("mean_reward", "sharpe", "reward_sum", "period_sharpe", "worst_period", "positive_share")
+GTE_MAX_PERIODS = 128
+
 
 class GteError(RuntimeError):
     """A libgte call failed (status code + the library's message)."""
@@ -185,6 +196,30 @@ class GteStrategyTradeStats(C.Structure):
     """struct gte_strategy_trade_stats (include/gte.h)."""
     _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in STRATEGY_TRADE_FIELDS] + \
                [("reserved", C.c_int32 * 4)]
+
+
+#: struct gte_period_stats (include/gte.h), in declaration order: one 32-byte record per (env, period)
+PERIOD_FIELDS = [("reward_sum", "<f8"), ("reward_sq_sum", "<f8"), ("steps", "<i8"), ("trades", "<i4"), ("episodes", "<i4")]
+#: numpy view of an array of gte_period_stats (gte_read_period_stats)
+PERIOD_DTYPE = list(PERIOD_FIELDS)
+
+
+class GtePeriodStats(C.Structure):
+    """struct gte_period_stats (include/gte.h)."""
+    _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in PERIOD_FIELDS]
+
+
+#: struct gte_strategy_period_stats (include/gte.h), in declaration order: one 48-byte record per (strategy, period)
+STRATEGY_PERIOD_FIELDS = [("reward_sum", "<f8"), ("reward_sq_sum", "<f8"), ("steps", "<i8"), ("trades", "<i8"),
+                          ("episodes", "<i8"), ("envs_stepped", "<i4")]
+#: numpy view of an array of gte_strategy_period_stats (gte_reduce_period_stats)
+STRATEGY_PERIOD_DTYPE = STRATEGY_PERIOD_FIELDS + [("reserved", "<i4")]
+
+
+class GteStrategyPeriodStats(C.Structure):
+    """struct gte_strategy_period_stats (include/gte.h)."""
+    _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in STRATEGY_PERIOD_FIELDS] + \
+               [("reserved", C.c_int32)]
 
 
 #: struct gte_strategy_stats (include/gte.h), in declaration order: one 128-byte record per strategy
@@ -387,6 +422,13 @@ SYMBOLS = {
     "gte_reduce_trade_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_rank_trade_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "gte_bind_periods": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "gte_track_periods": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
+    "gte_read_period_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gte_reduce_period_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "gte_rank_period_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_int32,
+                                        C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
     "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,

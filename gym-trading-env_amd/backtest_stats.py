@@ -28,6 +28,8 @@ class BacktestStats:
         self._derived = {}
         self._map = getattr(env, "_backtest_map", None)  # what the call that made these records ran with
         self._trades_ptr = getattr(env, "_trades_ptr", 0)  # the trade records, if that call kept them
+        # (address, B, generation) of the period records, if that call kept them
+        self._periods = getattr(env, "_periods", None)
         dev = env._t["obs"].device
         stride = np.dtype(_abi.BACKTEST_DTYPE).itemsize
         offsets = np.dtype(_abi.BACKTEST_DTYPE).fields
@@ -82,6 +84,15 @@ class BacktestStats:
             return None
         from .trade_stats import TradeStats
         return self._lazy("trade_stats", lambda: TradeStats(self._env, self._trades_ptr, self.steps, self._map))
+
+    @property
+    def period_stats(self):
+        """The same transitions split by market period, a `PeriodStats` with fields [N, B] — or None when the
+        call that made these records ran with period tracking off (`BatchedTradingEnv.track_periods`)."""
+        if not self._periods:
+            return None
+        from .period_stats import PeriodStats
+        return self._lazy("period_stats", lambda: PeriodStats(self._env, *self._periods, self._map))
 
     def numpy(self) -> np.ndarray:
         """The whole record array on the host, one transfer: a structured array [N] with the

@@ -248,6 +248,10 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._exits = None  # (rules tensor, rule_of_env tensor or None) bound by bind_exits, kept alive
         self._exit_state_ptr = 0  # device address of the exit states (0 before the first bind_exits)
         self._trades_ptr = 0  # device address of the trade records while track_trades() is on, else 0
+        # (device address of the period records, B, their generation) while track_periods() is on, else None; the
+        # generation counts the allocations: a PeriodStats of an earlier one views freed memory and must refuse
+        self._periods = None
+        self._period_records, self._period_generation = None, 0
         for d, s in enumerate(self.datasets):
             self.upload_dataset(d, s)
 
@@ -1201,6 +1205,61 @@ class BatchedTradingEnv(_VectorEnvBase):
         ptr = C.c_void_p()
         _abi.check(self._lib, self._lib.gte_track_trades(self._h, 1 if on else 0, C.byref(ptr)))
         self._trades_ptr = int(ptr.value or 0) if on else 0
+
+    def track_periods(self, period_of_row, n_periods=None):
+        """Keep PERIOD statistics next to the backtest statistics (`gte_bind_periods`, `gte_track_periods`):
+        ``period_of_row[t]`` is the period id of market row t — a calendar month, a walk-forward fold, train /
+        embargo / test (`gym_trading_env_amd.periods` makes such rows) — as one integer array [T], or a list of
+        them, one per dataset.  While on, `backtest()` and `backtest_signals()` maintain one 32-byte record per
+        (env, period): reward sum, sum of squares, transitions, position changes and episodes of the transitions
+        whose row lay in that period (a row with an id outside [0, n_periods), such as -1, counts nowhere; the
+        rule is stated in include/gte.h), reduced in registers while they step, and the `BacktestStats` they
+        return has them as `.period_stats`.  `n_periods` defaults to the largest id + 1; at most 128.
+        ``track_periods(None)`` turns tracking off: then every call launches exactly the kernels it launches
+        without this feature.  The first backtest call after a change clears the records whatever its `resume`
+        says.  Not together with `track_trades()`.  Needs a `reset()` before it; waits for the env's stream.
+        Another `n_periods` allocates new records and frees the old ones: a `PeriodStats` from before then
+        raises instead of reading them (clone the fields, or take `.numpy()`, of a result that is to be compared
+        with a run under another period count).  If binding a row fails, tracking is left off."""
+        ptr = C.c_void_p()
+        if period_of_row is None:
+            _abi.check(self._lib, self._lib.gte_track_periods(self._h, 0, C.byref(ptr)))
+            self._periods = None
+            return
+        D = len(self.datasets)
+        rows = list(period_of_row) if isinstance(period_of_row, (list, tuple)) and len(period_of_row) and \
+            np.ndim(period_of_row[0]) == 1 else [period_of_row] * D
+        if len(rows) != D:
+            raise ValueError(f"{len(rows)} period rows for {D} datasets")
+        staged = []
+        for d, row in enumerate(rows):
+            a = np.asarray(row.cpu() if hasattr(row, "cpu") else row)
+            if a.ndim != 1 or a.shape[0] != self.datasets[d].T:
+                raise ValueError(f"period_of_row of dataset {d}: shape {a.shape}, the dataset has {self.datasets[d].T} rows")
+            if a.dtype.kind not in "iu":
+                raise TypeError("period_of_row must hold integers")
+            if a.size and (a.min() < -128 or a.max() > 127):
+                raise ValueError("period ids must fit int8 (ids outside [0, n_periods) count nowhere)")
+            staged.append(np.ascontiguousarray(a, dtype=np.int8))
+        if n_periods is None:
+            n_periods = max(int(a.max()) for a in staged) + 1
+        if isinstance(n_periods, bool) or int(n_periods) != n_periods or not 1 <= int(n_periods) <= _abi.GTE_MAX_PERIODS:
+            raise ValueError(f"n_periods must lie in [1, {_abi.GTE_MAX_PERIODS}]")
+        # switch first: a refusal (no reset yet, trade tracking on, a capture) leaves the rows as they were
+        _abi.check(self._lib, self._lib.gte_track_periods(self._h, int(n_periods), C.byref(ptr)))
+        records = (int(ptr.value or 0), int(n_periods))
+        if records != self._period_records:  # another B: the library freed the records older results view
+            self._period_records = records
+            self._period_generation += 1
+        try:
+            for d, a in enumerate(staged):
+                _abi.check(self._lib, self._lib.gte_bind_periods(self._h, d, a.ctypes.data))
+        except Exception:
+            # a bind that fails partway would leave tracking on with some datasets on their old row or on none
+            self._periods = None
+            self._lib.gte_track_periods(self._h, 0, None)
+            raise
+        self._periods = records + (self._period_generation,)
 
     # -- signal tables: the action looked up on the device by the row an env stands on -----
     def bind_signals(self, signals, dataset=None):

@@ -98,6 +98,15 @@ struct gte_env {
   // backtest calls maintain them, and whether that changed since the last backtest call (which then clears)
   gte_trade_stats* tr_stats = nullptr;
   bool tr_on = false, tr_changed = false;
+  // gte_track_periods / gte_bind_periods: the [N][pd_B] period records (pd_B == 0: tracking off; pd_alloc_B: the B
+  // they were allocated for), whether tracking, B or a row changed since the last backtest call (which then
+  // clears), and the period row of every dataset (base null = none bound; the base IS the library's allocation)
+  // on the host and on the device
+  gte_period_stats* pd_stats = nullptr;
+  int32_t pd_B = 0, pd_alloc_B = 0;
+  bool pd_changed = false;
+  std::vector<gte::PeriodRow> h_prow;
+  gte::PeriodRow* d_prow = nullptr;
   // signal tables (gte_bind_signals): one descriptor per dataset (base null = none bound), the host
   // copy and the device array the kernels read; the lookup's output for gte_backtest_signals
   std::vector<gte::SignalTable> h_sig;
@@ -491,6 +500,24 @@ static int publish_signal_table(gte_env* E, int32_t d, const gte::SignalTable& t
   return GTE_OK;
 }
 
+// Dataset d's period row becomes r (base null = unbound), on the host and on the device, and the row it had is
+// freed; the caller has waited for the stream.  Nothing changes if the copy fails.
+static int publish_period_row(gte_env* E, int32_t d, const gte::PeriodRow& r) {
+  const gte::PeriodRow before = E->h_prow[d];
+  E->h_prow[d] = r;
+  const hipError_t e = hipMemcpy(E->d_prow, E->h_prow.data(), sizeof(gte::PeriodRow) * E->h_prow.size(),
+                                 hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    E->h_prow[d] = before;
+    return fail(GTE_ERR_HIP, "publishing the period row of dataset %d: %s", d, hipGetErrorString(e));
+  }
+  if (before.base) (void)hipFree(const_cast<int8_t*>(before.base));
+  // while tracking is on the next backtest call clears: its records would mix two period maps (off, nothing is
+  // kept, and switching on marks the change itself: an untracked backtest keeps honouring its `clear`)
+  if (E->pd_B > 0) E->pd_changed = true;
+  return GTE_OK;
+}
+
 int gte_upload_dataset(gte_env* E, int32_t d, const float* feat, const double* close,
                        const double* high, const double* low, int64_t T) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
@@ -550,6 +577,7 @@ int gte_upload_dataset(gte_env* E, int32_t d, const float* feat, const double* c
   }
   // T may have changed: the dataset's signal table was checked against the old one
   if (E->d_sig && E->h_sig[d].base) TRY(publish_signal_table(E, d, gte::SignalTable{nullptr, 0}));
+  if (E->d_prow && E->h_prow[d].base) TRY(publish_period_row(E, d, gte::PeriodRow{nullptr, 0}));  // and its period row
   return GTE_OK;
 }
 
@@ -1047,6 +1075,11 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   if (E->tr_changed) clear = 1;
   E->tr_changed = false;
   gte_trade_stats* const trades = E->tr_on ? E->tr_stats : nullptr;
+  // the same for period tracking (never on together with trades: gte_track_periods, gte_track_trades)
+  if (E->pd_changed) clear = 1;
+  E->pd_changed = false;
+  const bool periods = E->pd_B > 0;
+  const gte::Periods per = {E->d_prow, E->pd_stats, E->pd_B};
   // same-step mode: the terminal valuation comes from the terminal records, the env's or our own
   EnvRec* const terminal = E->p.final_rec ? E->p.final_rec : E->bt_final_rec;
   Params ps = E->p;
@@ -1055,6 +1088,8 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   hipError_t le = trades ? gte::launch_trade_begin(ps, E->bt_stats, trades, clear, E->stream)
                          : gte::launch_backtest_begin(ps, E->bt_stats, clear, E->stream);
   if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
+  if (periods && clear)  // a cleared period record is all zero, and a reset row changes none
+    HIPCHK(hipMemsetAsync(E->pd_stats, 0, sizeof(gte_period_stats) * N * (size_t)E->pd_B, E->stream));
   // one step as an ordinary launch (it also produces the observation and the terminal list), then
   // its results into the records
   auto step_and_fold = [&](int32_t k) -> int {
@@ -1064,8 +1099,9 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
     }
     const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
     TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->bt_final_rec));
-    const hipError_t fe = trades ? gte::launch_trade_fold(ps, E->bt_stats, trades, E->stream)
-                                 : gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
+    const hipError_t fe = trades    ? gte::launch_trade_fold(ps, E->bt_stats, trades, E->stream)
+                          : periods ? gte::launch_period_fold(ps, E->bt_stats, per, E->stream)
+                                    : gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
     if (fe != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(fe));
     return GTE_OK;
   };
@@ -1085,6 +1121,13 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
            : signals ? gte::launch_trade_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, trades,
                                                         n_steps - 1, L.state_epw, E->stream)
                      : gte::launch_trade_summary(ps, actions, E->bt_stats, trades, n_steps - 1, L.state_epw, E->stream);
+    else if (periods)  // the same three launches with the open period's record in registers (gte_periods.hip)
+      le = signals && E->exits.rules
+               ? gte::launch_period_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, per,
+                                                 n_steps - 1, L.state_epw, E->stream)
+           : signals ? gte::launch_period_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, per,
+                                                         n_steps - 1, L.state_epw, E->stream)
+                     : gte::launch_period_summary(ps, actions, E->bt_stats, per, n_steps - 1, L.state_epw, E->stream);
     else
       le = signals && E->exits.rules
                ? gte::launch_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, n_steps - 1,
@@ -1103,6 +1146,10 @@ static int backtest_entry(gte_env* E, const char* who, const int32_t* actions, c
   if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
   if (stream_capturing(E))
     return fail(GTE_ERR_STATE, "%s inside a stream capture: a backtest is one launch already, run it eagerly", who);
+  if (E->pd_B > 0)
+    for (int d = 0; d < E->p.D; ++d)
+      if (!E->d_prow || !E->h_prow[d].base)
+        return fail(GTE_ERR_STATE, "%s: period tracking is on and dataset %d has no period row (gte_bind_periods)", who, d);
   HIPCHK(hipSetDevice(E->cfg.device));
   const int rc = backtest(E, actions, strategy, n_steps, clear);
   ledger().withdraw(E, FLAGS);  // (as after a rollout: the next step stores densely)
@@ -1438,6 +1485,9 @@ int gte_track_trades(gte_env* E, int32_t on, gte_trade_stats** records_device) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_trades before gte_reset");
   if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_trades inside a stream capture");
+  if (on && E->pd_B > 0)
+    return fail(GTE_ERR_STATE, "gte_track_trades: period tracking is on, and trade and period records together are "
+                "not implemented (gte_track_periods(env, 0, ...) first)");
   HIPCHK(hipSetDevice(E->cfg.device));
   if (on && !E->tr_stats) TRY(dev_alloc_late(E, &E->tr_stats, (size_t)E->p.N));
   HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the records
@@ -1456,6 +1506,138 @@ int gte_read_trade_stats(gte_env* E, int32_t first, int32_t count, gte_trade_sta
   HIPCHK(hipStreamSynchronize(E->stream));
   if (count > 0)
     HIPCHK(hipMemcpy(out, E->tr_stats + first, sizeof(gte_trade_stats) * (size_t)count, hipMemcpyDeviceToHost));
+  return GTE_OK;
+}
+
+int gte_bind_periods(gte_env* E, int32_t d, const int8_t* period_of_row) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  const Params& p = E->p;
+  if (d < 0 || d >= p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bind_periods inside a stream capture");
+  const int64_t T = E->h_ds[d].T;
+  if (period_of_row && T <= 0) return fail(GTE_ERR_STATE, "gte_bind_periods: dataset %d was never uploaded", d);
+  if (!period_of_row && !E->d_prow) return GTE_OK;  // nothing was ever bound
+  HIPCHK(hipSetDevice(E->cfg.device));
+  if (!E->d_prow) {
+    E->h_prow.assign((size_t)p.D, gte::PeriodRow{nullptr, 0});
+    TRY(dev_alloc(E, &E->d_prow, (size_t)p.D));
+  }
+  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight read the rows
+  if (!period_of_row) {
+    if (E->h_prow[d].base) TRY(publish_period_row(E, d, gte::PeriodRow{nullptr, 0}));
+    return GTE_OK;
+  }
+  const size_t T16 = (size_t)round_up_16(T);
+  void* row = nullptr;
+  hipError_t e = hipMalloc(&row, T16);
+  if (e == hipSuccess) e = hipMemset(row, 0xFF, T16);  // the padding: -1, a row of no period
+  if (e == hipSuccess) e = hipMemcpy(row, period_of_row, (size_t)T, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (row) (void)hipFree(row);
+    return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "period row of dataset %d: %s", d,
+                hipGetErrorString(e));
+  }
+  const int rc = publish_period_row(E, d, gte::PeriodRow{(const int8_t*)row, (int32_t)T16});
+  if (rc != GTE_OK) (void)hipFree(row);
+  return rc;
+}
+
+int gte_track_periods(gte_env* E, int32_t n_periods, gte_period_stats** records_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_periods < 0 || n_periods > GTE_MAX_PERIODS)
+    return fail(GTE_ERR_INVALID, "n_periods %d outside [0, %d]", n_periods, GTE_MAX_PERIODS);
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_periods before gte_reset");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_periods inside a stream capture");
+  if (n_periods > 0 && E->tr_on)
+    return fail(GTE_ERR_STATE, "gte_track_periods: trade tracking is on, and trade and period records together are "
+                "not implemented (gte_track_trades(env, 0, ...) first)");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the records
+  if (n_periods > 0 && n_periods != E->pd_alloc_B) {
+    void* fresh = nullptr;
+    const hipError_t e = hipMalloc(&fresh, sizeof(gte_period_stats) * (size_t)E->p.N * (size_t)n_periods);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "period records (%d envs x %d periods): %s",
+                  E->p.N, n_periods, hipGetErrorString(e));
+    }
+    if (E->pd_stats) (void)hipFree(E->pd_stats);
+    E->pd_stats = (gte_period_stats*)fresh;  // (cleared by the next backtest call: pd_changed)
+    E->pd_alloc_B = n_periods;
+  }
+  if (n_periods != E->pd_B) E->pd_changed = true;
+  E->pd_B = n_periods;
+  if (records_device) *records_device = E->pd_stats;
+  return GTE_OK;
+}
+
+int gte_read_period_stats(gte_env* E, int32_t first, int32_t count, gte_period_stats* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (!E->pd_stats) return fail(GTE_ERR_STATE, "gte_read_period_stats before gte_track_periods");
+  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
+    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(hipStreamSynchronize(E->stream));
+  const size_t B = (size_t)E->pd_alloc_B;
+  if (count > 0)
+    HIPCHK(hipMemcpy(out, E->pd_stats + (size_t)first * B, sizeof(gte_period_stats) * (size_t)count * B,
+                     hipMemcpyDeviceToHost));
+  return GTE_OK;
+}
+
+int gte_reduce_period_stats(gte_env* E, const gte_period_stats* records_device, int32_t n_periods, int32_t n_strategies,
+                            const int32_t* group_offsets_device, const int32_t* group_envs_device,
+                            gte_strategy_period_stats* out_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  if (n_periods < 1 || n_periods > GTE_MAX_PERIODS)
+    return fail(GTE_ERR_INVALID, "n_periods %d outside [1, %d]", n_periods, GTE_MAX_PERIODS);
+  if (!out_device || ((uintptr_t)out_device & 15))
+    return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
+  if ((uintptr_t)records_device & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
+  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
+    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
+  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
+    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reduce_period_stats inside a stream capture");
+  if (!records_device && !E->pd_stats)
+    return fail(GTE_ERR_STATE, "gte_reduce_period_stats before gte_track_periods: the env has no period records yet");
+  if (!records_device && n_periods != E->pd_alloc_B)
+    return fail(GTE_ERR_INVALID, "n_periods %d: the env's records have %d", n_periods, E->pd_alloc_B);
+  const gte_period_stats* const records = records_device ? records_device : E->pd_stats;
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const hipError_t e = gte::launch_reduce_period_stats(records, E->p.N, n_periods, n_strategies, E->cfg.env_id_base,
+                                                       group_offsets_device, group_envs_device, out_device, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "period reduction launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_rank_period_stats(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                          int32_t n_periods, const uint64_t period_mask[2], int32_t metric, int64_t min_steps, int32_t k,
+                          int32_t* top_index_device, double* top_score_device, double* scores_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  if (n_periods < 1 || n_periods > GTE_MAX_PERIODS)
+    return fail(GTE_ERR_INVALID, "n_periods %d outside [1, %d]", n_periods, GTE_MAX_PERIODS);
+  if (!period_mask) return fail(GTE_ERR_INVALID, "period_mask is NULL");
+  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
+  if (metric < GTE_PERIOD_METRIC_MEAN_REWARD || metric > GTE_PERIOD_METRIC_POSITIVE_SHARE)
+    return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
+  if (!stats_device || ((uintptr_t)stats_device & 15))
+    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  if (!top_index_device || ((uintptr_t)top_index_device & 3) || !top_score_device || ((uintptr_t)top_score_device & 7))
+    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
+  if ((uintptr_t)scores_device & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_rank_period_stats inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  TRY(rank_scratch(E, n_strategies));
+  hipError_t e = gte::launch_period_scores(stats_device, n_strategies, n_periods, period_mask, metric, min_steps,
+                                           scores_device, E->rank_score[0], E->rank_index[0], E->stream);
+  if (e == hipSuccess)
+    e = gte::launch_rank_select(n_strategies, k, top_index_device, top_score_device, E->rank_score, E->rank_index,
+                                E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "period ranking launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
 
@@ -2033,6 +2215,9 @@ void gte_destroy(gte_env* E) {
       if (ptr) (void)hipFree(ptr);
   for (int32_t* q : {E->d_q_idx, E->d_q_pos, E->d_q_ds})
     if (q) (void)hipFree(q);
+  if (E->pd_stats) (void)hipFree(E->pd_stats);
+  for (const gte::PeriodRow& r : E->h_prow)
+    if (r.base) (void)hipFree(const_cast<int8_t*>(r.base));
   if (E->h_snap) (void)hipHostFree(E->h_snap);
   if (E->h_logpack) (void)hipHostFree(E->h_logpack);
   if (E->ev0) (void)hipEventDestroy(E->ev0);

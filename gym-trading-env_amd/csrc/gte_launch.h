@@ -128,6 +128,28 @@ hipError_t launch_trade_exit_summary(const Params& p, const SignalTable* tables,
 hipError_t launch_trade_fold(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades,
                              hipStream_t stream);
 
+// --- gte_periods.hip: the backtest launches above with the period statistics (gte_track_periods, include/gte.h)
+struct PeriodRow {  // one dataset's period row (gte_bind_periods), library-owned
+  const int8_t* base;  // null = none bound
+  int32_t len;         // bytes: round_up(T, 16), the bytes past T hold -1
+};
+struct Periods {  // what the period kernels are given
+  const PeriodRow* rows;      // device array [p.D], all bound
+  gte_period_stats* records;  // device [N][B]
+  int32_t B;                  // 1 .. GTE_MAX_PERIODS
+};
+// launch_backtest_summary / launch_signal_summary / launch_exit_summary with the open period's record in registers
+hipError_t launch_period_summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, const Periods& per,
+                                 int n_steps, int epw, hipStream_t stream);
+hipError_t launch_period_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                        gte_backtest_stats* stats, const Periods& per, int n_steps, int epw,
+                                        hipStream_t stream);
+hipError_t launch_period_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                      const ExitRules& rules, gte_backtest_stats* stats, const Periods& per,
+                                      int n_steps, int epw, hipStream_t stream);
+// launch_backtest_fold that also folds the step into records[e][b]
+hipError_t launch_period_fold(const Params& p, gte_backtest_stats* stats, const Periods& per, hipStream_t stream);
+
 // --- gte_signals.hip: signal tables written on the device from indicator rules (gte_build_signals,
 // include/gte.h): table rows 0 .. n_rules-1, bytes 0 .. round_up(T, 16)-1 of each; the caller has checked
 // alignments and strides
@@ -172,6 +194,16 @@ hipError_t launch_reduce_trade_stats(const gte_trade_stats* records, int n_envs,
 // the score kernel alone: candidate list 0 (cand_score, cand_index: S entries), launch_rank_select follows
 hipError_t launch_trade_scores(const gte_strategy_trade_stats* stats, int n_strategies, int metric, int64_t min_trades,
                                double* scores, double* cand_score, int32_t* cand_index, hipStream_t stream);
+
+// --- gte_period_strategy.hip: the same for period records (gte_reduce_period_stats, gte_rank_period_stats,
+// include/gte.h): records [n_envs][n_periods] -> out [n_strategies][n_periods]
+hipError_t launch_reduce_period_stats(const gte_period_stats* records, int n_envs, int n_periods, int n_strategies,
+                                      int64_t env_id_base, const int32_t* group_offsets, const int32_t* group_envs,
+                                      gte_strategy_period_stats* out, hipStream_t stream);
+// the score kernel alone (period_mask: host, two words): candidate list 0, launch_rank_select follows
+hipError_t launch_period_scores(const gte_strategy_period_stats* stats, int n_strategies, int n_periods,
+                                const uint64_t period_mask[2], int metric, int64_t min_steps, double* scores,
+                                double* cand_score, int32_t* cand_index, hipStream_t stream);
 
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,

@@ -1,0 +1,61 @@
+"""Period rows for `BatchedTradingEnv.track_periods`: one small integer per market row that says which period
+the row belongs to — equal blocks, train / embargo / test splits, calendar periods of a DatetimeIndex.  Host-side
+NumPy; every function returns an int8 array [T] with ids 0 .. B-1 and -1 for rows that count nowhere."""
+from __future__ import annotations
+
+import numpy as np
+
+#: what libgte keeps per env (GTE_MAX_PERIODS, include/gte.h)
+MAX_PERIODS = 128
+
+
+def _checked(ids: np.ndarray) -> np.ndarray:
+    if ids.size and int(ids.max()) >= MAX_PERIODS:
+        raise ValueError(f"{int(ids.max()) + 1} periods: at most {MAX_PERIODS} are kept per env")
+    return ids.astype(np.int8)
+
+
+def blocks(T: int, n: int) -> np.ndarray:
+    """n consecutive blocks of (almost) equal length over T rows: row t is in block ``t * n // T`` (walk-forward
+    folds; block sizes differ by at most one row)."""
+    T, n = int(T), int(n)
+    if T < 1 or not 1 <= n <= min(T, MAX_PERIODS):
+        raise ValueError(f"blocks(T={T}, n={n}): 1 <= n <= min(T, {MAX_PERIODS}) required")
+    return _checked(np.arange(T, dtype=np.int64) * n // T)
+
+
+def split(T: int, fractions, embargo: int = 0) -> np.ndarray:
+    """Consecutive segments with the given fractions of T rows (they must sum to 1), e.g. ``(0.6, 0.4)`` for
+    train / test: segment j ends at ``round(T * sum(fractions[:j + 1]))``, the last at T.  The first `embargo`
+    rows of every segment but the first get -1: they count in no period, so an indicator's memory of the
+    previous segment does not leak into the next one's figures."""
+    T, embargo = int(T), int(embargo)
+    f = np.asarray(fractions, dtype=np.float64)
+    if f.ndim != 1 or not 1 <= len(f) <= MAX_PERIODS or (f <= 0).any() or abs(float(f.sum()) - 1.0) > 1e-9:
+        raise ValueError("fractions: 1 .. 128 positive numbers that sum to 1")
+    if T < len(f) or embargo < 0:
+        raise ValueError("T >= len(fractions) and embargo >= 0 required")
+    edges = np.rint(np.cumsum(f) * T).astype(np.int64)
+    edges[-1] = T
+    starts = np.concatenate(([0], edges[:-1]))
+    if (edges <= starts).any():
+        raise ValueError(f"split(T={T}): a segment would be empty")
+    out = np.full(T, -1, dtype=np.int64)
+    for j, (a, b) in enumerate(zip(starts, edges)):
+        out[min(b, a + (embargo if j else 0)):b] = j
+    return _checked(out)
+
+
+def from_index(index, freq: str = "M") -> np.ndarray:
+    """Calendar periods of a pandas DatetimeIndex (or anything ``pandas.DatetimeIndex`` accepts): rows of the
+    same calendar period `freq` (a pandas period alias: "D", "W", "M", "Q", "Y") share an id, ids count from 0
+    at the earliest period PRESENT in the index, in time order (a calendar period without rows takes no id)."""
+    import pandas as pd
+    idx = pd.DatetimeIndex(index)
+    if getattr(idx, "tz", None) is not None:
+        idx = idx.tz_localize(None)
+    ordinals = np.asarray(idx.to_period(freq).asi8)
+    uniq, ids = np.unique(ordinals, return_inverse=True)
+    if len(uniq) > MAX_PERIODS:
+        raise ValueError(f"{len(uniq)} periods of frequency {freq!r}: at most {MAX_PERIODS} are kept per env")
+    return _checked(ids.astype(np.int64))

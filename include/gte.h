@@ -694,6 +694,80 @@ int gte_track_trades(gte_env* env, int32_t on, gte_trade_stats** records_device)
  * GTE_ERR_STATE before the first gte_track_trades(env, 1, ...). */
 int gte_read_trade_stats(gte_env* env, int32_t first, int32_t count, gte_trade_stats* out);
 
+/* ---- PERIOD STATISTICS: the sums and counters of gte_backtest_stats split by MARKET PERIOD.  Every market row
+ * carries a small period id (a calendar month, a walk-forward fold, train / embargo / test), and every backtest
+ * path keeps one 32-byte record per (env, period), reduced while it steps: out-of-sample checks, period by
+ * period returns and the [S, B] matrix everything further starts from, without per-step rows.  Opt-in
+ * (gte_track_periods); with tracking off every call launches exactly the kernels it launches without this
+ * feature.  This text is the specification; the reference has no counterpart.
+ *
+ * RECORDS.  gte_period_stats[N][B], env-major (record of env e and period b at e * B + b), owned by the env on
+ * the device.  PERIOD ROWS.  One int8 row per resident dataset: period_of_row[d][i] is the period of market row i
+ * of dataset d (gte_bind_periods).
+ *
+ * TIMELINE.  It is the one of gte_backtest_stats: the same transitions, the same r_t, position values p_t and
+ * flags; what is and what is not a transition is stated there.  PER TRANSITION of env e, run directly before that
+ * record's own update, so `prev_position` and `ended` below are the fields of the env's gte_backtest_stats
+ * BEFORE the transition:
+ *
+ *     i = the row the env stood on before the step, d its dataset then
+ *         (the row whose signal byte gte_backtest_signals looks up; after the step it is _idx - 1 of the env's
+ *          record, or of its terminal record when the step reset it in same-step mode)
+ *     b = period_of_row[d][i];   if (!(0 <= b && b < B)) nothing;      an embargo row, a warm-up row
+ *     R = records[e][b]:
+ *       R.steps += 1;  R.reward_sum += r_t;  R.reward_sq_sum += r_t * r_t;
+ *       if (p_t != prev_position) R.trades += 1;
+ *       if (flags != 0 && !ended) R.episodes += 1;
+ *
+ * Every floating operation is one IEEE f64 operation as written.  Each sum is the plain left-to-right sum over
+ * that (env, period)'s transitions in step order since the last clear, whatever the launches, chunks and paths in
+ * between: a kernel that keeps the open period's record in registers continues from the stored value when the
+ * env enters a period.  A reset row changes no record.  No table byte can index outside the records.
+ *
+ * IDENTITIES.  With every row of every dataset in period 0 and B = 1, records[e][0].steps / reward_sum /
+ * reward_sq_sum / trades / episodes are bit for bit the fields of env e's gte_backtest_stats.  With every row in
+ * some period, the sums over b of steps, trades and episodes equal that record's counters exactly.
+ *
+ * CLEARING: all 32 bytes zero. */
+#define GTE_MAX_PERIODS 128
+typedef struct gte_period_stats {   /* 32 bytes, two 16-byte pieces */
+  double  reward_sum;      /* sum of r_t over the period's transitions, in step order */
+  double  reward_sq_sum;   /* sum of r_t * r_t                                         */
+  int64_t steps;           /* transitions                                              */
+  int32_t trades;          /* of them, those gte_backtest_stats.trades counts          */
+  int32_t episodes;        /* of them, those gte_backtest_stats.episodes counts        */
+} gte_period_stats;
+#ifdef __cplusplus
+static_assert(sizeof(gte_period_stats) == 32, "period statistics: two 16-byte pieces");
+#endif
+/* The period row of dataset ds: period_of_row is HOST int8 [T_ds], T_ds the rows of the dataset as uploaded.
+ * Unlike gte_bind_signals the call COPIES (it is T bytes) into a library-owned device row padded to
+ * round_up(T, 16) with -1, so an aligned 16-byte load anywhere in it is legal.  NULL unbinds; gte_upload_dataset
+ * of ds unbinds too (T may have changed).  A bind, a re-bind or an unbind makes the first backtest call after it
+ * clear the records like a change of tracking.  Waits for the env's stream; refused inside a stream capture and
+ * for a dataset that was never uploaded (GTE_ERR_STATE); GTE_ERR_INVALID for ds outside [0, n_datasets). */
+int gte_bind_periods(gte_env* env, int32_t ds, const int8_t* period_of_row);
+/* n_periods in 1 .. GTE_MAX_PERIODS: gte_backtest and gte_backtest_signals maintain the period records from now
+ * on, with B = n_periods — with or without exit rules bound, on the fused path (gte_periods.hip: the
+ * from-registers kernels with the open period's record in registers) and on the step-by-step path, in all three
+ * auto-reset modes — and the gte_backtest_stats records, the env state and the exit state come out bit for bit
+ * as with tracking off.  n_periods == 0: tracking stops; the records keep what they hold.  The call allocates
+ * N * B * 32 bytes (GTE_ERR_OOM on failure, with tracking left as it was) and allocates afresh when B changes
+ * (the old records are freed: an address an earlier call returned is dead from then on, and so is every view
+ * of it a caller kept).  The FIRST backtest call after a change — on, off, another B, a (re-)bind —
+ * clears both kinds of record whatever its `clear` says, so they always cover the same transitions.  While
+ * tracking is on, a backtest with a resident dataset that has no period row bound is refused (GTE_ERR_STATE).
+ * Period tracking and trade tracking together are not implemented: whichever of gte_track_periods and
+ * gte_track_trades would turn the second one on is refused (GTE_ERR_STATE).  *records_device (may be NULL)
+ * receives the DEVICE address of the records (NULL before they exist).  The call waits for the env's stream and
+ * is refused before gte_reset and inside a stream capture (GTE_ERR_STATE); GTE_ERR_INVALID for n_periods
+ * outside [0, GTE_MAX_PERIODS]. */
+int gte_track_periods(gte_env* env, int32_t n_periods, gte_period_stats** records_device);
+/* The count * B records of envs first .. first+count-1 into HOST memory: waits for the env's stream, one
+ * transfer.  B is that of the records as they stand, the n_periods of the last gte_track_periods(env, B >= 1,
+ * ...): out holds count * B records of it, not of an earlier B.  GTE_ERR_STATE before the first such call. */
+int gte_read_period_stats(gte_env* env, int32_t first, int32_t count, gte_period_stats* out);
+
 /* ---- SIGNAL TABLES BUILT ON THE DEVICE from indicator rules: a parameter sweep passes a small bank of
  * indicators and one 32-byte rule per strategy, and the device writes the int8 [n_rules][T] table that
  * gte_bind_signals accepts — no host table, no host-to-device copy of it.
@@ -1000,6 +1074,73 @@ typedef enum gte_trade_metric {
 int gte_rank_trade_stats(gte_env* env, const gte_strategy_trade_stats* stats_device, int32_t n_strategies,
                          int32_t metric, int64_t min_trades, int32_t k, int32_t* top_index_device,
                          double* top_score_device, double* scores_device /* [n_strategies] or NULL */);
+
+/* ---- PERIOD STATISTICS PER STRATEGY, AND THEIR RANKING OVER A SET OF PERIODS: the N * B gte_period_stats
+ * folded into one record per (strategy, period), gte_strategy_period_stats[S][B] strategy-major, and the best k
+ * strategies by a score taken over any subset of the periods — rank on the training periods, read the same
+ * strategies on the test periods.  MEMBERS, the skipping rule and the ONE FIXED ORDER of the f64 sums (eight
+ * interleaved accumulators over the member list, closed as ((a0 + a1) + a2) ...) are those of
+ * gte_reduce_backtest_stats, applied per (strategy, period): the same records give the same bits for any launch
+ * geometry.  THE RECORD of strategy s and period b over the members' records [e][b]:
+ *   reward_sum, reward_sq_sum   f64 sums in the fixed order;
+ *   steps, trades, episodes     exact 64-bit sums of the members' counters;
+ *   envs_stepped                members that are not skipped and have steps > 0 in period b.
+ * A strategy without members gets zeros.  reserved is written as zero. */
+typedef struct gte_strategy_period_stats {     /* 48 bytes, three 16-byte pieces */
+  double  reward_sum, reward_sq_sum;
+  int64_t steps, trades, episodes;
+  int32_t envs_stepped;
+  int32_t reserved;
+} gte_strategy_period_stats;
+#ifdef __cplusplus
+static_assert(sizeof(gte_strategy_period_stats) == 48, "strategy period statistics: three 16-byte pieces");
+#endif
+/* records_device == NULL: the env's own N * B records, n_periods being their B (GTE_ERR_STATE before
+ * gte_track_periods allocated them, GTE_ERR_INVALID for another n_periods); else a caller-owned DEVICE array of
+ * N * n_periods gte_period_stats, 16-byte aligned.  1 <= n_periods <= GTE_MAX_PERIODS.  out_device: DEVICE array
+ * of S * n_periods records, 16-byte aligned, all 48 bytes of each written.  The group lists, the launch (one, on
+ * the env's stream, no host synchronisation) and the other error codes are those of gte_reduce_backtest_stats.
+ * One thread per (strategy, period), the threads of a strategy neighbours across its periods and 256 / B
+ * strategies per 256-thread workgroup; they walk the member list together, one member after the other, so a
+ * member's B records are one contiguous read. */
+int gte_reduce_period_stats(gte_env* env, const gte_period_stats* records_device, int32_t n_periods,
+                            int32_t n_strategies, const int32_t* group_offsets_device,
+                            const int32_t* group_envs_device, gte_strategy_period_stats* out_device);
+/* The score a strategy is ranked by, from its B gte_strategy_period_stats and a set of periods.  P is the set of
+ * periods b < B whose bit is set in period_mask (bit b % 64 of word b / 64), in ascending order.  Every operation
+ * is one IEEE f64 operation as written (an int64 converts to f64 first), sqrt correctly rounded, comparisons
+ * plain:
+ *     n  = the sum over P of steps (int64);
+ *     s1 = 0.0; s2 = 0.0; over P: s1 = s1 + reward_sum_b;  s2 = s2 + reward_sq_sum_b;
+ *     over the periods of P with steps_b > 0, x_b = reward_sum_b:
+ *       c = their number;  t1 = 0.0; t2 = 0.0;  t1 = t1 + x_b;  t2 = t2 + x_b * x_b;
+ *       lo = +inf;  if (x_b < lo) lo = x_b;      up = the number of them with x_b > 0.0
+ *   MEAN_REWARD     s1 / n
+ *   SHARPE          the GTE_METRIC_SHARPE formulas on s1, s2, n:  m = s1 / n;  q = s2 / n;  v = q - m * m;
+ *                   if (!(v > 0.0)) v = 0.0;  m / sqrt(v)
+ *   REWARD_SUM      s1
+ *   PERIOD_SHARPE   the same formulas on t1, t2, c: mean / population deviation of the period returns
+ *   WORST_PERIOD    lo, and NaN when c == 0
+ *   POSITIVE_SHARE  up / c
+ * A selection without a stepped period scores NaN under every metric but REWARD_SUM (0.0) and is not ranked
+ * under any. */
+typedef enum gte_period_metric {
+  GTE_PERIOD_METRIC_MEAN_REWARD = 0,
+  GTE_PERIOD_METRIC_SHARPE = 1,
+  GTE_PERIOD_METRIC_REWARD_SUM = 2,
+  GTE_PERIOD_METRIC_PERIOD_SHARPE = 3,
+  GTE_PERIOD_METRIC_WORST_PERIOD = 4,
+  GTE_PERIOD_METRIC_POSITIVE_SHARE = 5
+} gte_period_metric;
+/* gte_rank_strategies over period records: strategy s is RANKED iff n >= max(1, min_steps) and its score is not
+ * NaN.  period_mask: HOST uint64 [2].  One score launch, then the selection launches of gte_rank_strategies on
+ * the same library-owned scratch; order, ties, NaN, padding (-1 / NaN), k (1 <= k <= GTE_RANK_MAX, may exceed
+ * S), scores_device, alignments and error codes are those of gte_rank_strategies; GTE_ERR_INVALID also for
+ * n_periods outside [1, GTE_MAX_PERIODS] and a NULL period_mask. */
+int gte_rank_period_stats(gte_env* env, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                          int32_t n_periods, const uint64_t period_mask[2], int32_t metric, int64_t min_steps,
+                          int32_t k, int32_t* top_index_device, double* top_score_device,
+                          double* scores_device /* [n_strategies] or NULL */);
 
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
