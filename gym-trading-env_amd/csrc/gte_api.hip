@@ -1114,27 +1114,13 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   else report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
   if (n_steps > 1) {
     TRY(age_order(E, n_steps - 1));
-    if (trades)  // the same three launches with the trade record in registers as well (gte_trades.hip)
-      le = signals && E->exits.rules
-               ? gte::launch_trade_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, trades,
-                                                n_steps - 1, L.state_epw, E->stream)
-           : signals ? gte::launch_trade_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, trades,
-                                                        n_steps - 1, L.state_epw, E->stream)
-                     : gte::launch_trade_summary(ps, actions, E->bt_stats, trades, n_steps - 1, L.state_epw, E->stream);
-    else if (periods)  // the same three launches with the open period's record in registers (gte_periods.hip)
-      le = signals && E->exits.rules
-               ? gte::launch_period_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, per,
-                                                 n_steps - 1, L.state_epw, E->stream)
-           : signals ? gte::launch_period_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, per,
-                                                         n_steps - 1, L.state_epw, E->stream)
-                     : gte::launch_period_summary(ps, actions, E->bt_stats, per, n_steps - 1, L.state_epw, E->stream);
-    else
-      le = signals && E->exits.rules
-               ? gte::launch_exit_summary(ps, E->d_sig, E->sig_S, strategy, E->exits, E->bt_stats, n_steps - 1,
-                                          L.state_epw, E->stream)
-           : signals ? gte::launch_signal_summary(ps, E->d_sig, E->sig_S, strategy, E->bt_stats, n_steps - 1,
-                                                  L.state_epw, E->stream)
-                   : gte::launch_backtest_summary(ps, actions, E->bt_stats, n_steps - 1, L.state_epw, E->stream);
+    // one launch, its actions from `src`; with a tracker on, the unit that keeps that record in registers as well
+    const gte::SummarySource src = {actions, E->d_sig, E->sig_S, strategy, E->exits.rules ? &E->exits : nullptr};
+    const int32_t k = n_steps - 1, epw = L.state_epw;
+    le = trades    ? gte::launch_trade_summary(ps, src, E->bt_stats, trades, k, epw, E->stream)
+         : periods ? gte::launch_period_summary(ps, src, E->bt_stats, per, k, epw, E->stream)
+         : signals ? gte::launch_signal_summary(ps, src, E->bt_stats, k, epw, E->stream)
+                   : gte::launch_backtest_summary(ps, src, E->bt_stats, k, epw, E->stream);
     if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   }
   return step_and_fold(n_steps - 1);

@@ -2,10 +2,10 @@
 // and time exits decided from the env's own path, next to the signal-table lookup.  Own translation
 // unit: nothing here can perturb the code generated for the kernels of gte_backtest.hip.
 //
-//   gte_backtest_exit_kernel    gte_backtest_signal_kernel (same geometry, same piece-in-registers lookup,
-//                               same record handling) with the env's exit state in registers as well: the
-//                               state is loaded once and stored once per launch, the rule is loaded once,
-//                               and a step issues no memory request the signal kernel does not issue.
+//   gte_backtest_exit_kernel    the third row of the table in gte_backtest.hip without a tracker: what
+//                               summary_body (gte_summary_body.h) does with ExitSource — the signal lookup with
+//                               the env's exit state and rule in registers — kept HAND-WRITTEN here, the one
+//                               exception to that header (the comment at the kernel says why).
 //   gte_exit_actions_kernel     gte_signal_actions_kernel with rules bound: brings the state up to date
 //                               from the env record, decides, and keeps the decision as a memo so that a
 //                               second call before the env has stepped changes nothing.
@@ -13,7 +13,7 @@
 //
 // Both paths run exit_sync() / exit_decide() on the same values, so they give the same exit state and
 // actions bit for bit (tests/test_gpu_exits.py).  Compiled WITHOUT GTE_HOT_ONLY like gte_backtest.hip.
-#include "gte_exit_regs.h"
+#include "gte_summary_body.h"
 
 namespace gte {
 
@@ -52,12 +52,12 @@ __global__ __launch_bounds__(256) void gte_exit_actions_kernel(const Params p, c
   actions[e] = act;
 }
 
-// gte_backtest_signal_kernel (gte_backtest.hip: geometry, piece fetch, record handling — see there) with the
-// exit state x and the rule R of the lane's env in registers.  Before a step the lane decides from x, the
-// table byte and the env's registers; after it, it updates x from what the step left in them, recognising
-// resets the way backtest_step does (a same-step reset by the step's flags, a next-step one by needs_reset
-// before the step, a frozen step by a _step that did not move).  v_seen / i_seen / step_seen are the env's own
-// registers during the launch and are written out with the state at the end.
+// THE EXCEPTION to gte_summary_body.h: summary_body(p, stats, ExitSource(tables, S, strategy, rules), NoTracker(),
+// n_steps, epw) written out by hand, as it was before that header.  Through the shared body this one kernel
+// measured about 1 % slower than this text ("One body for the nine fused backtest kernels";
+// profiles/summary_body_bench.log) and the cause was not found in its listing, so the text stays until it is.
+// It must be kept in step with summary_body() and ExitSource by hand: geometry, piece fetch and its bounds, the
+// memo, the order inside a step and how resets are recognised are explained there.
 __global__ __launch_bounds__(256) void gte_backtest_exit_kernel(const Params p, const SignalTable* tables,
                                                                 const int S, const int32_t* strategy,
                                                                 const ExitRules rules, gte_backtest_stats* stats,
@@ -141,8 +141,6 @@ __global__ __launch_bounds__(256) void gte_backtest_exit_kernel(const Params p, 
   }
 }
 
-static bool exit_rules_usable(const ExitRules& r) { return r.rules && r.n_rules >= 1 && r.state; }
-
 hipError_t launch_exit_init(gte_exit_state* state, int n, hipStream_t stream) {
   if (!state || n < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gte_exit_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, state, n);
@@ -151,21 +149,17 @@ hipError_t launch_exit_init(gte_exit_state* state, int n, hipStream_t stream) {
 
 hipError_t launch_exit_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
                                const ExitRules& rules, int32_t* actions, hipStream_t stream) {
-  if (!tables || S < 1 || !actions || !exit_rules_usable(rules)) return hipErrorInvalidValue;
+  if (!tables_usable(tables, S) || !actions || !exit_rules_usable(rules)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gte_exit_actions_kernel, dim3((p.N + 255) / 256), dim3(256), 0, stream, p, tables, S,
                      strategy, rules, actions);
   return hipGetLastError();
 }
 
-hipError_t launch_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                               const ExitRules& rules, gte_backtest_stats* stats, int n_steps, int epw,
-                               hipStream_t stream) {
-  // (what launch_signal_summary refuses: trajectory rows; same-step mode without terminal records)
-  if (p.log.rows != nullptr || (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) || epw < 1 ||
-      epw > 64 || !tables || S < 1 || !exit_rules_usable(rules))
-    return hipErrorInvalidValue;
+hipError_t launch_exit_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats, int n_steps,
+                               int epw, hipStream_t stream) {
+  if (summary_refused(p, src, epw) || src.actions || !src.rules) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gte_backtest_exit_kernel, dim3(rollout_blocks(p.N, epw)), dim3(64 * ROLLOUT_WAVES), 0, stream,
-                     p, tables, S, strategy, rules, stats, n_steps, epw);
+                     p, src.tables, src.S, src.strategy, *src.rules, stats, n_steps, epw);
   return hipGetLastError();
 }
 

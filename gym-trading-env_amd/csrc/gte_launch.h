@@ -69,66 +69,25 @@ hipError_t launch_rollout_state(const Params& p, const RolloutArgs& r, int n_ste
 int rollout_blocks_per_cu(const Params& p, int nt);
 hipError_t launch_rollout(const Params& p, const RolloutArgs& r, int nt, int blocks, hipStream_t stream);
 
-// --- gte_backtest.hip: K steps in one launch that keep per-env statistics instead of per-step rows
-// clear != 0: zero the records and anchor them at the envs' current state; else bring the
-// bookkeeping fields up to date with the records (a gte_reset since the previous call)
-hipError_t launch_backtest_begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream);
-// n_steps steps from registers (the geometry of launch_rollout_state); p.final_rec must be set in
-// same-step mode: the lane that wrote an env's terminal record reads the terminal valuation back
-hipError_t launch_backtest_summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, int n_steps,
-                                   int epw, hipStream_t stream);
-// ONE step into the records, from what an ordinary step launch left in p's buffers
-hipError_t launch_backtest_fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream);
-
-// ... and the same with every step's action looked up in signal tables (gte_bind_signals, include/gte.h)
+// --- the backtest summaries (gte_backtest.hip, gte_exits.hip, gte_trades.hip, gte_periods.hip): K steps in one
+// launch that keep per-env statistics instead of per-step rows
 struct SignalTable {  // one dataset's signal table (gte_bind_signals): row s starts at base + s * stride
   const int8_t* base;  // null = none bound
   int64_t stride;      // bytes, a multiple of 16 and >= round_up(T, 16)
 };
-// the action the tables give every env for its next step (tables: device array [p.D], all bound;
-// S strategies; strategy: device i32 [N] or null = (env_id_base + e) % S) -> actions i32 [N]
-hipError_t launch_signal_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                                 int32_t* actions, hipStream_t stream);
-// launch_backtest_summary with that lookup, at the env's own row, in place of the [K][N] actions
-hipError_t launch_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                                 gte_backtest_stats* stats, int n_steps, int epw, hipStream_t stream);
-
-// --- gte_exits.hip: the two lookups above with exit rules bound (gte_bind_exit_rules, include/gte.h)
 struct ExitRules {  // what a bind left: the caller's rules and map, the library's per-env state
   const gte_exit_rule* rules;  // device [n_rules]
   const int32_t* rule_of_env;  // device i32 [N], or null = strategy of the env % n_rules
   gte_exit_state* state;       // device [N]
   int32_t n_rules;
 };
-// every state as a bind leaves it: the next decision sees a reset row
-hipError_t launch_exit_init(gte_exit_state* state, int n, hipStream_t stream);
-// launch_signal_actions that also brings the exit states up to date, decides the exits and keeps the memo
-hipError_t launch_exit_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                               const ExitRules& rules, int32_t* actions, hipStream_t stream);
-// launch_signal_summary with the exit state of every env in registers next to its statistics
-hipError_t launch_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                               const ExitRules& rules, gte_backtest_stats* stats, int n_steps, int epw,
-                               hipStream_t stream);
-
-// --- gte_trades.hip: the backtest launches above with the trade statistics (gte_track_trades, include/gte.h)
-// kept as well: `trades` is the device array of the N trade records, next to `stats`
-// launch_backtest_begin for both records
-hipError_t launch_trade_begin(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades, int clear,
-                              hipStream_t stream);
-// launch_backtest_summary / launch_signal_summary / launch_exit_summary with the trade record in registers too
-hipError_t launch_trade_summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats,
-                                gte_trade_stats* trades, int n_steps, int epw, hipStream_t stream);
-hipError_t launch_trade_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                                       gte_backtest_stats* stats, gte_trade_stats* trades, int n_steps, int epw,
-                                       hipStream_t stream);
-hipError_t launch_trade_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                                     const ExitRules& rules, gte_backtest_stats* stats, gte_trade_stats* trades,
-                                     int n_steps, int epw, hipStream_t stream);
-// launch_backtest_fold for both records
-hipError_t launch_trade_fold(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades,
-                             hipStream_t stream);
-
-// --- gte_periods.hip: the backtest launches above with the period statistics (gte_track_periods, include/gte.h)
+struct SummarySource {  // where a from-registers launch takes every step's action from
+  const int32_t* actions;     // device i32 [K][N]; null: looked up in the signal tables, at the env's own row
+  const SignalTable* tables;  // device array [p.D], all bound (gte_bind_signals)
+  int32_t S;                  // strategies
+  const int32_t* strategy;    // device i32 [N] or null = (env_id_base + e) % S
+  const ExitRules* rules;     // exit rules decided next to the lookup (gte_bind_exit_rules), or null = none
+};
 struct PeriodRow {  // one dataset's period row (gte_bind_periods), library-owned
   const int8_t* base;  // null = none bound
   int32_t len;         // bytes: round_up(T, 16), the bytes past T hold -1
@@ -138,15 +97,68 @@ struct Periods {  // what the period kernels are given
   gte_period_stats* records;  // device [N][B]
   int32_t B;                  // 1 .. GTE_MAX_PERIODS
 };
-// launch_backtest_summary / launch_signal_summary / launch_exit_summary with the open period's record in registers
-hipError_t launch_period_summary(const Params& p, const int32_t* actions, gte_backtest_stats* stats, const Periods& per,
-                                 int n_steps, int epw, hipStream_t stream);
-hipError_t launch_period_signal_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                                        gte_backtest_stats* stats, const Periods& per, int n_steps, int epw,
-                                        hipStream_t stream);
-hipError_t launch_period_exit_summary(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
-                                      const ExitRules& rules, gte_backtest_stats* stats, const Periods& per,
-                                      int n_steps, int epw, hipStream_t stream);
+// what every launcher below checks, written once
+// a lookup needs tables and a strategy count
+inline bool tables_usable(const SignalTable* tables, int S) { return tables && S >= 1; }
+inline bool exit_rules_usable(const ExitRules& r) { return r.rules && r.n_rules >= 1 && r.state; }
+// what the from-registers kernels do not do: trajectory rows (the step kernel writes them, gte_kernel); in
+// same-step mode they need somewhere for the terminal records; epw envs per wavefront; and a source to read
+inline bool summary_refused(const Params& p, const SummarySource& src, int epw) {
+  return p.log.rows != nullptr || (p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr) || epw < 1 ||
+         epw > 64 ||
+         (!src.actions && (!tables_usable(src.tables, src.S) || (src.rules && !exit_rules_usable(*src.rules))));
+}
+// ONE step folded in from what an ordinary launch left needs the terminal records in same-step mode too
+inline bool fold_refused(const Params& p) { return p.autoreset == GTE_AUTORESET_SAME_STEP && p.final_rec == nullptr; }
+
+// --- gte_backtest.hip
+// clear != 0: zero the records and anchor them at the envs' current state; else bring the
+// bookkeeping fields up to date with the records (a gte_reset since the previous call)
+hipError_t launch_backtest_begin(const Params& p, gte_backtest_stats* stats, int clear, hipStream_t stream);
+// n_steps steps from registers (the geometry of launch_rollout_state) with src.actions, the [K][N] actions.
+// p.final_rec must be set in same-step mode: the lane that wrote an env's terminal record reads the terminal
+// valuation back
+hipError_t launch_backtest_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats, int n_steps,
+                                   int epw, hipStream_t stream);
+// ... with every step's action looked up instead (src.actions null), at the env's own row; with src.rules the
+// exits are decided as well (then through launch_exit_summary)
+hipError_t launch_signal_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats, int n_steps,
+                                 int epw, hipStream_t stream);
+// ONE step into the records, from what an ordinary step launch left in p's buffers
+hipError_t launch_backtest_fold(const Params& p, gte_backtest_stats* stats, hipStream_t stream);
+// the action the tables give every env for its next step (tables: device array [p.D], all bound;
+// S strategies; strategy: device i32 [N] or null = (env_id_base + e) % S) -> actions i32 [N]
+hipError_t launch_signal_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                                 int32_t* actions, hipStream_t stream);
+
+// --- gte_exits.hip: the lookups with exit rules bound (gte_bind_exit_rules, include/gte.h)
+// every state as a bind leaves it: the next decision sees a reset row
+hipError_t launch_exit_init(gte_exit_state* state, int n, hipStream_t stream);
+// launch_signal_actions that also brings the exit states up to date, decides the exits and keeps the memo
+hipError_t launch_exit_actions(const Params& p, const SignalTable* tables, int S, const int32_t* strategy,
+                               const ExitRules& rules, int32_t* actions, hipStream_t stream);
+// launch_signal_summary's launch for a source with rules, the exit state of every env in registers next to its
+// statistics: the kernel stays in this unit, so launch_signal_summary comes through here; not meant to be
+// called from anywhere else
+hipError_t launch_exit_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats, int n_steps,
+                               int epw, hipStream_t stream);
+
+// --- gte_trades.hip: the backtest launches above with the trade statistics (gte_track_trades, include/gte.h)
+// kept as well: `trades` is the device array of the N trade records, next to `stats`
+// launch_backtest_begin for both records
+hipError_t launch_trade_begin(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades, int clear,
+                              hipStream_t stream);
+// launch_backtest_summary with the trade record in registers too, whatever the source
+hipError_t launch_trade_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats,
+                                gte_trade_stats* trades, int n_steps, int epw, hipStream_t stream);
+// launch_backtest_fold for both records
+hipError_t launch_trade_fold(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades,
+                             hipStream_t stream);
+
+// --- gte_periods.hip: the backtest launches above with the period statistics (gte_track_periods, include/gte.h)
+// launch_backtest_summary with the open period's record in registers, whatever the source
+hipError_t launch_period_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats,
+                                 const Periods& per, int n_steps, int epw, hipStream_t stream);
 // launch_backtest_fold that also folds the step into records[e][b]
 hipError_t launch_period_fold(const Params& p, gte_backtest_stats* stats, const Periods& per, hipStream_t stream);
 

@@ -277,3 +277,4 @@ def test_exit_kernels_use_no_scratch():
     for k in kernels.values():
         assert k["scratch"] == 0, k
         assert k["occupancy"] >= 2, k
+    th._assert_kernels_found(list(kernels.values()), ("gte_backtest_exit_kernel",), 2)

@@ -216,11 +216,23 @@ def test_kernel_register_budget(source, min_occupancy):
     10+ us per step, and scratch use doubles the store traffic.  A change to the
     shared device code that pushes the hot instantiations over their budget fails here, on the
     CPU, before anything is measured.  gte_backtest.hip: its two from-registers kernels carry an env
-    and its statistics record through all fused steps (142 and 152 VGPRs, 3 waves/SIMD); written as
+    and its statistics record through all fused steps (142 and 153 VGPRs, 3 waves/SIMD); written as
     a plain loop body the compiler kept the env's registers in scratch memory."""
-    for k in _resource_usage(source):
+    kernels = _resource_usage(source)
+    for k in kernels:
         assert k["scratch"] == 0, k
         assert k["occupancy"] >= min_occupancy, k
+    if source == "gte_backtest.hip":
+        _assert_kernels_found(kernels, ("gte_backtest_kernel", "gte_backtest_signal_kernel"), 3)
+
+
+def _assert_kernels_found(kernels, names, min_occupancy):
+    """each from-registers backtest kernel is in the unit it is looked for in, by name, without scratch and at
+    the occupancy it had before csrc/gte_summary_body.h held its body"""
+    for name in names:
+        found = [k for k in kernels if re.search(rf"_ZN3gte\d+{name}E", k["name"])]
+        assert len(found) == 1, (name, [k["name"] for k in kernels])
+        assert found[0]["scratch"] == 0 and found[0]["occupancy"] >= min_occupancy, found[0]
 
 
 def test_features_compiled_out_of_the_hot_translation_units_are_guarded():
@@ -436,6 +448,30 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
         assert [n for n, t in src.items() if re.search(rf"constexpr \w+ {const}\b", t)] == ["gte_plan.h"], const
     for macro in ("GTE_WAVES", "GTE_LEAN_U"):
         assert [n for n, t in src.items() if re.search(rf"#\s*define {macro}\b", t)] == ["gte_plan.h"], macro
+
+
+def test_the_fused_backtest_step_is_written_once():
+    """The from-registers backtest kernels (three action sources x three trackers) are one body, summary_body() of
+    gte_summary_body.h, called with two policies — with ONE hand-written exception, gte_backtest_exit_kernel in
+    gte_exits.hip, which measured about 1 % slower through the shared body ("One body for the nine fused
+    backtest kernels").  So the fused step exists twice, in the header and in that kernel, and nowhere else: a
+    further hand-copied kernel fails here before anything runs.  (gte_exit_actions_kernel, the lookup outside a
+    fused launch, has an exit_decide of its own.)"""
+    src = _csrc_sources()
+    units = ("gte_backtest.hip", "gte_exits.hip", "gte_trades.hip", "gte_periods.hip")
+    body = "gte_summary_body.h"
+    count = lambda needle: {n: src[n].count(needle) for n in units + (body,) if needle in src[n]}
+    kernel = lambda name: re.search(rf"void {name}\(.*?\n\}}\n", src["gte_exits.hip"], re.S).group(0)
+    by_hand = kernel("gte_backtest_exit_kernel")
+    assert count("phase_a<MODE_STEP>(") == {body: 1, "gte_exits.hip": 1} and by_hand.count("phase_a<MODE_STEP>(") == 1
+    assert count("exit_decide(") == {body: 1, "gte_exits.hip": 2}
+    assert by_hand.count("exit_decide(") == 1 and kernel("gte_exit_actions_kernel").count("exit_decide(") == 1
+    # the other eight kernels are calls of the body, in the files they always had
+    assert count("summary_body(") == {body: 1, "gte_backtest.hip": 2, "gte_trades.hip": 3, "gte_periods.hip": 3}
+    csrc = os.path.join(ROOT, "gym-trading-env_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):  # (comments and the Makefile too)
+        if os.path.isfile(os.path.join(csrc, name)) and not name.endswith(".so"):
+            assert "GTE_SIGNAL_BYTE_LOAD" not in open(os.path.join(csrc, name), errors="replace").read(), name
 
 
 _HOLDS_VARIANT = re.compile(r"(?i:variant)|^kv$|^DENSE$|^ROLLOUT")  # names of things that hold kernel_variant bits

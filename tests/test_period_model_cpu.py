@@ -325,3 +325,6 @@ def test_period_kernel_register_budget(source):
     for k in kernels:
         assert k["scratch"] == 0, k
         assert k["occupancy"] >= 2, k
+    if source == "gte_periods.hip":
+        test_host_cpu._assert_kernels_found(
+            kernels, ("gte_period_backtest_kernel", "gte_period_signal_kernel", "gte_period_exit_kernel"), 2)

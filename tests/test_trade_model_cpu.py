@@ -176,3 +176,6 @@ def test_trade_kernel_register_budget(source, min_occupancy):
     for k in kernels:
         assert k["scratch"] == 0, k
         assert k["occupancy"] >= min_occupancy, k
+    if source == "gte_trades.hip":
+        test_host_cpu._assert_kernels_found(
+            kernels, ("gte_trade_backtest_kernel", "gte_trade_signal_kernel", "gte_trade_exit_kernel"), 2)

@@ -15,8 +15,9 @@ other rows, which changes what is traded and not what is computed.
 
     python tools/signal_bench.py [--k 512] [--reps 9] [--shapes c3 c2]
 
-GTE_LIBRARY=<another build of libgte.so> times that build (the byte-per-step variant of the fused
-kernel: make -C gym-trading-env_amd/csrc libgte_exp.so EXP=-DGTE_SIGNAL_BYTE_LOAD=1).
+GTE_LIBRARY=<another build of libgte.so> times that build.  (At commit 5644e99 the fused kernel had a
+byte-per-step variant behind a macro, built with `make libgte_exp.so EXP=-DGTE_SIGNAL_BYTE_LOAD=1` and timed
+this way; the A/B is finished, profiles/signal_bench.log keeps it, and the macro no longer exists.)
 """
 import argparse
 import json
