@@ -11,7 +11,7 @@ from ._abi import GteError  # noqa: F401
 
 __all__ = ["TradingEnv", "MultiDatasetTradingEnv", "BatchedTradingEnv", "SB3TradingVecEnv", "GteError",
            "BacktestStats", "StrategyStats", "ExitState", "TradeStats", "StrategyTradeStats",
-           "PeriodStats", "StrategyPeriodStats", "periods",
+           "PeriodStats", "StrategyPeriodStats", "RealityCheck", "periods",
            "basic_reward_function", "dynamic_feature_last_position_taken",
            "dynamic_feature_real_position"]
 
@@ -24,6 +24,7 @@ _LAZY = {
     "BacktestStats": "backtest_stats", "StrategyStats": "backtest_stats", "ExitState": "exit_state",
     "TradeStats": "trade_stats", "StrategyTradeStats": "trade_stats",
     "PeriodStats": "period_stats", "StrategyPeriodStats": "period_stats",
+    "RealityCheck": "reality_check",
 }
 
 

@@ -78,6 +78,9 @@ PERIOD_METRIC_POSITIVE_SHARE = 5
 #: the same by name, in enum order (StrategyPeriodStats.score / .top take either)
 PERIOD_METRICS = ("mean_reward", "sharpe", "reward_sum", "period_sharpe", "worst_period", "positive_share")
 GTE_MAX_PERIODS = 128
+# gte_reality_check: resamples per slab of the moment sums, and the most resamples of one call
+GTE_BOOT_SLAB = 256
+GTE_BOOT_MAX_RESAMPLES = 65536
 
 
 class GteError(RuntimeError):
@@ -220,6 +223,22 @@ class GteStrategyPeriodStats(C.Structure):
     """struct gte_strategy_period_stats (include/gte.h)."""
     _fields_ = [(n, {"<i8": C.c_int64, "<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in STRATEGY_PERIOD_FIELDS] + \
                [("reserved", C.c_int32)]
+
+
+#: struct gte_reality_check_summary (include/gte.h), in declaration order: one 24-byte record
+REALITY_CHECK_SUMMARY_DTYPE = [("best_mean", "<f8"), ("best", "<i4"), ("count_rc", "<i4"), ("eligible", "<i4"),
+                               ("reserved", "<i4")]
+
+
+class GteRealityCheckSummary(C.Structure):
+    """struct gte_reality_check_summary (include/gte.h)."""
+    _fields_ = [(n, {"<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in REALITY_CHECK_SUMMARY_DTYPE]
+
+
+class GteRealityCheckOut(C.Structure):
+    """struct gte_reality_check_out (include/gte.h): device pointers, kept as integers."""
+    _fields_ = [(n, C.c_void_p) for n in ("mean", "boot_sum", "boot_sq_sum", "count_ge", "count_adj", "max_stat",
+                                          "max_index", "summary")]
 
 
 #: struct gte_strategy_stats (include/gte.h), in declaration order: one 128-byte record per strategy
@@ -429,6 +448,9 @@ SYMBOLS = {
                                           C.c_void_p]),
     "gte_rank_period_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_int32,
                                         C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gte_bootstrap_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]),
+    "gte_reality_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_void_p,
+                                    C.c_void_p, C.c_int32, _P(GteRealityCheckOut)]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
     "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,

@@ -121,6 +121,9 @@ struct gte_env {
   double* rank_score[2] = {nullptr, nullptr};
   int32_t* rank_index[2] = {nullptr, nullptr};
   int64_t rank_entries[2] = {0, 0};
+  // gte_reality_check: its scratch (gte_bootstrap.hip), kept the same way
+  void* boot_scratch = nullptr;
+  size_t boot_bytes = 0;
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -1624,6 +1627,71 @@ int gte_rank_period_stats(gte_env* E, const gte_strategy_period_stats* stats_dev
     e = gte::launch_rank_select(n_strategies, k, top_index_device, top_score_device, E->rank_score, E->rank_index,
                                 E->stream);
   if (e != hipSuccess) return fail(GTE_ERR_HIP, "period ranking launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_bootstrap_weights(gte_env* E, int32_t n, int32_t n_resamples, double block, uint64_t seed,
+                          double* weights_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n < 2 || n > GTE_MAX_PERIODS) return fail(GTE_ERR_INVALID, "n %d outside [2, %d]", n, GTE_MAX_PERIODS);
+  if (n_resamples < 1 || n_resamples > GTE_BOOT_MAX_RESAMPLES)
+    return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
+  if (!(block >= 1.0)) return fail(GTE_ERR_INVALID, "block must be >= 1.0");
+  if (!weights_device || ((uintptr_t)weights_device & 7))
+    return fail(GTE_ERR_INVALID, "weights_device must be an 8-byte aligned device array");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bootstrap_weights inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  double t = floor(4294967296.0 / block);
+  if (t > 4294967295.0) t = 4294967295.0;
+  const hipError_t e = gte::launch_bootstrap_weights(n, n_resamples, (uint32_t)t, block == 1.0 ? 1 : 0, seed,
+                                                     weights_device, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "bootstrap weights launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                      int32_t n_periods, const uint64_t period_mask[2], const double* benchmark_device,
+                      const double* weights_device, int32_t n_resamples, const gte_reality_check_out* out) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  if (n_periods < 1 || n_periods > GTE_MAX_PERIODS)
+    return fail(GTE_ERR_INVALID, "n_periods %d outside [1, %d]", n_periods, GTE_MAX_PERIODS);
+  if (n_resamples < 1 || n_resamples > GTE_BOOT_MAX_RESAMPLES)
+    return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
+  if (!period_mask) return fail(GTE_ERR_INVALID, "period_mask is NULL");
+  int n = 0;
+  for (int b = 0; b < 128; ++b) {
+    if (!((period_mask[b >> 6] >> (b & 63)) & 1)) continue;
+    if (b >= n_periods) return fail(GTE_ERR_INVALID, "period_mask selects period %d, at or above n_periods %d", b, n_periods);
+    ++n;
+  }
+  if (n < 2) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: at least two are needed", n);
+  if (!stats_device || ((uintptr_t)stats_device & 15))
+    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  if (!weights_device || ((uintptr_t)weights_device & 7) || ((uintptr_t)benchmark_device & 7))
+    return fail(GTE_ERR_INVALID, "weights_device (required) and benchmark_device must be 8-byte aligned device arrays");
+  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
+  if (!out->mean || !out->boot_sum || !out->boot_sq_sum || !out->max_stat || !out->summary ||
+      (((uintptr_t)out->mean | (uintptr_t)out->boot_sum | (uintptr_t)out->boot_sq_sum | (uintptr_t)out->max_stat |
+        (uintptr_t)out->summary) & 7))
+    return fail(GTE_ERR_INVALID, "out: mean, boot_sum, boot_sq_sum, max_stat and summary must be 8-byte aligned device pointers");
+  if (!out->count_ge || !out->count_adj || !out->max_index ||
+      (((uintptr_t)out->count_ge | (uintptr_t)out->count_adj | (uintptr_t)out->max_index) & 3))
+    return fail(GTE_ERR_INVALID, "out: count_ge, count_adj and max_index must be 4-byte aligned device pointers");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reality_check inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const size_t need = gte::reality_check_scratch_bytes(n_strategies, n, n_resamples);
+  if (E->boot_bytes < need) {  // (the old one stays until gte_destroy: launches in flight may use it)
+    const size_t bytes = need > 2 * E->boot_bytes ? need : 2 * E->boot_bytes;
+    uint8_t* fresh = nullptr;
+    TRY(dev_alloc(E, &fresh, bytes, false));
+    E->boot_scratch = fresh;
+    E->boot_bytes = bytes;
+  }
+  const hipError_t e = gte::launch_reality_check(stats_device, n_strategies, n_periods, period_mask, n,
+                                                 benchmark_device, weights_device, n_resamples, *out, E->boot_scratch,
+                                                 E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "reality check launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
 

@@ -217,6 +217,19 @@ hipError_t launch_period_scores(const gte_strategy_period_stats* stats, int n_st
                                 const uint64_t period_mask[2], int metric, int64_t min_steps, double* scores,
                                 double* cand_score, int32_t* cand_index, hipStream_t stream);
 
+// --- gte_bootstrap.hip: the bootstrap reality check (gte_bootstrap_weights, gte_reality_check, include/gte.h);
+// the caller has checked alignments
+// w[R][n] of the stationary bootstrap: thr and always (block == 1.0) as include/gte.h states them
+hipError_t launch_bootstrap_weights(int n, int n_resamples, uint32_t thr, int always, uint64_t seed, double* weights,
+                                    hipStream_t stream);
+// bytes of library-owned scratch one reality check of S strategies, n selected periods and R resamples needs
+size_t reality_check_scratch_bytes(int n_strategies, int n, int n_resamples);
+// gather, resample pass and close (period_mask: host, two words, n bits set, none at or above n_periods)
+hipError_t launch_reality_check(const gte_strategy_period_stats* stats, int n_strategies, int n_periods,
+                                const uint64_t period_mask[2], int n, const double* benchmark, const double* weights,
+                                int n_resamples, const gte_reality_check_out& out, void* scratch,
+                                hipStream_t stream);
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

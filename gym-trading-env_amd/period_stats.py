@@ -237,6 +237,17 @@ class StrategyPeriodStats:
         r = int((index >= 0).sum().item())
         return index[:r], top[:r]
 
+    def reality_check(self, periods=None, n_resamples=1000, block=1.0, seed=0, benchmark=None, weights=None):
+        """White's Reality Check of this leaderboard over `periods`, on the device (`gte_reality_check`): is the
+        best strategy's mean period return better than what luck alone gives the best of S tries?  A
+        `RealityCheck`.  `n_resamples` resamples of the stationary bootstrap with mean block length `block`
+        (in periods) and `seed` — the same arguments give the same bits; `weights` (NumPy or torch, [R, n] for n
+        selected periods) overrides the generated table; `benchmark` (NumPy or torch, [B]) is subtracted period by
+        period, e.g. buy-and-hold's period returns.  A strategy counts only if it stepped in every selected period
+        and all its period returns are finite.  Nothing here waits for the device."""
+        from . import reality_check
+        return reality_check.run(self, periods, n_resamples, block, seed, benchmark, weights)
+
     def numpy(self) -> np.ndarray:
         """The records on the host, one transfer: a structured array [S, B] of `STRATEGY_PERIOD_DTYPE`."""
         raw = self._records.cpu().numpy()

@@ -1,6 +1,7 @@
 """Period rows for `BatchedTradingEnv.track_periods`: one small integer per market row that says which period
 the row belongs to — equal blocks, train / embargo / test splits, calendar periods of a DatetimeIndex.  Host-side
-NumPy; every function returns an int8 array [T] with ids 0 .. B-1 and -1 for rows that count nowhere."""
+NumPy; every function but the last returns an int8 array [T] with ids 0 .. B-1 and -1 for rows that count nowhere.
+`bootstrap_weights` makes the resampling table of a bootstrap over periods, on the device."""
 from __future__ import annotations
 
 import numpy as np
@@ -59,3 +60,12 @@ def from_index(index, freq: str = "M") -> np.ndarray:
     if len(uniq) > MAX_PERIODS:
         raise ValueError(f"{len(uniq)} periods of frequency {freq!r}: at most {MAX_PERIODS} are kept per env")
     return _checked(ids.astype(np.int64))
+
+
+def bootstrap_weights(env, n, n_resamples, block=1.0, seed=0):
+    """The stationary bootstrap's resampling weights over `n` selected periods, made on the env's device
+    (`gte_bootstrap_weights`): a torch f64 tensor [n_resamples, n], entry [r, i] the number of times position i is
+    drawn in resample r.  `block` >= 1 is the mean block length (1: every draw independent).  What
+    `StrategyPeriodStats.reality_check` uses unless it is given `weights=`."""
+    from .reality_check import bootstrap_weights as make
+    return make(env, n, n_resamples, block, seed)

@@ -1142,6 +1142,80 @@ int gte_rank_period_stats(gte_env* env, const gte_strategy_period_stats* stats_d
                           int32_t k, int32_t* top_index_device, double* top_score_device,
                           double* scores_device /* [n_strategies] or NULL */);
 
+/* ---- BOOTSTRAP REALITY CHECK OF A LEADERBOARD (White 2000): is the best of S strategies better than what luck
+ * alone gives the best of S tries?  A bootstrap over time blocks of the MAXIMUM over all strategies of their
+ * centred mean period return, from the [S, B] gte_strategy_period_stats on the device.  The [R, S] matrix of
+ * resampled statistics is never written.  One fixed order of IEEE f64 operations, every one of them ONE operation
+ * as written (no fused multiply-add): the same inputs give the same bits for any launch geometry.
+ *
+ * RESAMPLING WEIGHTS, gte_bootstrap_weights.  weights[r * n + i] (f64) is how many times position i of the n
+ * selected periods is drawn in resample r; each row sums to n.  The stationary bootstrap (Politis & Romano 1994)
+ * on the circular sequence 0 .. n-1 with mean block length `block`:
+ *     thr = (uint32) min(floor(4294967296.0 / block), 4294967295.0)                       (host, once)
+ *     draw j = 0 .. n-1 of resample r:
+ *       o = philox4x32_10(counter = {r, j, 0, 0x424F4F54 'BOOT'}, key = {seed low word, seed high word})
+ *       a new block starts iff j == 0 or block == 1.0 or o[0] < thr:    pos = mulhi32(o[1], n)
+ *       otherwise:                                                       pos = (pos + 1) % n
+ *       weights[r][pos] += 1.0
+ * One thread per resample, one launch on the env's stream, no host synchronisation.  Writes the n_resamples * n
+ * doubles of weights_device and nothing else.
+ *
+ * THE RESAMPLE PASS AND THE CLOSE, gte_reality_check.  P = p_0 < ... < p_{n-1}, the periods whose bit is set in
+ * period_mask (bit b % 64 of word b / 64; HOST uint64 [2]).  weights_device: DEVICE f64 [n_resamples * n], made
+ * by gte_bootstrap_weights or by the caller — any finite weights, zeros and non-integers included (a jackknife,
+ * a circular block scheme).  benchmark_device: DEVICE f64 [n_periods] (buy-and-hold's period returns) or NULL.
+ * Strategy s is ELIGIBLE iff for every b in P steps_b > 0 and reward_sum_b is finite; of a record only steps
+ * and reward_sum are read, and only for b in P.  Per eligible strategy:
+ *     d_i = reward_sum[s][p_i] - benchmark[p_i]            (no subtraction at all without a benchmark)
+ *     t = 0.0; over i ascending: t = t + d_i;              mean_s = t / (double)n
+ *     resample r:  a = 0.0; over i ascending: a = a + weights[r][i] * d_i;      c_rs = a / (double)n - mean_s
+ * WRITTEN (all of every array, R = n_resamples):
+ *     mean[s]          mean_s; NaN for an ineligible strategy
+ *     max_stat[r]      m = -inf; over eligible s ascending: if (c_rs > m) m = c_rs        (a NaN never wins)
+ *     max_index[r]     the s that set m last, the lowest that attains the maximum; -1 when none compared greater
+ *     boot_sum[s], boot_sq_sum[s], count_ge[s]    resamples cut into slabs of GTE_BOOT_SLAB; within a slab
+ *                      q1 = 0.0; q2 = 0.0; over r ascending: q1 = q1 + c_rs; q2 = q2 + c_rs * c_rs;
+ *                      ge += (c_rs >= mean_s);  then from 0.0 the slabs' q1, q2, ge added in ascending slab order.
+ *                      NaN, NaN, 0 for an ineligible strategy
+ *     count_adj[s]     the number of r with max_stat[r] >= mean_s; 0 for an ineligible strategy
+ *     summary          best: m = -inf; over eligible s ascending: if (mean_s > m) { m = mean_s; best = s; }, -1
+ *                      when none compared greater; best_mean = mean[best] (NaN for best == -1);
+ *                      count_rc = count_adj[best] (0 for best == -1); eligible = the number of eligible strategies
+ * The Reality Check p-value is count_rc / R; the single-step adjusted p-value of strategy s is count_adj[s] / R,
+ * its naive one count_ge[s] / R.
+ * Five launches on the env's stream, no atomics, no host synchronisation; the staging array d[n][S] and the
+ * partial results live in library-owned scratch, allocated by the first call and again when a call outgrows it
+ * (as gte_rank_strategies keeps its lists).  The inputs are only read; the outputs must not overlap them or
+ * each other.
+ *
+ * BOTH return GTE_ERR_INVALID, with nothing launched and nothing written, for: a NULL env or required pointer
+ * (benchmark_device alone may be NULL) or one not aligned for its type (stats_device: 16 bytes); n < 2 or
+ * n > GTE_MAX_PERIODS; a mask with fewer than two bits set, or a bit at or above n_periods; n_periods outside
+ * [1, GTE_MAX_PERIODS]; n_resamples outside [1, GTE_BOOT_MAX_RESAMPLES]; block below 1.0 or NaN;
+ * n_strategies < 1.  GTE_ERR_STATE inside a stream capture. */
+#define GTE_BOOT_SLAB 256
+#define GTE_BOOT_MAX_RESAMPLES 65536
+int gte_bootstrap_weights(gte_env* env, int32_t n, int32_t n_resamples, double block, uint64_t seed,
+                          double* weights_device /* [n_resamples * n] */);
+typedef struct gte_reality_check_summary {   /* 24 bytes */
+  double  best_mean;
+  int32_t best;
+  int32_t count_rc;
+  int32_t eligible;
+  int32_t reserved;        /* written as zero */
+} gte_reality_check_summary;
+typedef struct gte_reality_check_out {       /* DEVICE pointers, all required */
+  double  *mean, *boot_sum, *boot_sq_sum;    /* f64 [n_strategies] */
+  int32_t *count_ge, *count_adj;             /* i32 [n_strategies] */
+  double  *max_stat;                         /* f64 [n_resamples] */
+  int32_t *max_index;                        /* i32 [n_resamples] */
+  gte_reality_check_summary* summary;        /* one record */
+} gte_reality_check_out;
+int gte_reality_check(gte_env* env, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                      int32_t n_periods, const uint64_t period_mask[2],
+                      const double* benchmark_device /* [n_periods] or NULL */, const double* weights_device,
+                      int32_t n_resamples, const gte_reality_check_out* out);
+
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
 /* Same-step auto-reset with gte_config.final_obs: struct-of-arrays snapshot (device pointers,

@@ -1,0 +1,405 @@
+"""The bootstrap reality check on the device (gte_bootstrap_weights, gte_reality_check, include/gte.h) against its
+model (tests/bootstrap_model.py), bit for bit on every output, NaN as NaN: the weights over a grid of n, R, block;
+the resample pass and the close over S x B x R with masks in both words, a benchmark, values from 1e-300 to 1e300,
+ineligible and duplicate strategies and caller-made weights; determinism and isolation; every refusal, with the
+outputs untouched; the Python pipeline end to end; the example."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import bootstrap_model as bm
+from gym_trading_env_amd import _abi
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED = (0xB007 << 32) | 12345   # the high word set
+OUTPUTS = (("mean", np.float64), ("boot_sum", np.float64), ("boot_sq_sum", np.float64), ("count_ge", np.int32),
+           ("count_adj", np.int32), ("max_stat", np.float64), ("max_index", np.int32))
+
+
+@pytest.fixture(scope="module")
+def env():
+    from gym_trading_env_amd.batched import BatchedTradingEnv
+    rng = np.random.default_rng(0)
+    close = 100.0 * np.exp(np.cumsum(rng.normal(0, 1e-2, 60)))
+    feat = rng.normal(0, 1, (60, 3)).astype(np.float32)
+    e = BatchedTradingEnv((feat, close), num_envs=64, positions=[-1, 0, 1], windows=None)
+    yield e
+    e.close()
+
+
+def _words(mask):
+    w = (C.c_uint64 * 2)(0, 0)
+    for b in np.flatnonzero(mask):
+        w[int(b) >> 6] |= 1 << (int(b) & 63)
+    return w
+
+
+# ---- the weights ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", [2, 3, 64, 65, 127, 128])
+def test_weights_equal_the_model(env, n):
+    from gym_trading_env_amd import periods
+    for R in (1, 255, 256, 257, 1000):
+        for block in (1.0, 1.5, 4.0, 1e9):
+            got = periods.bootstrap_weights(env, n, R, block=block, seed=SEED)
+            assert got.is_cuda and tuple(got.shape) == (R, n) and str(got.dtype) == "torch.float64"
+            want = bm.weights(n, R, block, SEED)
+            assert got.cpu().numpy().tobytes() == want.tobytes(), (n, R, block)
+    other = periods.bootstrap_weights(env, n, 257, block=1.5, seed=SEED + 1).cpu().numpy()
+    assert other.tobytes() != bm.weights(n, 257, 1.5, SEED).tobytes() and (other.sum(axis=1) == n).all()
+
+
+# ---- the resample pass and the close ----------------------------------------------------------------------------
+
+def craft(S, B, seed, mask, wild, dead=False):
+    """[S, B] strategy period records: period returns over twelve decades, rows that dominate and their duplicates
+    (a tie goes to the lowest index), tiny rows; with `wild`, returns up to 1e300 of both signs whose sums overflow;
+    ineligible rows (no step, NaN, +inf, -inf in a selected period) and NaN / inf / no step in UNSELECTED periods,
+    which must not matter"""
+    rng = np.random.default_rng(seed)
+    x = rng.normal(0, 1, (S, B)) * 10.0 ** rng.integers(-6, 6, (S, 1))
+    steps = rng.integers(1, 50, (S, B))
+    sel, unsel = np.flatnonzero(mask), np.flatnonzero(~mask)
+    def put(k, values=None, b=None, step=None):   # strategy k, where there is one
+        if k >= S:
+            return
+        if step is not None:
+            steps[k, b] = step
+        elif b is not None:
+            x[k, b] = values
+        else:
+            x[k] = values
+    if S > 3:
+        put(3, rng.normal(0, 1, B) * 1e7)                       # dominates in many resamples ...
+        put(17, x[3])                                           # ... and so does its duplicate, which never wins
+        put(40, x[3])
+    put(5, rng.normal(0, 1, B) * 1e-300)
+    put(6, rng.normal(0, 1, B) * 1e-310)                        # subnormal returns
+    if wild:
+        put(7, rng.choice([1e300, -1e300, 1e299], B))
+        put(8, np.full(B, 1.7e308))                             # t and a overflow, inf - inf follows
+        if S > 9:
+            put(9, -x[8])
+    for k, bad in ((11, np.nan), (12, np.inf), (13, -np.inf)):
+        put(k, bad, b=sel[k % len(sel)])
+    put(14, b=sel[-1], step=0)
+    put(15, b=sel[0], step=-3)
+    if len(unsel):
+        x[:, unsel[0]] = np.nan
+        x[::2, unsel[-1]] = np.inf
+        steps[:, unsel[-1]] = 0
+    if dead:
+        steps[:, sel[0]] = 0
+    return bm.records(x, steps)
+
+
+def run_check(env, stats, mask, benchmark, w, fill=None):
+    """gte_reality_check over host-made records and weights -> dict of host arrays, like the model's"""
+    import torch
+    dev = env._t["obs"].device
+    S, B = stats.shape
+    R = w.shape[0]
+    d_stats = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(dev)
+    d_w = torch.from_numpy(np.ascontiguousarray(w)).to(dev)
+    d_b = None if benchmark is None else torch.from_numpy(np.ascontiguousarray(benchmark)).to(dev)
+    out = {k: torch.full((S if k not in ("max_stat", "max_index") else R,), -7, dtype=getattr(torch, np.dtype(t).name),
+                         device=dev) for k, t in OUTPUTS}
+    out["summary"] = torch.full((24,), 0xAB, dtype=torch.uint8, device=dev)
+    ptrs = _abi.GteRealityCheckOut(**{k: v.data_ptr() for k, v in out.items()})
+    torch.cuda.synchronize()
+    _abi.check(env._lib, env._lib.gte_reality_check(
+        env._h, C.c_void_p(d_stats.data_ptr()), S, B, _words(mask), None if d_b is None else C.c_void_p(d_b.data_ptr()),
+        C.c_void_p(d_w.data_ptr()), R, C.byref(ptrs)))
+    env.synchronize()
+    got = {k: v.cpu().numpy() for k, v in out.items()}
+    got["summary"] = got["summary"].view(bm.SUMMARY)
+    got["stats_after"] = d_stats.cpu().numpy().tobytes()
+    return got
+
+
+def assert_same(got, want, tag):
+    for k, t in OUTPUTS:
+        g, w = got[k], want[k]
+        assert g.dtype == t and g.shape == w.shape, (tag, k)
+        same = bm.same_f64(g, w) if t is np.float64 else np.array_equal(g, w)
+        if not same:
+            bad = [i for i in range(len(w)) if not (bm.same_f64(g[i:i + 1], w[i:i + 1]) if t is np.float64 else g[i] == w[i])]
+            pytest.fail(f"{tag}: {k} differs at {len(bad)} of {len(w)} places, first {[(i, g[i], w[i]) for i in bad[:5]]}")
+    gs, ws = got["summary"][0], want["summary"][0]
+    for f in ("best", "count_rc", "eligible", "reserved"):
+        assert gs[f] == ws[f], (tag, f, gs, ws)
+    assert bm.same_f64(np.array([gs["best_mean"]]), np.array([ws["best_mean"]])), (tag, gs, ws)
+
+
+def _masks(B):
+    every = np.ones(B, bool)
+    if B == 2:
+        return every, every
+    skip = np.arange(B) % 2 == 1                  # B = 128: 64 periods, bits in both words
+    skip[B - 1] = True
+    if B == 128:
+        skip[[63, 64]] = True
+    return every, skip
+
+
+@pytest.mark.parametrize("B", [2, 7, 128])
+@pytest.mark.parametrize("S", [1, 63, 64, 65, 257, 1000])
+def test_pass_and_close_equal_the_model(env, S, B):
+    """Five calls per (S, B), one per R, across the slab edge at 256 and two slabs and a rest (513), the chunk of 16
+    resamples cut short (1, 255, 257, 513); S below, at and above a wavefront, a tile of 256 and several tiles."""
+    every, skip = _masks(B)
+    rng = np.random.default_rng(S * 131 + B)
+    cases = [(1, every, False, "made", False), (255, skip, True, "made", True), (256, every, True, "own", False),
+             (257, skip, False, "made", True), (513, every, False, "made4", True)]
+    seen_tie = seen_nan = False
+    for R, mask, with_benchmark, kind, wild in cases:
+        n = int(mask.sum())
+        stats = craft(S, B, S + B + R, mask, wild)
+        if kind == "own":      # a caller's table: zeros, non-integers, a jackknife row, a negative weight
+            w = rng.choice([0.0, 0.5, 1.0, 2.25, 1e-3], (R, n)) * rng.choice([1.0, 1.0, 3.0], (R, 1))
+            w[0] = n / (n - 1.0)
+            w[0, 0] = 0.0
+            w[1, n - 1] = -1.5
+        else:
+            w = bm.weights(n, R, 4.0 if kind == "made4" else 1.0, SEED)
+        benchmark = None
+        if with_benchmark:
+            benchmark = rng.normal(0, 1e3, B)
+            benchmark[~mask] = np.nan             # an unselected period's entry is never used
+        got = run_check(env, stats, mask, benchmark, w)
+        want = bm.reality_check(stats, mask, benchmark, w)
+        assert_same(got, want, f"S={S} B={B} R={R}")
+        assert got["stats_after"] == stats.tobytes()
+        seen_tie = seen_tie or bool((want["max_index"] == 3 % S).any())
+        seen_nan = seen_nan or bool(np.isnan(want["boot_sum"][want["eligible"]]).any())
+        if S > 17:
+            assert not np.isin(want["max_index"], [17, 40]).any()      # the duplicates of strategy 3 never win
+            assert want["eligible"].sum() < S
+    assert seen_tie and (seen_nan or S < 10)
+
+
+def test_nobody_eligible(env):
+    mask = np.arange(7) != 2
+    stats = craft(300, 7, 1, mask, True, dead=True)
+    w = bm.weights(6, 40, 2.0, SEED)
+    got = run_check(env, stats, mask, None, w)
+    assert_same(got, bm.reality_check(stats, mask, None, w), "dead")
+    assert (got["max_index"] == -1).all() and (got["max_stat"] == -np.inf).all()
+    s = got["summary"][0]
+    assert s["best"] == -1 and np.isnan(s["best_mean"]) and s["count_rc"] == 0 and s["eligible"] == 0
+    assert np.isnan(got["mean"]).all() and np.isnan(got["boot_sum"]).all() and not got["count_adj"].any()
+
+
+def test_determinism_and_isolation(env):
+    from gym_trading_env_amd import periods
+    mask = np.arange(70) % 3 != 0
+    n = int(mask.sum())
+    stats = craft(700, 70, 5, mask, True)
+    w = bm.weights(n, 300, 3.0, SEED)
+    bench = np.random.default_rng(1).normal(0, 1, 70)
+    keys = [k for k, _ in OUTPUTS] + ["summary"]
+    first = run_check(env, stats, mask, bench, w)
+    again = run_check(env, stats, mask, bench, w)
+    for k in keys:
+        assert first[k].tobytes() == again[k].tobytes(), k
+    assert first["stats_after"] == stats.tobytes()
+    # unrelated launches in between: other weights, a larger check that makes the library take new scratch, a smaller one
+    periods.bootstrap_weights(env, 128, 1000, block=2.0, seed=1)
+    big = craft(3000, 128, 6, np.ones(128, bool), False)
+    run_check(env, big, np.ones(128, bool), None, bm.weights(128, 17, 1.0, 3))
+    run_check(env, craft(5, 3, 7, np.ones(3, bool), False), np.ones(3, bool), None, bm.weights(3, 600, 1.0, 3))
+    third = run_check(env, stats, mask, bench, w)
+    for k in keys:
+        assert first[k].tobytes() == third[k].tobytes(), k
+
+
+# ---- refusals -------------------------------------------------------------------------------------------------
+
+def test_refusals_leave_every_output_untouched(env):
+    import torch
+    lib, h = env._lib, env._h
+    dev = env._t["obs"].device
+    err = lambda: lib.gte_last_error().decode()
+    S, B, R, n = 10, 6, 20, 4
+    mask = np.array([1, 1, 0, 1, 1, 0], bool)
+    stats = craft(S, B, 1, mask, False)
+    d_stats = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(dev)
+    d_w = torch.from_numpy(bm.weights(n, R, 1.0, 1)).to(dev)
+    out = {k: torch.full((64,), 0x5A, dtype=torch.uint8, device=dev) for k, _ in OUTPUTS}
+    out["max_stat"] = torch.full((R * 8,), 0x5A, dtype=torch.uint8, device=dev)
+    out["max_index"] = torch.full((R * 4,), 0x5A, dtype=torch.uint8, device=dev)
+    for k in ("mean", "boot_sum", "boot_sq_sum"):
+        out[k] = torch.full((S * 8,), 0x5A, dtype=torch.uint8, device=dev)
+    out["summary"] = torch.full((24,), 0x5A, dtype=torch.uint8, device=dev)
+    w_out = torch.full((R * n * 8,), 0x5A, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    ptrs = lambda **over: _abi.GteRealityCheckOut(**{**{k: v.data_ptr() for k, v in out.items()}, **over})
+    st, wp, words = C.c_void_p(d_stats.data_ptr()), C.c_void_p(d_w.data_ptr()), _words(mask)
+    INVALID = _abi.GTE_ERR_INVALID
+
+    def check(*args):
+        return lib.gte_reality_check(*args)
+    good = ptrs()
+    assert check(None, st, S, B, words, None, wp, R, C.byref(good)) == INVALID
+    assert check(h, None, S, B, words, None, wp, R, C.byref(good)) == INVALID and "stats_device" in err()
+    assert check(h, C.c_void_p(d_stats.data_ptr() + 8), S, B, words, None, wp, R, C.byref(good)) == INVALID
+    assert check(h, st, 0, B, words, None, wp, R, C.byref(good)) == INVALID and "n_strategies" in err()
+    for bad_B in (0, -1, 129):
+        assert check(h, st, S, bad_B, words, None, wp, R, C.byref(good)) == INVALID and "n_periods" in err()
+    assert check(h, st, S, B, None, None, wp, R, C.byref(good)) == INVALID and "period_mask" in err()
+    for bad_mask in (np.zeros(6, bool), np.array([0, 0, 1, 0, 0, 0], bool)):
+        assert check(h, st, S, B, _words(bad_mask), None, wp, R, C.byref(good)) == INVALID and "at least two" in err()
+    for bit in (6, 64, 127):   # a bit at or above n_periods, in either word
+        over = _words(mask)
+        over[bit >> 6] |= 1 << (bit & 63)
+        assert check(h, st, S, B, over, None, wp, R, C.byref(good)) == INVALID and "at or above n_periods" in err()
+    for bad_R in (0, -5, 65537):
+        assert check(h, st, S, B, words, None, wp, bad_R, C.byref(good)) == INVALID and "n_resamples" in err()
+    assert check(h, st, S, B, words, None, None, R, C.byref(good)) == INVALID and "weights_device" in err()
+    assert check(h, st, S, B, words, C.c_void_p(d_w.data_ptr() + 4), wp, R, C.byref(good)) == INVALID
+    assert check(h, st, S, B, words, None, wp, R, None) == INVALID and "out is NULL" in err()
+    for k in out:
+        assert check(h, st, S, B, words, None, wp, R, C.byref(ptrs(**{k: None}))) == INVALID and "out:" in err(), k
+    assert check(h, st, S, B, words, None, wp, R, C.byref(ptrs(count_ge=out["count_ge"].data_ptr() + 2))) == INVALID
+
+    def weights(*args):
+        return lib.gte_bootstrap_weights(*args)
+    wo = C.c_void_p(w_out.data_ptr())
+    assert weights(None, n, R, 1.0, 1, wo) == INVALID
+    for bad_n in (1, 0, -2, 129):
+        assert weights(h, bad_n, R, 1.0, 1, wo) == INVALID and "n " in err()
+    for bad_R in (0, -1, 65537):
+        assert weights(h, n, bad_R, 1.0, 1, wo) == INVALID and "n_resamples" in err()
+    for bad_block in (0.999, 0.0, -1.0, float("nan")):
+        assert weights(h, n, R, bad_block, 1, wo) == INVALID and "block" in err()
+    assert weights(h, n, R, 1.0, 1, None) == INVALID and "weights_device" in err()
+    assert weights(h, n, R, 1.0, 1, C.c_void_p(w_out.data_ptr() + 4)) == INVALID
+    env.synchronize()
+    torch.cuda.synchronize()
+    for k, v in list(out.items()) + [("weights", w_out)]:
+        assert bool((v == 0x5A).all()), f"{k} was written by a refused call"
+    assert d_stats.cpu().numpy().tobytes() == stats.tobytes()
+    # and the Python side says the same before any call is made
+    from gym_trading_env_amd import periods
+    for bad in (dict(n=1), dict(n=129), dict(n_resamples=0), dict(n_resamples=65537), dict(block=0.5),
+                dict(block=float("nan"))):
+        with pytest.raises(ValueError):
+            periods.bootstrap_weights(env, **{**dict(n=4, n_resamples=10), **bad})
+    # inside a stream capture: refused, nothing launched
+    seen = []
+
+    def body(i):
+        try:
+            periods.bootstrap_weights(env, 4, 10)
+        except _abi.GteError as e:
+            seen.append(e)
+            raise
+    env.reset()
+    with pytest.raises(Exception):
+        env.capture_steps(body, 2)
+    torch.cuda.synchronize()
+    assert len(seen) == 1 and seen[0].status == _abi.GTE_ERR_STATE and "stream capture" in str(seen[0])
+
+
+# ---- end to end -----------------------------------------------------------------------------------------------
+
+def test_pipeline_backtest_to_reality_check():
+    """256 envs, 16 strategies, 6 periods: backtest_signals -> period_stats.by_strategy().reality_check(...) equals the
+    model applied to .numpy() of the same fold; a benchmark and a caller's table go the same way."""
+    import gym_trading_env_amd as gte
+    import torch
+    from gym_trading_env_amd import periods
+    N, S, T = 256, 16, 400
+    rng = np.random.default_rng(11)
+    close = 100.0 * np.exp(np.cumsum(rng.normal(0, 1e-2, T)))
+    feat = rng.normal(0, 1, (T, 3)).astype(np.float32)
+    env = gte.BatchedTradingEnv((feat, close), num_envs=N, positions=[-1, 0, 1], windows=None, trading_fees=1e-4,
+                                max_episode_duration=40, autoreset="next_step", seed=4)
+    table = np.repeat(rng.integers(0, 3, (S, T // 4)), 4, axis=1).astype(np.int8)
+    table[5] = -1                                      # strategy 5 holds its first position
+    env.bind_signals(table)
+    env.reset()
+    env.track_periods(periods.blocks(T, 6))
+    by = env.backtest_signals(150).period_stats.by_strategy()
+    host = by.numpy()
+    sel = [0, 1, 2, 4]
+    mask = np.isin(np.arange(6), sel)
+    rc = by.reality_check(periods=sel, n_resamples=300, block=2, seed=7)
+    assert isinstance(rc, gte.RealityCheck) and rc.num_resamples == 300 and rc.periods == sel
+    w = bm.weights(4, 300, 2.0, 7)
+    assert rc.weights.cpu().numpy().tobytes() == w.tobytes()
+    want = bm.reality_check(host, mask, None, w)
+    got = rc.numpy()
+    for k in ("mean", "boot_sum", "boot_sq_sum"):
+        assert bm.same_f64(got[k], want[k]), k
+    assert bm.same_f64(got["max_stats"], want["max_stat"])
+    for k, wk in (("max_index", "max_index"), ("count_ge", "count_ge"), ("count_adj", "count_adj"), ("eligible", "eligible")):
+        np.testing.assert_array_equal(got[k], want[wk], err_msg=k)
+    p_rc, naive, adjusted = bm.p_values(want, 300)
+    ok = want["eligible"]
+    assert ok.sum() >= 8 and rc.num_eligible == int(ok.sum())
+    assert rc.p_value == p_rc and rc.best == int(want["summary"][0]["best"]) and rc.best >= 0
+    assert rc.best_mean == float(want["summary"][0]["best_mean"])
+    np.testing.assert_array_equal(got["p_adjusted"][ok], adjusted[ok])
+    np.testing.assert_array_equal(got["p_individual"][ok], naive[ok])
+    assert np.isnan(got["p_adjusted"][~ok]).all() and rc.p_adjusted.is_cuda and rc.std_error.is_cuda
+    R = 300.0
+    with np.errstate(all="ignore"):
+        se = np.sqrt(np.maximum(want["boot_sq_sum"] / R - (want["boot_sum"] / R) ** 2, 0.0))
+    np.testing.assert_allclose(got["std_error"][ok], se[ok], rtol=1e-12, atol=0.0)
+    assert rc.p_value == float(rc.p_adjusted[rc.best])
+    # a benchmark (NumPy, then torch) and a caller's table
+    bench = rng.normal(0, 1e-3, 6)
+    own = rng.choice([0.0, 1.0, 2.0, 0.5], (77, 4))
+    want = bm.reality_check(host, mask, bench, own)
+    for b_arg, w_arg in ((bench, own), (torch.from_numpy(bench).cuda(), torch.from_numpy(own).cuda())):
+        rc2 = by.reality_check(periods=mask, benchmark=b_arg, weights=w_arg)
+        assert rc2.num_resamples == 77
+        got = rc2.numpy()
+        assert bm.same_f64(got["mean"], want["mean"]) and bm.same_f64(got["max_stats"], want["max_stat"])
+        np.testing.assert_array_equal(got["count_adj"], want["count_adj"])
+        assert rc2.p_value == bm.p_values(want, 77)[0]
+    with pytest.raises(ValueError, match="at least two"):
+        by.reality_check(periods=[3])
+    with pytest.raises(ValueError, match="weights must have shape"):
+        by.reality_check(periods=sel, weights=np.ones((5, 3)))
+    with pytest.raises(ValueError, match="benchmark must have shape"):
+        by.reality_check(periods=sel, benchmark=np.ones(5))
+    assert by.numpy().tobytes() == host.tobytes()       # the check changes no record
+    env.close()
+
+
+def test_reality_check_example(capsys):
+    """examples/backtest_reality_check.py runs at a small shape and prints its two pairs of p-values, which are the
+    result objects'."""
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    try:
+        import backtest_reality_check as ex
+    finally:
+        sys.path.pop(0)
+    out = ex.main(n_fast=3, n_slow=3, replicas=16, K=900, T=1500, n_periods=12, n_train=8, n_resamples=200)
+    text = capsys.readouterr().out
+    lines = [l for l in text.splitlines() if "Reality Check p-value" in l]
+    assert len(lines) == 2 and lines[0].startswith("random walk") and lines[1].startswith("one real edge")
+    for line, case in zip(lines, (out["noise"], out["edge"])):
+        naive = float(line.split("best naive p-value")[1].split()[0])
+        rc = float(line.split("Reality Check p-value")[1].split()[0])
+        assert 0.0 <= naive <= 1.0 and 0.0 <= rc <= 1.0
+        assert abs(naive - case["p_naive"]) < 5.1e-4 and abs(rc - case["p_reality"]) < 5.1e-4
+        check = case["check"]
+        assert check.num_resamples == 200 and check.periods == list(range(8)) and case["eligible"] >= 2
+        host = case["by_strategy"]
+        want = bm.reality_check(host, np.arange(12) < 8, None, bm.weights(8, 200, 2.0, 7))
+        assert case["p_reality"] == bm.p_values(want, 200)[0] and case["best"] == int(want["summary"][0]["best"])
+    assert out["edge"]["strategies"] == out["noise"]["strategies"] + 1
+    # every strategy stepped in every training period, and the one that peeks leads and is significant at the usual
+    # 5 % level although it competes with the whole sweep
+    for case in (out["noise"], out["edge"]):
+        assert case["eligible"] == case["strategies"]
+    peek = out["edge"]["strategies"] - 1
+    assert out["edge"]["best"] == peek and out["edge"]["p_adjusted"][peek] <= 0.05 and out["edge"]["p_reality"] <= 0.05
