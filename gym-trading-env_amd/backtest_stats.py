@@ -3,11 +3,10 @@ libgte (struct gte_backtest_stats, include/gte.h) as torch views of device memor
 figures a backtest is read for, derived from them on the device when first asked for."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _abi
+from .strategy_records import StrategyRecords, field_views, metric_code, resolve_strategy_map
 
 
 class BacktestStats:
@@ -23,18 +22,14 @@ class BacktestStats:
     FIELDS = tuple(n for n, _ in _abi.BACKTEST_FIELDS)
 
     def __init__(self, env, ptr: int):
-        from .batched import _device_view
         self._env = env
         self._derived = {}
         self._map = getattr(env, "_backtest_map", None)  # what the call that made these records ran with
         self._trades_ptr = getattr(env, "_trades_ptr", 0)  # the trade records, if that call kept them
         # (address, B, generation) of the period records, if that call kept them
         self._periods = getattr(env, "_periods", None)
-        dev = env._t["obs"].device
-        stride = np.dtype(_abi.BACKTEST_DTYPE).itemsize
-        offsets = np.dtype(_abi.BACKTEST_DTYPE).fields
-        for name, typestr in _abi.BACKTEST_FIELDS:
-            setattr(self, name, _device_view(ptr + offsets[name][1], (env.num_envs,), typestr, dev, (stride,)))
+        vars(self).update(field_views(ptr, _abi.BACKTEST_FIELDS, _abi.BACKTEST_DTYPE, (env.num_envs,),
+                                      env._t["obs"].device))
 
     def _lazy(self, key, make):
         if key not in self._derived:
@@ -113,31 +108,15 @@ class BacktestStats:
         runs, so after a later `backtest()` / `backtest_signals()` it folds that call's records — while the
         default map and S stay those captured when this object was made.  Fold first, or pass the later
         call's `strategy` / `n_strategies`.  The launch is enqueued on the env's stream (see `StrategyStats`)."""
-        if strategy is None and n_strategies is None:
-            if self._map is None:
-                raise ValueError("by_strategy() of a backtest() result needs n_strategies (and strategy=, unless "
-                                 "env e follows strategy (env_id_base + e) % S)")
-            strategy, n_strategies = self._map
-        elif n_strategies is None:
-            if self._map is None:
-                raise ValueError("by_strategy(strategy=...) needs n_strategies")
-            n_strategies = self._map[1]
+        strategy, n_strategies = resolve_strategy_map(self._map, strategy, n_strategies)
         return StrategyStats._reduce(self._env, None, strategy, n_strategies)
 
 
 def _metric_code(metric) -> int:
-    if isinstance(metric, str):
-        if metric.lower() not in _abi.STRATEGY_METRICS:
-            raise ValueError(f"unknown metric {metric!r}: one of {', '.join(_abi.STRATEGY_METRICS)}")
-        return _abi.STRATEGY_METRICS.index(metric.lower())
-    if isinstance(metric, (bool, float)) or int(metric) != metric:
-        raise TypeError("metric must be a name or a METRIC_* constant")
-    if not 0 <= int(metric) < len(_abi.STRATEGY_METRICS):
-        raise ValueError(f"unknown metric {metric}: 0 .. {len(_abi.STRATEGY_METRICS) - 1}")
-    return int(metric)
+    return metric_code(metric, _abi.STRATEGY_METRICS, "METRIC")
 
 
-class StrategyStats:
+class StrategyStats(StrategyRecords):
     """Per-strategy statistics of a backtest: the env records of a `BacktestStats` folded over the
     members of each strategy by one device launch (struct gte_strategy_stats, include/gte.h), and the
     ranking of the strategies by a score, also on the device (`gte_rank_strategies`).
@@ -153,71 +132,18 @@ class StrategyStats:
     env moved to another stream (`gte_set_stream`) is the caller's to order.  `top()` alone waits: it trims
     its result to the number of ranked strategies, which it reads back (`numpy()` is a transfer)."""
 
-    FIELDS = tuple(n for n, _ in _abi.STRATEGY_FIELDS)
-    METRICS = _abi.STRATEGY_METRICS
+    DTYPE, RECORD_FIELDS = _abi.STRATEGY_DTYPE, _abi.STRATEGY_FIELDS
+    FIELDS = tuple(n for n, _ in RECORD_FIELDS)
+    METRICS, METRIC_PREFIX = _abi.STRATEGY_METRICS, "METRIC"
+    REDUCE, RANK = "gte_reduce_backtest_stats", "gte_rank_strategies"
 
     def __init__(self, env, records, inputs=()):
-        from .batched import _device_view
-        self._env = env
-        self._records = records  # uint8 [S, 128], CUDA
-        self._keep = inputs      # what the reduction reads: alive while the launch may be in flight
-        self._derived = {}
-        self.num_strategies = int(records.shape[0])
-        dt = np.dtype(_abi.STRATEGY_DTYPE)
-        for name, typestr in _abi.STRATEGY_FIELDS:
-            setattr(self, name, _device_view(records.data_ptr() + dt.fields[name][1], (self.num_strategies,), typestr,
-                                             records.device, (dt.itemsize,)))
+        super().__init__(env, records, inputs, (int(records.shape[0]),))  # records: uint8 [S, 128], CUDA
 
     # -- construction ---------------------------------------------------------------------------
-    @staticmethod
-    def _groups(env, strategy, S):
-        """An explicit map int32 [N] -> the CSR lists of gte_reduce_backtest_stats, built on the device:
-        members by increasing env id (a stable sort of the map), offsets by searchsorted."""
-        torch = env._torch
-        dev = env._t["obs"].device
-        if isinstance(strategy, torch.Tensor) and strategy.is_cuda:
-            if strategy.dtype not in (torch.int32, torch.int64):
-                raise TypeError("strategy must be integers")
-            m = strategy
-        else:
-            a = np.asarray(strategy.numpy() if isinstance(strategy, torch.Tensor) else strategy)
-            if a.dtype.kind not in "iu":
-                raise TypeError("strategy must be integers")
-            if a.size and (a.min() < 0 or a.max() >= S):
-                raise IndexError(f"strategy outside [0, {S})")
-            m = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64))).to(dev)
-        if tuple(m.shape) != (env.num_envs,):
-            raise ValueError(f"expected strategy of shape ({env.num_envs},)")
-        m = m.to(torch.int64)
-        order = torch.sort(m, stable=True).indices
-        sorted_map = m[order]
-        # envs whose strategy lies outside [0, S) belong to nobody: offsets[0] skips the negative ones,
-        # offsets[S] stops before those >= S
-        bounds = torch.arange(S + 1, dtype=torch.int64, device=dev)
-        offsets = torch.searchsorted(sorted_map, bounds).to(torch.int32).contiguous()
-        return offsets, order.to(torch.int32).contiguous()
-
     @classmethod
     def _reduce(cls, env, records, strategy, n_strategies):
-        torch = env._torch
-        if torch is None:
-            raise ValueError("strategy statistics need output='torch'")
-        if isinstance(n_strategies, bool) or int(n_strategies) != n_strategies:
-            raise TypeError("n_strategies must be an integer")
-        S = int(n_strategies)
-        if S < 1:
-            raise ValueError("n_strategies must be >= 1")
-        dev = env._t["obs"].device
-        offsets = members = None
-        if strategy is not None:
-            offsets, members = cls._groups(env, strategy, S)
-        with torch.cuda.device(dev):
-            out = torch.empty((S, 128), dtype=torch.uint8, device=dev)
-        _abi.check(env._lib, env._lib.gte_reduce_backtest_stats(
-            env._h, None if records is None else C.c_void_p(records.data_ptr()), S,
-            None if offsets is None else C.c_void_p(offsets.data_ptr()),
-            None if members is None else C.c_void_p(members.data_ptr()), C.c_void_p(out.data_ptr())))
-        return cls(env, out, (records, offsets, members))
+        return cls(env, *cls._fold(env, records, strategy, n_strategies))
 
     @classmethod
     def from_records(cls, env, records, strategy=None, n_strategies=None) -> "StrategyStats":
@@ -251,11 +177,6 @@ class StrategyStats:
         return cls._reduce(env, dev_records, strategy, n_strategies)
 
     # -- figures ---------------------------------------------------------------------------------
-    def _lazy(self, key, make):
-        if key not in self._derived:
-            self._derived[key] = make()
-        return self._derived[key]
-
     @property
     def mean_reward(self):
         """Mean step reward over all transitions of the strategy's envs."""
@@ -287,26 +208,10 @@ class StrategyStats:
             return var.clamp_min(0.0).sqrt()
         return self._lazy("episode_return_std", make)
 
-    def _rank(self, metric, min_episodes, k, want_scores):
-        env, torch = self._env, self._env._torch
-        code = _metric_code(metric)
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.GTE_RANK_MAX:
-            raise ValueError(f"k must lie in [1, {_abi.GTE_RANK_MAX}]")
-        dev = self._records.device
-        with torch.cuda.device(dev):
-            index = torch.empty((int(k),), dtype=torch.int32, device=dev)
-            top = torch.empty((int(k),), dtype=torch.float64, device=dev)
-            scores = torch.empty((self.num_strategies,), dtype=torch.float64, device=dev) if want_scores else None
-        _abi.check(env._lib, env._lib.gte_rank_strategies(
-            env._h, C.c_void_p(self._records.data_ptr()), self.num_strategies, code, int(min_episodes), int(k),
-            C.c_void_p(index.data_ptr()), C.c_void_p(top.data_ptr()),
-            None if scores is None else C.c_void_p(scores.data_ptr())))
-        return index, top, scores
-
     def score(self, metric):
         """The score of every strategy under `metric` (a name of `METRICS` or a `METRIC_*` constant), f64
         [S] on the device, as `gte_rank_strategies` computes it — NaN included."""
-        code = _metric_code(metric)
+        code = self._code(metric)
         return self._lazy(("score", code), lambda: self._rank(code, 0, 1, True)[2])
 
     def top(self, k, metric="mean_episode_return", min_episodes=1):
@@ -315,11 +220,4 @@ class StrategyStats:
         finished episodes and a score that is not NaN; equal scores order by index.  Waits for the device: the
         ranked count is read back to trim the result (`gte_rank_strategies` itself does not wait and pads with
         -1 / NaN)."""
-        index, top, _ = self._rank(metric, min_episodes, k, False)
-        r = int((index >= 0).sum().item())
-        return index[:r], top[:r]
-
-    def numpy(self) -> np.ndarray:
-        """The records on the host, one transfer: a structured array [S] of `STRATEGY_DTYPE`."""
-        raw = self._records.cpu().numpy()
-        return raw.view(np.dtype(_abi.STRATEGY_DTYPE)).reshape(self.num_strategies).copy()
+        return self._top(metric, min_episodes, k)

@@ -1186,6 +1186,65 @@ static bool spans_overlap(const RowSpan& r, const RowSpan& w, int64_t T16) {
   return r0 < w1 && w0 < r1;
 }
 
+// ---- what the reductions, rankings and reads of the per-env record families share: each family's entry
+// points run these in the order they always refused in, `who` being the entry point for the message ----
+// the head of every gte_reduce_* / gte_rank_* call and of gte_reality_check
+static int check_strategies(const gte_env* E, int32_t n_strategies) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
+  return GTE_OK;
+}
+
+static int check_n_periods(int32_t n_periods, int lo) {
+  if (n_periods >= lo && n_periods <= GTE_MAX_PERIODS) return GTE_OK;
+  return fail(GTE_ERR_INVALID, "n_periods %d outside [%d, %d]", n_periods, lo, GTE_MAX_PERIODS);
+}
+
+static int check_period_mask(const uint64_t* period_mask) {
+  return period_mask ? GTE_OK : fail(GTE_ERR_INVALID, "period_mask is NULL");
+}
+
+static int check_reduce_args(gte_env* E, const char* who, const void* records, const int32_t* group_offsets,
+                             const int32_t* group_envs, const void* out) {
+  if (!out || ((uintptr_t)out & 15)) return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
+  if ((uintptr_t)records & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
+  if ((group_offsets == nullptr) != (group_envs == nullptr))
+    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
+  if (((uintptr_t)group_offsets & 3) || ((uintptr_t)group_envs & 3))
+    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "%s inside a stream capture", who);
+  return GTE_OK;
+}
+
+// metric in [lo, hi], the family's first and last
+static int check_rank_args(gte_env* E, const char* who, int32_t k, int32_t metric, int lo, int hi, const void* stats,
+                           const int32_t* top_index, const double* top_score, const double* scores) {
+  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
+  if (metric < lo || metric > hi) return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
+  if (!stats || ((uintptr_t)stats & 15))
+    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  if (!top_index || ((uintptr_t)top_index & 3) || !top_score || ((uintptr_t)top_score & 7))
+    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
+  if ((uintptr_t)scores & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "%s inside a stream capture", who);
+  return GTE_OK;
+}
+
+// rows first .. first + count - 1 of a per-env record array (`base`: row_bytes per env, or NULL before the call
+// `before` made it) to the host, after everything enqueued on the env's stream
+static int read_records(gte_env* E, const char* who, const char* before, const void* base, size_t row_bytes,
+                        int32_t first, int32_t count, void* out) {
+  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (!base) return fail(GTE_ERR_STATE, "%s before %s", who, before);
+  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
+    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(hipStreamSynchronize(E->stream));
+  if (count > 0)
+    HIPCHK(hipMemcpy(out, (const char*)base + (size_t)first * row_bytes, (size_t)count * row_bytes, hipMemcpyDeviceToHost));
+  return GTE_OK;
+}
+
 int gte_bind_signals(gte_env* E, int32_t d, const int8_t* signals_device, int32_t n_strategies,
                      int64_t row_stride) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
@@ -1266,15 +1325,8 @@ int gte_bind_exit_rules(gte_env* E, const gte_exit_rule* rules_device, int32_t n
 }
 
 int gte_read_exit_state(gte_env* E, int32_t first, int32_t count, gte_exit_state* out) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (!E->exits.state) return fail(GTE_ERR_STATE, "gte_read_exit_state before gte_bind_exit_rules");
-  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
-    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  if (count > 0)
-    HIPCHK(hipMemcpy(out, E->exits.state + first, sizeof(gte_exit_state) * (size_t)count, hipMemcpyDeviceToHost));
-  return GTE_OK;
+  return read_records(E, "gte_read_exit_state", "gte_bind_exit_rules", E ? E->exits.state : nullptr,
+                      sizeof(gte_exit_state), first, count, out);
 }
 
 int gte_build_signals(gte_env* E, int32_t d, const float* indicators_device, int32_t n_indicators,
@@ -1356,16 +1408,9 @@ int gte_build_indicators(gte_env* E, int32_t d, const gte_indicator_spec* specs_
 int gte_reduce_backtest_stats(gte_env* E, const gte_backtest_stats* records_device, int32_t n_strategies,
                               const int32_t* group_offsets_device, const int32_t* group_envs_device,
                               gte_strategy_stats* out_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  if (!out_device || ((uintptr_t)out_device & 15))
-    return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
-  if ((uintptr_t)records_device & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
-  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
-    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
-  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
-    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reduce_backtest_stats inside a stream capture");
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_reduce_args(E, "gte_reduce_backtest_stats", records_device, group_offsets_device, group_envs_device,
+                        out_device));
   const gte_backtest_stats* const records = records_device ? records_device : E->bt_stats;
   if (!records) return fail(GTE_ERR_STATE, "gte_reduce_backtest_stats before gte_backtest: the env has no records yet");
   HIPCHK(hipSetDevice(E->cfg.device));
@@ -1388,20 +1433,22 @@ static int rank_scratch(gte_env* E, int32_t n_strategies) {
   return GTE_OK;
 }
 
+// how gte_rank_trade_stats and gte_rank_period_stats end: their score kernel (e: its launch) has filled
+// candidate list 0, the selection launches of gte_strategy.hip follow
+static int rank_select(gte_env* E, hipError_t e, const char* what, int32_t n_strategies, int32_t k, int32_t* top_index,
+                       double* top_score) {
+  if (e == hipSuccess)
+    e = gte::launch_rank_select(n_strategies, k, top_index, top_score, E->rank_score, E->rank_index, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "%s ranking launch: %s", what, hipGetErrorString(e));
+  return GTE_OK;
+}
+
 int gte_rank_strategies(gte_env* E, const gte_strategy_stats* stats_device, int32_t n_strategies, int32_t metric,
                         int64_t min_episodes, int32_t k, int32_t* top_index_device, double* top_score_device,
                         double* scores_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
-  if (metric < GTE_METRIC_MEAN_REWARD || metric > GTE_METRIC_WORST_REWARD_SUM)
-    return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
-  if (!stats_device || ((uintptr_t)stats_device & 15))
-    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
-  if (!top_index_device || ((uintptr_t)top_index_device & 3) || !top_score_device || ((uintptr_t)top_score_device & 7))
-    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
-  if ((uintptr_t)scores_device & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_rank_strategies inside a stream capture");
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_rank_args(E, "gte_rank_strategies", k, metric, GTE_METRIC_MEAN_REWARD, GTE_METRIC_WORST_REWARD_SUM,
+                      stats_device, top_index_device, top_score_device, scores_device));
   HIPCHK(hipSetDevice(E->cfg.device));
   TRY(rank_scratch(E, n_strategies));
   const hipError_t e = gte::launch_rank_strategies(stats_device, n_strategies, metric, min_episodes, k,
@@ -1414,16 +1461,9 @@ int gte_rank_strategies(gte_env* E, const gte_strategy_stats* stats_device, int3
 int gte_reduce_trade_stats(gte_env* E, const gte_trade_stats* records_device, int32_t n_strategies,
                            const int32_t* group_offsets_device, const int32_t* group_envs_device,
                            gte_strategy_trade_stats* out_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  if (!out_device || ((uintptr_t)out_device & 15))
-    return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
-  if ((uintptr_t)records_device & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
-  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
-    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
-  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
-    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reduce_trade_stats inside a stream capture");
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_reduce_args(E, "gte_reduce_trade_stats", records_device, group_offsets_device, group_envs_device,
+                        out_device));
   const gte_trade_stats* const records = records_device ? records_device : E->tr_stats;
   if (!records) return fail(GTE_ERR_STATE, "gte_reduce_trade_stats before gte_track_trades: the env has no trade records yet");
   HIPCHK(hipSetDevice(E->cfg.device));
@@ -1436,38 +1476,20 @@ int gte_reduce_trade_stats(gte_env* E, const gte_trade_stats* records_device, in
 int gte_rank_trade_stats(gte_env* E, const gte_strategy_trade_stats* stats_device, int32_t n_strategies, int32_t metric,
                          int64_t min_trades, int32_t k, int32_t* top_index_device, double* top_score_device,
                          double* scores_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
-  if (metric < GTE_TRADE_METRIC_WIN_RATE || metric > GTE_TRADE_METRIC_NEG_MAX_LOSS_STREAK)
-    return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
-  if (!stats_device || ((uintptr_t)stats_device & 15))
-    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
-  if (!top_index_device || ((uintptr_t)top_index_device & 3) || !top_score_device || ((uintptr_t)top_score_device & 7))
-    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
-  if ((uintptr_t)scores_device & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_rank_trade_stats inside a stream capture");
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_rank_args(E, "gte_rank_trade_stats", k, metric, GTE_TRADE_METRIC_WIN_RATE,
+                      GTE_TRADE_METRIC_NEG_MAX_LOSS_STREAK, stats_device, top_index_device, top_score_device,
+                      scores_device));
   HIPCHK(hipSetDevice(E->cfg.device));
   TRY(rank_scratch(E, n_strategies));
-  hipError_t e = gte::launch_trade_scores(stats_device, n_strategies, metric, min_trades, scores_device,
-                                          E->rank_score[0], E->rank_index[0], E->stream);
-  if (e == hipSuccess)
-    e = gte::launch_rank_select(n_strategies, k, top_index_device, top_score_device, E->rank_score, E->rank_index,
-                                E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "trade ranking launch: %s", hipGetErrorString(e));
-  return GTE_OK;
+  const hipError_t e = gte::launch_trade_scores(stats_device, n_strategies, metric, min_trades, scores_device,
+                                                E->rank_score[0], E->rank_index[0], E->stream);
+  return rank_select(E, e, "trade", n_strategies, k, top_index_device, top_score_device);
 }
 
 int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backtest_stats* out) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (!E->bt_stats) return fail(GTE_ERR_STATE, "gte_read_backtest_stats before gte_backtest");
-  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
-    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  if (count > 0)
-    HIPCHK(hipMemcpy(out, E->bt_stats + first, sizeof(gte_backtest_stats) * (size_t)count, hipMemcpyDeviceToHost));
-  return GTE_OK;
+  return read_records(E, "gte_read_backtest_stats", "gte_backtest", E ? E->bt_stats : nullptr,
+                      sizeof(gte_backtest_stats), first, count, out);
 }
 
 int gte_track_trades(gte_env* E, int32_t on, gte_trade_stats** records_device) {
@@ -1487,15 +1509,8 @@ int gte_track_trades(gte_env* E, int32_t on, gte_trade_stats** records_device) {
 }
 
 int gte_read_trade_stats(gte_env* E, int32_t first, int32_t count, gte_trade_stats* out) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (!E->tr_stats) return fail(GTE_ERR_STATE, "gte_read_trade_stats before gte_track_trades");
-  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
-    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  if (count > 0)
-    HIPCHK(hipMemcpy(out, E->tr_stats + first, sizeof(gte_trade_stats) * (size_t)count, hipMemcpyDeviceToHost));
-  return GTE_OK;
+  return read_records(E, "gte_read_trade_stats", "gte_track_trades", E ? E->tr_stats : nullptr,
+                      sizeof(gte_trade_stats), first, count, out);
 }
 
 int gte_bind_periods(gte_env* E, int32_t d, const int8_t* period_of_row) {
@@ -1534,8 +1549,7 @@ int gte_bind_periods(gte_env* E, int32_t d, const int8_t* period_of_row) {
 
 int gte_track_periods(gte_env* E, int32_t n_periods, gte_period_stats** records_device) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_periods < 0 || n_periods > GTE_MAX_PERIODS)
-    return fail(GTE_ERR_INVALID, "n_periods %d outside [0, %d]", n_periods, GTE_MAX_PERIODS);
+  TRY(check_n_periods(n_periods, 0));
   if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_periods before gte_reset");
   if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_periods inside a stream capture");
   if (n_periods > 0 && E->tr_on)
@@ -1562,34 +1576,17 @@ int gte_track_periods(gte_env* E, int32_t n_periods, gte_period_stats** records_
 }
 
 int gte_read_period_stats(gte_env* E, int32_t first, int32_t count, gte_period_stats* out) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (!E->pd_stats) return fail(GTE_ERR_STATE, "gte_read_period_stats before gte_track_periods");
-  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
-    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  const size_t B = (size_t)E->pd_alloc_B;
-  if (count > 0)
-    HIPCHK(hipMemcpy(out, E->pd_stats + (size_t)first * B, sizeof(gte_period_stats) * (size_t)count * B,
-                     hipMemcpyDeviceToHost));
-  return GTE_OK;
+  return read_records(E, "gte_read_period_stats", "gte_track_periods", E ? E->pd_stats : nullptr,
+                      E ? sizeof(gte_period_stats) * (size_t)E->pd_alloc_B : 0, first, count, out);
 }
 
 int gte_reduce_period_stats(gte_env* E, const gte_period_stats* records_device, int32_t n_periods, int32_t n_strategies,
                             const int32_t* group_offsets_device, const int32_t* group_envs_device,
                             gte_strategy_period_stats* out_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  if (n_periods < 1 || n_periods > GTE_MAX_PERIODS)
-    return fail(GTE_ERR_INVALID, "n_periods %d outside [1, %d]", n_periods, GTE_MAX_PERIODS);
-  if (!out_device || ((uintptr_t)out_device & 15))
-    return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
-  if ((uintptr_t)records_device & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
-  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
-    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
-  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
-    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reduce_period_stats inside a stream capture");
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_n_periods(n_periods, 1));
+  TRY(check_reduce_args(E, "gte_reduce_period_stats", records_device, group_offsets_device, group_envs_device,
+                        out_device));
   if (!records_device && !E->pd_stats)
     return fail(GTE_ERR_STATE, "gte_reduce_period_stats before gte_track_periods: the env has no period records yet");
   if (!records_device && n_periods != E->pd_alloc_B)
@@ -1605,29 +1602,17 @@ int gte_reduce_period_stats(gte_env* E, const gte_period_stats* records_device, 
 int gte_rank_period_stats(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
                           int32_t n_periods, const uint64_t period_mask[2], int32_t metric, int64_t min_steps, int32_t k,
                           int32_t* top_index_device, double* top_score_device, double* scores_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  if (n_periods < 1 || n_periods > GTE_MAX_PERIODS)
-    return fail(GTE_ERR_INVALID, "n_periods %d outside [1, %d]", n_periods, GTE_MAX_PERIODS);
-  if (!period_mask) return fail(GTE_ERR_INVALID, "period_mask is NULL");
-  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
-  if (metric < GTE_PERIOD_METRIC_MEAN_REWARD || metric > GTE_PERIOD_METRIC_POSITIVE_SHARE)
-    return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
-  if (!stats_device || ((uintptr_t)stats_device & 15))
-    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
-  if (!top_index_device || ((uintptr_t)top_index_device & 3) || !top_score_device || ((uintptr_t)top_score_device & 7))
-    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
-  if ((uintptr_t)scores_device & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_rank_period_stats inside a stream capture");
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_n_periods(n_periods, 1));
+  TRY(check_period_mask(period_mask));
+  TRY(check_rank_args(E, "gte_rank_period_stats", k, metric, GTE_PERIOD_METRIC_MEAN_REWARD,
+                      GTE_PERIOD_METRIC_POSITIVE_SHARE, stats_device, top_index_device, top_score_device,
+                      scores_device));
   HIPCHK(hipSetDevice(E->cfg.device));
   TRY(rank_scratch(E, n_strategies));
-  hipError_t e = gte::launch_period_scores(stats_device, n_strategies, n_periods, period_mask, metric, min_steps,
-                                           scores_device, E->rank_score[0], E->rank_index[0], E->stream);
-  if (e == hipSuccess)
-    e = gte::launch_rank_select(n_strategies, k, top_index_device, top_score_device, E->rank_score, E->rank_index,
-                                E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "period ranking launch: %s", hipGetErrorString(e));
-  return GTE_OK;
+  const hipError_t e = gte::launch_period_scores(stats_device, n_strategies, n_periods, period_mask, metric, min_steps,
+                                                 scores_device, E->rank_score[0], E->rank_index[0], E->stream);
+  return rank_select(E, e, "period", n_strategies, k, top_index_device, top_score_device);
 }
 
 int gte_bootstrap_weights(gte_env* E, int32_t n, int32_t n_resamples, double block, uint64_t seed,
@@ -1652,13 +1637,11 @@ int gte_bootstrap_weights(gte_env* E, int32_t n, int32_t n_resamples, double blo
 int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
                       int32_t n_periods, const uint64_t period_mask[2], const double* benchmark_device,
                       const double* weights_device, int32_t n_resamples, const gte_reality_check_out* out) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  if (n_periods < 1 || n_periods > GTE_MAX_PERIODS)
-    return fail(GTE_ERR_INVALID, "n_periods %d outside [1, %d]", n_periods, GTE_MAX_PERIODS);
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_n_periods(n_periods, 1));
   if (n_resamples < 1 || n_resamples > GTE_BOOT_MAX_RESAMPLES)
     return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
-  if (!period_mask) return fail(GTE_ERR_INVALID, "period_mask is NULL");
+  TRY(check_period_mask(period_mask));
   int n = 0;
   for (int b = 0; b < 128; ++b) {
     if (!((period_mask[b >> 6] >> (b & 63)) & 1)) continue;

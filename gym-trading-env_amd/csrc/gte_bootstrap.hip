@@ -24,6 +24,7 @@
 // benchmark[b] for the same b; w[r * n + i] for r < R, i < n; the scratch and the outputs as written by the
 // kernels before.  What is written: the outputs gte.h lists, and the library's scratch (BootScratch).
 #include "gte_launch.h"
+#include "gte_members.h"
 
 namespace gte {
 
@@ -61,9 +62,9 @@ hipError_t launch_bootstrap_weights(int n, int n_resamples, uint32_t thr, int al
 
 // ---- the reality check
 
-struct BootMask {
-  uint64_t w[2];
-};
+// PeriodMask (gte_members.h) under the name the gather kernel's symbol carries: a kernel's name spells out its
+// parameter types, and this kernel's code is to stay what it was byte for byte
+struct BootMask : PeriodMask {};
 
 __global__ __launch_bounds__(256) void gte_boot_gather_kernel(const gte_strategy_period_stats* __restrict__ stats, int S,
                                                               int B, const BootMask mask, int n,
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void gte_boot_gather_kernel(const gte_strategy
   double sum = 0.0;
   int i = 0;
   for (int b = 0; b < B; ++b) {
-    if (!((mask.w[b >> 6] >> (b & 63)) & 1)) continue;
+    if (!mask.has(b)) continue;
     const double x = t[b].reward_sum;
     ok = ok && t[b].steps > 0 && __builtin_isfinite(x);
     const double d = benchmark ? x - benchmark[b] : x;
@@ -314,7 +315,7 @@ hipError_t launch_reality_check(const gte_strategy_period_stats* stats, int n_st
   const int S = n_strategies, R = n_resamples;
   const int slabs = (R + GTE_BOOT_SLAB - 1) / GTE_BOOT_SLAB, tiles = (int)(((int64_t)S + BOOT_TILE - 1) / BOOT_TILE);
   const BootScratch b = boot_carve(scratch, S, n, R);
-  const BootMask mask = {{period_mask[0], period_mask[1]}};
+  const BootMask mask = {{{period_mask[0], period_mask[1]}}};
   const unsigned per_strategy = (unsigned)(((int64_t)S + 255) / 256);
   hipLaunchKernelGGL(gte_boot_gather_kernel, dim3(per_strategy), dim3(256), 0, stream, stats, S, n_periods, mask, n,
                      benchmark, b.D, b.elig, out.mean);

@@ -20,6 +20,7 @@
 // clamped into [0, N]; group_offsets at s and s + 1 for s < S.  What is written: the 48 bytes of out[s * B + b]
 // for s < S, b < B; scores[s], cand_score[s], cand_index[s] for s < S.
 #include "gte_launch.h"
+#include "gte_members.h"
 
 namespace gte {
 
@@ -28,32 +29,6 @@ static_assert(sizeof(gte_strategy_period_stats) == 48 && offsetof(gte_strategy_p
               "gte_strategy_period_stats: 48 bytes (include/gte.h)");
 
 constexpr int PS_THREADS = 256;
-
-// the member list of strategy s: n places; place m holds env first + m * S (default map) or envs[lo + m]
-struct PsMembers {
-  int n, lo;
-  long long first;
-};
-__device__ __forceinline__ PsMembers ps_members(int s, int N, int S, unsigned first_shift, const int32_t* offsets) {
-  PsMembers g = {0, 0, 0};
-  if (offsets) {
-    const int o0 = offsets[s], o1 = offsets[s + 1];
-    g.lo = o0 < 0 ? 0 : o0 > N ? N : o0;
-    const int hi = o1 < g.lo ? g.lo : o1 > N ? N : o1;
-    g.n = hi - g.lo;
-  } else {
-    g.first = ((unsigned)s + first_shift) % (unsigned)S;
-    g.n = g.first < N ? (int)(((long long)N - g.first + S - 1) / S) : 0;
-  }
-  return g;
-}
-
-// env of place m < g.n, or -1 where the entry names no env in [0, N)
-__device__ __forceinline__ long long ps_env(const PsMembers& g, const int32_t* envs, int N, int S, int m) {
-  if (!envs) return g.first + (long long)m * S;
-  const int id = envs[g.lo + m];
-  return (unsigned)id < (unsigned)N ? (long long)id : -1;
-}
 
 typedef double __attribute__((ext_vector_type(2))) ps_double2;
 
@@ -68,7 +43,7 @@ __global__ __launch_bounds__(PS_THREADS) void gte_period_reduce_kernel(const gte
   const long long s64 = (long long)blockIdx.x * per_block + local;
   if (local >= per_block || s64 >= S) return;
   const int s = (int)s64;
-  const PsMembers g = ps_members(s, N, S, first_shift, offsets);
+  const Members g = members_of(s, N, S, first_shift, offsets);
   double r1[8], r2[8];
 #pragma unroll
   for (int a = 0; a < 8; ++a) r1[a] = r2[a] = 0.0;
@@ -80,7 +55,7 @@ __global__ __launch_bounds__(PS_THREADS) void gte_period_reduce_kernel(const gte
 #pragma unroll
     for (int a = 0; a < 8; ++a) {  // eight members' loads in flight (a is a constant after unrolling)
       const int m = base + a;
-      const long long e = m < g.n ? ps_env(g, envs, N, S, m) : -1;
+      const long long e = m < g.n ? member_env(g, envs, N, S, m) : -1;
       have[a] = e >= 0;
       if (have[a]) {
         const ps_double2* q = reinterpret_cast<const ps_double2*>(rec + e * B + b);
@@ -118,7 +93,7 @@ hipError_t launch_reduce_period_stats(const gte_period_stats* records, int n_env
       (group_offsets == nullptr) != (group_envs == nullptr))
     return hipErrorInvalidValue;
   const int64_t S = n_strategies;
-  const unsigned first_shift = (unsigned)((S - ((env_id_base % S) + S) % S) % S);  // (s + shift) % S = (s - base) mod S
+  const unsigned first_shift = members_first_shift(env_id_base, S);
   const int64_t per_block = PS_THREADS / n_periods;
   hipLaunchKernelGGL(gte_period_reduce_kernel, dim3((unsigned)((S + per_block - 1) / per_block)), dim3(PS_THREADS), 0,
                      stream, records, n_envs, n_periods, n_strategies, first_shift, group_offsets, group_envs, out);
@@ -126,10 +101,6 @@ hipError_t launch_reduce_period_stats(const gte_period_stats* records, int n_env
 }
 
 // ---- ranking
-
-struct PeriodMask {
-  uint64_t w[2];
-};
 
 __global__ __launch_bounds__(256) void gte_period_score_kernel(const gte_strategy_period_stats* __restrict__ stats, int S,
                                                                int B, const PeriodMask mask, int metric,
@@ -142,7 +113,7 @@ __global__ __launch_bounds__(256) void gte_period_score_kernel(const gte_strateg
   long long n = 0, c = 0, up = 0;
   double s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0, lo = __builtin_inf();
   for (int b = 0; b < B; ++b) {
-    if (!((mask.w[b >> 6] >> (b & 63)) & 1)) continue;
+    if (!mask.has(b)) continue;
     const double x = t[b].reward_sum;
     n += t[b].steps;
     s1 = s1 + x;

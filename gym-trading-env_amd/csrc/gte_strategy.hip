@@ -30,6 +30,7 @@
 // at s and s + 1 for s < S.  What is written: the 128 bytes of out[s] for s < S; scores[s]; the
 // candidate lists up to the sizes launch_rank_strategies states; top_index / top_score [k].
 #include "gte_launch.h"
+#include "gte_members.h"
 
 namespace gte {
 
@@ -65,28 +66,9 @@ __device__ __forceinline__ unsigned long long st_u64(double d) { return (unsigne
 // i64, the maximum and the extremes followed); what a piece's lane computed on halves that are not of
 // that type is never read.
 
-// the member list of strategy s: n places; place m holds env first + m * S (default map) or envs[lo + m]
-struct StMembers {
-  int n, lo;
-  long long first;
-};
-__device__ __forceinline__ StMembers st_members(int s, int N, int S, unsigned first_shift, const int32_t* offsets) {
-  StMembers g = {0, 0, 0};
-  if (offsets) {
-    const int o0 = offsets[s], o1 = offsets[s + 1];
-    g.lo = o0 < 0 ? 0 : o0 > N ? N : o0;
-    const int hi = o1 < g.lo ? g.lo : o1 > N ? N : o1;
-    g.n = hi - g.lo;
-  } else {
-    g.first = ((unsigned)s + first_shift) % (unsigned)S;
-    g.n = g.first < N ? (int)(((long long)N - g.first + S - 1) / S) : 0;
-  }
-  return g;
-}
-
 // piece c of the member at place m, or zeros (which add nothing anywhere) when the place is past the list's
 // end or names no env in [0, N); *ok says which.  The load itself always happens, at record 0 if need be
-__device__ __forceinline__ st_u2 st_load(const gte_backtest_stats* rec, int N, int S, const StMembers& g,
+__device__ __forceinline__ st_u2 st_load(const gte_backtest_stats* rec, int N, int S, const Members& g,
                                          const int32_t* envs, int m, int c, bool* ok) {
   const bool in = m < g.n;
   long long e;
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(64 * ST_WAVES) void gte_strategy_reduce_kernel(
   const long long s64 = ((long long)blockIdx.x * ST_WAVES + (threadIdx.x >> 6)) * 8 + (lane >> 3);
   const bool live = s64 < S;
   const int s = live ? (int)s64 : 0;
-  StMembers g = st_members(s, N, S, first_shift, offsets);
+  Members g = members_of(s, N, S, first_shift, offsets);
   if (!live) g.n = 0;
 
   double d0[8], d1[8];
@@ -219,7 +201,7 @@ __global__ __launch_bounds__(64 * BLK_WAVES) void gte_strategy_reduce_block_kern
   const int c = lane & 7, q = lane >> 3;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int s = blockIdx.x;  // (the grid is S workgroups)
-  const StMembers g = st_members(s, N, S, first_shift, offsets);
+  const Members g = members_of(s, N, S, first_shift, offsets);
   const int mine = g.n > w ? (g.n - w + 7) / 8 : 0;  // places of this accumulator: w + 8 t, t < mine
 
   double a0 = 0.0, a1 = 0.0;
@@ -275,7 +257,7 @@ hipError_t launch_reduce_strategies(const gte_backtest_stats* records, int n_env
   if (!records || !out || n_envs < 1 || n_strategies < 1 || (group_offsets == nullptr) != (group_envs == nullptr))
     return hipErrorInvalidValue;
   const int64_t S = n_strategies;
-  const unsigned first_shift = (unsigned)((S - ((env_id_base % S) + S) % S) % S);  // (s + shift) % S = (s - base) mod S
+  const unsigned first_shift = members_first_shift(env_id_base, S);
   // a workgroup per strategy once the average list has 32 members (half of what one load instruction of its
   // eight wavefronts fetches); speed only: the records do not depend on it
   if ((int64_t)n_envs >= 32 * S)

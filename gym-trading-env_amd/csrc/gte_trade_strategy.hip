@@ -20,6 +20,7 @@
 // [0, N]; group_offsets at s and s + 1 for s < S.  What is written: the 128 bytes of out[s] for s < S;
 // scores[s], cand_score[s], cand_index[s] for s < S.
 #include "gte_launch.h"
+#include "gte_members.h"
 
 namespace gte {
 
@@ -29,32 +30,6 @@ static_assert(sizeof(gte_strategy_trade_stats) == 128 && offsetof(gte_strategy_t
               "gte_strategy_trade_stats: 128 bytes (include/gte.h)");
 
 constexpr int TS_BLK_WAVES = 8;  // wavefronts of the block kernel = accumulators of the stated order
-
-// the member list of strategy s: n places; place m holds env first + m * S (default map) or envs[lo + m]
-struct TsMembers {
-  int n, lo;
-  long long first;
-};
-__device__ __forceinline__ TsMembers ts_members(int s, int N, int S, unsigned first_shift, const int32_t* offsets) {
-  TsMembers g = {0, 0, 0};
-  if (offsets) {
-    const int o0 = offsets[s], o1 = offsets[s + 1];
-    g.lo = o0 < 0 ? 0 : o0 > N ? N : o0;
-    const int hi = o1 < g.lo ? g.lo : o1 > N ? N : o1;
-    g.n = hi - g.lo;
-  } else {
-    g.first = ((unsigned)s + first_shift) % (unsigned)S;
-    g.n = g.first < N ? (int)(((long long)N - g.first + S - 1) / S) : 0;
-  }
-  return g;
-}
-
-// env of place m < g.n, or -1 where the entry names no env in [0, N)
-__device__ __forceinline__ long long ts_env(const TsMembers& g, const int32_t* envs, int N, int S, int m) {
-  if (!envs) return g.first + (long long)m * S;
-  const int id = envs[g.lo + m];
-  return (unsigned)id < (unsigned)N ? (long long)id : -1;
-}
 
 // what a strategy gathers besides the three f64 sums: order-free, but for which of two equal extremes stays —
 // the one met first in MEMBER order, so the place travels with the value
@@ -115,7 +90,7 @@ __global__ __launch_bounds__(256) void gte_trade_reduce_kernel(const gte_trade_s
   const long long s64 = (long long)blockIdx.x * 256 + threadIdx.x;
   if (s64 >= S) return;
   const int s = (int)s64;
-  const TsMembers g = ts_members(s, N, S, first_shift, offsets);
+  const Members g = members_of(s, N, S, first_shift, offsets);
   double gp[8], gl[8], sq[8];
 #pragma unroll
   for (int a = 0; a < 8; ++a) gp[a] = gl[a] = sq[a] = 0.0;
@@ -124,7 +99,7 @@ __global__ __launch_bounds__(256) void gte_trade_reduce_kernel(const gte_trade_s
 #pragma unroll
     for (int a = 0; a < 8; ++a) {  // (a is a constant after unrolling: the accumulators stay in registers)
       const int m = base + a;
-      const long long e = m < g.n ? ts_env(g, envs, N, S, m) : -1;
+      const long long e = m < g.n ? member_env(g, envs, N, S, m) : -1;
       if (e >= 0) {
         const gte_trade_stats r = rec[e];
         gp[a] += r.gross_profit;
@@ -149,7 +124,7 @@ __global__ __launch_bounds__(64 * TS_BLK_WAVES) void gte_trade_reduce_block_kern
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int s = blockIdx.x;  // (the grid is S workgroups)
-  const TsMembers g = ts_members(s, N, S, first_shift, offsets);
+  const Members g = members_of(s, N, S, first_shift, offsets);
   const int mine = g.n > w ? (g.n - w + 7) / 8 : 0;  // places of this accumulator: w + 8 t, t < mine
 
   double a_gp = 0.0, a_gl = 0.0, a_sq = 0.0;
@@ -157,7 +132,7 @@ __global__ __launch_bounds__(64 * TS_BLK_WAVES) void gte_trade_reduce_block_kern
   for (int tb = 0; tb < mine; tb += 64) {
     const int t = tb + lane;
     const int m = w + 8 * t;
-    const long long e = t < mine ? ts_env(g, envs, N, S, m) : -1;
+    const long long e = t < mine ? member_env(g, envs, N, S, m) : -1;
     double x_gp = 0.0, x_gl = 0.0, x_sq = 0.0;
     if (e >= 0) {
       const gte_trade_stats r = rec[e];
@@ -205,7 +180,7 @@ hipError_t launch_reduce_trade_stats(const gte_trade_stats* records, int n_envs,
   if (!records || !out || n_envs < 1 || n_strategies < 1 || (group_offsets == nullptr) != (group_envs == nullptr))
     return hipErrorInvalidValue;
   const int64_t S = n_strategies;
-  const unsigned first_shift = (unsigned)((S - ((env_id_base % S) + S) % S) % S);  // (s + shift) % S = (s - base) mod S
+  const unsigned first_shift = members_first_shift(env_id_base, S);
   // a workgroup per strategy once the average list has 32 members; speed only: the records do not depend on it
   if ((int64_t)n_envs >= 32 * S)
     hipLaunchKernelGGL(gte_trade_reduce_block_kernel, dim3((unsigned)S), dim3(64 * TS_BLK_WAVES), 0, stream, records,

@@ -5,6 +5,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
+from .strategy_records import field_views
 
 
 class ExitState:
@@ -23,8 +24,7 @@ class ExitState:
         self._env = env
         dev = env._t["obs"].device
         dt = np.dtype(_abi.EXIT_STATE_DTYPE)
-        for name, typestr in _abi.EXIT_STATE_FIELDS:
-            setattr(self, name, _device_view(ptr + dt.fields[name][1], (env.num_envs,), typestr, dev, (dt.itemsize,)))
+        vars(self).update(field_views(ptr, _abi.EXIT_STATE_FIELDS, dt, (env.num_envs,), dev))
         self.exits = _device_view(ptr + dt.fields["exits"][1], (env.num_envs, 4), "<i4", dev, (dt.itemsize, 4))
 
     def numpy(self) -> np.ndarray:

@@ -5,12 +5,10 @@ over any subset of the periods on the device — rank on the training periods, r
 test periods."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _abi
-from .backtest_stats import StrategyStats
+from .strategy_records import StrategyRecords, field_views, mask_words, resolve_strategy_map
 
 
 class PeriodStats:
@@ -49,11 +47,9 @@ class PeriodStats:
             raise AttributeError(name)
         self._alive()
         if name not in self._views:
-            from .batched import _device_view
-            e, B, dt = self._env, self.num_periods, np.dtype(_abi.PERIOD_DTYPE)
-            typestr = dict(_abi.PERIOD_FIELDS)[name]
-            self._views[name] = _device_view(self._ptr + dt.fields[name][1], (e.num_envs, B), typestr,
-                                             e._t["obs"].device, (B * dt.itemsize, dt.itemsize))
+            e = self._env
+            self._views.update(field_views(self._ptr, [(name, dict(_abi.PERIOD_FIELDS)[name])], _abi.PERIOD_DTYPE,
+                                           (e.num_envs, self.num_periods), e._t["obs"].device))
         return self._views[name]
 
     def numpy(self) -> np.ndarray:
@@ -71,28 +67,8 @@ class PeriodStats:
         the map and the S of the `backtest_signals()` call that produced the records — are those of
         `BacktestStats.by_strategy`; like there, what is folded is what the live records hold when this runs."""
         self._alive()
-        if strategy is None and n_strategies is None:
-            if self._map is None:
-                raise ValueError("by_strategy() of a backtest() result needs n_strategies (and strategy=, unless "
-                                 "env e follows strategy (env_id_base + e) % S)")
-            strategy, n_strategies = self._map
-        elif n_strategies is None:
-            if self._map is None:
-                raise ValueError("by_strategy(strategy=...) needs n_strategies")
-            n_strategies = self._map[1]
+        strategy, n_strategies = resolve_strategy_map(self._map, strategy, n_strategies)
         return StrategyPeriodStats._reduce(self._env, strategy, n_strategies, self.num_periods)
-
-
-def _period_metric_code(metric) -> int:
-    if isinstance(metric, str):
-        if metric.lower() not in _abi.PERIOD_METRICS:
-            raise ValueError(f"unknown metric {metric!r}: one of {', '.join(_abi.PERIOD_METRICS)}")
-        return _abi.PERIOD_METRICS.index(metric.lower())
-    if isinstance(metric, (bool, float)) or int(metric) != metric:
-        raise TypeError("metric must be a name or a PERIOD_METRIC_* constant")
-    if not 0 <= int(metric) < len(_abi.PERIOD_METRICS):
-        raise ValueError(f"unknown metric {metric}: 0 .. {len(_abi.PERIOD_METRICS) - 1}")
-    return int(metric)
 
 
 class PeriodSelection:
@@ -124,7 +100,7 @@ class PeriodSelection:
         return s if periods_per_year is None else s * float(periods_per_year) ** 0.5
 
 
-class StrategyPeriodStats:
+class StrategyPeriodStats(StrategyRecords):
     """Per-strategy, per-period statistics: the period records of a `PeriodStats` folded over the members of
     each strategy by one device launch (struct gte_strategy_period_stats, include/gte.h), and the ranking of the
     strategies by a score over a subset of the periods, also on the device (`gte_rank_period_stats`).
@@ -135,42 +111,19 @@ class StrategyPeriodStats:
     `periods` is an iterable of period ids, a bool mask [B], or None for all periods.  Launches are enqueued on
     the env's stream as in `StrategyStats`; `top()` alone waits."""
 
-    FIELDS = tuple(n for n, _ in _abi.STRATEGY_PERIOD_FIELDS)
-    METRICS = _abi.PERIOD_METRICS
+    DTYPE, RECORD_FIELDS = _abi.STRATEGY_PERIOD_DTYPE, _abi.STRATEGY_PERIOD_FIELDS
+    FIELDS = tuple(n for n, _ in RECORD_FIELDS)
+    METRICS, METRIC_PREFIX = _abi.PERIOD_METRICS, "PERIOD_METRIC"
+    REDUCE, RANK = "gte_reduce_period_stats", "gte_rank_period_stats"
 
     def __init__(self, env, records, n_periods, inputs=()):
-        from .batched import _device_view
-        self._env = env
-        self._records = records  # uint8 [S * B, 48], CUDA
-        self._keep = inputs      # what the reduction reads: alive while the launch may be in flight
-        self._derived = {}
         self.num_periods = B = int(n_periods)
-        self.num_strategies = S = int(records.shape[0]) // B
-        dt = np.dtype(_abi.STRATEGY_PERIOD_DTYPE)
-        for name, typestr in _abi.STRATEGY_PERIOD_FIELDS:
-            setattr(self, name, _device_view(records.data_ptr() + dt.fields[name][1], (S, B), typestr, records.device,
-                                             (B * dt.itemsize, dt.itemsize)))
+        super().__init__(env, records, inputs, (int(records.shape[0]) // B, B))  # records: uint8 [S * B, 48], CUDA
 
     @classmethod
     def _reduce(cls, env, strategy, n_strategies, n_periods):
-        torch = env._torch
-        if torch is None:
-            raise ValueError("strategy statistics need output='torch'")
-        if isinstance(n_strategies, bool) or int(n_strategies) != n_strategies:
-            raise TypeError("n_strategies must be an integer")
-        S = int(n_strategies)
-        if S < 1:
-            raise ValueError("n_strategies must be >= 1")
-        dev = env._t["obs"].device
-        offsets = members = None
-        if strategy is not None:
-            offsets, members = StrategyStats._groups(env, strategy, S)
-        with torch.cuda.device(dev):
-            out = torch.empty((S * n_periods, 48), dtype=torch.uint8, device=dev)
-        _abi.check(env._lib, env._lib.gte_reduce_period_stats(
-            env._h, None, n_periods, S, None if offsets is None else C.c_void_p(offsets.data_ptr()),
-            None if members is None else C.c_void_p(members.data_ptr()), C.c_void_p(out.data_ptr())))
-        return cls(env, out, n_periods, (offsets, members))
+        out, inputs = cls._fold(env, None, strategy, n_strategies, n_periods, (n_periods,))
+        return cls(env, out, n_periods, inputs)
 
     def _mask(self, periods):
         """bool [B] on the host from an iterable of ids, a bool mask [B], or None (all)."""
@@ -191,25 +144,9 @@ class StrategyPeriodStats:
             m[b] = True
         return m
 
-    def _rank(self, metric, periods, min_steps, k, want_scores):
-        env, torch = self._env, self._env._torch
-        code = _period_metric_code(metric)
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.GTE_RANK_MAX:
-            raise ValueError(f"k must lie in [1, {_abi.GTE_RANK_MAX}]")
-        mask = self._mask(periods)
-        words = (C.c_uint64 * 2)(0, 0)
-        for b in np.flatnonzero(mask):
-            words[int(b) >> 6] |= 1 << (int(b) & 63)
-        dev = self._records.device
-        with torch.cuda.device(dev):
-            index = torch.empty((int(k),), dtype=torch.int32, device=dev)
-            top = torch.empty((int(k),), dtype=torch.float64, device=dev)
-            scores = torch.empty((self.num_strategies,), dtype=torch.float64, device=dev) if want_scores else None
-        _abi.check(env._lib, env._lib.gte_rank_period_stats(
-            env._h, C.c_void_p(self._records.data_ptr()), self.num_strategies, self.num_periods, words, code,
-            int(min_steps), int(k), C.c_void_p(index.data_ptr()), C.c_void_p(top.data_ptr()),
-            None if scores is None else C.c_void_p(scores.data_ptr())))
-        return index, top, scores
+    def _periods_args(self, periods):
+        """What the rank call takes between S and the metric: B and the mask's words, made when it asks."""
+        return lambda: (self.num_periods, mask_words(self._mask(periods)))
 
     def select(self, periods) -> PeriodSelection:
         """The pooled figures of a set of periods per strategy: `steps`, `reward_sum`, `mean_reward`,
@@ -219,23 +156,17 @@ class StrategyPeriodStats:
     def score(self, metric, periods=None):
         """The score of every strategy under `metric` (a name of `METRICS` or a `PERIOD_METRIC_*` constant) over
         `periods`, f64 [S] on the device, as `gte_rank_period_stats` computes it — NaN included."""
-        code = _period_metric_code(metric)
+        code = self._code(metric)
         mask = self._mask(periods)
-        return self._lazy(("score", code, mask.tobytes()), lambda: self._rank(code, mask, 1, 1, True)[2])
-
-    def _lazy(self, key, make):
-        if key not in self._derived:
-            self._derived[key] = make()
-        return self._derived[key]
+        return self._lazy(("score", code, mask.tobytes()),
+                          lambda: self._rank(code, 1, 1, True, self._periods_args(mask))[2])
 
     def top(self, k, metric="sharpe", periods=None, min_steps=1):
         """The k best strategies over `periods`: ``(index int32 [r], score f64 [r])`` on the device, best first,
         r = min(k, ranked strategies).  Ranked are those with at least max(1, `min_steps`) transitions in the
         selected periods and a score that is not NaN; equal scores order by index.  Waits for the device, like
         `StrategyStats.top`."""
-        index, top, _ = self._rank(metric, periods, min_steps, k, False)
-        r = int((index >= 0).sum().item())
-        return index[:r], top[:r]
+        return self._top(metric, min_steps, k, self._periods_args(periods))
 
     def reality_check(self, periods=None, n_resamples=1000, block=1.0, seed=0, benchmark=None, weights=None):
         """White's Reality Check of this leaderboard over `periods`, on the device (`gte_reality_check`): is the
@@ -248,7 +179,3 @@ class StrategyPeriodStats:
         from . import reality_check
         return reality_check.run(self, periods, n_resamples, block, seed, benchmark, weights)
 
-    def numpy(self) -> np.ndarray:
-        """The records on the host, one transfer: a structured array [S, B] of `STRATEGY_PERIOD_DTYPE`."""
-        raw = self._records.cpu().numpy()
-        return raw.view(np.dtype(_abi.STRATEGY_PERIOD_DTYPE)).reshape(self.num_strategies, self.num_periods).copy()

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from .strategy_records import mask_words
 
 
 def bootstrap_weights(env, n, n_resamples, block=1.0, seed=0):
@@ -119,9 +120,7 @@ def run(owner, periods=None, n_resamples=1000, block=1.0, seed=0, benchmark=None
     n = len(ids)
     if n < 2:
         raise ValueError("a reality check needs at least two selected periods")
-    words = (C.c_uint64 * 2)(0, 0)
-    for b in ids:
-        words[b >> 6] |= 1 << (b & 63)
+    words = mask_words(mask)
     dev = owner._records.device
     S, B = owner.num_strategies, owner.num_periods
     if weights is None:

@@ -4,12 +4,10 @@ include/gte.h) as torch views of device memory and the figures a backtest report
 StrategyTradeStats, the same folded per strategy and ranked on the device."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _abi
-from .backtest_stats import StrategyStats
+from .strategy_records import StrategyRecords, field_views, resolve_strategy_map
 
 
 class TradeStats:
@@ -25,15 +23,12 @@ class TradeStats:
     FIELDS = tuple(n for n, _ in _abi.TRADE_FIELDS)
 
     def __init__(self, env, ptr: int, steps, strategy_map=None):
-        from .batched import _device_view
         self._env = env
         self._derived = {}
         self._steps = steps      # the transitions of the same records' gte_backtest_stats (exposure_share)
         self._map = strategy_map  # what the call that made these records ran with
-        dev = env._t["obs"].device
-        dt = np.dtype(_abi.TRADE_DTYPE)
-        for name, typestr in _abi.TRADE_FIELDS:
-            setattr(self, name, _device_view(ptr + dt.fields[name][1], (env.num_envs,), typestr, dev, (dt.itemsize,)))
+        vars(self).update(field_views(ptr, _abi.TRADE_FIELDS, _abi.TRADE_DTYPE, (env.num_envs,),
+                                      env._t["obs"].device))
 
     def _lazy(self, key, make):
         if key not in self._derived:
@@ -78,31 +73,11 @@ class TradeStats:
         `StrategyTradeStats`.  `strategy` / `n_strategies` and their defaults — the map and the S of the
         `backtest_signals()` call that produced the records — are those of `BacktestStats.by_strategy`; like
         there, what is folded is what the live records hold when this runs."""
-        if strategy is None and n_strategies is None:
-            if self._map is None:
-                raise ValueError("by_strategy() of a backtest() result needs n_strategies (and strategy=, unless "
-                                 "env e follows strategy (env_id_base + e) % S)")
-            strategy, n_strategies = self._map
-        elif n_strategies is None:
-            if self._map is None:
-                raise ValueError("by_strategy(strategy=...) needs n_strategies")
-            n_strategies = self._map[1]
+        strategy, n_strategies = resolve_strategy_map(self._map, strategy, n_strategies)
         return StrategyTradeStats._reduce(self._env, strategy, n_strategies)
 
 
-def _trade_metric_code(metric) -> int:
-    if isinstance(metric, str):
-        if metric.lower() not in _abi.TRADE_METRICS:
-            raise ValueError(f"unknown metric {metric!r}: one of {', '.join(_abi.TRADE_METRICS)}")
-        return _abi.TRADE_METRICS.index(metric.lower())
-    if isinstance(metric, (bool, float)) or int(metric) != metric:
-        raise TypeError("metric must be a name or a TRADE_METRIC_* constant")
-    if not 0 <= int(metric) < len(_abi.TRADE_METRICS):
-        raise ValueError(f"unknown metric {metric}: 0 .. {len(_abi.TRADE_METRICS) - 1}")
-    return int(metric)
-
-
-class StrategyTradeStats:
+class StrategyTradeStats(StrategyRecords):
     """Per-strategy trade statistics: the trade records of a `TradeStats` folded over the members of each
     strategy by one device launch (struct gte_strategy_trade_stats, include/gte.h), and the ranking of the
     strategies by a per-trade score, also on the device (`gte_rank_trade_stats`).
@@ -113,78 +88,26 @@ class StrategyTradeStats:
     strided view of the result records, which this object owns.  Launches are enqueued on the env's stream as
     in `StrategyStats`; `top()` alone waits."""
 
-    FIELDS = tuple(n for n, _ in _abi.STRATEGY_TRADE_FIELDS)
-    METRICS = _abi.TRADE_METRICS
+    DTYPE, RECORD_FIELDS = _abi.STRATEGY_TRADE_DTYPE, _abi.STRATEGY_TRADE_FIELDS
+    FIELDS = tuple(n for n, _ in RECORD_FIELDS)
+    METRICS, METRIC_PREFIX = _abi.TRADE_METRICS, "TRADE_METRIC"
+    REDUCE, RANK = "gte_reduce_trade_stats", "gte_rank_trade_stats"
 
     def __init__(self, env, records, inputs=()):
-        from .batched import _device_view
-        self._env = env
-        self._records = records  # uint8 [S, 128], CUDA
-        self._keep = inputs      # what the reduction reads: alive while the launch may be in flight
-        self._derived = {}
-        self.num_strategies = int(records.shape[0])
-        dt = np.dtype(_abi.STRATEGY_TRADE_DTYPE)
-        for name, typestr in _abi.STRATEGY_TRADE_FIELDS:
-            setattr(self, name, _device_view(records.data_ptr() + dt.fields[name][1], (self.num_strategies,), typestr,
-                                             records.device, (dt.itemsize,)))
+        super().__init__(env, records, inputs, (int(records.shape[0]),))  # records: uint8 [S, 128], CUDA
 
     @classmethod
     def _reduce(cls, env, strategy, n_strategies):
-        torch = env._torch
-        if torch is None:
-            raise ValueError("strategy statistics need output='torch'")
-        if isinstance(n_strategies, bool) or int(n_strategies) != n_strategies:
-            raise TypeError("n_strategies must be an integer")
-        S = int(n_strategies)
-        if S < 1:
-            raise ValueError("n_strategies must be >= 1")
-        dev = env._t["obs"].device
-        offsets = members = None
-        if strategy is not None:
-            offsets, members = StrategyStats._groups(env, strategy, S)
-        with torch.cuda.device(dev):
-            out = torch.empty((S, 128), dtype=torch.uint8, device=dev)
-        _abi.check(env._lib, env._lib.gte_reduce_trade_stats(
-            env._h, None, S, None if offsets is None else C.c_void_p(offsets.data_ptr()),
-            None if members is None else C.c_void_p(members.data_ptr()), C.c_void_p(out.data_ptr())))
-        return cls(env, out, (offsets, members))
-
-    def _lazy(self, key, make):
-        if key not in self._derived:
-            self._derived[key] = make()
-        return self._derived[key]
-
-    def _rank(self, metric, min_trades, k, want_scores):
-        env, torch = self._env, self._env._torch
-        code = _trade_metric_code(metric)
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.GTE_RANK_MAX:
-            raise ValueError(f"k must lie in [1, {_abi.GTE_RANK_MAX}]")
-        dev = self._records.device
-        with torch.cuda.device(dev):
-            index = torch.empty((int(k),), dtype=torch.int32, device=dev)
-            top = torch.empty((int(k),), dtype=torch.float64, device=dev)
-            scores = torch.empty((self.num_strategies,), dtype=torch.float64, device=dev) if want_scores else None
-        _abi.check(env._lib, env._lib.gte_rank_trade_stats(
-            env._h, C.c_void_p(self._records.data_ptr()), self.num_strategies, code, int(min_trades), int(k),
-            C.c_void_p(index.data_ptr()), C.c_void_p(top.data_ptr()),
-            None if scores is None else C.c_void_p(scores.data_ptr())))
-        return index, top, scores
+        return cls(env, *cls._fold(env, None, strategy, n_strategies))
 
     def score(self, metric):
         """The score of every strategy under `metric` (a name of `METRICS` or a `TRADE_METRIC_*` constant), f64
         [S] on the device, as `gte_rank_trade_stats` computes it — NaN included."""
-        code = _trade_metric_code(metric)
+        code = self._code(metric)
         return self._lazy(("score", code), lambda: self._rank(code, 1, 1, True)[2])
 
     def top(self, k, metric="profit_factor", min_trades=1):
         """The k best strategies: ``(index int32 [r], score f64 [r])`` on the device, best first, r = min(k,
         ranked strategies).  Ranked are those with at least max(1, `min_trades`) closed trades and a score that
         is not NaN; equal scores order by index.  Waits for the device, like `StrategyStats.top`."""
-        index, top, _ = self._rank(metric, min_trades, k, False)
-        r = int((index >= 0).sum().item())
-        return index[:r], top[:r]
-
-    def numpy(self) -> np.ndarray:
-        """The records on the host, one transfer: a structured array [S] of `STRATEGY_TRADE_DTYPE`."""
-        raw = self._records.cpu().numpy()
-        return raw.view(np.dtype(_abi.STRATEGY_TRADE_DTYPE)).reshape(self.num_strategies).copy()
+        return self._top(metric, min_trades, k)

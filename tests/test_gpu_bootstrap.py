@@ -245,9 +245,16 @@ def test_refusals_leave_every_output_untouched(env):
     def check(*args):
         return lib.gte_reality_check(*args)
     good = ptrs()
-    assert check(None, st, S, B, words, None, wp, R, C.byref(good)) == INVALID
+    assert check(None, st, S, B, words, None, wp, R, C.byref(good)) == INVALID and "env is NULL" in err()
     assert check(h, None, S, B, words, None, wp, R, C.byref(good)) == INVALID and "stats_device" in err()
     assert check(h, C.c_void_p(d_stats.data_ptr() + 8), S, B, words, None, wp, R, C.byref(good)) == INVALID
+    assert "stats_device must be a 16-byte aligned" in err()
+    # wrong in several ways: the check that stands first reports
+    assert check(h, None, 0, 0, None, None, None, 0, None) == INVALID and "n_strategies must be >= 1" in err()
+    assert check(h, None, S, 0, None, None, None, 0, None) == INVALID and "n_periods 0 outside [1, 128]" in err()
+    assert check(h, None, S, B, None, None, None, 0, None) == INVALID and "n_resamples 0 outside" in err()
+    assert check(h, None, S, B, None, None, None, R, None) == INVALID and "period_mask is NULL" in err()
+    assert check(h, None, S, B, words, None, None, R, None) == INVALID and "stats_device" in err()
     assert check(h, st, 0, B, words, None, wp, R, C.byref(good)) == INVALID and "n_strategies" in err()
     for bad_B in (0, -1, 129):
         assert check(h, st, S, bad_B, words, None, wp, R, C.byref(good)) == INVALID and "n_periods" in err()
@@ -262,15 +269,17 @@ def test_refusals_leave_every_output_untouched(env):
         assert check(h, st, S, B, words, None, wp, bad_R, C.byref(good)) == INVALID and "n_resamples" in err()
     assert check(h, st, S, B, words, None, None, R, C.byref(good)) == INVALID and "weights_device" in err()
     assert check(h, st, S, B, words, C.c_void_p(d_w.data_ptr() + 4), wp, R, C.byref(good)) == INVALID
+    assert "benchmark_device must be 8-byte aligned" in err()
     assert check(h, st, S, B, words, None, wp, R, None) == INVALID and "out is NULL" in err()
     for k in out:
         assert check(h, st, S, B, words, None, wp, R, C.byref(ptrs(**{k: None}))) == INVALID and "out:" in err(), k
     assert check(h, st, S, B, words, None, wp, R, C.byref(ptrs(count_ge=out["count_ge"].data_ptr() + 2))) == INVALID
+    assert "must be 4-byte aligned device pointers" in err()
 
     def weights(*args):
         return lib.gte_bootstrap_weights(*args)
     wo = C.c_void_p(w_out.data_ptr())
-    assert weights(None, n, R, 1.0, 1, wo) == INVALID
+    assert weights(None, n, R, 1.0, 1, wo) == INVALID and "env is NULL" in err()
     for bad_n in (1, 0, -2, 129):
         assert weights(h, bad_n, R, 1.0, 1, wo) == INVALID and "n " in err()
     for bad_R in (0, -1, 65537):
@@ -279,6 +288,7 @@ def test_refusals_leave_every_output_untouched(env):
         assert weights(h, n, R, bad_block, 1, wo) == INVALID and "block" in err()
     assert weights(h, n, R, 1.0, 1, None) == INVALID and "weights_device" in err()
     assert weights(h, n, R, 1.0, 1, C.c_void_p(w_out.data_ptr() + 4)) == INVALID
+    assert "weights_device must be an 8-byte aligned device array" in err()
     env.synchronize()
     torch.cuda.synchronize()
     for k, v in list(out.items()) + [("weights", w_out)]:

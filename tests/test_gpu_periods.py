@@ -598,9 +598,13 @@ def test_refusals():
     out = torch.empty((3 * 2, 48), dtype=torch.uint8, device="cuda")
     assert lib.gte_reduce_period_stats(h, None, 2, 3, None, None, C.c_void_p(out.data_ptr())) == _abi.GTE_ERR_STATE
     assert "before gte_track_periods" in err()
-    assert lib.gte_track_periods(None, 1, C.byref(ptr)) == _abi.GTE_ERR_INVALID
+    assert lib.gte_track_periods(None, 1, C.byref(ptr)) == _abi.GTE_ERR_INVALID and "env is NULL" in err()
     for B in (-1, 129):
-        assert lib.gte_track_periods(h, B, C.byref(ptr)) == _abi.GTE_ERR_INVALID and "n_periods" in err()
+        assert lib.gte_track_periods(h, B, C.byref(ptr)) == _abi.GTE_ERR_INVALID
+        assert f"n_periods {B} outside [0, 128]" in err()
+    # (state before range, NULL before state)
+    assert lib.gte_read_period_stats(h, 60, 5, rec.ctypes.data) == _abi.GTE_ERR_STATE and "before gte_track_periods" in err()
+    assert lib.gte_read_period_stats(h, 60, 5, None) == _abi.GTE_ERR_INVALID and "NULL argument" in err()
     for B in (0, 129):
         with pytest.raises(ValueError, match="n_periods"):
             env.track_periods(row, B)
@@ -648,10 +652,64 @@ def test_refusals():
     o = C.c_void_p(out.data_ptr())
     assert lib.gte_rank_period_stats(h, o, 3, 2, mask, 6, 1, 4, *args) == _abi.GTE_ERR_INVALID and "metric 6 unknown" in err()
     assert lib.gte_rank_period_stats(h, o, 3, 2, mask, 0, 1, 0, *args) == _abi.GTE_ERR_INVALID
+    assert "k must lie in [1, 256]" in err()
     assert lib.gte_rank_period_stats(h, o, 3, 129, mask, 0, 1, 4, *args) == _abi.GTE_ERR_INVALID
-    assert lib.gte_rank_period_stats(h, o, 3, 2, None, 0, 1, 4, *args) == _abi.GTE_ERR_INVALID and "period_mask" in err()
+    assert "n_periods 129 outside [1, 128]" in err()
+    assert lib.gte_rank_period_stats(h, o, 3, 2, None, 0, 1, 4, *args) == _abi.GTE_ERR_INVALID and "period_mask is NULL" in err()
     assert lib.gte_reduce_period_stats(h, None, 2, 0, None, None, o) == _abi.GTE_ERR_INVALID
+    assert "n_strategies must be >= 1" in err()
     assert lib.gte_reduce_period_stats(h, None, 2, 3, C.c_void_p(idx.data_ptr()), None, o) == _abi.GTE_ERR_INVALID
+    assert "both or neither" in err()
+    # every refusal gte_reduce_backtest_stats / gte_rank_strategies make (test_gpu_strategy_stats.py), for ITS reason:
+    # 64 envs, 8 strategies, 3 periods; nothing below launches
+    INVALID = _abi.GTE_ERR_INVALID
+    out8 = torch.zeros((8 * 3 + 1, 48), dtype=torch.uint8, device="cuda")
+    rec8 = torch.zeros((64 * 3 + 1, 32), dtype=torch.uint8, device="cuda")
+    lists = torch.zeros((80,), dtype=torch.int32, device="cuda")
+    idx8 = torch.zeros((256 + 1,), dtype=torch.int32, device="cuda")
+    top8 = torch.zeros((256 + 1,), dtype=torch.float64, device="cuda")
+    q = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    reduce = lambda *a: lib.gte_reduce_period_stats(h, *a)
+    rank = lambda *a: lib.gte_rank_period_stats(h, *a)
+    for B in (0, 129):
+        assert reduce(q(rec8), B, 8, None, None, q(out8)) == INVALID and f"n_periods {B} outside [1, 128]" in err()
+    assert reduce(q(rec8), 3, 8, None, None, None) == INVALID and "out_device must be a 16-byte aligned" in err()
+    assert reduce(q(rec8), 3, 8, None, None, q(out8, 8)) == INVALID and "out_device must be a 16-byte aligned" in err()
+    assert reduce(q(rec8, 8), 3, 8, None, None, q(out8)) == INVALID and "records must be 16-byte aligned" in err()
+    assert reduce(q(rec8), 3, 8, None, q(lists), q(out8)) == INVALID and "both or neither" in err()
+    assert reduce(q(rec8), 3, 8, q(lists, 2), q(lists), q(out8)) == INVALID and "group lists must be 4-byte aligned" in err()
+    assert reduce(q(rec8), 3, 8, q(lists), q(lists, 2), q(out8)) == INVALID and "group lists must be 4-byte aligned" in err()
+    assert reduce(q(rec8, 8), 0, 0, q(lists), None, None) == INVALID and "n_strategies must be >= 1" in err()  # the order
+    assert reduce(q(rec8, 8), 0, 8, q(lists), None, None) == INVALID and "n_periods 0 outside" in err()
+    assert reduce(q(rec8, 8), 3, 8, q(lists), None, None) == INVALID and "out_device" in err()
+    assert reduce(q(rec8, 8), 3, 8, q(lists), None, q(out8)) == INVALID and "records must be" in err()
+    assert reduce(None, 3, 8, q(lists), None, q(out8)) == INVALID and "both or neither" in err()  # (before the env's B)
+    assert lib.gte_reduce_period_stats(None, None, 0, 0, None, None, None) == INVALID and "env is NULL" in err()
+    stats_text, top_text = "stats_device must be a 16-byte aligned", "top_index_device (int32 [k]) and top_score_device"
+    m3 = (C.c_uint64 * 2)(7, 0)
+    ok = (q(idx8), q(top8), None)
+    assert rank(q(out8), 0, 3, m3, 0, 1, 8, *ok) == INVALID and "n_strategies must be >= 1" in err()
+    assert rank(q(out8), 8, 0, m3, 0, 1, 8, *ok) == INVALID and "n_periods 0 outside [1, 128]" in err()
+    for k in (0, -1, 257):
+        assert rank(q(out8), 8, 3, m3, 0, 1, k, *ok) == INVALID and "k must lie in [1, 256]" in err()
+    assert rank(q(out8), 8, 3, m3, -1, 1, 8, *ok) == INVALID and "metric -1 unknown" in err()
+    assert rank(None, 8, 3, m3, 0, 1, 8, *ok) == INVALID and stats_text in err()
+    assert rank(q(out8, 8), 8, 3, m3, 0, 1, 8, *ok) == INVALID and stats_text in err()
+    assert rank(q(out8), 8, 3, m3, 0, 1, 8, None, q(top8), None) == INVALID and top_text in err()
+    assert rank(q(out8), 8, 3, m3, 0, 1, 8, q(idx8), None, None) == INVALID and top_text in err()
+    assert rank(q(out8), 8, 3, m3, 0, 1, 8, q(idx8, 2), q(top8), None) == INVALID and top_text in err()
+    assert rank(q(out8), 8, 3, m3, 0, 1, 8, q(idx8), q(top8, 4), None) == INVALID and top_text in err()
+    assert rank(q(out8), 8, 3, m3, 0, 1, 8, q(idx8), q(top8), q(top8, 4)) == INVALID and "scores_device must be 8-byte" in err()
+    assert rank(None, 0, 0, None, -1, 1, 0, None, None, q(top8, 4)) == INVALID and "n_strategies must be" in err()  # the order
+    assert rank(None, 8, 0, None, -1, 1, 0, None, None, q(top8, 4)) == INVALID and "n_periods 0 outside" in err()
+    assert rank(None, 8, 3, None, -1, 1, 0, None, None, q(top8, 4)) == INVALID and "period_mask is NULL" in err()
+    assert rank(None, 8, 3, m3, -1, 1, 0, None, None, q(top8, 4)) == INVALID and "k must lie" in err()
+    assert rank(None, 8, 3, m3, -1, 1, 8, None, None, q(top8, 4)) == INVALID and "metric -1 unknown" in err()
+    assert rank(None, 8, 3, m3, 0, 1, 8, None, None, q(top8, 4)) == INVALID and stats_text in err()
+    assert rank(q(out8), 8, 3, m3, 0, 1, 8, None, None, q(top8, 4)) == INVALID and top_text in err()
+    assert lib.gte_read_period_stats(h, -1, 5, rec.ctypes.data) == INVALID and "env range [-1, 4) outside [0, 64)" in err()
+    assert lib.gte_read_period_stats(h, 0, -1, rec.ctypes.data) == INVALID and "outside [0, 64)" in err()
+    assert lib.gte_read_period_stats(None, 60, 5, rec.ctypes.data) == INVALID and "NULL argument" in err()
     with pytest.raises(ValueError, match="n_strategies"):
         p.by_strategy()
     with pytest.raises(ValueError, match="unknown metric"):

@@ -265,25 +265,48 @@ def test_refusals_and_errors(envs):
         assert b"before gte_backtest" in lib.gte_last_error()
         rec = torch.zeros((64, 128), dtype=torch.uint8, device=dev)
         assert reduce(p(rec), 8, None, None, p(out)) == _abi.GTE_OK
-        assert reduce(p(rec), 0, None, None, p(out)) == INVALID
-        assert reduce(p(rec), 8, None, None, None) == INVALID
-        assert reduce(p(rec), 8, None, None, p(out, 8)) == INVALID
-        assert reduce(p(rec, 8), 8, None, None, p(out)) == INVALID
-        assert reduce(p(rec), 8, p(lists), None, p(out)) == INVALID
-        assert reduce(p(rec), 8, None, p(lists), p(out)) == INVALID
+        why = lambda text: text in lib.gte_last_error()  # (each refusal for ITS reason)
+        assert reduce(p(rec), 0, None, None, p(out)) == INVALID and why(b"n_strategies must be >= 1")
+        assert reduce(p(rec), 8, None, None, None) == INVALID and why(b"out_device must be a 16-byte aligned")
+        assert reduce(p(rec), 8, None, None, p(out, 8)) == INVALID and why(b"out_device must be a 16-byte aligned")
+        assert reduce(p(rec, 8), 8, None, None, p(out)) == INVALID and why(b"records must be 16-byte aligned")
+        assert reduce(p(rec), 8, p(lists), None, p(out)) == INVALID and why(b"both or neither")
+        assert reduce(p(rec), 8, None, p(lists), p(out)) == INVALID and why(b"both or neither")
+        assert reduce(p(rec), 8, p(lists, 2), p(lists), p(out)) == INVALID and why(b"group lists must be 4-byte aligned")
+        assert reduce(p(rec), 8, p(lists), p(lists, 2), p(out)) == INVALID and why(b"group lists must be 4-byte aligned")
+        assert reduce(None, 8, None, None, p(out)) == STATE and why(b"before gte_backtest")
+        # wrong in two ways: the check that stands first reports
+        assert reduce(p(rec, 8), 0, None, None, None) == INVALID and why(b"n_strategies must be >= 1")
+        assert reduce(p(rec, 8), 8, p(lists), None, None) == INVALID and why(b"out_device")
+        assert reduce(None, 8, p(lists), None, p(out)) == INVALID and why(b"both or neither")
+        assert lib.gte_reduce_backtest_stats(None, p(rec), 0, None, None, None) == INVALID and why(b"env is NULL")
         assert rank(p(out), 8, 0, 1, 8, p(idx), p(top), None) == _abi.GTE_OK
-        assert rank(p(out), 0, 0, 1, 8, p(idx), p(top), None) == INVALID
+        assert rank(p(out), 0, 0, 1, 8, p(idx), p(top), None) == INVALID and why(b"n_strategies must be >= 1")
         for k in (0, -1, 257):
-            assert rank(p(out), 8, 0, 1, k, p(idx), p(top), None) == INVALID
+            assert rank(p(out), 8, 0, 1, k, p(idx), p(top), None) == INVALID and why(b"k must lie in [1, 256]")
         for metric in (-1, 6):
             assert rank(p(out), 8, metric, 1, 8, p(idx), p(top), None) == INVALID
-        assert rank(None, 8, 0, 1, 8, p(idx), p(top), None) == INVALID
-        assert rank(p(out, 8), 8, 0, 1, 8, p(idx), p(top), None) == INVALID
-        assert rank(p(out), 8, 0, 1, 8, None, p(top), None) == INVALID
-        assert rank(p(out), 8, 0, 1, 8, p(idx), None, None) == INVALID
-        assert rank(p(out), 8, 0, 1, 8, p(idx, 2), p(top), None) == INVALID
-        assert rank(p(out), 8, 0, 1, 8, p(idx), p(top, 4), None) == INVALID
-        assert rank(p(out), 8, 0, 1, 8, p(idx), p(top), p(top, 4)) == INVALID
+            assert why(b"metric %d unknown" % metric)
+        stats_text, top_text = b"stats_device must be a 16-byte aligned", b"top_index_device (int32 [k]) and top_score_device"
+        assert rank(None, 8, 0, 1, 8, p(idx), p(top), None) == INVALID and why(stats_text)
+        assert rank(p(out, 8), 8, 0, 1, 8, p(idx), p(top), None) == INVALID and why(stats_text)
+        assert rank(p(out), 8, 0, 1, 8, None, p(top), None) == INVALID and why(top_text)
+        assert rank(p(out), 8, 0, 1, 8, p(idx), None, None) == INVALID and why(top_text)
+        assert rank(p(out), 8, 0, 1, 8, p(idx, 2), p(top), None) == INVALID and why(top_text)
+        assert rank(p(out), 8, 0, 1, 8, p(idx), p(top, 4), None) == INVALID and why(top_text)
+        assert rank(p(out), 8, 0, 1, 8, p(idx), p(top), p(top, 4)) == INVALID and why(b"scores_device must be 8-byte aligned")
+        assert rank(None, 0, -1, 1, 0, None, None, p(top, 4)) == INVALID and why(b"n_strategies must be >= 1")
+        assert rank(None, 8, -1, 1, 0, None, None, p(top, 4)) == INVALID and why(b"k must lie")
+        assert rank(None, 8, -1, 1, 8, None, None, p(top, 4)) == INVALID and why(b"metric -1 unknown")
+        assert rank(None, 8, 0, 1, 8, None, None, p(top, 4)) == INVALID and why(stats_text)
+        assert rank(p(out), 8, 0, 1, 8, None, None, p(top, 4)) == INVALID and why(top_text)
+        # the reads: gte_read_backtest_stats
+        host = np.empty(64, dtype=sm.BACKTEST)
+        read = lib.gte_read_backtest_stats
+        assert read(fresh._h, 0, 64, host.ctypes.data) == STATE and why(b"gte_read_backtest_stats before gte_backtest")
+        assert read(fresh._h, 60, 5, None) == INVALID and why(b"NULL argument")
+        assert read(None, 0, 1, host.ctypes.data) == INVALID and why(b"NULL argument")
+        assert read(fresh._h, 60, 5, host.ctypes.data) == STATE and why(b"before gte_backtest")  # (state before range)
         fresh.synchronize()
         # inside a stream capture: refused with its reason (the capture fails, the env works on)
         fresh.reset()

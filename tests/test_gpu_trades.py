@@ -353,7 +353,10 @@ def test_refusals():
     out = torch.empty((3, 128), dtype=torch.uint8, device="cuda")
     assert lib.gte_reduce_trade_stats(h, None, 3, None, None, C.c_void_p(out.data_ptr())) == _abi.GTE_ERR_STATE
     assert "before gte_track_trades" in err()
-    assert lib.gte_track_trades(None, 1, C.byref(ptr)) == _abi.GTE_ERR_INVALID
+    assert lib.gte_track_trades(None, 1, C.byref(ptr)) == _abi.GTE_ERR_INVALID and "env is NULL" in err()
+    # (state before range, NULL before state)
+    assert lib.gte_read_trade_stats(h, 60, 5, rec.ctypes.data) == _abi.GTE_ERR_STATE and "before gte_track_trades" in err()
+    assert lib.gte_read_trade_stats(h, 60, 5, None) == _abi.GTE_ERR_INVALID and "NULL argument" in err()
     seen = []
 
     def body(i):
@@ -377,8 +380,52 @@ def test_refusals():
     assert lib.gte_rank_trade_stats(h, C.c_void_p(out.data_ptr()), 3, 6, 1, 4, *args) == _abi.GTE_ERR_INVALID
     assert "metric 6 unknown" in err()
     assert lib.gte_rank_trade_stats(h, C.c_void_p(out.data_ptr()), 3, 0, 1, 0, *args) == _abi.GTE_ERR_INVALID
+    assert "k must lie in [1, 256]" in err()
     assert lib.gte_reduce_trade_stats(h, None, 0, None, None, C.c_void_p(out.data_ptr())) == _abi.GTE_ERR_INVALID
+    assert "n_strategies must be >= 1" in err()
     assert lib.gte_reduce_trade_stats(h, None, 3, C.c_void_p(idx.data_ptr()), None, C.c_void_p(out.data_ptr())) == _abi.GTE_ERR_INVALID
+    assert "both or neither" in err()
+    # every refusal gte_reduce_backtest_stats / gte_rank_strategies make (test_gpu_strategy_stats.py), for ITS reason:
+    # 64 envs, 8 strategies; nothing below launches
+    INVALID = _abi.GTE_ERR_INVALID
+    out8 = torch.zeros((8 + 1, 128), dtype=torch.uint8, device="cuda")
+    rec8 = torch.zeros((64 + 1, 128), dtype=torch.uint8, device="cuda")
+    lists = torch.zeros((80,), dtype=torch.int32, device="cuda")
+    idx8 = torch.zeros((256 + 1,), dtype=torch.int32, device="cuda")
+    top8 = torch.zeros((256 + 1,), dtype=torch.float64, device="cuda")
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    reduce = lambda *a: lib.gte_reduce_trade_stats(h, *a)
+    rank = lambda *a: lib.gte_rank_trade_stats(h, *a)
+    assert reduce(None, 8, None, None, None) == INVALID and "out_device must be a 16-byte aligned" in err()
+    assert reduce(None, 8, None, None, p(out8, 8)) == INVALID and "out_device must be a 16-byte aligned" in err()
+    assert reduce(p(rec8, 8), 8, None, None, p(out8)) == INVALID and "records must be 16-byte aligned" in err()
+    assert reduce(None, 8, None, p(lists), p(out8)) == INVALID and "both or neither" in err()
+    assert reduce(None, 8, p(lists, 2), p(lists), p(out8)) == INVALID and "group lists must be 4-byte aligned" in err()
+    assert reduce(None, 8, p(lists), p(lists, 2), p(out8)) == INVALID and "group lists must be 4-byte aligned" in err()
+    assert reduce(p(rec8, 8), 0, p(lists), None, None) == INVALID and "n_strategies must be >= 1" in err()  # the order
+    assert reduce(p(rec8, 8), 8, p(lists), None, None) == INVALID and "out_device" in err()
+    assert reduce(p(rec8, 8), 8, p(lists), None, p(out8)) == INVALID and "records must be" in err()
+    assert lib.gte_reduce_trade_stats(None, None, 0, None, None, None) == INVALID and "env is NULL" in err()
+    stats_text, top_text = "stats_device must be a 16-byte aligned", "top_index_device (int32 [k]) and top_score_device"
+    assert rank(p(out8), 0, 0, 1, 8, p(idx8), p(top8), None) == INVALID and "n_strategies must be >= 1" in err()
+    for k in (0, -1, 257):
+        assert rank(p(out8), 8, 0, 1, k, p(idx8), p(top8), None) == INVALID and "k must lie in [1, 256]" in err()
+    assert rank(p(out8), 8, -1, 1, 8, p(idx8), p(top8), None) == INVALID and "metric -1 unknown" in err()
+    assert rank(None, 8, 0, 1, 8, p(idx8), p(top8), None) == INVALID and stats_text in err()
+    assert rank(p(out8, 8), 8, 0, 1, 8, p(idx8), p(top8), None) == INVALID and stats_text in err()
+    assert rank(p(out8), 8, 0, 1, 8, None, p(top8), None) == INVALID and top_text in err()
+    assert rank(p(out8), 8, 0, 1, 8, p(idx8), None, None) == INVALID and top_text in err()
+    assert rank(p(out8), 8, 0, 1, 8, p(idx8, 2), p(top8), None) == INVALID and top_text in err()
+    assert rank(p(out8), 8, 0, 1, 8, p(idx8), p(top8, 4), None) == INVALID and top_text in err()
+    assert rank(p(out8), 8, 0, 1, 8, p(idx8), p(top8), p(top8, 4)) == INVALID and "scores_device must be 8-byte aligned" in err()
+    assert rank(None, 0, -1, 1, 0, None, None, p(top8, 4)) == INVALID and "n_strategies must be >= 1" in err()  # the order
+    assert rank(None, 8, -1, 1, 0, None, None, p(top8, 4)) == INVALID and "k must lie" in err()
+    assert rank(None, 8, -1, 1, 8, None, None, p(top8, 4)) == INVALID and "metric -1 unknown" in err()
+    assert rank(None, 8, 0, 1, 8, None, None, p(top8, 4)) == INVALID and stats_text in err()
+    assert rank(p(out8), 8, 0, 1, 8, None, None, p(top8, 4)) == INVALID and top_text in err()
+    assert lib.gte_read_trade_stats(h, -1, 5, rec.ctypes.data) == INVALID and "env range [-1, 4) outside [0, 64)" in err()
+    assert lib.gte_read_trade_stats(h, 0, -1, rec.ctypes.data) == INVALID and "outside [0, 64)" in err()
+    assert lib.gte_read_trade_stats(None, 60, 5, rec.ctypes.data) == INVALID and "NULL argument" in err()
     with pytest.raises(ValueError, match="n_strategies"):
         t.by_strategy()
     with pytest.raises(ValueError, match="unknown metric"):

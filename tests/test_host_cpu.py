@@ -416,8 +416,10 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
     defined = {}
     for name in units + sorted(h for h in src if h.endswith(".h") and h != "gte_launch.h"):
         text = src[name]
-        # (gte_ledger.h: host bookkeeping only, no device code and no cross-file gte:: function)
-        assert name in ("gte_device.h", "gte_ledger.h", "gte_plan.h") or "gte_launch.h" in _included(src, name), name
+        # (gte_ledger.h: host bookkeeping only, no device code and no cross-file gte:: function; gte_members.h:
+        # forceinline and inline rules only, compiled for the host by tests/test_strategy_records_cpu.py)
+        no_launch_h = ("gte_device.h", "gte_ledger.h", "gte_plan.h", "gte_members.h")
+        assert name in no_launch_h or "gte_launch.h" in _included(src, name), name
         for fn, (sig, is_def) in _signatures(text).items():
             assert is_def, f"{name} declares {fn} itself"
             assert fn not in defined, f"{fn} is defined in {name} and in {defined[fn]}"

@@ -60,8 +60,8 @@ def main():
     a = ap.parse_args()
     import torch
     from gym_trading_env_amd import _abi
-    from gym_trading_env_amd.backtest_stats import StrategyStats
     from gym_trading_env_amd.batched import BatchedTradingEnv, _device_view
+    from gym_trading_env_amd.strategy_records import strategy_groups
     if not torch.cuda.is_available():
         sys.exit("strategy_reduce_bench needs the GPU: nothing here can be timed without it")
     feat, close = bench.synthetic_dataset(0, 2000, 2)
@@ -75,7 +75,7 @@ def main():
         field = {n: _device_view(rec.data_ptr() + bt.fields[n][1], (N,), t, dev, (128,)) for n, t in _abi.BACKTEST_FIELDS}
         R = N // S
         m = torch.from_numpy(np.random.default_rng(1).permutation(np.arange(N) % S)).to(dev)
-        offsets, members = StrategyStats._groups(env, m, S)
+        offsets, members = strategy_groups(env, m, S)
         out = torch.empty((S, 128), dtype=torch.uint8, device=dev)
         idx = torch.empty((32,), dtype=torch.int32, device=dev)
         top = torch.empty((32,), dtype=torch.float64, device=dev)
@@ -127,7 +127,7 @@ def main():
         assert torch.equal(top, torch.topk(scores, 32).values)
 
         legs = [("dev-default", lambda: dev_reduce(False)), ("dev-map", lambda: dev_reduce(True)),
-                ("lists", lambda: StrategyStats._groups(env, m, S)), ("torch-default", torch_default),
+                ("lists", lambda: strategy_groups(env, m, S)), ("torch-default", torch_default),
                 ("torch-map", torch_map), ("host", host), ("rank-32", rank),
                 ("torch-topk", lambda: torch.topk(scores, 32))]
         times = {n: [] for n, _ in legs}
