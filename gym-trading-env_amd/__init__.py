@@ -10,7 +10,7 @@ from . import _abi, config, staging  # noqa: F401
 from ._abi import GteError  # noqa: F401
 
 __all__ = ["TradingEnv", "MultiDatasetTradingEnv", "BatchedTradingEnv", "SB3TradingVecEnv", "GteError",
-           "BacktestStats", "StrategyStats", "ExitState", "TradeStats", "StrategyTradeStats",
+           "BacktestStats", "StrategyStats", "ExitState", "TradeStats", "StrategyTradeStats", "TradeList",
            "PeriodStats", "StrategyPeriodStats", "RealityCheck", "periods",
            "basic_reward_function", "dynamic_feature_last_position_taken",
            "dynamic_feature_real_position"]
@@ -22,7 +22,7 @@ _LAZY = {
     "dynamic_feature_real_position": "defaults", "History": "history",
     "SB3TradingVecEnv": "sb3", "BatchedHistory": "batched_history", "DeviceArray": "device_array",
     "BacktestStats": "backtest_stats", "StrategyStats": "backtest_stats", "ExitState": "exit_state",
-    "TradeStats": "trade_stats", "StrategyTradeStats": "trade_stats",
+    "TradeStats": "trade_stats", "StrategyTradeStats": "trade_stats", "TradeList": "trade_list",
     "PeriodStats": "period_stats", "StrategyPeriodStats": "period_stats",
     "RealityCheck": "reality_check",
 }

@@ -186,6 +186,28 @@ class GteTradeStats(C.Structure):
                [("reserved", C.c_int32 * 2)]
 
 
+#: struct gte_trade (include/gte.h), in declaration order: one 48-byte record per closed trade of the trade list
+TRADE_LIST_FIELDS = [(n, "<f8") for n in ("open_value", "close_value", "position")] + \
+    [(n, "<i4") for n in ("entry_row", "exit_row", "hold", "dataset", "kind", "flags")]
+#: numpy view of an array of gte_trade (gte_read_trade_list)
+TRADE_LIST_DTYPE = TRADE_LIST_FIELDS
+#: gte_trade.kind
+TRADE_KIND_FLAT, TRADE_KIND_REVERSAL, TRADE_KIND_FORCED = 0, 1, 2
+GTE_MAX_TRADE_LIST = 1 << 20
+
+
+class GteTrade(C.Structure):
+    """struct gte_trade (include/gte.h)."""
+    _fields_ = [(n, {"<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in TRADE_LIST_FIELDS]
+
+
+class GteTradeBatch(C.Structure):
+    """struct gte_trade_batch (include/gte.h): what gte_read_trade_list leaves, pointers into library-owned host
+    memory."""
+    _fields_ = [("n_ids", C.c_int32), ("capacity", C.c_int32), ("n_trades", C.c_int64),
+                ("first", C.POINTER(C.c_int64)), ("closed", C.POINTER(C.c_int32)), ("trades", C.POINTER(GteTrade))]
+
+
 #: struct gte_strategy_trade_stats (include/gte.h), in declaration order: one 128-byte record per strategy
 STRATEGY_TRADE_FIELDS = [(n, "<i8") for n in ("closed", "wins", "losses", "forced", "reversals", "exposure",
                                               "hold_sum")] + \
@@ -438,6 +460,9 @@ SYMBOLS = {
     "gte_read_exit_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gte_track_trades": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
     "gte_read_trade_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gte_track_trade_list": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
+    "gte_read_trade_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _P(GteTradeBatch)]),
+    "gte_pack_trade_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "gte_reduce_trade_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_rank_trade_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),

@@ -248,6 +248,7 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._exits = None  # (rules tensor, rule_of_env tensor or None) bound by bind_exits, kept alive
         self._exit_state_ptr = 0  # device address of the exit states (0 before the first bind_exits)
         self._trades_ptr = 0  # device address of the trade records while track_trades() is on, else 0
+        self._trade_list_capacity = 0  # capacity of the trade list while track_trades(list_capacity=...) keeps one
         # (device address of the period records, B, their generation) while track_periods() is on, else None; the
         # generation counts the allocations: a PeriodStats of an earlier one views freed memory and must refuse
         self._periods = None
@@ -1194,17 +1195,28 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._backtest_map = None  # (no strategies: by_strategy() needs its arguments)
         return BacktestStats(self, ptr.value)
 
-    def track_trades(self, on=True):
+    def track_trades(self, on=True, list_capacity=0):
         """Keep round-trip TRADE statistics next to the backtest statistics (`gte_track_trades`): while on,
         `backtest()` and `backtest_signals()` maintain a second 128-byte record per env — closed trades, wins and
         losses, gross profit and loss, best and worst trade, holding times, time in the market, losing streaks
         (the rule is stated in include/gte.h) — reduced in registers while they step, and the `BacktestStats`
         they return has them as `.trade_stats`.  Off (the default) every call launches exactly the kernels it
-        launches without this feature.  The first backtest call after a change clears both records whatever
-        its `resume` says.  Needs a `reset()` before it; waits for the env's stream."""
+        launches without this feature.  `list_capacity` > 0 (`gte_track_trade_list`) also keeps a PER-TRADE LIST:
+        the first `list_capacity` closed trades of every env since the records were cleared — entry and exit row,
+        the two valuations, the position, the holding time and how it ended — written where the trade closes and
+        read with `stats.trade_stats.trades()`; 0 turns the list off, and so does ``track_trades(False)``.  The
+        first backtest call after a change — on, off, another capacity — clears the records whatever its
+        `resume` says.  Needs a `reset()` before it; waits for the env's stream."""
+        if isinstance(list_capacity, bool) or int(list_capacity) != list_capacity:
+            raise TypeError("list_capacity must be an integer")
         ptr = C.c_void_p()
         _abi.check(self._lib, self._lib.gte_track_trades(self._h, 1 if on else 0, C.byref(ptr)))
         self._trades_ptr = int(ptr.value or 0) if on else 0
+        if not on:
+            self._trade_list_capacity = 0  # (switching tracking off turned the list off)
+        elif self._trade_list_capacity or int(list_capacity):
+            _abi.check(self._lib, self._lib.gte_track_trade_list(self._h, int(list_capacity), None))
+            self._trade_list_capacity = int(list_capacity)
 
     def track_periods(self, period_of_row, n_periods=None):
         """Keep PERIOD statistics next to the backtest statistics (`gte_bind_periods`, `gte_track_periods`):

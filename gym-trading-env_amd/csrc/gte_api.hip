@@ -98,6 +98,16 @@ struct gte_env {
   // backtest calls maintain them, and whether that changed since the last backtest call (which then clears)
   gte_trade_stats* tr_stats = nullptr;
   bool tr_on = false, tr_changed = false;
+  // gte_track_trade_list: the [N][tl_cap] list (tl_cap == 0: off; tl_alloc_cap: the capacity it was allocated
+  // for) and the open_row of every env; a change sets tr_changed.  gte_read_trade_list: its device block (ids,
+  // first, closed, trades) and the host copy `out` points into
+  gte_trade* tl_list = nullptr;
+  int32_t* tl_open_row = nullptr;
+  int32_t tl_cap = 0, tl_alloc_cap = 0;
+  void* tl_dev = nullptr;
+  size_t tl_dev_bytes = 0;
+  void* tl_host = nullptr;
+  size_t tl_host_bytes = 0;
   // gte_track_periods / gte_bind_periods: the [N][pd_B] period records (pd_B == 0: tracking off; pd_alloc_B: the B
   // they were allocated for), whether tracking, B or a row changed since the last backtest call (which then
   // clears), and the period row of every dataset (base null = none bound; the base IS the library's allocation)
@@ -1078,6 +1088,9 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   if (E->tr_changed) clear = 1;
   E->tr_changed = false;
   gte_trade_stats* const trades = E->tr_on ? E->tr_stats : nullptr;
+  // ... with the trade list on, through the unit that writes it as well (gte_trade_list.hip)
+  const bool listed = trades && E->tl_cap > 0;
+  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
   // the same for period tracking (never on together with trades: gte_track_periods, gte_track_trades)
   if (E->pd_changed) clear = 1;
   E->pd_changed = false;
@@ -1088,8 +1101,9 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   Params ps = E->p;
   ps.perm = nullptr;  // identity order, as in the state-only rollout: per-env loads and stores coalesce
   ps.final_rec = terminal;
-  hipError_t le = trades ? gte::launch_trade_begin(ps, E->bt_stats, trades, clear, E->stream)
-                         : gte::launch_backtest_begin(ps, E->bt_stats, clear, E->stream);
+  hipError_t le = listed   ? gte::launch_trade_list_begin(ps, E->bt_stats, trades, tl, clear, E->stream)
+                  : trades ? gte::launch_trade_begin(ps, E->bt_stats, trades, clear, E->stream)
+                           : gte::launch_backtest_begin(ps, E->bt_stats, clear, E->stream);
   if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   if (periods && clear)  // a cleared period record is all zero, and a reset row changes none
     HIPCHK(hipMemsetAsync(E->pd_stats, 0, sizeof(gte_period_stats) * N * (size_t)E->pd_B, E->stream));
@@ -1102,7 +1116,8 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
     }
     const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
     TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->bt_final_rec));
-    const hipError_t fe = trades    ? gte::launch_trade_fold(ps, E->bt_stats, trades, E->stream)
+    const hipError_t fe = listed    ? gte::launch_trade_list_fold(ps, E->bt_stats, trades, tl, E->stream)
+                          : trades  ? gte::launch_trade_fold(ps, E->bt_stats, trades, E->stream)
                           : periods ? gte::launch_period_fold(ps, E->bt_stats, per, E->stream)
                                     : gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
     if (fe != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(fe));
@@ -1120,7 +1135,8 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
     // one launch, its actions from `src`; with a tracker on, the unit that keeps that record in registers as well
     const gte::SummarySource src = {actions, E->d_sig, E->sig_S, strategy, E->exits.rules ? &E->exits : nullptr};
     const int32_t k = n_steps - 1, epw = L.state_epw;
-    le = trades    ? gte::launch_trade_summary(ps, src, E->bt_stats, trades, k, epw, E->stream)
+    le = listed    ? gte::launch_trade_list_summary(ps, src, E->bt_stats, trades, tl, k, epw, E->stream)
+         : trades  ? gte::launch_trade_summary(ps, src, E->bt_stats, trades, k, epw, E->stream)
          : periods ? gte::launch_period_summary(ps, src, E->bt_stats, per, k, epw, E->stream)
          : signals ? gte::launch_signal_summary(ps, src, E->bt_stats, k, epw, E->stream)
                    : gte::launch_backtest_summary(ps, src, E->bt_stats, k, epw, E->stream);
@@ -1492,6 +1508,13 @@ int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backte
                       sizeof(gte_backtest_stats), first, count, out);
 }
 
+// the list turned off: its memory goes back (N * capacity * 48 bytes; the env's stream is idle), open_row stays
+static void drop_trade_list(gte_env* E) {
+  if (E->tl_list) (void)hipFree(E->tl_list);
+  E->tl_list = nullptr;
+  E->tl_cap = E->tl_alloc_cap = 0;
+}
+
 int gte_track_trades(gte_env* E, int32_t on, gte_trade_stats** records_device) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_trades before gte_reset");
@@ -1504,7 +1527,152 @@ int gte_track_trades(gte_env* E, int32_t on, gte_trade_stats** records_device) {
   HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the records
   if ((on != 0) != E->tr_on) E->tr_changed = true;
   E->tr_on = on != 0;
+  if (!on && E->tl_cap > 0) {  // the list goes with the tracking
+    drop_trade_list(E);
+    E->tr_changed = true;
+  }
   if (records_device) *records_device = E->tr_stats;
+  return GTE_OK;
+}
+
+int gte_track_trade_list(gte_env* E, int32_t capacity, gte_trade** list_device) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (capacity < 0 || capacity > GTE_MAX_TRADE_LIST)
+    return fail(GTE_ERR_INVALID, "gte_track_trade_list: capacity %d outside [0, %d]", capacity, GTE_MAX_TRADE_LIST);
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_trade_list before gte_reset");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_trade_list inside a stream capture");
+  if (capacity > 0 && !E->tr_on)
+    return fail(GTE_ERR_STATE, "gte_track_trade_list: trade tracking is off (gte_track_trades(env, 1, ...) first)");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the list
+  if (capacity > 0 && capacity != E->tl_alloc_cap) {
+    void *fresh = nullptr, *rows = E->tl_open_row;
+    hipError_t e = hipMalloc(&fresh, sizeof(gte_trade) * (size_t)E->p.N * (size_t)capacity);
+    if (e == hipSuccess && !rows) {
+      e = hipMalloc(&rows, sizeof(int32_t) * (size_t)E->p.N);
+      if (e != hipSuccess) (void)hipFree(fresh);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "trade list (%d envs x %d trades): %s", E->p.N,
+                  capacity, hipGetErrorString(e));
+    }
+    if (E->tl_list) (void)hipFree(E->tl_list);
+    E->tl_list = (gte_trade*)fresh;  // (never zeroed: `closed` says what of it is valid)
+    E->tl_open_row = (int32_t*)rows;  // (written by the next backtest call's clearing: tr_changed)
+    E->tl_alloc_cap = capacity;
+  }
+  if (capacity != E->tl_cap) E->tr_changed = true;
+  E->tl_cap = capacity;
+  if (capacity == 0) drop_trade_list(E);
+  if (list_device) *list_device = E->tl_list;
+  return GTE_OK;
+}
+
+// what both gathers check first
+static int trade_list_on(gte_env* E, const char* who) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (E->tl_cap < 1 || !E->tl_list || !E->tr_stats)
+    return fail(GTE_ERR_STATE, "%s: the trade list is off (gte_track_trade_list)", who);
+  // a switch of tracking, of the list or of its capacity since the last backtest call: `closed` still counts the
+  // trades of before, and the list (fresh memory, never zeroed) holds none of them
+  if (E->tr_changed)
+    return fail(GTE_ERR_STATE, "%s: the trade list was switched and no backtest call has cleared the records since: "
+                "it holds nothing yet", who);
+  return GTE_OK;
+}
+
+static size_t round_up_16z(size_t n) { return (n + 15) & ~(size_t)15; }
+
+int gte_read_trade_list(gte_env* E, const int32_t* env_ids, int32_t n_ids, gte_trade_batch* out) {
+  TRY(trade_list_on(E, "gte_read_trade_list"));
+  if (!out) return fail(GTE_ERR_INVALID, "NULL argument");
+  const int N = E->p.N;
+  if (!env_ids) n_ids = N;
+  if (n_ids < 0) return fail(GTE_ERR_INVALID, "n_ids must be >= 0");
+  for (int32_t i = 0; env_ids && i < n_ids; ++i)
+    if (env_ids[i] < 0 || env_ids[i] >= N) return fail(GTE_ERR_INVALID, "env_ids[%d] = %d out of range", i, env_ids[i]);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  // the device block: [ids i32 n -> 16] [first i64 n+1 | closed i32 n -> 16] [trades]; the host copy: from `first` on
+  const size_t n = (size_t)n_ids;
+  const size_t ids_bytes = round_up_16z(4 * n), head = round_up_16z(8 * (n + 1) + 4 * n);
+  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
+  int64_t total = 0;
+  char* b = nullptr;
+  int64_t* first = nullptr;
+  // count and scan; one read of the total; if the block cannot hold that many records it grows and is counted
+  // into again; then the pack
+  for (int pass = 0; pass < 2; ++pass) {
+    const size_t need = ids_bytes + head + sizeof(gte_trade) * (size_t)total;
+    if (pass == 1 && need <= E->tl_dev_bytes) break;
+    if (need > E->tl_dev_bytes) {
+      void* fresh = nullptr;
+      const size_t bytes = need + need / 2;
+      const hipError_t e = hipMalloc(&fresh, bytes);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "trade list block (%zu bytes): %s", bytes,
+                    hipGetErrorString(e));
+      }
+      HIPCHK(hipStreamSynchronize(E->stream));  // (a gather in flight writes the old block)
+      if (E->tl_dev) (void)hipFree(E->tl_dev);
+      E->tl_dev = fresh;
+      E->tl_dev_bytes = bytes;
+    }
+    b = (char*)E->tl_dev;
+    first = (int64_t*)(b + ids_bytes);
+    if (env_ids && n) HIPCHK(hipMemcpyAsync(b, env_ids, 4 * n, hipMemcpyHostToDevice, E->stream));
+    const hipError_t le = gte::launch_trade_list_scan(E->tr_stats, tl, N, env_ids ? (const int32_t*)b : nullptr, n_ids,
+                                                      first, (int32_t*)(first + n + 1), E->stream);
+    if (le != hipSuccess) return fail(GTE_ERR_HIP, "trade list scan launch: %s", hipGetErrorString(le));
+    if (pass == 0) {
+      HIPCHK(hipMemcpyAsync(&total, first + n, 8, hipMemcpyDeviceToHost, E->stream));
+      HIPCHK(hipStreamSynchronize(E->stream));
+    }
+  }
+  if (total > 0) {
+    const hipError_t le = gte::launch_trade_list_pack(tl, N, env_ids ? (const int32_t*)b : nullptr, n_ids, first,
+                                                      (gte_trade*)(b + ids_bytes + head), total, E->stream);
+    if (le != hipSuccess) return fail(GTE_ERR_HIP, "trade list pack launch: %s", hipGetErrorString(le));
+  }
+  const size_t bytes = head + sizeof(gte_trade) * (size_t)total;
+  if (bytes > E->tl_host_bytes) {
+    if (E->tl_host) HIPCHK(hipHostFree(E->tl_host));
+    E->tl_host = nullptr; E->tl_host_bytes = 0;
+    HIPCHK(hipHostMalloc(&E->tl_host, bytes + bytes / 2, hipHostMallocDefault));
+    E->tl_host_bytes = bytes + bytes / 2;
+  }
+  HIPCHK(hipMemcpyAsync(E->tl_host, (char*)E->tl_dev + ids_bytes, bytes, hipMemcpyDeviceToHost, E->stream));
+  HIPCHK(hipStreamSynchronize(E->stream));
+  out->n_ids = n_ids;
+  out->capacity = E->tl_cap;
+  out->n_trades = total;
+  out->first = (const int64_t*)E->tl_host;
+  out->closed = (const int32_t*)(out->first + n + 1);
+  out->trades = (const gte_trade*)((const char*)E->tl_host + head);
+  return GTE_OK;
+}
+
+int gte_pack_trade_list(gte_env* E, const int32_t* env_ids_device, int32_t n_ids, int64_t* first_device,
+                        int32_t* closed_device, gte_trade* trades_device, int64_t max_trades) {
+  TRY(trade_list_on(E, "gte_pack_trade_list"));
+  if (!env_ids_device) n_ids = E->p.N;
+  if (n_ids < 0) return fail(GTE_ERR_INVALID, "n_ids must be >= 0");
+  if (max_trades < 0 || (max_trades > 0 && !trades_device))
+    return fail(GTE_ERR_INVALID, "trades_device (gte_trade [max_trades]) is NULL or max_trades < 0");
+  if (!first_device || ((uintptr_t)first_device & 7) || (n_ids > 0 && !closed_device) ||
+      ((uintptr_t)closed_device & 3) || ((uintptr_t)env_ids_device & 3))
+    return fail(GTE_ERR_INVALID, "first_device (int64 [n_ids + 1]), closed_device and env_ids_device (int32 [n_ids]) "
+                "must be aligned device pointers");
+  if ((uintptr_t)trades_device & 15) return fail(GTE_ERR_INVALID, "trades_device must be 16-byte aligned");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
+  hipError_t le = gte::launch_trade_list_scan(E->tr_stats, tl, E->p.N, env_ids_device, n_ids, first_device,
+                                              closed_device, E->stream);
+  if (le == hipSuccess && max_trades > 0 && n_ids > 0)
+    le = gte::launch_trade_list_pack(tl, E->p.N, env_ids_device, n_ids, first_device, trades_device, max_trades,
+                                     E->stream);
+  if (le != hipSuccess) return fail(GTE_ERR_HIP, "trade list gather launch: %s", hipGetErrorString(le));
   return GTE_OK;
 }
 
@@ -2253,6 +2421,9 @@ void gte_destroy(gte_env* E) {
   for (int32_t* q : {E->d_q_idx, E->d_q_pos, E->d_q_ds})
     if (q) (void)hipFree(q);
   if (E->pd_stats) (void)hipFree(E->pd_stats);
+  for (void* q : {(void*)E->tl_list, (void*)E->tl_open_row, E->tl_dev})
+    if (q) (void)hipFree(q);
+  if (E->tl_host) (void)hipHostFree(E->tl_host);
   for (const gte::PeriodRow& r : E->h_prow)
     if (r.base) (void)hipFree(const_cast<int8_t*>(r.base));
   if (E->h_snap) (void)hipHostFree(E->h_snap);

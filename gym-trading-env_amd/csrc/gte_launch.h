@@ -155,6 +155,31 @@ hipError_t launch_trade_summary(const Params& p, const SummarySource& src, gte_b
 hipError_t launch_trade_fold(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades,
                              hipStream_t stream);
 
+// --- gte_trade_list.hip: the launches of gte_trades.hip with the trade list kept as well (gte_track_trade_list,
+// include/gte.h), and the gather of gte_read_trade_list / gte_pack_trade_list
+struct TradeList {  // what the list kernels are given, library-owned
+  gte_trade* list;    // device [N][capacity], env-major
+  int32_t* open_row;  // device i32 [N]: the row the open trade of every env was decided at
+  int32_t capacity;   // 1 .. GTE_MAX_TRADE_LIST
+};
+// launch_trade_begin, and open_row where a record is cleared or takes a reset row
+hipError_t launch_trade_list_begin(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades,
+                                   const TradeList& tl, int clear, hipStream_t stream);
+// launch_trade_summary whose closes write their record
+hipError_t launch_trade_list_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats,
+                                     gte_trade_stats* trades, const TradeList& tl, int n_steps, int epw,
+                                     hipStream_t stream);
+// launch_trade_fold whose closes write their record
+hipError_t launch_trade_list_fold(const Params& p, gte_backtest_stats* stats, gte_trade_stats* trades,
+                                  const TradeList& tl, hipStream_t stream);
+// ids (device i32 [n_ids], or null = envs 0 .. n_ids-1) -> closed[j] (the env's `closed`; -1 for an id outside
+// [0, n_envs)) and first[0 .. n_ids], the running sum of min(closed, capacity)
+hipError_t launch_trade_list_scan(const gte_trade_stats* trades, const TradeList& tl, int n_envs, const int32_t* ids,
+                                  int n_ids, int64_t* first, int32_t* closed, hipStream_t stream);
+// ... and the valid records of request j to out[first[j] ..), those below max_out only
+hipError_t launch_trade_list_pack(const TradeList& tl, int n_envs, const int32_t* ids, int n_ids, const int64_t* first,
+                                  gte_trade* out, int64_t max_out, hipStream_t stream);
+
 // --- gte_periods.hip: the backtest launches above with the period statistics (gte_track_periods, include/gte.h)
 // launch_backtest_summary with the open period's record in registers, whatever the source
 hipError_t launch_period_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats,

@@ -1,6 +1,7 @@
 // gte_summary_body.h — the ONE loop of the nine from-registers backtest kernels: an action source times a
 // tracker.  A kernel is one call of summary_body() with its two policies, in the file it always had
-// (gte_backtest.hip, gte_exits.hip, gte_trades.hip, gte_periods.hip hold the table of which is which), so a
+// (gte_backtest.hip, gte_exits.hip, gte_trades.hip, gte_periods.hip hold the table of which is which;
+// gte_trade_list.hip adds the three of gte_trades.hip once more, with TradeListTracker, its own tracker), so a
 // unit still compiles alone and holds the code of its own tracker only.  ONE kernel is not:
 // gte_backtest_exit_kernel (gte_exits.hip) is this body with ExitSource and NoTracker written out by hand,
 // because it measured about 1 % slower as a call — a change to the step here is made there too.  fold_body(), at the end, is the ONE
@@ -19,9 +20,10 @@
 // plain loop body the compiler kept the env's registers in scratch memory (tests: test_kernel_register_budget).
 //
 // The order inside a step: the source decides the action; the tracker takes what it needs from before the
-// step; the speculative piece fetch; phase A; the source's update; the tracker's step; backtest_step(); the
-// corrective piece fetch.  The tracker runs directly BEFORE backtest_step(), so that a.ended is the env's
-// needs_reset before the step, a.step_seen its _step before it and a.prev_position its position before it.
+// step; the speculative piece fetch; phase A; the source's update; the tracker's landed() and step;
+// backtest_step(); the corrective piece fetch.  The tracker runs directly BEFORE backtest_step(), so that
+// a.ended is the env's needs_reset before the step, a.step_seen its _step before it and a.prev_position its
+// position before it.
 //
 // The piece cursor.  A source or tracker that reads a byte per market row (`pieces`) keeps the aligned
 // 16-byte piece of its row that holds idx in registers and shifts the wanted byte out (signal_byte).  The
@@ -40,7 +42,8 @@
 //
 // A source has: pieces, init(p, active, e, s), dataset(dsi), piece(idx), limit(), decide(p, s, active, e,
 // k, n_steps) -> action, after(p, s, pv, so), store(e, s, episode).  A tracker has: pieces, init(active, e),
-// dataset(dsi), piece(idx), limit(), before(idx), step(a, p, e, step_after, pv, pos_after, reward, flags),
+// dataset(dsi), piece(idx), limit(), before(idx, dsi) — the row and the dataset the env stands on before the
+// step —, landed(idx) — the row it stands on after it —, step(a, p, e, step_after, pv, pos_after, reward, flags),
 // store(e).  Both hold their own registers and have __forceinline__ members only.
 #pragma once
 #include "gte_exit_regs.h"
@@ -167,7 +170,8 @@ struct NoTracker {
   __device__ __forceinline__ void dataset(int32_t) {}
   __device__ __forceinline__ void piece(int32_t) {}
   __device__ __forceinline__ int32_t limit() const { return 0; }
-  __device__ __forceinline__ void before(int32_t) {}
+  __device__ __forceinline__ void before(int32_t, int32_t) {}
+  __device__ __forceinline__ void landed(int32_t) {}
   __device__ __forceinline__ void step(const gte_backtest_stats&, const Params&, int, int32_t, double, int32_t, double,
                                        int32_t) {}
   __device__ __forceinline__ void store(int) {}
@@ -186,10 +190,12 @@ struct TradeTracker {
   __device__ __forceinline__ void dataset(int32_t) {}
   __device__ __forceinline__ void piece(int32_t) {}
   __device__ __forceinline__ int32_t limit() const { return 0; }
-  __device__ __forceinline__ void before(int32_t) {}
+  __device__ __forceinline__ void before(int32_t, int32_t) {}
+  __device__ __forceinline__ void landed(int32_t) {}
   __device__ __forceinline__ void step(const gte_backtest_stats& a, const Params& p, int e, int32_t step_after,
                                        double pv, int32_t pos_after, double reward, int32_t flags) {
-    trade_step(t, a, p, e, step_after, pv, pos_after, reward, flags);
+    NoTradeSink none;
+    trade_step(t, a, p, e, step_after, pv, pos_after, reward, flags, none);
   }
   __device__ __forceinline__ void store(int e) { store_trades(trades + e, t); }
 };
@@ -211,7 +217,8 @@ struct PeriodTracker {
   __device__ __forceinline__ void dataset(int32_t dsi) { prow = per.rows[dsi]; }
   __device__ __forceinline__ void piece(int32_t idx) { pw = period_piece(prow.base, prow.len, idx); }
   __device__ __forceinline__ int32_t limit() const { return prow.len; }
-  __device__ __forceinline__ void before(int32_t idx) { b = signal_byte(pw, idx); }
+  __device__ __forceinline__ void before(int32_t idx, int32_t) { b = signal_byte(pw, idx); }
+  __device__ __forceinline__ void landed(int32_t) {}
   __device__ __forceinline__ void step(const gte_backtest_stats& a, const Params& p, int e, int32_t step_after, double,
                                        int32_t pos_after, double reward, int32_t flags) {
     period_step(o, mine, per.B, b, a, p, e, step_after, pos_after, reward, flags);
@@ -253,7 +260,7 @@ __device__ __forceinline__ void summary_body(const Params& p, gte_backtest_stats
   ObsJob job;
   auto run_a = [&](int k) {
     const int32_t now = src.decide(p, s, active, e, k, n_steps);
-    trk.before(s.idx);
+    trk.before(s.idx, s.dsi);
     if constexpr (pieces) {
       const int32_t lim = Src::pieces ? src.limit() : trk.limit();
       if (active && k + 1 < n_steps && (s.idx & 15) == 15 && s.idx + 1 < lim) fetch(s.idx + 1);
@@ -264,6 +271,7 @@ __device__ __forceinline__ void summary_body(const Params& p, gte_backtest_stats
                        /*write_record=*/k == n_steps - 1, &pc, &so);
     if (active) {
       src.after(p, s, pv, so);
+      trk.landed(s.idx);
       trk.step(a, p, e, s.step, pv, s.pos, so.reward, so.flags);
       backtest_step(a, p, e, s.step, pv, s.pos, so.reward, so.flags);
     }

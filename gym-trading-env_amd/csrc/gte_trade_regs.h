@@ -63,6 +63,18 @@ __device__ __forceinline__ void trade_reset_row(gte_trade_stats& t, double v0, d
   t.open_len = 0;
 }
 
+// What trade_transition() and trade_step() tell a kernel that keeps more than the sums (the trade list,
+// gte_trade_list.hip), each with the record as it stands directly BEFORE trade_close(): close(t, v, flat, flags)
+// for a trade left to flat (closed at v) or reversed / resized (closed at t.last_valuation), forced(t, v, flags)
+// for the close at an episode's end; open() where open_value is set by a position change; reset_row() at a reset
+// row.  The kernels of gte_trades.hip pass none: every member is empty.
+struct NoTradeSink {
+  __device__ __forceinline__ void close(const gte_trade_stats&, double, bool, int32_t) const {}
+  __device__ __forceinline__ void forced(const gte_trade_stats&, double, int32_t) const {}
+  __device__ __forceinline__ void open() const {}
+  __device__ __forceinline__ void reset_row() const {}
+};
+
 // the open trade closed at valuation vc (include/gte.h states the order): the one f64 division of a trade
 __device__ __forceinline__ void trade_close(gte_trade_stats& t, double vc) {
   const double ret = vc / t.open_value - 1.0;
@@ -86,24 +98,28 @@ __device__ __forceinline__ void trade_close(gte_trade_stats& t, double vc) {
 }
 
 // One transition of an episode that has not ended (include/gte.h states the order)
-__device__ __forceinline__ void trade_transition(gte_trade_stats& t, double v, double pos, int32_t flags) {
+template <class Sink>
+__device__ __forceinline__ void trade_transition(gte_trade_stats& t, double v, double pos, int32_t flags, Sink& sink) {
   if (pos != t.open_position) {
     if (t.open_position != 0.0) {
       // left to flat: at v, which is the valuation before less the fees of leaving; a reversal or a resize:
       // at the valuation before, the flip's fees count against the new trade
       const bool flat = pos == 0.0;
+      sink.close(t, v, flat, flags);
       trade_close(t, flat ? v : t.last_valuation);
       t.reversals += flat ? 0 : 1;
     }
     t.open_position = pos;
     t.open_value = t.last_valuation;
     t.open_len = 0;
+    sink.open();
   }
   if (t.open_position != 0.0) {
     t.open_len += 1;
     t.exposure += 1;
   }
   if (flags != 0 && t.open_position != 0.0) {
+    sink.forced(t, v, flags);
     trade_close(t, v);
     t.forced += 1;
     t.open_position = 0.0;
@@ -115,9 +131,10 @@ __device__ __forceinline__ void trade_transition(gte_trade_stats& t, double v, d
 // trade is defined by valuations), called directly BEFORE it, so that a.ended is the env's needs_reset before
 // the step and a.step_seen its _step before it.  Next-step resets, same-step resets (terminal valuation and
 // position from the terminal record) and frozen steps are recognised exactly as backtest_step() does.
+template <class Sink>
 __device__ __forceinline__ void trade_step(gte_trade_stats& t, const gte_backtest_stats& a, const Params& p, int e,
                                            int32_t step_after, double pv_after, int32_t pos_after, double reward,
-                                           int32_t flags) {
+                                           int32_t flags, Sink& sink) {
   (void)reward;
   const bool nr = a.ended != 0;
   const bool stepped = !(nr && (p.autoreset == GTE_AUTORESET_NEXT_STEP || step_after == a.step_seen));
@@ -130,10 +147,14 @@ __device__ __forceinline__ void trade_step(gte_trade_stats& t, const gte_backtes
       pos = reinterpret_cast<const int4*>(r)[0].z;
       v = reinterpret_cast<const double2*>(&r->asset)[2].x;
     }
-    if (!nr) trade_transition(t, v, p.positions[pos], flags);  // (after the episode's end: changes nothing)
-    if (reset_after) trade_reset_row(t, pv_after, p.positions[pos_after]);
+    if (!nr) trade_transition(t, v, p.positions[pos], flags, sink);  // (after the episode's end: changes nothing)
+    if (reset_after) {
+      trade_reset_row(t, pv_after, p.positions[pos_after]);
+      sink.reset_row();
+    }
   } else if (p.autoreset == GTE_AUTORESET_NEXT_STEP) {
     trade_reset_row(t, pv_after, p.positions[pos_after]);
+    sink.reset_row();
   }
 }
 

@@ -68,6 +68,23 @@ class TradeStats:
         _abi.check(e._lib, e._lib.gte_read_trade_stats(e._h, 0, e.num_envs, out.ctypes.data))
         return out
 
+    def trades(self, env_ids=None, strategy=None) -> "TradeList":
+        """The per-trade list (`track_trades(list_capacity=...)`) of the envs `env_ids` (any order, repeats allowed;
+        None: all envs), or of the member envs of the strategies `strategy` (an id or a sequence of ids, e.g.
+        ``by_strategy().top(10)[0]``) under the map of the `backtest_signals()` call that made these records: a
+        `TradeList`.  One gather on the device and one transfer (`gte_read_trade_list`); like `numpy()` it reads
+        what the live records hold when it runs."""
+        from .trade_list import TradeList
+        return TradeList._read(self._env, self._map, env_ids, strategy)
+
+    def trades_device(self, env_ids=None, max_trades=None):
+        """The same gather with its results left on the device (`gte_pack_trade_list`): ``(first int64 [n + 1],
+        closed int32 [n], trades uint8 [n_trades, 48])``; `env_ids`: an int32 CUDA tensor, None for all envs.
+        Without `max_trades` the total is read back once to size the block (one wait); with it nothing is waited
+        for, the block has `max_trades` records, and ``first[n]`` says how many there were."""
+        from .trade_list import pack_trades
+        return pack_trades(self._env, env_ids, max_trades)
+
     def by_strategy(self, strategy=None, n_strategies=None) -> "StrategyTradeStats":
         """These records folded into one record per strategy, on the device (`gte_reduce_trade_stats`): a
         `StrategyTradeStats`.  `strategy` / `n_strategies` and their defaults — the map and the S of the

@@ -661,7 +661,30 @@ int gte_read_exit_state(gte_env* env, int32_t first, int32_t count, gte_exit_sta
  * value, open_value = last_valuation = its current portfolio_valuation.
  *
  * The record is defined by valuations, not rewards: it does not depend on the reward kind, and every f64
- * field is a function of state the kernels reproduce by value. */
+ * field is a function of state the kernels reproduce by value.
+ *
+ * THE TRADE LIST (gte_track_trade_list; opt-in on top of gte_track_trades): one 48-byte gte_trade per closed
+ * trade next to the sums, list[N][capacity] env-major, owned by the env on the device.  ROWS: for a transition t,
+ * row_t and ds_t are the market row (_idx) and the dataset the env stood on BEFORE the step; after the
+ * transition it stands on row_t + 1; row_0 is the row a reset row put it on.  The env keeps one more value,
+ * open_row (one int32 per env, owned by the library; NOT a field of gte_trade_stats, whose reserved words stay
+ * zero), and the text above gains:
+ *
+ *     where it sets  open_value = last_valuation   (a position change), also   open_row = row_t;
+ *     AT A RESET ROW of any kind, also            open_row = row_0;
+ *     CLEARING, also                              open_row = the row the env stands on;
+ *     close(vc) FIRST writes, if closed < capacity,
+ *         list[e][closed] = { open_value, vc, open_position, open_row, exit_row, open_len, ds_t, kind, flags_t }
+ *       and then does what it does above, with
+ *         kind 0  left to flat:         exit_row = row_t       the order executes at that row's price
+ *         kind 1  reversal / resize:    exit_row = row_t
+ *         kind 2  forced by the end:    exit_row = row_t + 1   the trade is marked at the row the episode ended on
+ *
+ * So exit_row - entry_row == hold for every record, and a reversal on the terminal step writes two records,
+ * kind 1 and then kind 2 with hold == 1.  The list keeps the FIRST `capacity` trades of an env since the last
+ * clearing while `closed` goes on counting: min(closed, capacity) records are valid, closed > capacity means
+ * truncated.  The list has no counter of its own and is never zeroed.  A trade's return is
+ * close_value / open_value - 1.0, one f64 division and one subtraction: the ret of close() bit for bit. */
 typedef struct gte_trade_stats {     /* 128 bytes, eight 16-byte pieces */
   double  open_value;       /* valuation the open trade was decided at                      */
   double  open_position;    /* position value of the open trade; 0.0: none open             */
@@ -680,11 +703,27 @@ typedef struct gte_trade_stats {     /* 128 bytes, eight 16-byte pieces */
 #ifdef __cplusplus
 static_assert(sizeof(gte_trade_stats) == 128, "trade statistics: eight 16-byte pieces");
 #endif
+/* One record of the trade list (THE TRADE LIST, in the text above) */
+typedef struct gte_trade {           /* 48 bytes, three 16-byte pieces */
+  double  open_value;   /* valuation the trade was decided at (the record's open_value) */
+  double  close_value;  /* the vc of close(vc)                                          */
+  double  position;     /* position value held                                          */
+  int32_t entry_row, exit_row;   /* market rows (_idx)                                  */
+  int32_t hold;         /* open_len at the close                                        */
+  int32_t dataset;      /* ds_t of the transition that closed it                        */
+  int32_t kind;         /* 0 left to flat, 1 reversal / resize, 2 forced by the episode's end */
+  int32_t flags;        /* flags of the transition that closed it (bit0 terminated, bit1 truncated) */
+} gte_trade;
+#ifdef __cplusplus
+static_assert(sizeof(gte_trade) == 48, "trade list record: three 16-byte pieces");
+#endif
+#define GTE_MAX_TRADE_LIST (1 << 20)
 /* on != 0: gte_backtest and gte_backtest_signals maintain BOTH records of every env from now on — with or
  * without exit rules bound, on the fused path (gte_trades.hip: the from-registers kernels with the trade
  * record in registers as well) and on the step-by-step path, in all three auto-reset modes — and the
  * gte_backtest_stats records, the env state and the exit state come out bit for bit as with tracking off.
- * on == 0: tracking stops; the trade records keep what they hold.  The FIRST backtest call after a change of
+ * on == 0: tracking stops, and the trade list (gte_track_trade_list) is turned off with it; the trade records keep
+ * what they hold.  The FIRST backtest call after a change of
  * `on` clears both records whatever its `clear` says, so the two records always cover the same transitions.
  * The N trade records are allocated by the first call with on != 0; *records_device (may be NULL) receives
  * their DEVICE address (NULL before they exist), which stays the same until gte_destroy.  The call waits for
@@ -693,6 +732,49 @@ int gte_track_trades(gte_env* env, int32_t on, gte_trade_stats** records_device)
 /* Trade records first .. first+count-1 into HOST memory: waits for the env's stream, one transfer.
  * GTE_ERR_STATE before the first gte_track_trades(env, 1, ...). */
 int gte_read_trade_stats(gte_env* env, int32_t first, int32_t count, gte_trade_stats* out);
+/* The trade list (the text above).  capacity in 1 .. GTE_MAX_TRADE_LIST: from now on the backtest calls write
+ * every closed trade of an env into list[e][closed] as well, through the kernels of gte_trade_list.hip — the
+ * kernels of gte_trades.hip with the list, on the fused and on the step-by-step path, in all three auto-reset
+ * modes — and both records, the env state and the exit state come out bit for bit as with gte_track_trades
+ * alone.  capacity == 0 turns the list off; gte_track_trades(env, 0, ...) turns it off too.  With the list off
+ * every call launches exactly the kernels it launches without this feature.  The call allocates N * capacity *
+ * 48 bytes on the first call and on a change of capacity (GTE_ERR_OOM on failure, with everything left as it
+ * was; the old list is freed: an address an earlier call returned is dead from then on).  Turning the list off
+ * frees it as well.  Any change — on, off, another capacity — makes the FIRST backtest call after it clear the
+ * records whatever its `clear` says, like a switch of gte_track_trades; until that call the list holds nothing
+ * (its memory is fresh and `closed` still counts the trades of before), so gte_read_trade_list and
+ * gte_pack_trade_list are refused (GTE_ERR_STATE).  *list_device (may be NULL) receives the DEVICE address of
+ * the list (NULL while it is off).  The call waits for the env's stream; it is refused unless trade tracking is on, before gte_reset
+ * and inside a stream capture (GTE_ERR_STATE); GTE_ERR_INVALID for a capacity outside [0, GTE_MAX_TRADE_LIST]. */
+int gte_track_trade_list(gte_env* env, int32_t capacity, gte_trade** list_device);
+/* What gte_read_trade_list leaves: the valid records of the requested envs as ONE dense block, in request
+ * order.  The trades of request j are trades[first[j] .. first[j+1]), min(closed[j], capacity) of them, in close
+ * order; closed[j] is the env's `closed` (closed[j] > capacity: the list of that env is truncated). */
+typedef struct gte_trade_batch {
+  int32_t n_ids;            /* requests                                                  */
+  int32_t capacity;         /* of the list as it stands                                  */
+  int64_t n_trades;         /* records in `trades` == first[n_ids]                       */
+  const int64_t* first;     /* [n_ids + 1]                                               */
+  const int32_t* closed;    /* [n_ids]                                                   */
+  const gte_trade* trades;  /* [n_trades]                                                */
+} gte_trade_batch;
+/* env_ids: HOST int32 [n_ids], in any order, repeats allowed; NULL: all envs 0 .. N-1 (n_ids is then ignored).
+ * On the device a count-and-scan kernel computes first[] from min(closed, capacity) and a pack kernel copies each
+ * requested env's valid records into the block, one wavefront per request in 16-byte pieces; then one read of the
+ * total and one transfer.  `out` points into library-owned HOST memory, valid until the next call or
+ * gte_destroy.  Waits for the env's stream.  GTE_ERR_STATE while the list is off, and between a switch of tracking,
+ * of the list or of its capacity and the backtest call that clears the records; GTE_ERR_INVALID for an id
+ * outside [0, N) and for n_ids < 0. */
+int gte_read_trade_list(gte_env* env, const int32_t* env_ids, int32_t n_ids, gte_trade_batch* out);
+/* The same pack with caller-provided DEVICE memory, enqueued on the env's stream without waiting:
+ * env_ids_device int32 [n_ids] (NULL: all envs, n_ids is then ignored), first_device int64 [n_ids + 1],
+ * closed_device int32 [n_ids], trades_device gte_trade [max_trades], 16-byte aligned.  Records that would lie at
+ * or past max_trades are not written; first_device[n_ids] still holds the full total, so a caller may run the
+ * call with trades_device == NULL and max_trades == 0 first, read the total, and size the block for a second
+ * call.  An id outside [0, N) — the host cannot see it — gives an empty list with closed[j] == -1.
+ * GTE_ERR_STATE as gte_read_trade_list; GTE_ERR_INVALID for misaligned or missing pointers. */
+int gte_pack_trade_list(gte_env* env, const int32_t* env_ids_device, int32_t n_ids, int64_t* first_device,
+                        int32_t* closed_device, gte_trade* trades_device, int64_t max_trades);
 
 /* ---- PERIOD STATISTICS: the sums and counters of gte_backtest_stats split by MARKET PERIOD.  Every market row
  * carries a small period id (a calendar month, a walk-forward fold, train / embargo / test), and every backtest
