@@ -81,6 +81,12 @@ GTE_MAX_PERIODS = 128
 # gte_reality_check: resamples per slab of the moment sums, and the most resamples of one call
 GTE_BOOT_SLAB = 256
 GTE_BOOT_MAX_RESAMPLES = 65536
+# gte_cscv: the most groups and splits of one call, and the splits a workgroup takes
+GTE_CSCV_MAX_GROUPS = 32
+GTE_CSCV_MAX_SPLITS = 65536
+GTE_CSCV_CHUNK = 256
+#: the period metrics gte_cscv scores by
+CSCV_METRICS = ("mean_reward", "sharpe", "reward_sum")
 
 
 class GteError(RuntimeError):
@@ -261,6 +267,20 @@ class GteRealityCheckOut(C.Structure):
     """struct gte_reality_check_out (include/gte.h): device pointers, kept as integers."""
     _fields_ = [(n, C.c_void_p) for n in ("mean", "boot_sum", "boot_sq_sum", "count_ge", "count_adj", "max_stat",
                                           "max_index", "summary")]
+
+
+#: struct gte_cscv_summary (include/gte.h), in declaration order: one 24-byte record
+CSCV_SUMMARY_DTYPE = [(n, "<i4") for n in ("splits", "valid", "overfit", "loss", "eligible", "reserved")]
+
+
+class GteCscvSummary(C.Structure):
+    """struct gte_cscv_summary (include/gte.h)."""
+    _fields_ = [(n, C.c_int32) for n, _ in CSCV_SUMMARY_DTYPE]
+
+
+class GteCscvOut(C.Structure):
+    """struct gte_cscv_out (include/gte.h): device pointers, kept as integers."""
+    _fields_ = [(n, C.c_void_p) for n in ("best", "is_score", "oos_score", "below", "equal", "ranked", "summary")]
 
 
 #: struct gte_strategy_stats (include/gte.h), in declaration order: one 128-byte record per strategy
@@ -476,6 +496,8 @@ SYMBOLS = {
     "gte_bootstrap_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]),
     "gte_reality_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_void_p,
                                     C.c_void_p, C.c_int32, _P(GteRealityCheckOut)]),
+    "gte_cscv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                           C.c_int32, C.c_int32, _P(GteCscvOut)]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
     "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,

@@ -134,6 +134,9 @@ struct gte_env {
   // gte_reality_check: its scratch (gte_bootstrap.hip), kept the same way
   void* boot_scratch = nullptr;
   size_t boot_bytes = 0;
+  // gte_cscv: its scratch (gte_cscv.hip), kept the same way
+  void* cscv_scratch = nullptr;
+  size_t cscv_bytes = 0;
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -1843,6 +1846,70 @@ int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device,
                                                  benchmark_device, weights_device, n_resamples, *out, E->boot_scratch,
                                                  E->stream);
   if (e != hipSuccess) return fail(GTE_ERR_HIP, "reality check launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_cscv(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
+             const uint64_t* group_masks, int32_t n_groups, const uint32_t* is_groups, const uint32_t* oos_groups,
+             int32_t n_splits, int32_t metric, const gte_cscv_out* out) {
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_n_periods(n_periods, 1));
+  if (n_groups < 2 || n_groups > GTE_CSCV_MAX_GROUPS)
+    return fail(GTE_ERR_INVALID, "n_groups %d outside [2, %d]", n_groups, GTE_CSCV_MAX_GROUPS);
+  if (n_splits < 1 || n_splits > GTE_CSCV_MAX_SPLITS)
+    return fail(GTE_ERR_INVALID, "n_splits %d outside [1, %d]", n_splits, GTE_CSCV_MAX_SPLITS);
+  if (metric != GTE_PERIOD_METRIC_MEAN_REWARD && metric != GTE_PERIOD_METRIC_SHARPE &&
+      metric != GTE_PERIOD_METRIC_REWARD_SUM)
+    return fail(GTE_ERR_INVALID, "metric %d: gte_cscv scores by MEAN_REWARD, SHARPE or REWARD_SUM", metric);
+  if (!stats_device || ((uintptr_t)stats_device & 15))
+    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  if (!group_masks || ((uintptr_t)group_masks & 7))
+    return fail(GTE_ERR_INVALID, "group_masks must be an 8-byte aligned host array");
+  if (!is_groups || !oos_groups || (((uintptr_t)is_groups | (uintptr_t)oos_groups) & 3))
+    return fail(GTE_ERR_INVALID, "is_groups and oos_groups must be 4-byte aligned host arrays");
+  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
+  if (!out->is_score || !out->oos_score || !out->summary ||
+      (((uintptr_t)out->is_score | (uintptr_t)out->oos_score) & 7) || ((uintptr_t)out->summary & 3))
+    return fail(GTE_ERR_INVALID, "out: is_score and oos_score must be 8-byte, summary 4-byte aligned device pointers");
+  if (!out->best || !out->below || !out->equal || !out->ranked ||
+      (((uintptr_t)out->best | (uintptr_t)out->below | (uintptr_t)out->equal | (uintptr_t)out->ranked) & 3))
+    return fail(GTE_ERR_INVALID, "out: best, below, equal and ranked must be 4-byte aligned device pointers");
+  uint64_t seen[2] = {0, 0};
+  for (int g = 0; g < n_groups; ++g) {
+    const uint64_t w0 = group_masks[2 * g], w1 = group_masks[2 * g + 1];
+    if (!(w0 | w1)) return fail(GTE_ERR_INVALID, "group %d is empty", g);
+    for (int b = n_periods; b < 128; ++b)
+      if (((b < 64 ? w0 : w1) >> (b & 63)) & 1)
+        return fail(GTE_ERR_INVALID, "group %d selects period %d, at or above n_periods %d", g, b, n_periods);
+    if ((w0 & seen[0]) | (w1 & seen[1])) return fail(GTE_ERR_INVALID, "group %d shares a period with an earlier group", g);
+    seen[0] |= w0;
+    seen[1] |= w1;
+  }
+  const uint32_t all = n_groups == 32 ? 0xFFFFFFFFu : (1u << n_groups) - 1u;
+  for (int c = 0; c < n_splits; ++c) {
+    const uint32_t a = is_groups[c], b = oos_groups[c];
+    if (!a || !b) return fail(GTE_ERR_INVALID, "split %d has an empty %s side", c, !a ? "in-sample" : "out-of-sample");
+    if ((a | b) & ~all) return fail(GTE_ERR_INVALID, "split %d uses a group at or above n_groups %d", c, n_groups);
+    if (a & b) return fail(GTE_ERR_INVALID, "split %d has a group on both sides", c);
+  }
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_cscv inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const size_t need = gte::cscv_scratch_bytes(n_strategies, n_groups, n_splits);
+  if (E->cscv_bytes < need) {  // (the old one stays until gte_destroy: launches in flight may use it)
+    const size_t bytes = need > 2 * E->cscv_bytes ? need : 2 * E->cscv_bytes;
+    uint8_t* fresh = nullptr;
+    TRY(dev_alloc(E, &fresh, bytes, false));
+    E->cscv_scratch = fresh;
+    E->cscv_bytes = bytes;
+  }
+  // the three tables packed as gte_launch.h lays them out, so that one copy stages them
+  std::vector<uint8_t> tables(gte::cscv_table_bytes(n_groups, n_splits));
+  memcpy(tables.data(), group_masks, 16 * (size_t)n_groups);
+  memcpy(tables.data() + 16 * (size_t)n_groups, is_groups, 4 * (size_t)n_splits);
+  memcpy(tables.data() + 16 * (size_t)n_groups + 4 * (size_t)n_splits, oos_groups, 4 * (size_t)n_splits);
+  const hipError_t e = gte::launch_cscv(stats_device, n_strategies, n_periods, tables.data(), n_groups, n_splits,
+                                        metric, *out, E->cscv_scratch, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "cscv launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
 

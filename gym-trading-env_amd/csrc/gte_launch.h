@@ -255,6 +255,17 @@ hipError_t launch_reality_check(const gte_strategy_period_stats* stats, int n_st
                                 int n_resamples, const gte_reality_check_out& out, void* scratch,
                                 hipStream_t stream);
 
+// --- gte_cscv.hip: the probability of backtest overfitting (gte_cscv, include/gte.h); the caller has checked
+// alignments and the three tables
+// bytes of library-owned scratch one call with S strategies, G groups and C splits needs
+size_t cscv_scratch_bytes(int n_strategies, int n_groups, int n_splits);
+// bytes of the packed host tables: group_masks (G * 2 words), then is_groups (C words), then oos_groups (C words)
+size_t cscv_table_bytes(int n_groups, int n_splits);
+// the copy of the packed tables (host, read before this returns) and the six launches
+hipError_t launch_cscv(const gte_strategy_period_stats* stats, int n_strategies, int n_periods, const void* tables,
+                       int n_groups, int n_splits, int metric, const gte_cscv_out& out, void* scratch,
+                       hipStream_t stream);
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

@@ -179,3 +179,16 @@ class StrategyPeriodStats(StrategyRecords):
         from . import reality_check
         return reality_check.run(self, periods, n_resamples, block, seed, benchmark, weights)
 
+
+    def cscv(self, periods=None, groups=None, metric="sharpe", splits=None):
+        """The probability of backtest overfitting of this leaderboard by combinatorially symmetric
+        cross-validation over `periods`, on the device (`gte_cscv`): across every split of the period groups into
+        an in-sample and an out-of-sample half, how often does the in-sample winner land in the lower half out of
+        sample?  An `OverfitCheck`.  `groups`: an int G (the selected periods cut into G contiguous groups,
+        `periods.cscv_groups`), a uint64 table [G, 2] of group masks (then `periods` is not used), or None for the
+        largest even G <= min(selected periods, 16).  `splits=(is_groups, oos_groups)`, two uint32 arrays [C] with
+        bit g = group g, overrides the generated table of all G/2-subsets (`periods.cscv_splits`) — purged splits,
+        a walk-forward scheme.  `metric`: "sharpe", "mean_reward" or "reward_sum".  A strategy counts only if it
+        stepped in every group and all its group sums are finite.  Nothing here waits for the device."""
+        from . import overfit
+        return overfit.run(self, periods, groups, metric, splits)

@@ -1,13 +1,17 @@
 """Period rows for `BatchedTradingEnv.track_periods`: one small integer per market row that says which period
 the row belongs to — equal blocks, train / embargo / test splits, calendar periods of a DatetimeIndex.  Host-side
-NumPy; every function but the last returns an int8 array [T] with ids 0 .. B-1 and -1 for rows that count nowhere.
-`bootstrap_weights` makes the resampling table of a bootstrap over periods, on the device."""
+NumPy; the first three functions return an int8 array [T] with ids 0 .. B-1 and -1 for rows that count nowhere.
+`bootstrap_weights` makes the resampling table of a bootstrap over periods, on the device; `cscv_groups` and
+`cscv_splits` make the group and split tables of `StrategyPeriodStats.cscv`."""
 from __future__ import annotations
 
 import numpy as np
 
 #: what libgte keeps per env (GTE_MAX_PERIODS, include/gte.h)
 MAX_PERIODS = 128
+#: the most groups and splits of one `gte_cscv` call (GTE_CSCV_MAX_GROUPS, GTE_CSCV_MAX_SPLITS)
+CSCV_MAX_GROUPS = 32
+CSCV_MAX_SPLITS = 65536
 
 
 def _checked(ids: np.ndarray) -> np.ndarray:
@@ -69,3 +73,41 @@ def bootstrap_weights(env, n, n_resamples, block=1.0, seed=0):
     `StrategyPeriodStats.reality_check` uses unless it is given `weights=`."""
     from .reality_check import bootstrap_weights as make
     return make(env, n, n_resamples, block, seed)
+
+
+def cscv_groups(ids, n_groups) -> np.ndarray:
+    """The period ids, taken in ascending order, cut into `n_groups` contiguous groups of (almost) equal size, the
+    first ``len(ids) % n_groups`` one longer: a uint64 table [n_groups, 2], row g the mask of group g (bit b % 64 of
+    word b // 64 = period b), as `gte_cscv` takes it."""
+    ids = sorted({int(b) for b in ids})
+    G = int(n_groups)
+    if ids and not 0 <= ids[0] <= ids[-1] < MAX_PERIODS:
+        raise ValueError(f"period ids must lie in [0, {MAX_PERIODS})")
+    if not 2 <= G <= min(len(ids), CSCV_MAX_GROUPS):
+        raise ValueError(f"cscv_groups: {G} groups of {len(ids)} periods: 2 <= n_groups <= min(periods, "
+                         f"{CSCV_MAX_GROUPS}) required")
+    size, longer = divmod(len(ids), G)
+    words = [[0, 0] for _ in range(G)]
+    at = 0
+    for g in range(G):
+        for b in ids[at:at + size + (g < longer)]:
+            words[g][b >> 6] |= 1 << (b & 63)
+        at += size + (g < longer)
+    return np.array(words, dtype=np.uint64)
+
+
+def cscv_splits(n_groups):
+    """Every way of taking half of `n_groups` groups as in-sample, in lexicographic order of the chosen groups, the
+    other half out-of-sample: ``(is_groups, oos_groups)``, two uint32 arrays [C], C = C(G, G/2), bit g = group g.
+    Split c and split C - 1 - c are mirror images.  G must be even; G >= 20 has more than 65 536 splits and is
+    refused."""
+    from itertools import combinations
+    from math import comb
+    G = int(n_groups)
+    if G < 2 or G % 2 or G > CSCV_MAX_GROUPS:
+        raise ValueError(f"cscv_splits: n_groups must be even and lie in [2, {CSCV_MAX_GROUPS}], not {n_groups}")
+    if comb(G, G // 2) > CSCV_MAX_SPLITS:
+        raise ValueError(f"cscv_splits: {G} groups have {comb(G, G // 2)} splits, more than {CSCV_MAX_SPLITS}")
+    every = (1 << G) - 1
+    is_groups = np.array([sum(1 << g for g in pick) for pick in combinations(range(G), G // 2)], dtype=np.uint32)
+    return is_groups, (np.uint32(every) & ~is_groups).astype(np.uint32)

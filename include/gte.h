@@ -1298,6 +1298,75 @@ int gte_reality_check(gte_env* env, const gte_strategy_period_stats* stats_devic
                       const double* benchmark_device /* [n_periods] or NULL */, const double* weights_device,
                       int32_t n_resamples, const gte_reality_check_out* out);
 
+/* ---- PROBABILITY OF BACKTEST OVERFITTING by combinatorially symmetric cross-validation, CSCV (Bailey, Borwein,
+ * Lopez de Prado, Zhu 2017): how much does picking the best of S strategies overfit?  The periods are cut into G
+ * groups; every split takes some groups as in-sample (IS) and others as out-of-sample (OOS), picks the IS winner
+ * and looks where that winner ranks OOS among all strategies, from the [S, B] gte_strategy_period_stats on the
+ * device.  The [C, S] matrices of scores are never written.  One fixed order of IEEE f64 operations, every one of
+ * them ONE operation as written (no fused multiply-add): the same inputs give the same bits for any launch
+ * geometry.
+ *
+ * GROUPS.  group_masks: HOST uint64 [n_groups][2]; group g is the set of periods whose bit is set in
+ * group_masks[g] (bit b % 64 of word b / 64, as period_mask).  Groups are non-empty and pairwise disjoint;
+ * 2 <= n_groups <= GTE_CSCV_MAX_GROUPS.  Per strategy and group, over the group's periods b ascending:
+ *     a1 = 0.0; a1 = a1 + reward_sum_b;     a2 = 0.0; a2 = a2 + reward_sq_sum_b;     n_g = the sum of steps_b (int64)
+ * Of a record only these three fields are read, and only for periods in some group.  Strategy s is ELIGIBLE iff
+ * for every group n_g > 0 and a1, a2 are finite.
+ * THE SCORE of a strategy over a set Q of groups, over g in Q ascending:
+ *     s1 = 0.0; s1 = s1 + a1_g;     s2 = 0.0; s2 = s2 + a2_g;     n = the sum of n_g (int64)
+ * and then the GTE_PERIOD_METRIC_MEAN_REWARD, _SHARPE or _REWARD_SUM formulas of gte_rank_period_stats on
+ * (s1, s2, n), exactly as written there; the other three period metrics are refused.  When every group is a
+ * single period this is bit for bit the score gte_rank_period_stats gives for the same periods.
+ * SPLITS.  is_groups, oos_groups: HOST uint32 [n_splits]; split c has IS = the groups whose bit is set in
+ * is_groups[c] and OOS = those of oos_groups[c].  Both are non-empty, disjoint, and use no bit at or above
+ * n_groups; groups in neither are allowed (purging, an embargo).  1 <= n_splits <= GTE_CSCV_MAX_SPLITS.
+ * WRITTEN (all of every array, C = n_splits), IS_cs and OOS_cs being the scores of strategy s over the two sides:
+ *     best[c]       m = -inf; over eligible s ascending: if (IS_cs > m) { m = IS_cs; best = s; }; -1 when none
+ *                   compared greater (a NaN never wins; of equal scores the lowest index)
+ *     is_score[c]   m; NaN when best is -1
+ *     oos_score[c]  OOS_cs of s = best; NaN when best is -1
+ *     ranked[c]     the number of eligible s whose OOS_cs is not NaN
+ *     below[c]      the number of those with OOS_cs < oos_score[c]
+ *     equal[c]      the number of those with OOS_cs == oos_score[c], the winner included
+ *                   A split is VALID iff best >= 0 and oos_score[c] is not NaN; an invalid one has below = equal = 0.
+ *     summary       splits = C; valid = the number of valid splits; overfit = the number of valid splits with
+ *                   2 * below + equal <= ranked, which is the winner's mid-rank relative rank
+ *                   w = (below + (equal + 1) / 2) / (ranked + 1) being at most 1/2, as an integer comparison;
+ *                   loss = the number of valid splits with oos_score < 0.0; eligible = the number of eligible
+ *                   strategies
+ * The probability of backtest overfitting is overfit / valid, the probability of an out-of-sample loss
+ * loss / valid.
+ * The three host tables are checked and copied by the call: they are the caller's again when it returns.  Six
+ * launches on the env's stream after that copy (fold, IS/OOS pass, winners, rank pass, close, summary), no
+ * atomics, no host synchronisation beyond what the copy of the tables needs; the group sums [G][S] and the
+ * partial results [tiles][C] live in library-owned scratch, allocated by the first call and again when a call
+ * outgrows it (as gte_reality_check keeps its own).  A workgroup takes GTE_CSCV_CHUNK splits.  The inputs are only
+ * read; the outputs must not overlap them or each other.
+ *
+ * GTE_ERR_INVALID, with nothing launched and nothing written, for: a NULL env or pointer, or one not aligned for
+ * its type (stats_device: 16 bytes); n_strategies < 1; n_periods outside [1, GTE_MAX_PERIODS]; n_groups or
+ * n_splits outside their ranges; a metric other than the three; an empty group, one with a bit at or above
+ * n_periods, one that shares a period with an earlier group; a split with an empty side, a bit at or above
+ * n_groups, or a group on both sides — the message names the first offending group or split.  GTE_ERR_STATE
+ * inside a stream capture. */
+#define GTE_CSCV_MAX_GROUPS 32
+#define GTE_CSCV_MAX_SPLITS 65536
+#define GTE_CSCV_CHUNK 256
+typedef struct gte_cscv_summary {            /* 24 bytes */
+  int32_t splits, valid, overfit, loss, eligible;
+  int32_t reserved;        /* written as zero */
+} gte_cscv_summary;
+typedef struct gte_cscv_out {                /* DEVICE pointers, all required */
+  int32_t *best;                             /* i32 [n_splits] */
+  double  *is_score, *oos_score;             /* f64 [n_splits] */
+  int32_t *below, *equal, *ranked;           /* i32 [n_splits] */
+  gte_cscv_summary* summary;                 /* one record */
+} gte_cscv_out;
+int gte_cscv(gte_env* env, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
+             const uint64_t* group_masks /* HOST [n_groups][2] */, int32_t n_groups,
+             const uint32_t* is_groups /* HOST [n_splits] */, const uint32_t* oos_groups /* HOST [n_splits] */,
+             int32_t n_splits, int32_t metric, const gte_cscv_out* out);
+
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
 /* Same-step auto-reset with gte_config.final_obs: struct-of-arrays snapshot (device pointers,
