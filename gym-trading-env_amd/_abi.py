@@ -283,6 +283,21 @@ class GteCscvOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("best", "is_score", "oos_score", "below", "equal", "ranked", "summary")]
 
 
+#: struct gte_diversify_summary (include/gte.h), in declaration order: one 20-byte record
+DIVERSIFY_SUMMARY_DTYPE = [(n, "<i4") for n in ("picked", "candidates", "eligible", "remaining", "reserved")]
+
+
+class GteDiversifySummary(C.Structure):
+    """struct gte_diversify_summary (include/gte.h)."""
+    _fields_ = [(n, C.c_int32) for n, _ in DIVERSIFY_SUMMARY_DTYPE]
+
+
+class GteDiversifyOut(C.Structure):
+    """struct gte_diversify_out (include/gte.h): device pointers, kept as integers."""
+    _fields_ = [(n, C.c_void_p) for n in ("pick", "pick_score", "cluster_size", "owner", "owner_corr", "pick_corr",
+                                          "summary")]
+
+
 #: struct gte_strategy_stats (include/gte.h), in declaration order: one 128-byte record per strategy
 STRATEGY_FIELDS = [("steps", "<i8")] + \
     [(n, "<f8") for n in ("reward_sum", "reward_sq_sum", "ep_return_sum", "ep_return_sq_sum", "max_drawdown",
@@ -498,6 +513,8 @@ SYMBOLS = {
                                     C.c_void_p, C.c_int32, _P(GteRealityCheckOut)]),
     "gte_cscv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                            C.c_int32, C.c_int32, _P(GteCscvOut)]),
+    "gte_diversify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_void_p, C.c_double,
+                                C.c_int32, _P(GteDiversifyOut)]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
     "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,

@@ -137,6 +137,9 @@ struct gte_env {
   // gte_cscv: its scratch (gte_cscv.hip), kept the same way
   void* cscv_scratch = nullptr;
   size_t cscv_bytes = 0;
+  // gte_diversify: its scratch (gte_diversify.hip), kept the same way
+  void* div_scratch = nullptr;
+  size_t div_bytes = 0;
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -1910,6 +1913,48 @@ int gte_cscv(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t 
   const hipError_t e = gte::launch_cscv(stats_device, n_strategies, n_periods, tables.data(), n_groups, n_splits,
                                         metric, *out, E->cscv_scratch, E->stream);
   if (e != hipSuccess) return fail(GTE_ERR_HIP, "cscv launch: %s", hipGetErrorString(e));
+  return GTE_OK;
+}
+
+int gte_diversify(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
+                  const uint64_t period_mask[2], const double* scores_device, double max_corr, int32_t k,
+                  const gte_diversify_out* out) {
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_n_periods(n_periods, 1));
+  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
+  TRY(check_period_mask(period_mask));
+  int n = 0;
+  for (int b = 0; b < 128; ++b) {
+    if (!((period_mask[b >> 6] >> (b & 63)) & 1)) continue;
+    if (b >= n_periods) return fail(GTE_ERR_INVALID, "period_mask selects period %d, at or above n_periods %d", b, n_periods);
+    ++n;
+  }
+  if (n < 3) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: a correlation needs at least three", n);
+  if (max_corr != max_corr) return fail(GTE_ERR_INVALID, "max_corr is NaN");
+  if (!stats_device || ((uintptr_t)stats_device & 15))
+    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  if (!scores_device || ((uintptr_t)scores_device & 7))
+    return fail(GTE_ERR_INVALID, "scores_device must be an 8-byte aligned device array");
+  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
+  if (!out->pick_score || !out->owner_corr || !out->pick_corr ||
+      (((uintptr_t)out->pick_score | (uintptr_t)out->owner_corr | (uintptr_t)out->pick_corr) & 7))
+    return fail(GTE_ERR_INVALID, "out: pick_score, owner_corr and pick_corr must be 8-byte aligned device pointers");
+  if (!out->pick || !out->cluster_size || !out->owner || !out->summary ||
+      (((uintptr_t)out->pick | (uintptr_t)out->cluster_size | (uintptr_t)out->owner | (uintptr_t)out->summary) & 3))
+    return fail(GTE_ERR_INVALID, "out: pick, cluster_size, owner and summary must be 4-byte aligned device pointers");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_diversify inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const size_t need = gte::diversify_scratch_bytes(n_strategies, n, k);
+  if (E->div_bytes < need) {  // (the old one stays until gte_destroy: launches in flight may use it)
+    const size_t bytes = need > 2 * E->div_bytes ? need : 2 * E->div_bytes;
+    uint8_t* fresh = nullptr;
+    TRY(dev_alloc(E, &fresh, bytes, false));
+    E->div_scratch = fresh;
+    E->div_bytes = bytes;
+  }
+  const hipError_t e = gte::launch_diversify(stats_device, n_strategies, n_periods, period_mask, n, scores_device,
+                                             max_corr, k, *out, E->div_scratch, E->stream);
+  if (e != hipSuccess) return fail(GTE_ERR_HIP, "diversify launch: %s", hipGetErrorString(e));
   return GTE_OK;
 }
 

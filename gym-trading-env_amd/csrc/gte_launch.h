@@ -266,6 +266,15 @@ hipError_t launch_cscv(const gte_strategy_period_stats* stats, int n_strategies,
                        int n_groups, int n_splits, int metric, const gte_cscv_out& out, void* scratch,
                        hipStream_t stream);
 
+// --- gte_diversify.hip: the decorrelated leaderboard (gte_diversify, include/gte.h); the caller has checked
+// alignments and the mask
+// bytes of library-owned scratch one call with S strategies, n selected periods and k rounds needs
+size_t diversify_scratch_bytes(int n_strategies, int n, int k);
+// prepare, k rounds and close (period_mask: host, two words, n bits set, none at or above n_periods)
+hipError_t launch_diversify(const gte_strategy_period_stats* stats, int n_strategies, int n_periods,
+                            const uint64_t period_mask[2], int n, const double* scores, double max_corr, int k,
+                            const gte_diversify_out& out, void* scratch, hipStream_t stream);
+
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,
                       const int64_t* cursor, int L, const LogArrays& o, const uint8_t* mask, hipStream_t stream);

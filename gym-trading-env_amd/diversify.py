@@ -1,0 +1,130 @@
+"""Diversified — what `StrategyPeriodStats.diversified()` gives: a decorrelated leaderboard picked greedily on the
+device from the [S, B] period records (`gte_diversify`, include/gte.h).  The best strategy by score, everything whose
+period returns correlate with it above `max_corr` dropped, the best of what is left, and so on: the picks are a
+shortlist of different bets, what a pick dropped is its cluster, and once nothing is left the number of picks is the
+number of independent strategies the sweep held at that threshold."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from .strategy_records import mask_words
+
+
+class Diversified:
+    """The result of `StrategyPeriodStats.diversified()`.
+
+    Device tensors, none of which waits: ``picks`` int32 [k] (the strategy picked in every round, -1 from the round
+    on in which no candidate was left), ``scores`` f64 [k] (its score, NaN beside a -1), ``cluster_size`` int32 [k]
+    (how many candidates the round removed, the pick included), ``owner`` int32 [S] (the round that removed each
+    strategy; -1 for a candidate no round removed, -2 for a strategy that was no candidate: not stepped in every
+    correlation period, a period return that is not finite, a constant row, or a NaN score), ``owner_corr`` f64 [S]
+    (its correlation with the pick that removed it, NaN where ``owner`` < 0) and ``corr`` f64 [k, k] (the correlations
+    of the picks with one another, NaN beside a -1).
+
+    ``num_picked``, ``num_candidates``, ``num_eligible`` and ``remaining`` (the candidates still there after the
+    last round) are read from the device's summary record: these wait for the device, once.  ``exhausted`` is
+    ``remaining == 0``; ``effective_trials`` is then ``num_picked``, the number of clusters at this threshold, and
+    None while candidates remain.  ``k``, ``max_corr`` and ``corr_periods`` (the period ids the correlations are
+    taken over) describe the call."""
+
+    def __init__(self, env, k, max_corr, corr_periods, out, keep):
+        self._env, self._keep = env, keep   # every tensor the launches read, alive with the result
+        self.k, self.max_corr, self.corr_periods = int(k), float(max_corr), list(corr_periods)
+        self.picks, self.scores, self.cluster_size = out["pick"], out["pick_score"], out["cluster_size"]
+        self.owner, self.owner_corr = out["owner"], out["owner_corr"]
+        self.corr = out["pick_corr"].view(self.k, self.k)
+        self._summary_dev, self._summary = out["summary"], None
+
+    def _read(self):
+        if self._summary is None:
+            raw = self._summary_dev.cpu().numpy()
+            self._summary = raw.view(np.dtype(_abi.DIVERSIFY_SUMMARY_DTYPE))[0]
+        return self._summary
+
+    @property
+    def num_picked(self) -> int:
+        return int(self._read()["picked"])
+
+    @property
+    def num_candidates(self) -> int:
+        return int(self._read()["candidates"])
+
+    @property
+    def num_eligible(self) -> int:
+        return int(self._read()["eligible"])
+
+    @property
+    def remaining(self) -> int:
+        return int(self._read()["remaining"])
+
+    @property
+    def exhausted(self) -> bool:
+        return self.remaining == 0
+
+    @property
+    def effective_trials(self):
+        """`num_picked` once every candidate belongs to a cluster, else None: with candidates left the count is
+        only a lower bound."""
+        return self.num_picked if self.exhausted else None
+
+    def members(self, r):
+        """The strategies round `r` removed — the pick and what correlated with it above `max_corr` — as an int64
+        index tensor on the device, ascending."""
+        if isinstance(r, bool) or int(r) != r or not 0 <= int(r) < self.k:
+            raise IndexError(f"round {r} outside [0, {self.k})")
+        return (self.owner == int(r)).nonzero().flatten()
+
+    def numpy(self) -> dict:
+        """Everything on the host: the arrays above by name, and the summary's scalars."""
+        out = {k: getattr(self, k).cpu().numpy() for k in ("picks", "scores", "cluster_size", "owner", "owner_corr",
+                                                           "corr")}
+        out.update(num_picked=self.num_picked, num_candidates=self.num_candidates, num_eligible=self.num_eligible,
+                   remaining=self.remaining, exhausted=self.exhausted, effective_trials=self.effective_trials,
+                   k=self.k, max_corr=self.max_corr, corr_periods=list(self.corr_periods))
+        return out
+
+
+def run(owner, k, metric="sharpe", periods=None, max_corr=0.7, min_steps=1, corr_periods=None, scores=None) -> Diversified:
+    """`StrategyPeriodStats.diversified`: stage the arguments, enqueue the launches, wait for nothing."""
+    env, torch = owner._env, owner._env._torch
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.GTE_RANK_MAX:
+        raise ValueError(f"k must lie in [1, {_abi.GTE_RANK_MAX}]")
+    k = int(k)
+    max_corr = float(max_corr)
+    if max_corr != max_corr:
+        raise ValueError("max_corr must not be NaN")
+    mask = owner._mask(periods if corr_periods is None else corr_periods)
+    ids = [int(b) for b in np.flatnonzero(mask)]
+    if len(ids) < 3:
+        raise ValueError("a correlation needs at least three selected periods")
+    dev = owner._records.device
+    S, B = owner.num_strategies, owner.num_periods
+    if scores is None:
+        pooled = owner._mask(periods)
+        scores = owner.score(metric, pooled)
+        steps = owner.steps[:, [int(b) for b in np.flatnonzero(pooled)]].sum(dim=1)
+        scores = torch.where(steps >= max(1, int(min_steps)), scores, torch.full_like(scores, float("nan")))
+    else:
+        if not hasattr(scores, "is_cuda"):
+            scores = torch.from_numpy(np.ascontiguousarray(np.asarray(scores, dtype=np.float64)))
+        scores = scores.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(scores.shape) != (S,):
+            raise ValueError(f"scores must have shape ({S},), not {tuple(scores.shape)}")
+    with torch.cuda.device(dev):
+        out = dict(pick=torch.empty((k,), dtype=torch.int32, device=dev),
+                   pick_score=torch.empty((k,), dtype=torch.float64, device=dev),
+                   cluster_size=torch.empty((k,), dtype=torch.int32, device=dev),
+                   owner=torch.empty((S,), dtype=torch.int32, device=dev),
+                   owner_corr=torch.empty((S,), dtype=torch.float64, device=dev),
+                   pick_corr=torch.empty((k * k,), dtype=torch.float64, device=dev),
+                   summary=torch.empty((C.sizeof(_abi.GteDiversifySummary),), dtype=torch.uint8, device=dev))
+    # (the env launches on torch's current stream as it was when the env was made: the tensors made above are
+    # ordered with the launches, as in StrategyStats)
+    ptrs = _abi.GteDiversifyOut(**{name: v.data_ptr() for name, v in out.items()})
+    _abi.check(env._lib, env._lib.gte_diversify(
+        env._h, C.c_void_p(owner._records.data_ptr()), S, B, mask_words(mask), C.c_void_p(scores.data_ptr()), max_corr, k,
+        C.byref(ptrs)))
+    return Diversified(env, k, max_corr, ids, out, (owner, scores))

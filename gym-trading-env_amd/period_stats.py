@@ -192,3 +192,18 @@ class StrategyPeriodStats(StrategyRecords):
         stepped in every group and all its group sums are finite.  Nothing here waits for the device."""
         from . import overfit
         return overfit.run(self, periods, groups, metric, splits)
+
+    def diversified(self, k, metric="sharpe", periods=None, max_corr=0.7, min_steps=1, corr_periods=None, scores=None):
+        """A decorrelated leaderboard of at most `k` strategies, picked greedily on the device (`gte_diversify`):
+        the best strategy, everything whose period returns correlate with it above `max_corr` dropped, the best of
+        what is left, and so on.  A `Diversified`: the picks, the size of the cluster each one removed, which pick
+        removed every strategy, and — once no candidate is left — the number of independent strategies the sweep
+        held at this threshold.  The score is `score(metric, periods)`, with NaN for a strategy with fewer than
+        max(1, `min_steps`) transitions in `periods`: the candidates are the strategies `top()` ranks, less those
+        that did not step in every correlation period or whose period returns there are constant or not finite.
+        `scores` (NumPy or torch, f64 [S]; NaN = no candidate) overrides the metric — a trade metric, a negated
+        p-value.  The correlations are taken over `corr_periods` (default: `periods`), at least three.  The signed
+        correlation decides: a mirror strategy hedges the pick and stays.  The default `max_corr` of 0.7 is a
+        convention, not a finding; `effective_trials` moves with it.  Nothing here waits for the device."""
+        from . import diversify
+        return diversify.run(self, k, metric, periods, max_corr, min_steps, corr_periods, scores)

@@ -1367,6 +1367,73 @@ int gte_cscv(gte_env* env, const gte_strategy_period_stats* stats_device, int32_
              const uint32_t* is_groups /* HOST [n_splits] */, const uint32_t* oos_groups /* HOST [n_splits] */,
              int32_t n_splits, int32_t metric, const gte_cscv_out* out);
 
+/* ---- A DECORRELATED LEADERBOARD, PICKED GREEDILY: the best k of a sweep are usually k parameterisations of one
+ * bet.  Take the best strategy by the caller's scores, drop every strategy whose period returns correlate with it
+ * above max_corr, take the best of what is left, and so on for k rounds, from the [S, B] gte_strategy_period_stats
+ * on the device.  The picks are a diversified shortlist, what a pick dropped is its cluster, and when nothing is
+ * left the number of picks is the number of independent strategies the sweep held at that threshold.  No [S, S]
+ * matrix is written.  One fixed order of IEEE f64 operations, every one of them ONE operation as written (no fused
+ * multiply-add), sqrt and division correctly rounded: the same inputs give the same bits for any launch geometry.
+ *
+ * PERIODS AND ELIGIBILITY.  P = p_0 < ... < p_{n-1}, the periods whose bit is set in period_mask (bit b % 64 of word
+ * b / 64; HOST uint64 [2]), 3 <= n <= GTE_MAX_PERIODS.  Strategy s is ELIGIBLE iff for every b in P steps_b > 0 and
+ * reward_sum_b is finite (the rule of gte_reality_check), and its q below is finite and q > 0.0 (a constant row has no
+ * correlation).  Of a record only steps and reward_sum are read, and only for b in P.
+ * THE STANDARDISED ROW of an eligible strategy, x_i = reward_sum[s][p_i]:
+ *     t = 0.0; over i ascending: t = t + x_i;              m = t / (double)n
+ *     e_i = x_i - m
+ *     q = 0.0; over i ascending: q = q + e_i * e_i;        norm = sqrt(q)
+ *     u_i = e_i / norm
+ * THE CORRELATION of s with j:   c = 0.0; over i ascending: c = c + u_i[s] * u_i[j]
+ * CANDIDATES.  scores_device: DEVICE f64 [S], any score vector of the caller's (the scores_device of a gte_rank_*
+ * call, a negated p-value).  s is a CANDIDATE iff it is eligible and scores_device[s] is not NaN; +-inf are values
+ * like any other.
+ * THE GREEDY ROUNDS, r = 0 .. k-1, 1 <= k <= GTE_RANK_MAX.  All candidates start LIVE.
+ *     pick[r]       the live candidate with the highest score; equal scores go to the lowest index (-0.0 == 0.0, by
+ *                   comparison, as gte_rank_strategies orders).  With no candidate live: pick[r] = -1,
+ *                   pick_score[r] = NaN, cluster_size[r] = 0, and the same for every later round
+ *     otherwise, for every live s: c_s = the correlation of s with pick[r]; s LEAVES the live set iff s == pick[r]
+ *                   or c_s > max_corr (a NaN compares false and stays); then owner[s] = r and owner_corr[s] = c_s —
+ *                   for the pick itself too, whose owner_corr is the formula's own value, not a literal 1.0
+ *     cluster_size[r]   the number that left in round r
+ * WRITTEN (all of every array):
+ *     pick i32 [k], pick_score f64 [k] (scores_device[pick[r]] as it stands), cluster_size i32 [k]
+ *     owner i32 [S]       the round that claimed s; -1 for a candidate still live after k rounds; -2 for a strategy
+ *                         that is no candidate
+ *     owner_corr f64 [S]  NaN where owner < 0
+ *     pick_corr f64 [k][k]   the correlation of pick[a] with pick[b] by the formula above, for both orders (a
+ *                         multiplication commutes: the matrix is symmetric to the bit); NaN where either pick is -1
+ *     summary             picked = the number of rounds with a pick; candidates, eligible = the numbers of such
+ *                         strategies; remaining = the candidates still live after the last round; reserved = 0.
+ *                         remaining == 0: picked is the number of clusters at this threshold
+ * max_corr is any value but NaN: above 1 a round drops its pick alone, -inf makes round 0 take every candidate.
+ * k + 2 launches on the env's stream (prepare, one per round, close); the pick of a round never visits the host.  No
+ * atomics, no host synchronisation; the staging array u[n][S], the live bytes, two lists of the workgroups' best
+ * remaining candidates and the workgroups' counts live in library-owned scratch, allocated by the first call and
+ * again when a call outgrows it (as gte_reality_check keeps its own).  The inputs are only read; the outputs must not
+ * overlap them or each other.
+ *
+ * GTE_ERR_INVALID, with nothing launched and nothing written, for: a NULL env or pointer, or one not aligned for its
+ * type (stats_device: 16 bytes; f64: 8; i32 and the summary: 4); n_strategies < 1; n_periods outside
+ * [1, GTE_MAX_PERIODS]; k outside [1, GTE_RANK_MAX]; a mask with fewer than three bits set, or a bit at or above
+ * n_periods; a NaN max_corr.  GTE_ERR_STATE inside a stream capture. */
+typedef struct gte_diversify_summary {       /* 20 bytes */
+  int32_t picked, candidates, eligible, remaining;
+  int32_t reserved;        /* written as zero */
+} gte_diversify_summary;
+typedef struct gte_diversify_out {           /* DEVICE pointers, all required */
+  int32_t *pick;                             /* i32 [k] */
+  double  *pick_score;                       /* f64 [k] */
+  int32_t *cluster_size;                     /* i32 [k] */
+  int32_t *owner;                            /* i32 [n_strategies] */
+  double  *owner_corr;                       /* f64 [n_strategies] */
+  double  *pick_corr;                        /* f64 [k * k] */
+  gte_diversify_summary* summary;            /* one record */
+} gte_diversify_out;
+int gte_diversify(gte_env* env, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                  int32_t n_periods, const uint64_t period_mask[2], const double* scores_device /* [n_strategies] */,
+                  double max_corr, int32_t k, const gte_diversify_out* out);
+
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
 /* Same-step auto-reset with gte_config.final_obs: struct-of-arrays snapshot (device pointers,
