@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <utility>
@@ -49,6 +50,9 @@ static int fail(int code, const char* fmt, ...) {
       return fail(e_ == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP,          \
                   "%s failed: %s", #expr, hipGetErrorString(e_));                 \
   } while (0)
+
+// a library-owned device block that only grows: grow(), below, with the leaderboard analyses' checks
+struct Scratch { void* base = nullptr; size_t bytes = 0; };
 
 struct gte_env {
   gte_config cfg;
@@ -131,15 +135,9 @@ struct gte_env {
   double* rank_score[2] = {nullptr, nullptr};
   int32_t* rank_index[2] = {nullptr, nullptr};
   int64_t rank_entries[2] = {0, 0};
-  // gte_reality_check: its scratch (gte_bootstrap.hip), kept the same way
-  void* boot_scratch = nullptr;
-  size_t boot_bytes = 0;
-  // gte_cscv: its scratch (gte_cscv.hip), kept the same way
-  void* cscv_scratch = nullptr;
-  size_t cscv_bytes = 0;
-  // gte_diversify: its scratch (gte_diversify.hip), kept the same way
-  void* div_scratch = nullptr;
-  size_t div_bytes = 0;
+  // gte_reality_check, gte_cscv, gte_diversify: the scratch of each (gte_bootstrap.hip, gte_cscv.hip,
+  // gte_diversify.hip), a block of its own that grow() keeps the same way
+  Scratch boot_scratch, cscv_scratch, div_scratch;
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -1209,8 +1207,11 @@ static bool spans_overlap(const RowSpan& r, const RowSpan& w, int64_t T16) {
 }
 
 // ---- what the reductions, rankings and reads of the per-env record families share: each family's entry
-// points run these in the order they always refused in, `who` being the entry point for the message ----
-// the head of every gte_reduce_* / gte_rank_* call and of gte_reality_check
+// points run these in the order they always refused in, `who` being the entry point for the message.  The
+// leaderboard analyses of the [S, B] period records (gte_reality_check, gte_cscv, gte_diversify) take from here
+// as well what they share: the stats and resample checks, the walk over a period mask, the test of a list of
+// output pointers, the scratch each of them keeps and the tail after their launches ----
+// the head of every gte_reduce_* / gte_rank_* call and of the three analyses
 static int check_strategies(const gte_env* E, int32_t n_strategies) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
@@ -1224,6 +1225,55 @@ static int check_n_periods(int32_t n_periods, int lo) {
 
 static int check_period_mask(const uint64_t* period_mask) {
   return period_mask ? GTE_OK : fail(GTE_ERR_INVALID, "period_mask is NULL");
+}
+
+// n = the periods the two words select; a bit at or above n_periods is refused (how few are too few, and the
+// words for it, is the caller's)
+static int count_periods(const uint64_t* period_mask, int32_t n_periods, int* n) {
+  *n = 0;
+  for (int b = 0; b < 128; ++b) {
+    if (!((period_mask[b >> 6] >> (b & 63)) & 1)) continue;
+    if (b >= n_periods) return fail(GTE_ERR_INVALID, "period_mask selects period %d, at or above n_periods %d", b, n_periods);
+    ++*n;
+  }
+  return GTE_OK;
+}
+
+static int check_stats(const void* stats) {
+  if (stats && !((uintptr_t)stats & 15)) return GTE_OK;
+  return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+}
+
+static int check_n_resamples(int32_t n_resamples) {
+  if (n_resamples >= 1 && n_resamples <= GTE_BOOT_MAX_RESAMPLES) return GTE_OK;
+  return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
+}
+
+// every pointer of the list set, and none with a bit of `low_bits` (alignment less one) in its address
+static bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t low_bits) {
+  uintptr_t address_bits = 0;
+  for (const void* p : ptrs) {
+    if (!p) return false;
+    address_bits |= (uintptr_t)p;
+  }
+  return !(address_bits & low_bits);
+}
+
+// at least `need` bytes behind s->base: too small a block gives way to one of max(need, 2 * have) bytes (the old
+// one stays until gte_destroy: launches in flight may use it)
+static int grow(gte_env* E, Scratch* s, size_t need) {
+  if (s->bytes >= need) return GTE_OK;
+  const size_t bytes = need > 2 * s->bytes ? need : 2 * s->bytes;
+  uint8_t* fresh = nullptr;
+  TRY(dev_alloc(E, &fresh, bytes, false));
+  s->base = fresh;
+  s->bytes = bytes;
+  return GTE_OK;
+}
+
+// what an analysis returns once its launches are enqueued, `what` naming it
+static int launched(hipError_t e, const char* what) {
+  return e == hipSuccess ? GTE_OK : fail(GTE_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
 }
 
 static int check_reduce_args(gte_env* E, const char* who, const void* records, const int32_t* group_offsets,
@@ -1243,8 +1293,7 @@ static int check_rank_args(gte_env* E, const char* who, int32_t k, int32_t metri
                            const int32_t* top_index, const double* top_score, const double* scores) {
   if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
   if (metric < lo || metric > hi) return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
-  if (!stats || ((uintptr_t)stats & 15))
-    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  TRY(check_stats(stats));
   if (!top_index || ((uintptr_t)top_index & 3) || !top_score || ((uintptr_t)top_score & 7))
     return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
   if ((uintptr_t)scores & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
@@ -1793,8 +1842,7 @@ int gte_bootstrap_weights(gte_env* E, int32_t n, int32_t n_resamples, double blo
                           double* weights_device) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   if (n < 2 || n > GTE_MAX_PERIODS) return fail(GTE_ERR_INVALID, "n %d outside [2, %d]", n, GTE_MAX_PERIODS);
-  if (n_resamples < 1 || n_resamples > GTE_BOOT_MAX_RESAMPLES)
-    return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
+  TRY(check_n_resamples(n_resamples));
   if (!(block >= 1.0)) return fail(GTE_ERR_INVALID, "block must be >= 1.0");
   if (!weights_device || ((uintptr_t)weights_device & 7))
     return fail(GTE_ERR_INVALID, "weights_device must be an 8-byte aligned device array");
@@ -1802,10 +1850,9 @@ int gte_bootstrap_weights(gte_env* E, int32_t n, int32_t n_resamples, double blo
   HIPCHK(hipSetDevice(E->cfg.device));
   double t = floor(4294967296.0 / block);
   if (t > 4294967295.0) t = 4294967295.0;
-  const hipError_t e = gte::launch_bootstrap_weights(n, n_resamples, (uint32_t)t, block == 1.0 ? 1 : 0, seed,
-                                                     weights_device, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "bootstrap weights launch: %s", hipGetErrorString(e));
-  return GTE_OK;
+  return launched(gte::launch_bootstrap_weights(n, n_resamples, (uint32_t)t, block == 1.0 ? 1 : 0, seed,
+                                                weights_device, E->stream),
+                  "bootstrap weights");
 }
 
 int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
@@ -1813,43 +1860,25 @@ int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device,
                       const double* weights_device, int32_t n_resamples, const gte_reality_check_out* out) {
   TRY(check_strategies(E, n_strategies));
   TRY(check_n_periods(n_periods, 1));
-  if (n_resamples < 1 || n_resamples > GTE_BOOT_MAX_RESAMPLES)
-    return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
+  TRY(check_n_resamples(n_resamples));
   TRY(check_period_mask(period_mask));
-  int n = 0;
-  for (int b = 0; b < 128; ++b) {
-    if (!((period_mask[b >> 6] >> (b & 63)) & 1)) continue;
-    if (b >= n_periods) return fail(GTE_ERR_INVALID, "period_mask selects period %d, at or above n_periods %d", b, n_periods);
-    ++n;
-  }
+  int n;
+  TRY(count_periods(period_mask, n_periods, &n));
   if (n < 2) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: at least two are needed", n);
-  if (!stats_device || ((uintptr_t)stats_device & 15))
-    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
+  TRY(check_stats(stats_device));
   if (!weights_device || ((uintptr_t)weights_device & 7) || ((uintptr_t)benchmark_device & 7))
     return fail(GTE_ERR_INVALID, "weights_device (required) and benchmark_device must be 8-byte aligned device arrays");
   if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
-  if (!out->mean || !out->boot_sum || !out->boot_sq_sum || !out->max_stat || !out->summary ||
-      (((uintptr_t)out->mean | (uintptr_t)out->boot_sum | (uintptr_t)out->boot_sq_sum | (uintptr_t)out->max_stat |
-        (uintptr_t)out->summary) & 7))
+  if (!all_aligned({out->mean, out->boot_sum, out->boot_sq_sum, out->max_stat, out->summary}, 7))
     return fail(GTE_ERR_INVALID, "out: mean, boot_sum, boot_sq_sum, max_stat and summary must be 8-byte aligned device pointers");
-  if (!out->count_ge || !out->count_adj || !out->max_index ||
-      (((uintptr_t)out->count_ge | (uintptr_t)out->count_adj | (uintptr_t)out->max_index) & 3))
+  if (!all_aligned({out->count_ge, out->count_adj, out->max_index}, 3))
     return fail(GTE_ERR_INVALID, "out: count_ge, count_adj and max_index must be 4-byte aligned device pointers");
   if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reality_check inside a stream capture");
   HIPCHK(hipSetDevice(E->cfg.device));
-  const size_t need = gte::reality_check_scratch_bytes(n_strategies, n, n_resamples);
-  if (E->boot_bytes < need) {  // (the old one stays until gte_destroy: launches in flight may use it)
-    const size_t bytes = need > 2 * E->boot_bytes ? need : 2 * E->boot_bytes;
-    uint8_t* fresh = nullptr;
-    TRY(dev_alloc(E, &fresh, bytes, false));
-    E->boot_scratch = fresh;
-    E->boot_bytes = bytes;
-  }
-  const hipError_t e = gte::launch_reality_check(stats_device, n_strategies, n_periods, period_mask, n,
-                                                 benchmark_device, weights_device, n_resamples, *out, E->boot_scratch,
-                                                 E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "reality check launch: %s", hipGetErrorString(e));
-  return GTE_OK;
+  TRY(grow(E, &E->boot_scratch, gte::reality_check_scratch_bytes(n_strategies, n, n_resamples)));
+  return launched(gte::launch_reality_check(stats_device, n_strategies, n_periods, period_mask, n, benchmark_device,
+                                            weights_device, n_resamples, *out, E->boot_scratch.base, E->stream),
+                  "reality check");
 }
 
 int gte_cscv(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
@@ -1864,18 +1893,14 @@ int gte_cscv(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t 
   if (metric != GTE_PERIOD_METRIC_MEAN_REWARD && metric != GTE_PERIOD_METRIC_SHARPE &&
       metric != GTE_PERIOD_METRIC_REWARD_SUM)
     return fail(GTE_ERR_INVALID, "metric %d: gte_cscv scores by MEAN_REWARD, SHARPE or REWARD_SUM", metric);
-  if (!stats_device || ((uintptr_t)stats_device & 15))
-    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
-  if (!group_masks || ((uintptr_t)group_masks & 7))
-    return fail(GTE_ERR_INVALID, "group_masks must be an 8-byte aligned host array");
-  if (!is_groups || !oos_groups || (((uintptr_t)is_groups | (uintptr_t)oos_groups) & 3))
+  TRY(check_stats(stats_device));
+  if (!all_aligned({group_masks}, 7)) return fail(GTE_ERR_INVALID, "group_masks must be an 8-byte aligned host array");
+  if (!all_aligned({is_groups, oos_groups}, 3))
     return fail(GTE_ERR_INVALID, "is_groups and oos_groups must be 4-byte aligned host arrays");
   if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
-  if (!out->is_score || !out->oos_score || !out->summary ||
-      (((uintptr_t)out->is_score | (uintptr_t)out->oos_score) & 7) || ((uintptr_t)out->summary & 3))
+  if (!all_aligned({out->is_score, out->oos_score}, 7) || !all_aligned({out->summary}, 3))
     return fail(GTE_ERR_INVALID, "out: is_score and oos_score must be 8-byte, summary 4-byte aligned device pointers");
-  if (!out->best || !out->below || !out->equal || !out->ranked ||
-      (((uintptr_t)out->best | (uintptr_t)out->below | (uintptr_t)out->equal | (uintptr_t)out->ranked) & 3))
+  if (!all_aligned({out->best, out->below, out->equal, out->ranked}, 3))
     return fail(GTE_ERR_INVALID, "out: best, below, equal and ranked must be 4-byte aligned device pointers");
   uint64_t seen[2] = {0, 0};
   for (int g = 0; g < n_groups; ++g) {
@@ -1897,23 +1922,15 @@ int gte_cscv(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t 
   }
   if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_cscv inside a stream capture");
   HIPCHK(hipSetDevice(E->cfg.device));
-  const size_t need = gte::cscv_scratch_bytes(n_strategies, n_groups, n_splits);
-  if (E->cscv_bytes < need) {  // (the old one stays until gte_destroy: launches in flight may use it)
-    const size_t bytes = need > 2 * E->cscv_bytes ? need : 2 * E->cscv_bytes;
-    uint8_t* fresh = nullptr;
-    TRY(dev_alloc(E, &fresh, bytes, false));
-    E->cscv_scratch = fresh;
-    E->cscv_bytes = bytes;
-  }
+  TRY(grow(E, &E->cscv_scratch, gte::cscv_scratch_bytes(n_strategies, n_groups, n_splits)));
   // the three tables packed as gte_launch.h lays them out, so that one copy stages them
   std::vector<uint8_t> tables(gte::cscv_table_bytes(n_groups, n_splits));
   memcpy(tables.data(), group_masks, 16 * (size_t)n_groups);
   memcpy(tables.data() + 16 * (size_t)n_groups, is_groups, 4 * (size_t)n_splits);
   memcpy(tables.data() + 16 * (size_t)n_groups + 4 * (size_t)n_splits, oos_groups, 4 * (size_t)n_splits);
-  const hipError_t e = gte::launch_cscv(stats_device, n_strategies, n_periods, tables.data(), n_groups, n_splits,
-                                        metric, *out, E->cscv_scratch, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "cscv launch: %s", hipGetErrorString(e));
-  return GTE_OK;
+  return launched(gte::launch_cscv(stats_device, n_strategies, n_periods, tables.data(), n_groups, n_splits, metric,
+                                   *out, E->cscv_scratch.base, E->stream),
+                  "cscv");
 }
 
 int gte_diversify(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
@@ -1923,39 +1940,23 @@ int gte_diversify(gte_env* E, const gte_strategy_period_stats* stats_device, int
   TRY(check_n_periods(n_periods, 1));
   if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
   TRY(check_period_mask(period_mask));
-  int n = 0;
-  for (int b = 0; b < 128; ++b) {
-    if (!((period_mask[b >> 6] >> (b & 63)) & 1)) continue;
-    if (b >= n_periods) return fail(GTE_ERR_INVALID, "period_mask selects period %d, at or above n_periods %d", b, n_periods);
-    ++n;
-  }
+  int n;
+  TRY(count_periods(period_mask, n_periods, &n));
   if (n < 3) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: a correlation needs at least three", n);
   if (max_corr != max_corr) return fail(GTE_ERR_INVALID, "max_corr is NaN");
-  if (!stats_device || ((uintptr_t)stats_device & 15))
-    return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
-  if (!scores_device || ((uintptr_t)scores_device & 7))
-    return fail(GTE_ERR_INVALID, "scores_device must be an 8-byte aligned device array");
+  TRY(check_stats(stats_device));
+  if (!all_aligned({scores_device}, 7)) return fail(GTE_ERR_INVALID, "scores_device must be an 8-byte aligned device array");
   if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
-  if (!out->pick_score || !out->owner_corr || !out->pick_corr ||
-      (((uintptr_t)out->pick_score | (uintptr_t)out->owner_corr | (uintptr_t)out->pick_corr) & 7))
+  if (!all_aligned({out->pick_score, out->owner_corr, out->pick_corr}, 7))
     return fail(GTE_ERR_INVALID, "out: pick_score, owner_corr and pick_corr must be 8-byte aligned device pointers");
-  if (!out->pick || !out->cluster_size || !out->owner || !out->summary ||
-      (((uintptr_t)out->pick | (uintptr_t)out->cluster_size | (uintptr_t)out->owner | (uintptr_t)out->summary) & 3))
+  if (!all_aligned({out->pick, out->cluster_size, out->owner, out->summary}, 3))
     return fail(GTE_ERR_INVALID, "out: pick, cluster_size, owner and summary must be 4-byte aligned device pointers");
   if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_diversify inside a stream capture");
   HIPCHK(hipSetDevice(E->cfg.device));
-  const size_t need = gte::diversify_scratch_bytes(n_strategies, n, k);
-  if (E->div_bytes < need) {  // (the old one stays until gte_destroy: launches in flight may use it)
-    const size_t bytes = need > 2 * E->div_bytes ? need : 2 * E->div_bytes;
-    uint8_t* fresh = nullptr;
-    TRY(dev_alloc(E, &fresh, bytes, false));
-    E->div_scratch = fresh;
-    E->div_bytes = bytes;
-  }
-  const hipError_t e = gte::launch_diversify(stats_device, n_strategies, n_periods, period_mask, n, scores_device,
-                                             max_corr, k, *out, E->div_scratch, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "diversify launch: %s", hipGetErrorString(e));
-  return GTE_OK;
+  TRY(grow(E, &E->div_scratch, gte::diversify_scratch_bytes(n_strategies, n, k)));
+  return launched(gte::launch_diversify(stats_device, n_strategies, n_periods, period_mask, n, scores_device, max_corr,
+                                        k, *out, E->div_scratch.base, E->stream),
+                  "diversify");
 }
 
 int gte_add_limit_orders(gte_env* E, const int32_t* pos_index, const double* limit,

@@ -273,9 +273,7 @@ __global__ __launch_bounds__(1024) void gte_boot_summary_kernel(const uint8_t* _
   }
 }
 
-static size_t boot_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// the library's scratch of one gte_reality_check, carved out of one allocation (every piece 256-byte aligned)
+// the library's scratch of one gte_reality_check, carved out of one allocation (ScratchCarver, gte_launch.h)
 struct BootScratch {
   double *D, *pq1, *pq2, *pmax;
   int32_t *pge, *pidx;
@@ -284,18 +282,16 @@ struct BootScratch {
 };
 static BootScratch boot_carve(void* base, int64_t S, int n, int R) {
   const size_t slabs = (size_t)((R + GTE_BOOT_SLAB - 1) / GTE_BOOT_SLAB), tiles = (size_t)((S + BOOT_TILE - 1) / BOOT_TILE);
-  char* p = (char*)base;
-  size_t at = 0;
+  ScratchCarver c = {(char*)base, 0};
   BootScratch b;
-  auto take = [&](size_t bytes) { char* q = p + at; at += boot_up(bytes); return (void*)q; };
-  b.D = (double*)take(8 * (size_t)n * (size_t)S);
-  b.pq1 = (double*)take(8 * slabs * (size_t)S);
-  b.pq2 = (double*)take(8 * slabs * (size_t)S);
-  b.pmax = (double*)take(8 * tiles * (size_t)R);
-  b.pge = (int32_t*)take(4 * slabs * (size_t)S);
-  b.pidx = (int32_t*)take(4 * tiles * (size_t)R);
-  b.elig = (uint8_t*)take((size_t)S);
-  b.bytes = at;
+  b.D = c.take<double>((size_t)n * (size_t)S);
+  b.pq1 = c.take<double>(slabs * (size_t)S);
+  b.pq2 = c.take<double>(slabs * (size_t)S);
+  b.pmax = c.take<double>(tiles * (size_t)R);
+  b.pge = c.take<int32_t>(slabs * (size_t)S);
+  b.pidx = c.take<int32_t>(tiles * (size_t)R);
+  b.elig = c.take<uint8_t>((size_t)S);
+  b.bytes = c.at;
   return b;
 }
 

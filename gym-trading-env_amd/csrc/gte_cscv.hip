@@ -305,9 +305,7 @@ __global__ __launch_bounds__(1024) void gte_cscv_summary_kernel(const uint8_t* _
   }
 }
 
-static size_t cscv_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// the library's scratch of one gte_cscv, carved out of one allocation (every piece 256-byte aligned).  The three
+// the library's scratch of one gte_cscv, carved out of one allocation (ScratchCarver, gte_launch.h).  The three
 // host tables come first, packed as the host side packs them (CscvTables): one copy stages them.  The integer
 // partials of pass 2 take the bytes of pass 1's: the winner kernel has read those before pass 2 runs.
 struct CscvScratch {
@@ -321,26 +319,24 @@ struct CscvScratch {
 };
 static CscvScratch cscv_carve(void* base, int64_t S, int G, int C) {
   const size_t tiles = (size_t)((S + CSCV_TILE - 1) / CSCV_TILE), tc = tiles * (size_t)C;
-  char* p = (char*)base;
-  size_t at = 0;
+  ScratchCarver c = {(char*)base, 0};
   CscvScratch b;
-  auto take = [&](size_t bytes) { char* q = p + at; at += cscv_up(bytes); return (void*)q; };
   b.table_bytes = sizeof(PeriodMask) * (size_t)G + 8 * (size_t)C;
-  char* tables = (char*)take(b.table_bytes);  // groups, then the two split tables, back to back
+  char* tables = c.take<char>(b.table_bytes);  // groups, then the two split tables, back to back
   b.groups = (PeriodMask*)tables;
   b.isw = (uint32_t*)(tables + sizeof(PeriodMask) * (size_t)G);
   b.osw = b.isw + C;
-  b.A1 = (double*)take(8 * (size_t)G * (size_t)S);
-  b.A2 = (double*)take(8 * (size_t)G * (size_t)S);
-  b.NG = (long long*)take(8 * (size_t)G * (size_t)S);
-  b.pmax = (double*)take(8 * tc);
-  b.poos = (double*)take(8 * tc);
-  b.pidx = (int32_t*)take(4 * tc);
-  b.elig = (uint8_t*)take((size_t)S);
+  b.A1 = c.take<double>((size_t)G * (size_t)S);
+  b.A2 = c.take<double>((size_t)G * (size_t)S);
+  b.NG = c.take<long long>((size_t)G * (size_t)S);
+  b.pmax = c.take<double>(tc);
+  b.poos = c.take<double>(tc);
+  b.pidx = c.take<int32_t>(tc);
+  b.elig = c.take<uint8_t>((size_t)S);
   b.pbelow = (int32_t*)b.pmax;
   b.pequal = b.pbelow + tc;
   b.pranked = (int32_t*)b.poos;
-  b.bytes = at;
+  b.bytes = c.at;
   return b;
 }
 

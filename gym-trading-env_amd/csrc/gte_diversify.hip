@@ -323,9 +323,7 @@ __global__ __launch_bounds__(DIV_TILE) void gte_div_close_kernel(
   }
 }
 
-static size_t div_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// the library's scratch of one gte_diversify, carved out of one allocation (every piece 256-byte aligned)
+// the library's scratch of one gte_diversify, carved out of one allocation (ScratchCarver, gte_launch.h)
 struct DivScratch {
   double *U, *pscore[2];
   int32_t *pindex[2], *wg_left, *wg_eligible, *wg_candidates, *wg_live;
@@ -334,19 +332,17 @@ struct DivScratch {
 };
 static DivScratch div_carve(void* base, int64_t S, int n, int k) {
   const size_t tiles = (size_t)((S + DIV_TILE - 1) / DIV_TILE);
-  char* p = (char*)base;
-  size_t at = 0;
+  ScratchCarver c = {(char*)base, 0};
   DivScratch d;
-  auto take = [&](size_t bytes) { char* q = p + at; at += div_up(bytes); return (void*)q; };
-  d.U = (double*)take(8 * (size_t)n * (size_t)S);
-  for (int j = 0; j < 2; ++j) d.pscore[j] = (double*)take(8 * tiles);
-  for (int j = 0; j < 2; ++j) d.pindex[j] = (int32_t*)take(4 * tiles);
-  d.wg_left = (int32_t*)take(4 * (size_t)k * tiles);
-  d.wg_eligible = (int32_t*)take(4 * tiles);
-  d.wg_candidates = (int32_t*)take(4 * tiles);
-  d.wg_live = (int32_t*)take(4 * tiles);
-  d.live = (uint8_t*)take((size_t)S);
-  d.bytes = at;
+  d.U = c.take<double>((size_t)n * (size_t)S);
+  for (int j = 0; j < 2; ++j) d.pscore[j] = c.take<double>(tiles);
+  for (int j = 0; j < 2; ++j) d.pindex[j] = c.take<int32_t>(tiles);
+  d.wg_left = c.take<int32_t>((size_t)k * tiles);
+  d.wg_eligible = c.take<int32_t>(tiles);
+  d.wg_candidates = c.take<int32_t>(tiles);
+  d.wg_live = c.take<int32_t>(tiles);
+  d.live = c.take<uint8_t>((size_t)S);
+  d.bytes = c.at;
   return d;
 }
 

@@ -242,6 +242,20 @@ hipError_t launch_period_scores(const gte_strategy_period_stats* stats, int n_st
                                 const uint64_t period_mask[2], int metric, int64_t min_steps, double* scores,
                                 double* cand_score, int32_t* cand_index, hipStream_t stream);
 
+// --- the three leaderboard analyses below (gte_bootstrap.hip, gte_cscv.hip, gte_diversify.hip) each carve their
+// library-owned scratch out of one allocation with this: take<T>(count) is the next piece, every piece 256-byte
+// aligned; `at` ends as the bytes the pieces need, which is all a carver over a null base is asked for
+struct ScratchCarver {
+  char* base;
+  size_t at;
+  template <typename T>
+  T* take(size_t count) {
+    T* piece = (T*)(base + at);
+    at += (sizeof(T) * count + 255) & ~(size_t)255;
+    return piece;
+  }
+};
+
 // --- gte_bootstrap.hip: the bootstrap reality check (gte_bootstrap_weights, gte_reality_check, include/gte.h);
 // the caller has checked alignments
 // w[R][n] of the stationary bootstrap: thr and always (block == 1.0) as include/gte.h states them

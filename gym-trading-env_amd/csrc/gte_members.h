@@ -1,8 +1,9 @@
 // gte_members.h — which envs belong to a strategy, and which periods a mask selects: the two rules
 // include/gte.h promises for every reduction and ranking of per-strategy records, stated once for
-// gte_strategy.hip, gte_trade_strategy.hip, gte_period_strategy.hip and gte_bootstrap.hip.  Plain C++ behind
-// __device__ / __forceinline__ (tests/test_strategy_records_cpu.py compiles it for the host with both
-// defined away and holds it to tests/strategy_model.py).
+// gte_strategy.hip, gte_trade_strategy.hip, gte_period_strategy.hip and the three leaderboard analyses, which
+// all take their periods as a PeriodMask: gte_bootstrap.hip (as BootMask), gte_cscv.hip (one per group) and
+// gte_diversify.hip.  Plain C++ behind __device__ / __forceinline__ (tests/test_strategy_records_cpu.py
+// compiles it for the host with both defined away and holds it to tests/strategy_model.py).
 #pragma once
 #include <stdint.h>
 

@@ -7,13 +7,11 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from . import _abi
-from .strategy_records import mask_words
+from .strategy_records import LeaderboardResult, f64_on, is_int_in, make_outputs, mask_words
 
 
-class Diversified:
+class Diversified(LeaderboardResult):
     """The result of `StrategyPeriodStats.diversified()`.
 
     Device tensors, none of which waits: ``picks`` int32 [k] (the strategy picked in every round, -1 from the round
@@ -30,19 +28,15 @@ class Diversified:
     None while candidates remain.  ``k``, ``max_corr`` and ``corr_periods`` (the period ids the correlations are
     taken over) describe the call."""
 
+    SUMMARY_DTYPE = _abi.DIVERSIFY_SUMMARY_DTYPE
+    ARRAYS = ("picks", "scores", "cluster_size", "owner", "owner_corr", "corr")
+
     def __init__(self, env, k, max_corr, corr_periods, out, keep):
-        self._env, self._keep = env, keep   # every tensor the launches read, alive with the result
+        super().__init__(env, out, keep)
         self.k, self.max_corr, self.corr_periods = int(k), float(max_corr), list(corr_periods)
         self.picks, self.scores, self.cluster_size = out["pick"], out["pick_score"], out["cluster_size"]
         self.owner, self.owner_corr = out["owner"], out["owner_corr"]
         self.corr = out["pick_corr"].view(self.k, self.k)
-        self._summary_dev, self._summary = out["summary"], None
-
-    def _read(self):
-        if self._summary is None:
-            raw = self._summary_dev.cpu().numpy()
-            self._summary = raw.view(np.dtype(_abi.DIVERSIFY_SUMMARY_DTYPE))[0]
-        return self._summary
 
     @property
     def num_picked(self) -> int:
@@ -77,53 +71,38 @@ class Diversified:
             raise IndexError(f"round {r} outside [0, {self.k})")
         return (self.owner == int(r)).nonzero().flatten()
 
-    def numpy(self) -> dict:
-        """Everything on the host: the arrays above by name, and the summary's scalars."""
-        out = {k: getattr(self, k).cpu().numpy() for k in ("picks", "scores", "cluster_size", "owner", "owner_corr",
-                                                           "corr")}
-        out.update(num_picked=self.num_picked, num_candidates=self.num_candidates, num_eligible=self.num_eligible,
-                   remaining=self.remaining, exhausted=self.exhausted, effective_trials=self.effective_trials,
-                   k=self.k, max_corr=self.max_corr, corr_periods=list(self.corr_periods))
-        return out
+    def _scalars(self) -> dict:
+        return dict(num_picked=self.num_picked, num_candidates=self.num_candidates, num_eligible=self.num_eligible,
+                    remaining=self.remaining, exhausted=self.exhausted, effective_trials=self.effective_trials,
+                    k=self.k, max_corr=self.max_corr, corr_periods=list(self.corr_periods))
 
 
 def run(owner, k, metric="sharpe", periods=None, max_corr=0.7, min_steps=1, corr_periods=None, scores=None) -> Diversified:
     """`StrategyPeriodStats.diversified`: stage the arguments, enqueue the launches, wait for nothing."""
     env, torch = owner._env, owner._env._torch
-    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.GTE_RANK_MAX:
+    if not is_int_in(k, 1, _abi.GTE_RANK_MAX):
         raise ValueError(f"k must lie in [1, {_abi.GTE_RANK_MAX}]")
     k = int(k)
     max_corr = float(max_corr)
     if max_corr != max_corr:
         raise ValueError("max_corr must not be NaN")
-    mask = owner._mask(periods if corr_periods is None else corr_periods)
-    ids = [int(b) for b in np.flatnonzero(mask)]
-    if len(ids) < 3:
-        raise ValueError("a correlation needs at least three selected periods")
+    mask, ids = owner._selected(periods if corr_periods is None else corr_periods, 3,
+                                "a correlation needs at least three selected periods")
     dev = owner._records.device
     S, B = owner.num_strategies, owner.num_periods
     if scores is None:
-        pooled = owner._mask(periods)
+        pooled, pooled_ids = owner._selected(periods)
         scores = owner.score(metric, pooled)
-        steps = owner.steps[:, [int(b) for b in np.flatnonzero(pooled)]].sum(dim=1)
+        steps = owner.steps[:, pooled_ids].sum(dim=1)
         scores = torch.where(steps >= max(1, int(min_steps)), scores, torch.full_like(scores, float("nan")))
     else:
-        if not hasattr(scores, "is_cuda"):
-            scores = torch.from_numpy(np.ascontiguousarray(np.asarray(scores, dtype=np.float64)))
-        scores = scores.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(scores.shape) != (S,):
-            raise ValueError(f"scores must have shape ({S},), not {tuple(scores.shape)}")
-    with torch.cuda.device(dev):
-        out = dict(pick=torch.empty((k,), dtype=torch.int32, device=dev),
-                   pick_score=torch.empty((k,), dtype=torch.float64, device=dev),
-                   cluster_size=torch.empty((k,), dtype=torch.int32, device=dev),
-                   owner=torch.empty((S,), dtype=torch.int32, device=dev),
-                   owner_corr=torch.empty((S,), dtype=torch.float64, device=dev),
-                   pick_corr=torch.empty((k * k,), dtype=torch.float64, device=dev),
-                   summary=torch.empty((C.sizeof(_abi.GteDiversifySummary),), dtype=torch.uint8, device=dev))
+        scores = f64_on(torch, dev, scores, lambda s: s == (S,), f"scores must have shape ({S},)")
+    f64, i32 = torch.float64, torch.int32
+    out, ptrs = make_outputs(torch, dev, (("pick", i32, k), ("pick_score", f64, k), ("cluster_size", i32, k),
+                                          ("owner", i32, S), ("owner_corr", f64, S), ("pick_corr", f64, k * k)),
+                             _abi.GteDiversifyOut, _abi.GteDiversifySummary)
     # (the env launches on torch's current stream as it was when the env was made: the tensors made above are
     # ordered with the launches, as in StrategyStats)
-    ptrs = _abi.GteDiversifyOut(**{name: v.data_ptr() for name, v in out.items()})
     _abi.check(env._lib, env._lib.gte_diversify(
         env._h, C.c_void_p(owner._records.data_ptr()), S, B, mask_words(mask), C.c_void_p(scores.data_ptr()), max_corr, k,
         C.byref(ptrs)))

@@ -11,10 +11,10 @@ import ctypes as C
 import numpy as np
 
 from . import _abi, periods as period_rows
-from .strategy_records import metric_code
+from .strategy_records import LeaderboardResult, make_outputs, metric_code
 
 
-class OverfitCheck:
+class OverfitCheck(LeaderboardResult):
     """The result of `StrategyPeriodStats.cscv()`.
 
     Device tensors over the C splits, none of which waits: ``best`` int32 (the in-sample winner, -1 when no
@@ -31,26 +31,22 @@ class OverfitCheck:
     ``metric``, ``groups`` (the [G, 2] mask table), ``is_groups`` and ``oos_groups`` (the split tables, host) describe
     the call."""
 
+    SUMMARY_DTYPE = _abi.CSCV_SUMMARY_DTYPE
+    ARRAYS = ("best", "is_score", "oos_score", "below", "equal", "ranked", "valid", "rel_rank", "logit")
+
     def __init__(self, env, metric, groups, is_groups, oos_groups, out, keep):
-        self._env, self._keep = env, keep   # every tensor the launches read, alive with the result
+        super().__init__(env, out, keep)
         self.metric = _abi.PERIOD_METRICS[metric]
         self.groups, self.is_groups, self.oos_groups = groups, is_groups, oos_groups
         self.num_groups, self.num_splits = int(groups.shape[0]), int(is_groups.shape[0])
         self.best, self.is_score, self.oos_score = out["best"], out["is_score"], out["oos_score"]
         self.below, self.equal, self.ranked = out["below"], out["equal"], out["ranked"]
-        self._summary_dev, self._summary = out["summary"], None
         torch = env._torch
         f64 = torch.float64
         self.valid = (self.best >= 0) & ~torch.isnan(self.oos_score)
         w = (self.below.to(f64) + (self.equal.to(f64) + 1.0) / 2.0) / (self.ranked.to(f64) + 1.0)
         self.rel_rank = torch.where(self.valid, w, torch.full_like(w, float("nan")))
         self.logit = torch.log(self.rel_rank / (1.0 - self.rel_rank))
-
-    def _read(self):
-        if self._summary is None:
-            raw = self._summary_dev.cpu().numpy()
-            self._summary = raw.view(np.dtype(_abi.CSCV_SUMMARY_DTYPE))[0]
-        return self._summary
 
     @property
     def num_valid(self) -> int:
@@ -89,15 +85,11 @@ class OverfitCheck:
         both = torch.stack((slope, my - slope * mx)).cpu()
         return float(both[0]), float(both[1])
 
-    def numpy(self) -> dict:
-        """Everything on the host: the arrays above by name, and the summary's scalars."""
-        out = {k: getattr(self, k).cpu().numpy() for k in (
-            "best", "is_score", "oos_score", "below", "equal", "ranked", "valid", "rel_rank", "logit")}
+    def _scalars(self) -> dict:
         s = self._read()
-        out.update(pbo=self.pbo, prob_loss=self.prob_loss, num_valid=int(s["valid"]), num_overfit=int(s["overfit"]),
-                   num_loss=int(s["loss"]), num_eligible=int(s["eligible"]), num_splits=self.num_splits,
-                   num_groups=self.num_groups, metric=self.metric)
-        return out
+        return dict(pbo=self.pbo, prob_loss=self.prob_loss, num_valid=int(s["valid"]), num_overfit=int(s["overfit"]),
+                    num_loss=int(s["loss"]), num_eligible=int(s["eligible"]), num_splits=self.num_splits,
+                    num_groups=self.num_groups, metric=self.metric)
 
 
 def _table(a, dtype, what):
@@ -116,11 +108,9 @@ def run(owner, periods=None, groups=None, metric="sharpe", splits=None) -> Overf
     if _abi.PERIOD_METRICS[code] not in _abi.CSCV_METRICS:
         raise ValueError(f"cscv scores by one of {', '.join(_abi.CSCV_METRICS)}, not {_abi.PERIOD_METRICS[code]}")
     if groups is None or isinstance(groups, (int, np.integer)) and not isinstance(groups, bool):
-        ids = [int(b) for b in np.flatnonzero(owner._mask(periods))]
+        _, ids = owner._selected(periods, 2 if groups is None else 0, "cscv needs at least two selected periods")
         if groups is None:
             groups = min(len(ids), 16) // 2 * 2
-            if groups < 2:
-                raise ValueError("cscv needs at least two selected periods")
         table = period_rows.cscv_groups(ids, int(groups))
     else:
         table = _table(groups, np.uint64, "groups")
@@ -138,13 +128,11 @@ def run(owner, periods=None, groups=None, metric="sharpe", splits=None) -> Overf
     n_splits = int(is_groups.shape[0])
     dev = owner._records.device
     S, B = owner.num_strategies, owner.num_periods
-    with torch.cuda.device(dev):
-        out = {k: torch.empty((n_splits,), dtype=torch.int32, device=dev) for k in ("best", "below", "equal", "ranked")}
-        out.update({k: torch.empty((n_splits,), dtype=torch.float64, device=dev) for k in ("is_score", "oos_score")})
-        out["summary"] = torch.empty((C.sizeof(_abi.GteCscvSummary),), dtype=torch.uint8, device=dev)
+    spec = [(name, torch.int32, n_splits) for name in ("best", "below", "equal", "ranked")] + \
+           [(name, torch.float64, n_splits) for name in ("is_score", "oos_score")]
+    out, ptrs = make_outputs(torch, dev, spec, _abi.GteCscvOut, _abi.GteCscvSummary)
     # (the library copies the three host tables before it returns; the env launches on torch's current stream as it
     # was when the env was made, as in StrategyStats)
-    ptrs = _abi.GteCscvOut(**{k: v.data_ptr() for k, v in out.items()})
     _abi.check(env._lib, env._lib.gte_cscv(
         env._h, C.c_void_p(owner._records.data_ptr()), S, B, C.c_void_p(table.ctypes.data), G,
         C.c_void_p(is_groups.ctypes.data), C.c_void_p(oos_groups.ctypes.data), n_splits, code, C.byref(ptrs)))

@@ -144,6 +144,14 @@ class StrategyPeriodStats(StrategyRecords):
             m[b] = True
         return m
 
+    def _selected(self, periods, at_least=0, refusal=None):
+        """`_mask(periods)` and the ids it selects, ascending; fewer than `at_least` of them: ValueError(refusal)."""
+        mask = self._mask(periods)
+        ids = [int(b) for b in np.flatnonzero(mask)]
+        if len(ids) < at_least:
+            raise ValueError(refusal)
+        return mask, ids
+
     def _periods_args(self, periods):
         """What the rank call takes between S and the metric: B and the mask's words, made when it asks."""
         return lambda: (self.num_periods, mask_words(self._mask(periods)))

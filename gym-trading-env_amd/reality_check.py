@@ -6,10 +6,8 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from . import _abi
-from .strategy_records import mask_words
+from .strategy_records import LeaderboardResult, f64_on, is_int_in, make_outputs, mask_words
 
 
 def bootstrap_weights(env, n, n_resamples, block=1.0, seed=0):
@@ -21,7 +19,7 @@ def bootstrap_weights(env, n, n_resamples, block=1.0, seed=0):
     if torch is None:
         raise ValueError("bootstrap weights need output='torch'")
     for name, v in (("n", n), ("n_resamples", n_resamples), ("seed", seed)):
-        if isinstance(v, (bool, float)) or int(v) != v:
+        if not is_int_in(v, -float("inf"), float("inf"), floats=False):
             raise TypeError(f"{name} must be an integer")
     if not 2 <= int(n) <= _abi.GTE_MAX_PERIODS:
         raise ValueError(f"n must lie in [2, {_abi.GTE_MAX_PERIODS}]")
@@ -37,7 +35,7 @@ def bootstrap_weights(env, n, n_resamples, block=1.0, seed=0):
     return w
 
 
-class RealityCheck:
+class RealityCheck(LeaderboardResult):
     """The result of `StrategyPeriodStats.reality_check()`.
 
     Device tensors, none of which waits: ``mean`` f64 [S] (the mean period return of each strategy over the
@@ -53,15 +51,18 @@ class RealityCheck:
     three wait for the device, once.  ``num_resamples``, ``periods`` (the selected period ids) and ``weights`` (the
     [R, n] table that was used) describe the call."""
 
+    SUMMARY_DTYPE = _abi.REALITY_CHECK_SUMMARY_DTYPE
+    ARRAYS = ("mean", "std_error", "p_individual", "p_adjusted", "eligible", "max_stats", "max_index", "boot_sum",
+              "boot_sq_sum", "count_ge", "count_adj")
+
     def __init__(self, env, periods, weights, out, keep):
-        self._env, self._keep = env, keep   # every tensor the launches read, alive with the result
+        super().__init__(env, out, keep)
         self.periods = list(periods)
         self.weights = weights
         self.num_resamples = R = int(weights.shape[0])
         self.mean, self.boot_sum, self.boot_sq_sum = out["mean"], out["boot_sum"], out["boot_sq_sum"]
         self.count_ge, self.count_adj = out["count_ge"], out["count_adj"]
         self.max_stats, self.max_index = out["max_stat"], out["max_index"]
-        self._summary_dev, self._summary = out["summary"], None
         torch = env._torch
         owner = keep[0]  # eligible: stepped in every selected period, every period return finite (include/gte.h)
         self.eligible = (owner.steps[:, self.periods] > 0).all(dim=1) & \
@@ -74,12 +75,6 @@ class RealityCheck:
         nan = torch.full_like(self.mean, float("nan"))
         self.p_individual = torch.where(self.eligible, self.count_ge.to(torch.float64) / Rt, nan)
         self.p_adjusted = torch.where(self.eligible, self.count_adj.to(torch.float64) / Rt, nan)
-
-    def _read(self):
-        if self._summary is None:
-            raw = self._summary_dev.cpu().numpy()
-            self._summary = raw.view(np.dtype(_abi.REALITY_CHECK_SUMMARY_DTYPE))[0]
-        return self._summary
 
     @property
     def best(self) -> int:
@@ -100,56 +95,37 @@ class RealityCheck:
         s = self._read()
         return float(s["count_rc"]) / self.num_resamples if int(s["best"]) >= 0 else float("nan")
 
-    def numpy(self) -> dict:
-        """Everything on the host: the arrays above by name, and the summary's scalars."""
-        out = {k: getattr(self, k).cpu().numpy() for k in (
-            "mean", "std_error", "p_individual", "p_adjusted", "eligible", "max_stats", "max_index", "boot_sum",
-            "boot_sq_sum", "count_ge", "count_adj")}
+    def _scalars(self) -> dict:
         s = self._read()
-        out.update(best=int(s["best"]), best_mean=float(s["best_mean"]), count_rc=int(s["count_rc"]),
-                   num_eligible=int(s["eligible"]), p_value=self.p_value, num_resamples=self.num_resamples,
-                   periods=list(self.periods))
-        return out
+        return dict(best=int(s["best"]), best_mean=float(s["best_mean"]), count_rc=int(s["count_rc"]),
+                    num_eligible=int(s["eligible"]), p_value=self.p_value, num_resamples=self.num_resamples,
+                    periods=list(self.periods))
 
 
 def run(owner, periods=None, n_resamples=1000, block=1.0, seed=0, benchmark=None, weights=None) -> RealityCheck:
     """`StrategyPeriodStats.reality_check`: stage the arguments, enqueue the launches, wait for nothing."""
     env, torch = owner._env, owner._env._torch
-    mask = owner._mask(periods)
-    ids = [int(b) for b in np.flatnonzero(mask)]
+    mask, ids = owner._selected(periods, 2, "a reality check needs at least two selected periods")
     n = len(ids)
-    if n < 2:
-        raise ValueError("a reality check needs at least two selected periods")
-    words = mask_words(mask)
     dev = owner._records.device
     S, B = owner.num_strategies, owner.num_periods
     if weights is None:
         weights = bootstrap_weights(env, n, n_resamples, block, seed)
     else:
-        if not hasattr(weights, "is_cuda"):
-            weights = torch.from_numpy(np.ascontiguousarray(np.asarray(weights, dtype=np.float64)))
-        weights = weights.to(device=dev, dtype=torch.float64).contiguous()
-        if weights.dim() != 2 or weights.shape[1] != n or not 1 <= weights.shape[0] <= _abi.GTE_BOOT_MAX_RESAMPLES:
-            raise ValueError(f"weights must have shape [R, {n}] with 1 <= R <= {_abi.GTE_BOOT_MAX_RESAMPLES}, "
-                             f"not {tuple(weights.shape)}")
+        most = _abi.GTE_BOOT_MAX_RESAMPLES
+        weights = f64_on(torch, dev, weights, lambda s: len(s) == 2 and s[1] == n and 1 <= s[0] <= most,
+                         f"weights must have shape [R, {n}] with 1 <= R <= {most}")
     R = int(weights.shape[0])
     bench = None
     if benchmark is not None:
-        if not hasattr(benchmark, "is_cuda"):
-            benchmark = torch.from_numpy(np.ascontiguousarray(np.asarray(benchmark, dtype=np.float64)))
-        bench = benchmark.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(bench.shape) != (B,):
-            raise ValueError(f"benchmark must have shape ({B},), not {tuple(bench.shape)}")
-    with torch.cuda.device(dev):
-        out = {k: torch.empty((S,), dtype=torch.float64, device=dev) for k in ("mean", "boot_sum", "boot_sq_sum")}
-        out.update({k: torch.empty((S,), dtype=torch.int32, device=dev) for k in ("count_ge", "count_adj")})
-        out["max_stat"] = torch.empty((R,), dtype=torch.float64, device=dev)
-        out["max_index"] = torch.empty((R,), dtype=torch.int32, device=dev)
-        out["summary"] = torch.empty((C.sizeof(_abi.GteRealityCheckSummary),), dtype=torch.uint8, device=dev)
+        bench = f64_on(torch, dev, benchmark, lambda s: s == (B,), f"benchmark must have shape ({B},)")
+    f64, i32 = torch.float64, torch.int32
+    out, ptrs = make_outputs(torch, dev, (("mean", f64, S), ("boot_sum", f64, S), ("boot_sq_sum", f64, S),
+                                          ("count_ge", i32, S), ("count_adj", i32, S), ("max_stat", f64, R),
+                                          ("max_index", i32, R)), _abi.GteRealityCheckOut, _abi.GteRealityCheckSummary)
     # (the env launches on torch's current stream as it was when the env was made: the copies above are ordered
     # with the launches, as in StrategyStats)
-    ptrs = _abi.GteRealityCheckOut(**{k: v.data_ptr() for k, v in out.items()})
     _abi.check(env._lib, env._lib.gte_reality_check(
-        env._h, C.c_void_p(owner._records.data_ptr()), S, B, words, None if bench is None else C.c_void_p(bench.data_ptr()),
-        C.c_void_p(weights.data_ptr()), R, C.byref(ptrs)))
+        env._h, C.c_void_p(owner._records.data_ptr()), S, B, mask_words(mask),
+        None if bench is None else C.c_void_p(bench.data_ptr()), C.c_void_p(weights.data_ptr()), R, C.byref(ptrs)))
     return RealityCheck(env, ids, weights, out, (owner, bench, weights))

@@ -1,7 +1,9 @@
 """What the record families of a backtest share — the per-env records (`BacktestStats`, `TradeStats`,
 `PeriodStats`, `ExitState`) and their per-strategy folds (`StrategyStats`, `StrategyTradeStats`,
 `StrategyPeriodStats`): metric names, the default strategy map, the member lists of an explicit map, the field
-views, the period mask's two words, and `StrategyRecords`, the base of the three folds."""
+views, the period mask's two words, and `StrategyRecords`, the base of the three folds.  And what the analyses of
+a leaderboard share (reality_check.py, overfit.py, diversify.py): the staging of their arguments and outputs and
+`LeaderboardResult`, the base of their results."""
 from __future__ import annotations
 
 import ctypes as C
@@ -89,6 +91,57 @@ def _ptr(tensor):
     return None if tensor is None else C.c_void_p(tensor.data_ptr())
 
 
+def is_int_in(value, lo, hi, floats=True) -> bool:
+    """Is `value` an integer in [lo, hi]?  A bool is none, nor a float with a fraction — nor any float, unless
+    `floats`.  What to raise, and in which words, is the caller's."""
+    if isinstance(value, bool) or (isinstance(value, float) and not floats):
+        return False
+    return int(value) == value and lo <= int(value) <= hi
+
+
+def f64_on(torch, dev, values, fits, expected):
+    """`values`, NumPy or torch, as a contiguous f64 tensor on `dev`.  `fits(shape)` says whether its shape will
+    do; one that will not is refused as "`expected`, not (shape)"."""
+    if not hasattr(values, "is_cuda"):
+        values = torch.from_numpy(np.ascontiguousarray(np.asarray(values, dtype=np.float64)))
+    values = values.to(device=dev, dtype=torch.float64).contiguous()
+    if not fits(tuple(values.shape)):
+        raise ValueError(f"{expected}, not {tuple(values.shape)}")
+    return values
+
+
+def make_outputs(torch, dev, spec, out_struct, summary_struct):
+    """What a leaderboard analysis writes: a tensor on `dev` for every (name, dtype, length) of `spec` and the bytes
+    of its summary record, by name, and the `out_struct` of their addresses the libgte call takes."""
+    with torch.cuda.device(dev):
+        out = {name: torch.empty((length,), dtype=dtype, device=dev) for name, dtype, length in spec}
+        out["summary"] = torch.empty((C.sizeof(summary_struct),), dtype=torch.uint8, device=dev)
+    return out, out_struct(**{name: t.data_ptr() for name, t in out.items()})
+
+
+class LeaderboardResult:
+    """Base of what the analyses of a leaderboard give (`RealityCheck`, `OverfitCheck`, `Diversified`): the tensors
+    the launches read, kept alive with the result, and the device's summary record, read once and only when a scalar
+    is asked for.  A result states SUMMARY_DTYPE (its summary record), ARRAYS (the tensor attributes `numpy()`
+    brings to the host) and `_scalars()` (what `numpy()` adds to them)."""
+
+    def __init__(self, env, out, keep):
+        self._env, self._keep = env, keep   # every tensor the launches read, alive with the result
+        self._summary_dev, self._summary = out["summary"], None
+
+    def _read(self):
+        if self._summary is None:
+            raw = self._summary_dev.cpu().numpy()
+            self._summary = raw.view(np.dtype(self.SUMMARY_DTYPE))[0]
+        return self._summary
+
+    def numpy(self) -> dict:
+        """Everything on the host: the arrays above by name, and the summary's scalars."""
+        out = {name: getattr(self, name).cpu().numpy() for name in self.ARRAYS}
+        out.update(self._scalars())
+        return out
+
+
 class StrategyRecords:
     """Result records of a per-strategy fold, owned by the object, and their ranking on the device.  A family
     states DTYPE and RECORD_FIELDS (its record), METRICS and METRIC_PREFIX, and REDUCE and RANK (its libgte
@@ -138,7 +191,7 @@ class StrategyRecords:
         metric and k have passed: the call's arguments between S and the metric."""
         env, torch = self._env, self._env._torch
         code = self._code(metric)
-        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.GTE_RANK_MAX:
+        if not is_int_in(k, 1, _abi.GTE_RANK_MAX):
             raise ValueError(f"k must lie in [1, {_abi.GTE_RANK_MAX}]")
         between = extra()
         dev = self._records.device

@@ -13,24 +13,20 @@ import pytest
 
 import cscv_model as cm
 from gym_trading_env_amd import _abi, periods
+from leaderboard_gpu import GUARD, assert_arrays_same, board as _board, device_records, guarded, make_env
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUTPUTS = (("best", np.int32), ("is_score", np.float64), ("oos_score", np.float64), ("below", np.int32),
            ("equal", np.int32), ("ranked", np.int32))
-GUARD = 8          # elements of guard on either side of every output
 CHUNK = _abi.GTE_CSCV_CHUNK
 METRICS = (cm.MEAN_REWARD, cm.SHARPE, cm.REWARD_SUM)
 
 
 @pytest.fixture(scope="module")
 def env():
-    from gym_trading_env_amd.batched import BatchedTradingEnv
-    rng = np.random.default_rng(0)
-    close = 100.0 * np.exp(np.cumsum(rng.normal(0, 1e-2, 60)))
-    feat = rng.normal(0, 1, (60, 3)).astype(np.float32)
-    e = BatchedTradingEnv((feat, close), num_envs=64, positions=[-1, 0, 1], windows=None)
+    e = make_env()
     yield e
     e.close()
 
@@ -93,11 +89,6 @@ def craft(S, B, seed, groups, dead=False):
     return cm.records(x, sq, steps)
 
 
-def guarded(torch, dev, n, dtype, fill):
-    whole = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=dev)
-    return whole, whole[GUARD:GUARD + n]
-
-
 def run_cscv(env, stats, groups, is_g, oos_g, metric, clobber=False):
     """gte_cscv over host-made records and tables -> dict of host arrays, like the model's; every output stands between
     guard words, which must come back untouched"""
@@ -105,7 +96,7 @@ def run_cscv(env, stats, groups, is_g, oos_g, metric, clobber=False):
     dev = env._t["obs"].device
     S, B = stats.shape
     n = len(is_g)
-    d_stats = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(dev)
+    d_stats = device_records(env, stats)
     whole, out = {}, {}
     for k, t in OUTPUTS:
         whole[k], out[k] = guarded(torch, dev, n, getattr(torch, np.dtype(t).name), -7)
@@ -129,13 +120,7 @@ def run_cscv(env, stats, groups, is_g, oos_g, metric, clobber=False):
 
 
 def assert_same(got, want, tag):
-    for k, t in OUTPUTS:
-        g, w = got[k], want[k]
-        assert g.dtype == t and g.shape == w.shape, (tag, k)
-        same = cm.same_f64(g, w) if t is np.float64 else np.array_equal(g, w)
-        if not same:
-            bad = [i for i in range(len(w)) if not (cm.same_f64(g[i:i + 1], w[i:i + 1]) if t is np.float64 else g[i] == w[i])]
-            pytest.fail(f"{tag}: {k} differs at {len(bad)} of {len(w)} places, first {[(i, g[i], w[i]) for i in bad[:5]]}")
+    assert_arrays_same(got, want, [k for k, _ in OUTPUTS], [k for k, t in OUTPUTS if t is np.float64], tag, dict(OUTPUTS))
     assert got["summary"].tobytes() == want["summary"].tobytes(), (tag, got["summary"], want["summary"])
 
 
@@ -242,14 +227,6 @@ def test_winners_that_lose_out_of_sample(env):
 
 # ---- single-period groups: the existing ranking kernel says the same ---------------------------------------------
 
-def _board(env, stats):
-    import torch
-    from gym_trading_env_amd.period_stats import StrategyPeriodStats
-    S, B = stats.shape
-    d = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(env._t["obs"].device)
-    return StrategyPeriodStats(env, d, B)
-
-
 @pytest.mark.parametrize("metric", ["mean_reward", "sharpe", "reward_sum"])
 def test_single_period_groups_agree_with_the_ranking(env, metric):
     S, B = 333, 8
@@ -320,7 +297,7 @@ def test_refusals_leave_every_output_untouched(env):
     is_g, oos_g = periods.cscv_splits(G)
     n = len(is_g)
     stats = craft(S, B, 1, groups)
-    d_stats = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(dev)
+    d_stats = device_records(env, stats)
     out = {k: torch.full((n * 8,), 0x5A, dtype=torch.uint8, device=dev) for k, _ in OUTPUTS}
     out["summary"] = torch.full((24,), 0x5A, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()

@@ -15,11 +15,12 @@ import pytest
 
 import diversify_model as dm
 from gym_trading_env_amd import _abi
+from leaderboard_gpu import (GUARD, assert_arrays_same, board as _board, device_records, guarded, id_words as words,
+                             make_env)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 8          # elements of guard on either side of every output
 INF = float("inf")
 KS = (1, 3, 256)
 MAX_CORRS = (-INF, -0.5, 0.0, 0.9, 1.0, 2.0)
@@ -30,11 +31,7 @@ FLOATS = ("pick_score", "owner_corr", "pick_corr")
 
 @pytest.fixture(scope="module")
 def env():
-    from gym_trading_env_amd.batched import BatchedTradingEnv
-    rng = np.random.default_rng(0)
-    close = 100.0 * np.exp(np.cumsum(rng.normal(0, 1e-2, 60)))
-    feat = rng.normal(0, 1, (60, 3)).astype(np.float32)
-    e = BatchedTradingEnv((feat, close), num_envs=64, positions=[-1, 0, 1], windows=None)
+    e = make_env()
     yield e
     e.close()
 
@@ -87,18 +84,13 @@ def craft(S, B, ids, seed, dead=False):
     return dm.records(x, steps), scores
 
 
-def guarded(torch, dev, n, dtype, fill):
-    whole = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=dev)
-    return whole, whole[GUARD:GUARD + n]
-
-
 def run_div(env, stats, ids, scores, max_corr, k):
     """gte_diversify over host-made records and scores -> dict of host arrays, like the model's; every output stands
     between guard words, which must come back untouched, and the inputs must be what they were"""
     import torch
     dev = env._t["obs"].device
     S, B = stats.shape
-    d_stats = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(dev)
+    d_stats = device_records(env, stats)
     d_scores = torch.from_numpy(np.ascontiguousarray(scores, np.float64).copy()).to(dev)
     whole, out = {}, {}
     for name, n, dt in (("pick", k, torch.int32), ("pick_score", k, torch.float64), ("cluster_size", k, torch.int32),
@@ -107,9 +99,8 @@ def run_div(env, stats, ids, scores, max_corr, k):
         whole[name], out[name] = guarded(torch, dev, n, dt, -7)
     whole["summary"], out["summary"] = guarded(torch, dev, 20, torch.uint8, 0xAB)    # (8 bytes on either side)
     ptrs = _abi.GteDiversifyOut(**{name: v.data_ptr() for name, v in out.items()})
-    words = (C.c_uint64 * 2)(*[int(w) for w in dm.words_of(ids)])
     torch.cuda.synchronize()
-    _abi.check(env._lib, env._lib.gte_diversify(env._h, C.c_void_p(d_stats.data_ptr()), S, B, words,
+    _abi.check(env._lib, env._lib.gte_diversify(env._h, C.c_void_p(d_stats.data_ptr()), S, B, words(ids),
                                                 C.c_void_p(d_scores.data_ptr()), float(max_corr), k, C.byref(ptrs)))
     env.synchronize()
     got = {name: v.cpu().numpy() for name, v in out.items()}
@@ -124,16 +115,7 @@ def run_div(env, stats, ids, scores, max_corr, k):
 
 
 def assert_same(got, want, tag):
-    for name in ("pick", "pick_score", "cluster_size", "owner", "owner_corr", "pick_corr"):
-        g, w = got[name], want[name]
-        assert g.dtype == w.dtype and g.shape == w.shape, (tag, name, g.dtype, g.shape)
-        same = dm.same_f64(g, w) if name in FLOATS else np.array_equal(g, w)
-        if not same:
-            gf, wf = g.reshape(-1), w.reshape(-1)
-            bad = [i for i in range(len(wf)) if not (dm.same_f64(gf[i:i + 1], wf[i:i + 1]) if name in FLOATS
-                                                     else gf[i] == wf[i])]
-            pytest.fail(f"{tag}: {name} differs at {len(bad)} of {len(wf)} places, first "
-                        f"{[(i, gf[i], wf[i]) for i in bad[:5]]}")
+    assert_arrays_same(got, want, ("pick", "pick_score", "cluster_size", "owner", "owner_corr", "pick_corr"), FLOATS, tag)
     assert got["summary"].tobytes() == want["summary"].tobytes(), (tag, got["summary"], want["summary"])
 
 
@@ -274,14 +256,6 @@ def test_determinism_and_isolation(env):
 
 # ---- the existing ranking kernel says the same -----------------------------------------------------------------
 
-def _board(env, stats):
-    import torch
-    from gym_trading_env_amd.period_stats import StrategyPeriodStats
-    S, B = stats.shape
-    d = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(env._t["obs"].device)
-    return StrategyPeriodStats(env, d, B)
-
-
 @pytest.mark.parametrize("metric", ["sharpe", "mean_reward", "worst_period"])
 def test_a_threshold_that_drops_nothing_is_the_ranking(env, metric):
     """max_corr = +inf and the scores of gte_rank_period_stats: the picks and their scores are its top(k) over the
@@ -318,7 +292,7 @@ def test_refusals_leave_every_output_untouched(env):
     S, B, k = 10, 6, 4
     ids = [0, 1, 3, 4, 5]
     stats, scores = craft(S, B, ids, 1)
-    d_stats = torch.from_numpy(stats.view(np.uint8).reshape(S * B, 48).copy()).to(dev)
+    d_stats = device_records(env, stats)
     d_scores = torch.from_numpy(scores.copy()).to(dev)
     sizes = dict(pick=4 * k, pick_score=8 * k, cluster_size=4 * k, owner=4 * S, owner_corr=8 * S, pick_corr=8 * k * k,
                  summary=20)
@@ -326,7 +300,6 @@ def test_refusals_leave_every_output_untouched(env):
     torch.cuda.synchronize()
     ptrs = lambda **over: _abi.GteDiversifyOut(**{**{name: v.data_ptr() for name, v in out.items()}, **over})
     st, sc = C.c_void_p(d_stats.data_ptr()), C.c_void_p(d_scores.data_ptr())
-    words = lambda sel: (C.c_uint64 * 2)(*[int(w) for w in dm.words_of(sel)])
     good, mask = ptrs(), words(ids)
     INVALID = _abi.GTE_ERR_INVALID
 
