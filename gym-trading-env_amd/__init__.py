@@ -11,7 +11,7 @@ from ._abi import GteError  # noqa: F401
 
 __all__ = ["TradingEnv", "MultiDatasetTradingEnv", "BatchedTradingEnv", "SB3TradingVecEnv", "GteError",
            "BacktestStats", "StrategyStats", "ExitState", "TradeStats", "StrategyTradeStats", "TradeList",
-           "PeriodStats", "StrategyPeriodStats", "RealityCheck", "OverfitCheck", "Diversified", "periods",
+           "PeriodStats", "StrategyPeriodStats", "RealityCheck", "OverfitCheck", "Diversified", "Curves", "periods",
            "basic_reward_function", "dynamic_feature_last_position_taken",
            "dynamic_feature_real_position"]
 
@@ -25,6 +25,7 @@ _LAZY = {
     "TradeStats": "trade_stats", "StrategyTradeStats": "trade_stats", "TradeList": "trade_list",
     "PeriodStats": "period_stats", "StrategyPeriodStats": "period_stats",
     "RealityCheck": "reality_check", "OverfitCheck": "overfit", "Diversified": "diversify",
+    "Curves": "curves",
 }
 
 

@@ -161,6 +161,18 @@ class GteRolloutBufs(C.Structure):
                 ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("valuation", C.c_void_p)]
 
 
+#: struct gte_curve_bufs (include/gte.h), in declaration order, with the torch dtype name of each column
+CURVE_COLUMNS = [("valuation", "float64"), ("drawdown", "float64"), ("reward", "float64"),
+                 ("position", "int32"), ("row", "int32"), ("flags", "uint8")]
+#: the bits of the `flags` column (GTE_CURVE_*, include/gte.h)
+CURVE_TERMINATED, CURVE_TRUNCATED, CURVE_RESET, CURVE_FROZEN = 1, 2, 4, 8
+
+
+class GteCurveBufs(C.Structure):
+    """struct gte_curve_bufs (include/gte.h): the optional [R][N] columns of gte_backtest_curves."""
+    _fields_ = [(n, C.c_void_p) for n, _ in CURVE_COLUMNS]
+
+
 #: struct gte_backtest_stats (include/gte.h), in declaration order: one 128-byte record per env
 BACKTEST_FIELDS = [("steps", "<i8")] + \
     [(n, "<f8") for n in ("reward_sum", "reward_sq_sum", "peak", "max_drawdown", "cur_return",
@@ -491,6 +503,8 @@ SYMBOLS = {
     "gte_bind_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64]),
     "gte_signal_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gte_backtest_signals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
+    "gte_backtest_curves": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                      _P(GteCurveBufs), _P(C.c_void_p)]),
     "gte_bind_exit_rules": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, _P(C.c_void_p)]),
     "gte_read_exit_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gte_track_trades": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),

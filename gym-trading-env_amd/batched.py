@@ -1544,6 +1544,59 @@ class BatchedTradingEnv(_VectorEnvBase):
         self._backtest_map = (strategy, self.num_strategies)
         return BacktestStats(self, ptr.value)
 
+    def backtest_curves(self, K=None, *, actions=None, strategy=None, stride=1, resume=False, valuation=True,
+                        drawdown=False, reward=False, position=False, row=False, flags=True, out=None):
+        """`backtest_signals(K)` — or, with ``actions=`` int32 [K, N], `backtest(actions)` — that also keeps ROWS
+        (`gte_backtest_curves`): the equity curve and what goes with it, one row per `stride` steps and env, as
+        [R, N] device tensors with R = ceil(K / stride), written by the same launch from the registers that hold
+        the step.  Exactly one of `K` and `actions` is given; with `K` the bound signal tables decide, and the
+        exit rules while they are bound.  The columns: ``valuation`` (the window's last step), ``drawdown`` (its
+        deepest, against the record's running peak: the underwater curve), ``reward`` (its sum), ``position`` (the
+        position index), ``row`` (the market row), ``flags`` (terminated / truncated / reset / frozen, OR-ed) —
+        include/gte.h states each.  Records, `resume` and the state afterwards are those of the call without rows;
+        with ``resume=False`` the maximum of an env's drawdown column is its ``stats.max_drawdown`` to the bit.
+        `out`: a previous result with the same K, stride and columns, whose tensors are written again.  Not
+        together with trade or period tracking.  Returns a `Curves` (its ``stats`` is the `BacktestStats`)."""
+        from . import curves as cv
+        from .backtest_stats import BacktestStats
+        torch = self._torch
+        if (K is None) == (actions is None):
+            raise TypeError("backtest_curves takes either K (steps by the bound signal tables) or actions=")
+        if isinstance(stride, bool) or int(stride) != stride:
+            raise TypeError("stride must be an integer")
+        if actions is not None:
+            if strategy is not None:
+                raise TypeError("strategy goes with K (signal tables), not with actions=")
+            actions = self._sequence_actions(actions, "backtest_curves")
+            K = int(actions.shape[0])
+        else:
+            if self._reward_callable is not None or self._dyn_callables:
+                raise NotImplementedError("a fused backtest runs all steps on the device: custom Python "
+                                          "reward / dynamic-feature callables need step()")
+            strategy = self._strategy(strategy, "backtest_curves")
+            K = int(K)
+        if K < 1:
+            raise ValueError("backtest_curves: K must be >= 1")
+        keep = dict(valuation=valuation, drawdown=drawdown, reward=reward, position=position, row=row, flags=flags)
+        dev = self._t["obs"].device
+        cols = {}
+        if int(stride) >= 1:  # (else the library refuses below, with its message)
+            cols = cv.take_out(torch, out, cv.column_shapes(torch, keep, K, int(stride), self.num_envs), dev)
+        b = _abi.GteCurveBufs()
+        for c, t in cols.items():
+            setattr(b, c, t.data_ptr())
+        ptr = C.c_void_p()
+        self._keep = (actions, cols)  # alive until the launch has consumed them
+        self._keep_strategy = strategy
+        _abi.check(self._lib, self._lib.gte_backtest_curves(
+            self._h, None if actions is None else C.c_void_p(actions.data_ptr()),
+            None if strategy is None else C.c_void_p(strategy.data_ptr()), K, int(stride), 0 if resume else 1,
+            C.byref(b), C.byref(ptr)))
+        self._stepped()
+        # (as after backtest() / backtest_signals(): what by_strategy() maps with)
+        self._backtest_map = None if actions is not None else (strategy, self.num_strategies)
+        return cv.Curves(self, cols, BacktestStats(self, ptr.value), K, int(stride))
+
     # -- exit rules: stop-loss, trailing stop, take-profit and time exits per strategy --------
     def bind_exits(self, rules, rule_of_env=None):
         """Bind exit rules (`gte_bind_exit_rules`): while they are bound, `signal_actions()` and

@@ -98,6 +98,8 @@ struct gte_env {
   // of its own (the terminal valuation is read from them); allocated by the first call
   gte_backtest_stats* bt_stats = nullptr;
   EnvRec* bt_final_rec = nullptr;
+  // gte_backtest_curves: the window of every env that is open between the fused launch and the fold (gte_curves.hip)
+  gte::CurveCarry* cv_carry = nullptr;
   // gte_track_trades: the trade records (allocated by the first call that turns tracking on), whether the
   // backtest calls maintain them, and whether that changed since the last backtest call (which then clears)
   gte_trade_stats* tr_stats = nullptr;
@@ -1074,7 +1076,9 @@ static hipError_t launch_lookup(gte_env* E, const int32_t* strategy, int32_t* ac
   return gte::launch_signal_actions(E->p, E->d_sig, E->sig_S, strategy, actions, E->stream);
 }
 
-static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy, int32_t n_steps, int32_t clear) {
+// With `cv` (gte_backtest_curves) the launches are those of gte_curves.hip, which write the rows as well.
+static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy, int32_t n_steps, int32_t clear,
+                    gte::Curves* cv = nullptr) {
   const size_t N = (size_t)E->p.N;
   const LaunchPlan& L = E->plan;
   const bool signals = actions == nullptr;
@@ -1083,6 +1087,10 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   // stands for those launches; backtest_entry withdraws it afterwards
   ledger().wrote(E, {flag_span(E, E->p.terminated), flag_span(E, E->p.truncated)}, false, WINDOW);
   if (signals && !E->d_sig_actions) TRY(dev_alloc_late(E, &E->d_sig_actions, N));
+  if (cv) {  // the window that is open between two launches of a call (gte_curves.hip), allocated by the first such call
+    if (!E->cv_carry) TRY(dev_alloc_late(E, &E->cv_carry, N));
+    cv->carry = E->cv_carry;
+  }
   if (!E->bt_stats) {
     if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->bt_final_rec, N));
     TRY(dev_alloc_late(E, &E->bt_stats, N));  // (its wait covers the fill before it too)
@@ -1120,7 +1128,8 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
     }
     const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
     TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->bt_final_rec));
-    const hipError_t fe = listed    ? gte::launch_trade_list_fold(ps, E->bt_stats, trades, tl, E->stream)
+    const hipError_t fe = cv        ? gte::launch_curve_fold(ps, E->bt_stats, *cv, k, n_steps, E->stream)
+                          : listed  ? gte::launch_trade_list_fold(ps, E->bt_stats, trades, tl, E->stream)
                           : trades  ? gte::launch_trade_fold(ps, E->bt_stats, trades, E->stream)
                           : periods ? gte::launch_period_fold(ps, E->bt_stats, per, E->stream)
                                     : gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
@@ -1128,18 +1137,21 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
     return GTE_OK;
   };
   if (!L.fused_rollout) {
-    report_rollout_path(signals ? "backtest signals per-step" : "backtest per-step", n_steps);
+    report_rollout_path(cv ? "backtest curves per-step" : signals ? "backtest signals per-step" : "backtest per-step",
+                        n_steps);
     for (int32_t k = 0; k < n_steps; ++k) TRY(step_and_fold(k));
     return GTE_OK;
   }
-  if (signals) report_rollout_path(n_steps > 1 ? "backtest signals summary" : "backtest signals per-step", n_steps);
+  if (cv) report_rollout_path(n_steps > 1 ? "backtest curves summary" : "backtest curves per-step", n_steps);
+  else if (signals) report_rollout_path(n_steps > 1 ? "backtest signals summary" : "backtest signals per-step", n_steps);
   else report_rollout_path(n_steps > 1 ? "backtest summary" : "backtest per-step", n_steps);
   if (n_steps > 1) {
     TRY(age_order(E, n_steps - 1));
     // one launch, its actions from `src`; with a tracker on, the unit that keeps that record in registers as well
     const gte::SummarySource src = {actions, E->d_sig, E->sig_S, strategy, E->exits.rules ? &E->exits : nullptr};
     const int32_t k = n_steps - 1, epw = L.state_epw;
-    le = listed    ? gte::launch_trade_list_summary(ps, src, E->bt_stats, trades, tl, k, epw, E->stream)
+    le = cv        ? gte::launch_curve_summary(ps, src, E->bt_stats, *cv, k, epw, E->stream)
+         : listed  ? gte::launch_trade_list_summary(ps, src, E->bt_stats, trades, tl, k, epw, E->stream)
          : trades  ? gte::launch_trade_summary(ps, src, E->bt_stats, trades, k, epw, E->stream)
          : periods ? gte::launch_period_summary(ps, src, E->bt_stats, per, k, epw, E->stream)
          : signals ? gte::launch_signal_summary(ps, src, E->bt_stats, k, epw, E->stream)
@@ -1151,7 +1163,8 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
 
 // what gte_backtest and gte_backtest_signals (`who`) share once their own arguments are checked
 static int backtest_entry(gte_env* E, const char* who, const int32_t* actions, const int32_t* strategy,
-                          int32_t n_steps, int32_t clear, gte_backtest_stats** stats_device) {
+                          int32_t n_steps, int32_t clear, gte_backtest_stats** stats_device,
+                          gte::Curves* cv = nullptr) {
   if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
   if (stream_capturing(E))
     return fail(GTE_ERR_STATE, "%s inside a stream capture: a backtest is one launch already, run it eagerly", who);
@@ -1160,7 +1173,7 @@ static int backtest_entry(gte_env* E, const char* who, const int32_t* actions, c
       if (!E->d_prow || !E->h_prow[d].base)
         return fail(GTE_ERR_STATE, "%s: period tracking is on and dataset %d has no period row (gte_bind_periods)", who, d);
   HIPCHK(hipSetDevice(E->cfg.device));
-  const int rc = backtest(E, actions, strategy, n_steps, clear);
+  const int rc = backtest(E, actions, strategy, n_steps, clear, cv);
   ledger().withdraw(E, FLAGS);  // (as after a rollout: the next step stores densely)
   if (stats_device) *stats_device = E->bt_stats;
   return rc;
@@ -1370,6 +1383,29 @@ int gte_backtest_signals(gte_env* E, const int32_t* strategy_device, int32_t n_s
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   TRY(signals_ready(E, "gte_backtest_signals"));
   return backtest_entry(E, "gte_backtest_signals", nullptr, strategy_device, n_steps, clear, stats_device);
+}
+
+int gte_backtest_curves(gte_env* E, const int32_t* actions, const int32_t* strategy_device, int32_t n_steps,
+                        int32_t stride, int32_t clear, const gte_curve_bufs* bufs, gte_backtest_stats** stats_device) {
+  const char* const who = "gte_backtest_curves";
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!E->was_reset) return fail(GTE_ERR_STATE, "%s before gte_reset", who);
+  if (!bufs) return fail(GTE_ERR_INVALID, "%s: bufs is NULL", who);
+  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
+  if (stride < 1) return fail(GTE_ERR_INVALID, "%s: stride %d must be >= 1", who, stride);
+  if (!bufs->valuation && !bufs->drawdown && !bufs->reward && !bufs->position && !bufs->row && !bufs->flags)
+    return fail(GTE_ERR_INVALID, "%s: all six columns are NULL, nothing to keep", who);
+  if (((uintptr_t)bufs->valuation | (uintptr_t)bufs->drawdown | (uintptr_t)bufs->reward) & 7)
+    return fail(GTE_ERR_INVALID, "%s: valuation, drawdown and reward must be 8-byte aligned", who);
+  if (((uintptr_t)bufs->position | (uintptr_t)bufs->row) & 3)
+    return fail(GTE_ERR_INVALID, "%s: position and row must be 4-byte aligned", who);
+  if (E->tr_on || E->pd_B > 0)
+    return fail(GTE_ERR_STATE, "%s: %s tracking is on, and a launch keeps one tracker (gte_track_%s(env, 0, ...) first)",
+                who, E->tr_on ? "trade" : "period", E->tr_on ? "trades" : "periods");
+  if (!actions) TRY(signals_ready(E, who));
+  // (the carry is the library's: backtest() allocates it, on the env's device, and fills it in)
+  gte::Curves cv = {nullptr, stride, *bufs};
+  return backtest_entry(E, who, actions, actions ? nullptr : strategy_device, n_steps, clear, stats_device, &cv);
 }
 
 int gte_bind_exit_rules(gte_env* E, const gte_exit_rule* rules_device, int32_t n_rules,

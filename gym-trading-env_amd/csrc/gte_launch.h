@@ -180,6 +180,26 @@ hipError_t launch_trade_list_scan(const gte_trade_stats* trades, const TradeList
 hipError_t launch_trade_list_pack(const TradeList& tl, int n_envs, const int32_t* ids, int n_ids, const int64_t* first,
                                   gte_trade* out, int64_t max_out, hipStream_t stream);
 
+// --- gte_curves.hip: the backtest launches above that also write per-step rows (gte_backtest_curves, include/gte.h)
+struct CurveCarry {  // the window of one env that is open between two launches of a call
+  double reward, drawdown;  // its reward sum and drawdown maximum so far
+  int32_t flags;            // ... and its GTE_CURVE_* bits
+  int32_t reserved[3];      // -> two 16-byte pieces
+};
+struct Curves {  // what the curve kernels are given
+  CurveCarry* carry;    // device [N], library-owned
+  int32_t stride;       // steps per row, >= 1
+  gte_curve_bufs bufs;  // the caller's columns [R][N], any of them null = not kept (last: DESIGN.md, "Curves")
+};
+// launch_backtest_summary / launch_signal_summary, whatever the source, with the rows of the windows that close
+// inside the launch written and the window open at its end left in c.carry; the launch begins a call
+hipError_t launch_curve_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats, const Curves& c,
+                                int n_steps, int epw, hipStream_t stream);
+// launch_backtest_fold for step k of a call of n_call steps: takes the open window from c.carry, writes the row
+// where the step closes a window or is the call's last, else leaves the window in c.carry
+hipError_t launch_curve_fold(const Params& p, gte_backtest_stats* stats, const Curves& c, int k, int n_call,
+                             hipStream_t stream);
+
 // --- gte_periods.hip: the backtest launches above with the period statistics (gte_track_periods, include/gte.h)
 // launch_backtest_summary with the open period's record in registers, whatever the source
 hipError_t launch_period_summary(const Params& p, const SummarySource& src, gte_backtest_stats* stats,

@@ -850,6 +850,66 @@ int gte_track_periods(gte_env* env, int32_t n_periods, gte_period_stats** record
  * ...): out holds count * B records of it, not of an earlier B.  GTE_ERR_STATE before the first such call. */
 int gte_read_period_stats(gte_env* env, int32_t first, int32_t count, gte_period_stats* out);
 
+/* ---- CURVES: a backtest that also keeps ROWS — the equity curve, the underwater curve and what goes with them,
+ * one row per `stride` steps and env, written by the launch that holds the step in registers.  This text is the
+ * specification; tests/curve_model.py states it as a per-env loop.
+ *
+ * A step of an env is one of three kinds (struct gte_backtest_stats, above): a TRANSITION (the env advanced:
+ * TradingEnv.step, environments.py:233-272); a RESET ROW (next-step auto-reset: the env was reset instead of
+ * stepping, TradingEnv.reset, :163-199); a FROZEN step (no auto-reset, the episode has ended and
+ * _step did not move).  In same-step mode a transition that ends an episode is followed by a reset inside the
+ * same step.
+ *
+ * WINDOW j of a call covers its steps j * stride .. min((j + 1) * stride, n_steps) - 1; the last window of a call
+ * may be shorter, and no window reaches into the next call.  Row j of a column is at column[j * N + e], R =
+ * ceil(n_steps / stride) rows; rows at and beyond R are not touched.  Every column is optional: a NULL pointer
+ * means that column is not kept and costs nothing.
+ *   valuation  Valuation of the window's LAST step.  Transition: the valuation v_t the statistics fold for it (in
+ *              same-step mode at an episode end that is the terminal record's, not the new episode's).  Reset row:
+ *              the new episode's start valuation.  Frozen: the env's valuation as it stands.
+ *   position   Position INDEX that belongs to that valuation: the terminal one at a same-step episode end, the
+ *              reset position on a reset row.
+ *   row        Market row that valuation was taken at.  Transition: the row the env stood on before the step + 1.
+ *              Reset row: the row the env landed on.  Frozen: unchanged.
+ *   reward     m = 0.0; then m = m + r_t for every transition of the window, t ascending: one IEEE f64 addition
+ *              each, starting from +0.0 — so a window whose only reward is -0.0 holds +0.0.
+ *   drawdown   m = 0.0; for every transition of the window d = 1.0 - v_t / peak', where peak' is the record's
+ *              running peak after `if (v_t > peak) peak = v_t` — the d of gte_backtest_stats —, then
+ *              if (d > m) m = d.  A window without a transition holds 0.0; a NaN never enters (plain comparison,
+ *              as in max_drawdown).
+ *   flags      OR over the window's steps of the GTE_CURVE_* bits below; TERMINATED and TRUNCATED are the flags of
+ *              its transitions.
+ * The record's peak restarts at resets and is carried from call to call with clear == 0, as it is today: after a
+ * call with clear != 0 the maximum of an env's drawdown column IS its max_drawdown, and at stride 1 adding its
+ * reward column in row order gives its reward_sum, both to the bit. */
+#define GTE_CURVE_TERMINATED 1 /* a transition of the window raised `terminated`                              */
+#define GTE_CURVE_TRUNCATED 2  /* ... `truncated`                                                             */
+#define GTE_CURVE_RESET 4      /* a reset happened in a step of the window: a next-step reset row, or the
+                                  reset after a same-step episode end                                         */
+#define GTE_CURVE_FROZEN 8     /* a step of the window was frozen                                             */
+typedef struct gte_curve_bufs {
+  double  *valuation, *drawdown, *reward; /* DEVICE f64 [R][N] each, 8-byte aligned, or NULL */
+  int32_t *position, *row;                /* DEVICE i32 [R][N], 4-byte aligned, or NULL      */
+  uint8_t *flags;                         /* DEVICE u8  [R][N], or NULL                      */
+} gte_curve_bufs;
+/* n_steps TradingEnv.step calls (environments.py:233-272) exactly like gte_backtest (actions != NULL: DEVICE int32
+ * [n_steps][N]) or gte_backtest_signals (actions == NULL: the bound signal tables, and the exit rules while they
+ * are bound; strategy_device as there, ignored with actions) — the same records bit for bit, `clear`, post-state,
+ * *stats_device — that also write the rows above into bufs.  Where gte_rollout fuses, n_steps - 1 steps run in
+ * one launch of gte_curves.hip (the from-registers kernels with a tracker that stores a row whenever a window
+ * closes) and the last one as a step launch folded in by gte_curve_fold_kernel, which also closes the call's last
+ * window; a window open where the two meet travels in a library-owned 32-byte scratch per env.  Elsewhere every
+ * step is a step launch plus that fold.  The rows do not depend on the path.  Without this call every other call
+ * launches the kernels it launched before.
+ * Refused, with nothing launched and nothing written: GTE_ERR_INVALID for bufs == NULL or all six columns NULL,
+ * stride < 1, n_steps < 1, a column not aligned to its element; GTE_ERR_STATE while trade tracking (the trade
+ * list included) or period tracking is on — one tracker per launch, as trades and periods exclude each other —,
+ * inside a stream capture, before gte_reset, and with actions == NULL while a resident dataset has no signal
+ * table bound (as gte_backtest_signals).  The caller keeps the columns alive until the env's stream has run the
+ * call. */
+int gte_backtest_curves(gte_env* env, const int32_t* actions, const int32_t* strategy_device, int32_t n_steps,
+                        int32_t stride, int32_t clear, const gte_curve_bufs* bufs, gte_backtest_stats** stats_device);
+
 /* ---- SIGNAL TABLES BUILT ON THE DEVICE from indicator rules: a parameter sweep passes a small bank of
  * indicators and one 32-byte rule per strategy, and the device writes the int8 [n_rules][T] table that
  * gte_bind_signals accepts — no host table, no host-to-device copy of it.
