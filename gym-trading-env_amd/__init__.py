@@ -11,7 +11,8 @@ from ._abi import GteError  # noqa: F401
 
 __all__ = ["TradingEnv", "MultiDatasetTradingEnv", "BatchedTradingEnv", "SB3TradingVecEnv", "GteError",
            "BacktestStats", "StrategyStats", "ExitState", "TradeStats", "StrategyTradeStats", "TradeList",
-           "PeriodStats", "StrategyPeriodStats", "RealityCheck", "OverfitCheck", "Diversified", "Curves", "periods",
+           "PeriodStats", "StrategyPeriodStats", "RealityCheck", "OverfitCheck", "Diversified", "Curves", "TradeMonteCarlo",
+           "monte_carlo", "periods",
            "basic_reward_function", "dynamic_feature_last_position_taken",
            "dynamic_feature_real_position"]
 
@@ -25,14 +26,14 @@ _LAZY = {
     "TradeStats": "trade_stats", "StrategyTradeStats": "trade_stats", "TradeList": "trade_list",
     "PeriodStats": "period_stats", "StrategyPeriodStats": "period_stats",
     "RealityCheck": "reality_check", "OverfitCheck": "overfit", "Diversified": "diversify",
-    "Curves": "curves",
+    "Curves": "curves", "TradeMonteCarlo": "monte_carlo",
 }
 
 
 def __getattr__(name):
-    if name == "periods":  # (a plain NumPy module: period rows for BatchedTradingEnv.track_periods)
+    if name in ("periods", "monte_carlo"):  # (modules: period rows for track_periods; resample() over own pools)
         import importlib
-        return importlib.import_module(f"{__name__}.periods")
+        return importlib.import_module(f"{__name__}.{name}")
     if name in _LAZY:
         import importlib
         mod = importlib.import_module(f"{__name__}.{_LAZY[name]}")

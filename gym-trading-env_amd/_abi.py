@@ -87,6 +87,14 @@ GTE_CSCV_MAX_SPLITS = 65536
 GTE_CSCV_CHUNK = 256
 #: the period metrics gte_cscv scores by
 CSCV_METRICS = ("mean_reward", "sharpe", "reward_sum")
+# gte_trade_monte_carlo: resamples per slab of the sums, the most resamples, pools, path length and drawdown levels of
+# one call, and the largest pool the walk stages into LDS
+GTE_MC_SLAB = 256
+GTE_MC_MAX_RESAMPLES = 65536
+GTE_MC_MAX_POOLS = 65536
+GTE_MC_MAX_PATH = 1 << 20
+GTE_MC_MAX_LEVELS = 8
+GTE_MC_LDS_POOL = 8192
 
 
 class GteError(RuntimeError):
@@ -310,6 +318,21 @@ class GteDiversifyOut(C.Structure):
                                           "summary")]
 
 
+#: struct gte_mc_pool (include/gte.h), in declaration order: one 48-byte record per pool
+MC_POOL_DTYPE = [(n, "<f8") for n in ("final_sum", "final_sq_sum", "mdd_sum", "mdd_sq_sum")] + \
+    [(n, "<i4") for n in ("count_loss", "count_ruin", "pool_size", "path_len")]
+
+
+class GteMcPool(C.Structure):
+    """struct gte_mc_pool (include/gte.h)."""
+    _fields_ = [(n, {"<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in MC_POOL_DTYPE]
+
+
+class GteMcOut(C.Structure):
+    """struct gte_mc_out (include/gte.h): device pointers, kept as integers; the four columns may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("final", "max_drawdown", "low", "max_loss_streak", "pool", "dd_count")]
+
+
 #: struct gte_strategy_stats (include/gte.h), in declaration order: one 128-byte record per strategy
 STRATEGY_FIELDS = [("steps", "<i8")] + \
     [(n, "<f8") for n in ("reward_sum", "reward_sq_sum", "ep_return_sum", "ep_return_sq_sum", "max_drawdown",
@@ -529,6 +552,10 @@ SYMBOLS = {
                            C.c_int32, C.c_int32, _P(GteCscvOut)]),
     "gte_diversify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_void_p, C.c_double,
                                 C.c_int32, _P(GteDiversifyOut)]),
+    "gte_pool_trades": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int64]),
+    "gte_trade_monte_carlo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_uint64, C.c_double, _P(C.c_double), C.c_int32, _P(GteMcOut)]),
     "gte_build_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_int64]),
     "gte_compose_signals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,

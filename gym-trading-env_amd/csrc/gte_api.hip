@@ -137,9 +137,9 @@ struct gte_env {
   double* rank_score[2] = {nullptr, nullptr};
   int32_t* rank_index[2] = {nullptr, nullptr};
   int64_t rank_entries[2] = {0, 0};
-  // gte_reality_check, gte_cscv, gte_diversify: the scratch of each (gte_bootstrap.hip, gte_cscv.hip,
-  // gte_diversify.hip), a block of its own that grow() keeps the same way
-  Scratch boot_scratch, cscv_scratch, div_scratch;
+  // gte_reality_check, gte_cscv, gte_diversify, gte_trade_monte_carlo: the scratch of each (gte_bootstrap.hip,
+  // gte_cscv.hip, gte_diversify.hip, gte_montecarlo.hip), a block of its own that grow() keeps the same way
+  Scratch boot_scratch, cscv_scratch, div_scratch, mc_scratch;
   bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
   // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
   void* comm = nullptr;
@@ -1262,6 +1262,12 @@ static int check_n_resamples(int32_t n_resamples) {
   return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
 }
 
+// the pools of gte_pool_trades and gte_trade_monte_carlo
+static int check_n_pools(int32_t n_pools) {
+  if (n_pools >= 1 && n_pools <= GTE_MC_MAX_POOLS) return GTE_OK;
+  return fail(GTE_ERR_INVALID, "n_pools %d outside [1, %d]", n_pools, GTE_MC_MAX_POOLS);
+}
+
 // every pointer of the list set, and none with a bit of `low_bits` (alignment less one) in its address
 static bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t low_bits) {
   uintptr_t address_bits = 0;
@@ -1993,6 +1999,69 @@ int gte_diversify(gte_env* E, const gte_strategy_period_stats* stats_device, int
   return launched(gte::launch_diversify(stats_device, n_strategies, n_periods, period_mask, n, scores_device, max_corr,
                                         k, *out, E->div_scratch.base, E->stream),
                   "diversify");
+}
+
+int gte_pool_trades(gte_env* E, int32_t n_strategies, const int32_t* group_offsets_device,
+                    const int32_t* group_envs_device, const int32_t* strategies_device, int32_t n_pools,
+                    int64_t* first_device, int32_t* truncated_device, double* factors_device, int64_t max_factors) {
+  TRY(check_strategies(E, n_strategies));
+  TRY(check_n_pools(n_pools));
+  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
+    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
+  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
+    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
+  if (!all_aligned({strategies_device, truncated_device}, 3))
+    return fail(GTE_ERR_INVALID, "strategies_device and truncated_device (int32 [n_pools]) must be 4-byte aligned device pointers");
+  if (!all_aligned({first_device}, 7))
+    return fail(GTE_ERR_INVALID, "first_device (int64 [n_pools + 1]) must be an 8-byte aligned device pointer");
+  if (max_factors < 0 || (max_factors > 0 && !factors_device) || ((uintptr_t)factors_device & 7))
+    return fail(GTE_ERR_INVALID, "factors_device (f64 [max_factors]) is NULL or not 8-byte aligned, or max_factors < 0");
+  TRY(trade_list_on(E, "gte_pool_trades"));
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_pool_trades inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
+  hipError_t le = gte::launch_pool_count(E->tr_stats, tl, E->p.N, n_strategies, E->cfg.env_id_base,
+                                         group_offsets_device, group_envs_device, strategies_device, n_pools,
+                                         first_device, truncated_device, E->stream);
+  if (le == hipSuccess && max_factors > 0)
+    le = gte::launch_pool_pack(E->tr_stats, tl, E->p.N, n_strategies, E->cfg.env_id_base, group_offsets_device,
+                               group_envs_device, strategies_device, n_pools, first_device, factors_device,
+                               max_factors, E->stream);
+  return launched(le, "trade pool");
+}
+
+int gte_trade_monte_carlo(gte_env* E, const double* factors_device, const int64_t* first_device,
+                          const uint32_t* stream_device, int32_t n_pools, int32_t n_resamples, int32_t path_len,
+                          uint64_t seed, double ruin_level, const double* dd_levels, int32_t n_levels,
+                          const gte_mc_out* out) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  TRY(check_n_pools(n_pools));
+  if (n_resamples < 1 || n_resamples > GTE_MC_MAX_RESAMPLES)
+    return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_MC_MAX_RESAMPLES);
+  if (path_len < 0 || path_len > GTE_MC_MAX_PATH)
+    return fail(GTE_ERR_INVALID, "path_len %d outside [0, %d]", path_len, GTE_MC_MAX_PATH);
+  if (n_levels < 0 || n_levels > GTE_MC_MAX_LEVELS)
+    return fail(GTE_ERR_INVALID, "n_levels %d outside [0, %d]", n_levels, GTE_MC_MAX_LEVELS);
+  if (ruin_level != ruin_level) return fail(GTE_ERR_INVALID, "ruin_level is NaN");
+  if (!all_aligned({factors_device, first_device}, 7))
+    return fail(GTE_ERR_INVALID, "factors_device (f64) and first_device (int64 [n_pools + 1]) must be 8-byte aligned device pointers");
+  if ((uintptr_t)stream_device & 3) return fail(GTE_ERR_INVALID, "stream_device must be 4-byte aligned");
+  if (n_levels > 0 && !all_aligned({dd_levels}, 7))
+    return fail(GTE_ERR_INVALID, "dd_levels must be an 8-byte aligned host array of n_levels doubles");
+  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
+  if (!all_aligned({out->pool}, 15)) return fail(GTE_ERR_INVALID, "out: pool must be a 16-byte aligned device pointer");
+  if (((uintptr_t)out->final & 7) || ((uintptr_t)out->max_drawdown & 7) || ((uintptr_t)out->low & 7) ||
+      ((uintptr_t)out->max_loss_streak & 3))
+    return fail(GTE_ERR_INVALID, "out: final, max_drawdown and low must be 8-byte, max_loss_streak 4-byte aligned device pointers");
+  if (((uintptr_t)out->dd_count & 3) || (n_levels > 0 && !out->dd_count))
+    return fail(GTE_ERR_INVALID, "out: dd_count (int32 [n_pools * n_levels]) must be a 4-byte aligned device pointer");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_trade_monte_carlo inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  TRY(grow(E, &E->mc_scratch, gte::monte_carlo_scratch_bytes(n_pools, n_resamples, n_levels)));
+  return launched(gte::launch_trade_monte_carlo(factors_device, first_device, stream_device, n_pools, n_resamples,
+                                                path_len, seed, ruin_level, dd_levels, n_levels, *out,
+                                                E->mc_scratch.base, E->stream),
+                  "trade Monte Carlo");
 }
 
 int gte_add_limit_orders(gte_env* E, const int32_t* pos_index, const double* limit,

@@ -262,7 +262,8 @@ hipError_t launch_period_scores(const gte_strategy_period_stats* stats, int n_st
                                 const uint64_t period_mask[2], int metric, int64_t min_steps, double* scores,
                                 double* cand_score, int32_t* cand_index, hipStream_t stream);
 
-// --- the three leaderboard analyses below (gte_bootstrap.hip, gte_cscv.hip, gte_diversify.hip) each carve their
+// --- the three leaderboard analyses below (gte_bootstrap.hip, gte_cscv.hip, gte_diversify.hip) and the trade Monte
+// Carlo (gte_montecarlo.hip) each carve their
 // library-owned scratch out of one allocation with this: take<T>(count) is the next piece, every piece 256-byte
 // aligned; `at` ends as the bytes the pieces need, which is all a carver over a null base is asked for
 struct ScratchCarver {
@@ -308,6 +309,26 @@ size_t diversify_scratch_bytes(int n_strategies, int n, int k);
 hipError_t launch_diversify(const gte_strategy_period_stats* stats, int n_strategies, int n_periods,
                             const uint64_t period_mask[2], int n, const double* scores, double max_corr, int k,
                             const gte_diversify_out& out, void* scratch, hipStream_t stream);
+
+// --- gte_montecarlo.hip: the trade Monte Carlo (gte_pool_trades, gte_trade_monte_carlo, include/gte.h); the caller
+// has checked alignments and that the group pointers are both null or both set
+// strategies (device i32 [n_pools]) -> first[0 .. n_pools], the running sum of the pools' sizes, and truncated[q]
+hipError_t launch_pool_count(const gte_trade_stats* trades, const TradeList& tl, int n_envs, int n_strategies,
+                             int64_t env_id_base, const int32_t* group_offsets, const int32_t* group_envs,
+                             const int32_t* strategies, int n_pools, int64_t* first, int32_t* truncated,
+                             hipStream_t stream);
+// ... and the factors of request q to factors[first[q] ..), those below max_factors only
+hipError_t launch_pool_pack(const gte_trade_stats* trades, const TradeList& tl, int n_envs, int n_strategies,
+                            int64_t env_id_base, const int32_t* group_offsets, const int32_t* group_envs,
+                            const int32_t* strategies, int n_pools, const int64_t* first, double* factors,
+                            int64_t max_factors, hipStream_t stream);
+// bytes of library-owned scratch one resampling of n_pools pools, R resamples and n_levels drawdown levels needs
+size_t monte_carlo_scratch_bytes(int n_pools, int n_resamples, int n_levels);
+// the walk and the close (dd_levels: host, read before this returns)
+hipError_t launch_trade_monte_carlo(const double* factors, const int64_t* first, const uint32_t* streams, int n_pools,
+                                    int n_resamples, int path_len, uint64_t seed, double ruin_level,
+                                    const double* dd_levels, int n_levels, const gte_mc_out& out, void* scratch,
+                                    hipStream_t stream);
 
 // --- gte_aux.hip: trajectory log, values computed outside the step kernel, packed reads
 hipError_t launch_log(const EnvRec* rec, const double* reward64, const uint8_t* term, const uint8_t* trunc, int n,

@@ -128,3 +128,18 @@ class StrategyTradeStats(StrategyRecords):
         ranked strategies).  Ranked are those with at least max(1, `min_trades`) closed trades and a score that
         is not NaN; equal scores order by index.  Waits for the device, like `StrategyStats.top`."""
         return self._top(metric, min_trades, k)
+
+    def monte_carlo(self, strategies, n_resamples=1000, n_trades=None, seed=0, ruin=0.5,
+                    drawdown_levels=(0.1, 0.2, 0.3, 0.5), keep=("final", "max_drawdown")) -> "TradeMonteCarlo":
+        """How bad can these strategies get?  A Monte Carlo over the closed trades of each of `strategies` (ids on
+        the host, or an int32 CUDA tensor such as ``top(k)[0]``, which then never visits the host): `n_resamples`
+        paths of `n_trades` trades (None: as many as the strategy closed) drawn with replacement from the trade lists
+        of its member envs (`track_trades(list_capacity=...)`, the member lists of this fold) and compounded, all on
+        the device (`gte_pool_trades`, `gte_trade_monte_carlo`).  `ruin`: the equity level whose touch counts as ruin;
+        `drawdown_levels`: the drawdowns whose probability is counted; `keep`: the per-path columns to keep, of
+        ``final``, ``max_drawdown``, ``low``, ``max_loss_streak``.  A strategy's paths depend on its id, the seed and
+        its trades alone, not on who else was asked for; an id outside [0, S), such as a ranking's -1 padding, gives
+        an empty pool.  Like `trades()` it reads what the live lists hold when it runs.  Waits once, for the number
+        of trades, to size the block of factors.  Returns a `TradeMonteCarlo`."""
+        from .monte_carlo import run
+        return run(self, strategies, n_resamples, n_trades, seed, ruin, drawdown_levels, keep)

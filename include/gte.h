@@ -1494,6 +1494,98 @@ int gte_diversify(gte_env* env, const gte_strategy_period_stats* stats_device, i
                   int32_t n_periods, const uint64_t period_mask[2], const double* scores_device /* [n_strategies] */,
                   double max_corr, int32_t k, const gte_diversify_out* out);
 
+/* ---- TRADE MONTE CARLO: how bad can a chosen strategy get?  Its realised maximum drawdown and losing streak are
+ * ONE ordering of its closed trades.  Draw trades with replacement from its trade list, compound them, and read the
+ * distribution of final equity, maximum drawdown, lowest equity and losing streak — for many strategies at once, on
+ * the device.  One fixed order of IEEE f64 operations, every one of them ONE operation as written (no fused
+ * multiply-add), comparisons plain: the same inputs give the same bits for any launch geometry.  The walk step, the
+ * index mapping and the slab tree below are also stated as plain C++ in include/gte_mc.h, which a host program can
+ * compile to replay them.
+ *
+ * THE POOLS, gte_pool_trades.  Builds the pool of trade factors of each requested strategy from the env's live
+ * trade list (gte_track_trade_list).  MEMBERS and the skipping rule are exactly those of gte_reduce_backtest_stats
+ * (both group pointers NULL = the library's map over env_id_base; an entry that names no env in [0, N) is skipped).
+ * The pool of request q: the members of strategy strategies[q] in member order; of each member its first
+ * min(closed, capacity) list records in close order; each record contributes
+ *     factor = close_value / open_value                    (one f64 division; NaN, inf, 0 and negatives kept as they are)
+ * A strategy id outside [0, n_strategies) — the -1 padding of a ranking — gives an empty pool.  WRITTEN:
+ *     first[q], q = 0 .. n_pools    the running sum of the pools' sizes; first[n_pools] is always the full total
+ *     truncated[q]                  the number of members with closed > capacity (their lists kept the first ones)
+ *     factors[first[q] ..)          the pool of request q; a factor at or past max_factors is not written
+ * The two-pass protocol of gte_pack_trade_list: factors_device NULL with max_factors 0 counts only.  One
+ * count-and-scan launch and one pack launch on the env's stream, no atomics, no host synchronisation.
+ * GTE_ERR_INVALID, with nothing launched, for: a NULL env; n_pools outside [1, GTE_MC_MAX_POOLS]; n_strategies < 1;
+ * exactly one group pointer NULL; a NULL strategies_device, first_device or truncated_device; max_factors < 0, or
+ * > 0 with a NULL factors_device; a pointer not aligned for its type (i32: 4, i64 and f64: 8).  GTE_ERR_STATE
+ * exactly where gte_pack_trade_list returns it (the list is off, or was switched and not cleared since), and inside
+ * a stream capture.
+ *
+ * THE RESAMPLING, gte_trade_monte_carlo.  No tie to the trade list: factors_device / first_device are any pools — the
+ * ones above, a caller's own returns, a synthetic test.  Pool q is factors[first[q] .. first[q + 1]), its size
+ * P = first[q + 1] - first[q].  A pool with first[q + 1] < first[q], with P >= 2^31, or that reaches outside
+ * [first[0], first[n_pools]) is treated as EMPTY (P = 0): no content of `first` makes a kernel read outside
+ * factors[first[0] .. first[n_pools]).  THE CALLER'S OBLIGATION: first_device holds n_pools + 1 entries, and
+ * factors_device[first[0]] .. factors_device[first[n_pools] - 1] is readable device memory.  L = path_len if it is positive, else
+ * min(P, GTE_MC_MAX_PATH); L = 0 for an empty pool.  stream[q] is stream_device[q], or q when that is NULL.
+ * Per resample r = 0 .. n_resamples-1:
+ *     e = 1.0; peak = 1.0; mdd = 0.0; low = 1.0; streak = 0; max_streak = 0
+ *     for i = 0 .. L-1:
+ *         o = philox4x32_10(counter = {i >> 2, r, stream[q], 0x54524D43 'TRMC'}, key = {seed low word, seed high word})
+ *         j = mulhi32(o[i & 3], P);  f = factors[first[q] + j]
+ *         e = e * f
+ *         if (e > peak) peak = e
+ *         d = 1.0 - e / peak;  if (d > mdd) mdd = d
+ *         if (e < low) low = e
+ *         if (f < 1.0) { streak += 1; if (streak > max_streak) max_streak = streak; } else streak = 0
+ * Row r depends on (seed, stream[q], r, i) and the pool alone: not on n_resamples, not on the slot q.
+ * WRITTEN, R = n_resamples:
+ *     final, max_drawdown, low [q * R + r]   e, mdd, low after the walk (f64); max_loss_streak [q * R + r] max_streak
+ *                      (i32).  Each of the four may be NULL: it is then not written and costs no store.
+ *     pool[q]          final_sum, final_sq_sum (of final * final), mdd_sum, mdd_sq_sum (of mdd * mdd): resamples cut
+ *                      into slabs of GTE_MC_SLAB; within a slab 256 places hold x of resample slab * 256 + i, a
+ *                      place past R holds 0.0, then for h = 128, 64, ..., 1: x[i] = x[i] + x[i + h] for i < h; the
+ *                      slabs' x[0] added from 0.0 in ascending slab order.  count_loss: resamples with
+ *                      final < 1.0; count_ruin: with low <= ruin_level; pool_size = P; path_len = L.  Counts exact.
+ *     dd_count[q * n_levels + k]    resamples with mdd >= dd_levels[k]   (dd_levels: HOST f64 [n_levels], read
+ *                      before the call returns; may be NULL when n_levels is 0)
+ * A walk launch (one workgroup of 256 lanes = one slab of one pool, a lane a resample; a pool of at most
+ * GTE_MC_LDS_POOL factors is staged into LDS once, a larger one is read from global memory — the same bits either
+ * way) and a close launch on the env's stream; no atomics, no host synchronisation; the slabs' partial results live
+ * in library-owned scratch, allocated by the first call and again when a call outgrows it (as gte_reality_check
+ * keeps its own).  The inputs are only read; the outputs must not overlap them or each other.
+ * GTE_ERR_INVALID, with nothing launched and nothing written, for: a NULL env, factors_device, first_device, out,
+ * out->pool, or out->dd_count with n_levels > 0, or dd_levels with n_levels > 0; a pointer not aligned for its type
+ * (f64 and i64: 8; i32 and u32: 4; pool: 16); n_pools outside [1, GTE_MC_MAX_POOLS]; n_resamples outside
+ * [1, GTE_MC_MAX_RESAMPLES]; path_len outside [0, GTE_MC_MAX_PATH]; n_levels outside [0, GTE_MC_MAX_LEVELS]; a NaN
+ * ruin_level.  GTE_ERR_STATE inside a stream capture. */
+#define GTE_MC_SLAB 256
+#define GTE_MC_MAX_RESAMPLES 65536
+#define GTE_MC_MAX_POOLS 65536
+#define GTE_MC_MAX_PATH (1 << 20)
+#define GTE_MC_MAX_LEVELS 8
+#define GTE_MC_LDS_POOL 8192
+int gte_pool_trades(gte_env* env, int32_t n_strategies, const int32_t* group_offsets_device,
+                    const int32_t* group_envs_device, const int32_t* strategies_device /* [n_pools] */,
+                    int32_t n_pools, int64_t* first_device /* [n_pools + 1] */,
+                    int32_t* truncated_device /* [n_pools] */, double* factors_device /* [max_factors] or NULL */,
+                    int64_t max_factors);
+typedef struct gte_mc_pool {                 /* 48 bytes, three 16-byte pieces */
+  double  final_sum, final_sq_sum;
+  double  mdd_sum, mdd_sq_sum;
+  int32_t count_loss, count_ruin, pool_size, path_len;
+} gte_mc_pool;
+typedef struct gte_mc_out {                  /* DEVICE pointers */
+  double  *final, *max_drawdown, *low;       /* f64 [n_pools * n_resamples], each may be NULL */
+  int32_t *max_loss_streak;                  /* i32 [n_pools * n_resamples], may be NULL */
+  gte_mc_pool* pool;                         /* [n_pools], required */
+  int32_t *dd_count;                         /* i32 [n_pools * n_levels], required when n_levels > 0 */
+} gte_mc_out;
+int gte_trade_monte_carlo(gte_env* env, const double* factors_device, const int64_t* first_device,
+                          const uint32_t* stream_device /* [n_pools] or NULL: q */, int32_t n_pools,
+                          int32_t n_resamples, int32_t path_len /* 0: the pool's size */, uint64_t seed,
+                          double ruin_level, const double* dd_levels /* HOST [n_levels] */, int32_t n_levels,
+                          const gte_mc_out* out);
+
 /* Where the results of the last gte_step / gte_reset live (device pointers). */
 int gte_get_outputs(gte_env* env, gte_outputs* out);
 /* Same-step auto-reset with gte_config.final_obs: struct-of-arrays snapshot (device pointers,
