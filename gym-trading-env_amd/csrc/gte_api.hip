@@ -1,200 +1,13 @@
-// gte_api.hip — host side of libgte: the C ABI declared in include/gte.h.
+// gte_api.hip — host side of libgte: the C ABI declared in include/gte.h.  This unit: create / destroy, datasets,
+// the step path with all that launches through it (step, rollout, backtest()), outputs, state, the error channel;
+// the other entry points in gte_api_backtest / _leaderboard / _read.hip and gte_comm.hip (shared: gte_host.h).
 //
 // Owns the HBM-resident datasets, per-env state and outputs, validates the
 // arguments the way the reference constructor / reset do
 // (environments.py:79-125,163-199) and launches the kernels of
 // the other units (gte_launch.h).  No CPU path exists: without a gfx950 device every entry
 // point that needs one fails with GTE_ERR_NO_DEVICE.
-#include <hip/hip_runtime.h>
-
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <initializer_list>
-#include <new>
-#include <string>
-#include <utility>
-#include <vector>
-
-#include "gte_launch.h"
-#include "gte_ledger.h"
-#include "gte_plan.h"
-
-using gte::DatasetDesc;
-using gte::EnvRec;
-using gte::Params;
-using gte_plan::LaunchPlan;
-using gte_plan::SLIDE_AB_ORDER;
-using gte_ledger::FLAGS;
-using gte_ledger::WINDOW;
-using gte_ledger::ledger;
-
-static thread_local std::string g_err = "";
-
-static int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIPCHK(expr)                                                              \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(e_ == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP,          \
-                  "%s failed: %s", #expr, hipGetErrorString(e_));                 \
-  } while (0)
-
-// a library-owned device block that only grows: grow(), below, with the leaderboard analyses' checks
-struct Scratch { void* base = nullptr; size_t bytes = 0; };
-
-struct gte_env {
-  gte_config cfg;
-  Params p;
-  int n_cu = 0;  // compute units of cfg.device (require_device)
-  hipStream_t stream = nullptr;
-  hipStream_t own_stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<void*> allocs;       // everything freed in gte_destroy
-  std::vector<DatasetDesc> h_ds;   // host copy of the descriptor table
-  std::vector<void*> ds_allocs[4]; // per dataset: feat, close, high, low
-  DatasetDesc* d_ds = nullptr;
-  gte_outputs owned;
-  // staging buffers for host-side arguments
-  int32_t* d_actions = nullptr;
-  uint8_t* d_mask = nullptr;
-  int32_t *d_inj_idx = nullptr, *d_inj_pos = nullptr, *d_inj_ds = nullptr;
-  int32_t *d_q_idx = nullptr, *d_q_pos = nullptr, *d_q_ds = nullptr;
-  double* d_lo_limit_in = nullptr;  // staging for gte_add_limit_orders
-  uint8_t* d_lo_persist_in = nullptr;
-  bool finalized = false;
-  bool was_reset = false;
-  LaunchPlan plan;  // every launch choice, decided by the rules of gte_plan.h (plan_launches, finalize, rollout)
-  int32_t* term_base = nullptr;  // the two-slot terminal counter in use (owned or bound)
-  int term_slot = 0;       // slot the last launch added to
-  // L2-affinity processing order (plan.affinity_period)
-  int steps_since_rebuild = 0;
-  int32_t* d_perm = nullptr;
-  int32_t* d_slot_of_rank = nullptr;
-  int32_t* d_bins = nullptr;
-  gte::StateSoA soa = {};  // host-facing struct-of-arrays mirrors (gte_get_state)
-  gte::StateSoA fsoa = {}; // the same for the terminal records (gte_get_final_state)
-  gte::LogArrays log = {}; // device trajectory log (cfg.log_steps rows per env)
-  // Log cursor: the row count on the device, i64 [2] (log_cursor_other, gte_device.h).  A launch
-  // that appends a row when the terminal counter's slot is s reads log_cursor[s ^ 1] and writes
-  // log_cursor[s]; so whenever the stream is idle log_cursor[term_slot] == log_rows, the host's
-  // mirror of it (gte_get_log().rows, the host-side reads), which every host-side change of
-  // term_slot keeps true (park_cursor).  Nothing enqueued depends on a row index computed here.
-  int64_t* log_cursor = nullptr;
-  int64_t log_rows = 0;
-  int32_t* d_group_counter = nullptr; // the resident kernel's work queue (next group of envs)
-  // gte_backtest: the statistics records and, in same-step mode without final_obs, terminal records
-  // of its own (the terminal valuation is read from them); allocated by the first call
-  gte_backtest_stats* bt_stats = nullptr;
-  EnvRec* bt_final_rec = nullptr;
-  // gte_backtest_curves: the window of every env that is open between the fused launch and the fold (gte_curves.hip)
-  gte::CurveCarry* cv_carry = nullptr;
-  // gte_track_trades: the trade records (allocated by the first call that turns tracking on), whether the
-  // backtest calls maintain them, and whether that changed since the last backtest call (which then clears)
-  gte_trade_stats* tr_stats = nullptr;
-  bool tr_on = false, tr_changed = false;
-  // gte_track_trade_list: the [N][tl_cap] list (tl_cap == 0: off; tl_alloc_cap: the capacity it was allocated
-  // for) and the open_row of every env; a change sets tr_changed.  gte_read_trade_list: its device block (ids,
-  // first, closed, trades) and the host copy `out` points into
-  gte_trade* tl_list = nullptr;
-  int32_t* tl_open_row = nullptr;
-  int32_t tl_cap = 0, tl_alloc_cap = 0;
-  void* tl_dev = nullptr;
-  size_t tl_dev_bytes = 0;
-  void* tl_host = nullptr;
-  size_t tl_host_bytes = 0;
-  // gte_track_periods / gte_bind_periods: the [N][pd_B] period records (pd_B == 0: tracking off; pd_alloc_B: the B
-  // they were allocated for), whether tracking, B or a row changed since the last backtest call (which then
-  // clears), and the period row of every dataset (base null = none bound; the base IS the library's allocation)
-  // on the host and on the device
-  gte_period_stats* pd_stats = nullptr;
-  int32_t pd_B = 0, pd_alloc_B = 0;
-  bool pd_changed = false;
-  std::vector<gte::PeriodRow> h_prow;
-  gte::PeriodRow* d_prow = nullptr;
-  // signal tables (gte_bind_signals): one descriptor per dataset (base null = none bound), the host
-  // copy and the device array the kernels read; the lookup's output for gte_backtest_signals
-  std::vector<gte::SignalTable> h_sig;
-  gte::SignalTable* d_sig = nullptr;
-  int32_t sig_S = 0;  // strategies of every bound table (0 = none bound)
-  int32_t* d_sig_actions = nullptr;
-  // exit rules (gte_bind_exit_rules): the caller's rules and map (rules null = none bound) and the per-env
-  // state, allocated by the first bind
-  gte::ExitRules exits = {nullptr, nullptr, nullptr, 0};
-  // gte_rank_strategies: the two candidate lists (gte_strategy.hip), allocated by the first call and
-  // again when S outgrows them (the old ones stay until gte_destroy: launches in flight may read them)
-  double* rank_score[2] = {nullptr, nullptr};
-  int32_t* rank_index[2] = {nullptr, nullptr};
-  int64_t rank_entries[2] = {0, 0};
-  // gte_reality_check, gte_cscv, gte_diversify, gte_trade_monte_carlo: the scratch of each (gte_bootstrap.hip,
-  // gte_cscv.hip, gte_diversify.hip, gte_montecarlo.hip), a block of its own that grow() keeps the same way
-  Scratch boot_scratch, cscv_scratch, div_scratch, mc_scratch;
-  bool timer_marked = false;  // gte_timer_stop(NULL) recorded the end event already
-  // multi-GPU return exchange (gte_comm.hip): one RCCL communicator per env
-  void* comm = nullptr;
-  int comm_rank = 0, comm_world = 0;
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t comm_ready = nullptr;
-  hipEvent_t comm_done[4] = {nullptr, nullptr, nullptr, nullptr};  // ring: one per overlapped gather
-  int64_t comm_seq = 0;                                              // overlapped gathers so far
-  uint8_t* gathered_returns = nullptr;  // u8 [world, 6N], library-owned destination
-  void* h_snap = nullptr;  // pinned host memory for gte_read_envs: snapshots, then observations
-  size_t h_snap_bytes = 0;
-  bool view_reads = false; // gte_read_envs_view has been used: the buffer is kept at full size
-  void* h_logpack = nullptr;  // pinned host memory for gte_read_log_envs
-  size_t h_logpack_bytes = 0;
-  // sliding observation buffer (gte_bind_sliding_obs).  p.obs is its base, p.obs_rows = W + M and p.obs_head
-  // the head the last launch wrote at.  Whether the next step may slide, or store its flags sparsely, is
-  // for the ledger to say (gte_ledger.h)
-  bool sliding = false;
-};
-
-// bytes of E's own observation buffer, whichever layout it has
-static size_t own_obs_bytes(const gte_env* E) {
-  return sizeof(float) * (size_t)E->p.N * (size_t)obs_env_stride(E->p);
-}
-
-// what the ledger is told (gte_ledger.h): E's own observation buffer, a buffer of N flag bytes
-static gte_ledger::Span obs_span(const gte_env* E) { return {E->p.obs, own_obs_bytes(E)}; }
-static gte_ledger::Span flag_span(const gte_env* E, const uint8_t* flags) { return {flags, (size_t)E->p.N}; }
-
-template <typename T>
-static int dev_alloc(gte_env* E, T** out, size_t count, bool zero = true) {
-  void* ptr = nullptr;
-  size_t bytes = sizeof(T) * (count ? count : 1);
-  HIPCHK(hipMalloc(&ptr, bytes));
-  if (getenv("GTE_DEBUG_ALLOC")) fprintf(stderr, "[gte] alloc %p %zu bytes\n", ptr, bytes);
-  E->allocs.push_back(ptr);
-  if (zero) HIPCHK(hipMemset(ptr, 0, bytes));
-  *out = (T*)ptr;
-  return GTE_OK;
-}
-
-#define TRY(expr)            \
-  do {                       \
-    int rc_ = (expr);        \
-    if (rc_ != GTE_OK) return rc_; \
-  } while (0)
-
-// dev_alloc after create, for a buffer the env's stream uses next: the zero-fill ran on the null
-// stream and the env's stream is non-blocking, so wait for it here
-template <typename T>
-static int dev_alloc_late(gte_env* E, T** out, size_t count) {
-  TRY(dev_alloc(E, out, count));
-  HIPCHK(hipDeviceSynchronize());
-  return GTE_OK;
-}
+#include "gte_host.h"
 
 static int validate(const gte_config* c) {
   if (!c) return fail(GTE_ERR_INVALID, "config is NULL");
@@ -490,7 +303,7 @@ int gte_create(const gte_config* cfg, gte_env** out) {
   p.terminated = E->owned.terminated; p.truncated = E->owned.truncated;
   E->term_base = E->owned.term_count; p.term_ids = E->owned.term_ids;
   E->h_ds.assign((size_t)p.D, DatasetDesc{nullptr, nullptr, nullptr, nullptr, 0});
-  for (auto& v : E->ds_allocs) v.assign((size_t)p.D, nullptr);
+  for (auto& v : E->ds_allocs) v = std::vector<DeviceBlock>((size_t)p.D);
 
   rc = plan_launches(E);
   if (rc != GTE_OK) return create_failed(E, rc);
@@ -499,41 +312,6 @@ int gte_create(const gte_config* cfg, gte_env** out) {
     return create_failed(E, fail(GTE_ERR_HIP, "hipDeviceSynchronize failed after allocation"));
   report_plan(E, "create");
   *out = E;
-  return GTE_OK;
-}
-
-// Dataset d's signal table becomes t (base null = unbound), on the host and on the device; the
-// caller has waited for the stream.  Nothing changes if the copy fails.
-static int publish_signal_table(gte_env* E, int32_t d, const gte::SignalTable& t) {
-  const gte::SignalTable before = E->h_sig[d];
-  E->h_sig[d] = t;
-  const hipError_t e = hipMemcpy(E->d_sig, E->h_sig.data(), sizeof(gte::SignalTable) * E->h_sig.size(),
-                                 hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    E->h_sig[d] = before;
-    return fail(GTE_ERR_HIP, "publishing the signal table of dataset %d: %s", d, hipGetErrorString(e));
-  }
-  bool any = false;
-  for (const gte::SignalTable& x : E->h_sig) any = any || x.base != nullptr;
-  if (!any) E->sig_S = 0;
-  return GTE_OK;
-}
-
-// Dataset d's period row becomes r (base null = unbound), on the host and on the device, and the row it had is
-// freed; the caller has waited for the stream.  Nothing changes if the copy fails.
-static int publish_period_row(gte_env* E, int32_t d, const gte::PeriodRow& r) {
-  const gte::PeriodRow before = E->h_prow[d];
-  E->h_prow[d] = r;
-  const hipError_t e = hipMemcpy(E->d_prow, E->h_prow.data(), sizeof(gte::PeriodRow) * E->h_prow.size(),
-                                 hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    E->h_prow[d] = before;
-    return fail(GTE_ERR_HIP, "publishing the period row of dataset %d: %s", d, hipGetErrorString(e));
-  }
-  if (before.base) (void)hipFree(const_cast<int8_t*>(before.base));
-  // while tracking is on the next backtest call clears: its records would mix two period maps (off, nothing is
-  // kept, and switching on marks the change itself: an untracked backtest keeps honouring its `clear`)
-  if (E->pd_B > 0) E->pd_changed = true;
   return GTE_OK;
 }
 
@@ -567,36 +345,29 @@ int gte_upload_dataset(gte_env* E, int32_t d, const float* feat, const double* c
                            sizeof(double) * (size_t)T, sizeof(double) * (size_t)T};
   // new buffers first; the old ones stay in the descriptor table (and valid) until the new
   // table has been published, so a failure on the way leaves the env exactly as it was
-  void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-  auto undo = [&]() { for (void* q : dev) if (q) (void)hipFree(q); };
+  DeviceBlock dev[4];  // (a return on the way releases them)
   for (int k = 0; k < 4; ++k) {
     if (!srcs[k]) continue;
-    hipError_t e = hipMalloc(&dev[k], bytes[k]);
-    if (e == hipSuccess && getenv("GTE_DEBUG_ALLOC"))
-      fprintf(stderr, "[gte] dataset %d column %d at %p, %zu bytes\n", d, k, dev[k], bytes[k]);
-    if (e == hipSuccess) e = hipMemcpy(dev[k], srcs[k], bytes[k], hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      undo();
+    TRY(device_alloc(&dev[k], bytes[k], "uploading dataset %d: %s", d));
+    if (getenv("GTE_DEBUG_ALLOC"))
+      fprintf(stderr, "[gte] dataset %d column %d at %p, %zu bytes\n", d, k, dev[k].get(), bytes[k]);
+    const hipError_t e = hipMemcpy(dev[k].get(), srcs[k], bytes[k], hipMemcpyHostToDevice);
+    if (e != hipSuccess)
       return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "uploading dataset %d: %s", d,
                   hipGetErrorString(e));
-    }
   }
   const DatasetDesc before = E->h_ds[d];
-  E->h_ds[d] = DatasetDesc{(const float*)dev[0], (const double*)dev[1], (const double*)dev[2],
-                           (const double*)dev[3], T};
+  E->h_ds[d] = DatasetDesc{dev[0].as<const float>(), dev[1].as<const double>(), dev[2].as<const double>(),
+                           dev[3].as<const double>(), T};
   const hipError_t e = hipMemcpy(E->d_ds, E->h_ds.data(), sizeof(DatasetDesc) * p.D, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     E->h_ds[d] = before;
-    undo();
     return fail(GTE_ERR_HIP, "publishing the descriptor of dataset %d: %s", d, hipGetErrorString(e));
   }
-  for (int k = 0; k < 4; ++k) {
-    if (E->ds_allocs[k][d]) (void)hipFree(E->ds_allocs[k][d]);
-    E->ds_allocs[k][d] = dev[k];
-  }
+  for (int k = 0; k < 4; ++k) E->ds_allocs[k][d] = std::move(dev[k]);  // the old column is freed, the new one kept
   // T may have changed: the dataset's signal table was checked against the old one
-  if (E->d_sig && E->h_sig[d].base) TRY(publish_signal_table(E, d, gte::SignalTable{nullptr, 0}));
-  if (E->d_prow && E->h_prow[d].base) TRY(publish_period_row(E, d, gte::PeriodRow{nullptr, 0}));  // and its period row
+  if (E->signals.d_tab && E->signals.h_tab[d].base) TRY(publish_signal_table(E, d, gte::SignalTable{nullptr, 0}));
+  if (E->periods.d_row && E->periods.h_row[d].base) TRY(publish_period_row(E, d, DeviceBlock()));  // and its period row
   return GTE_OK;
 }
 
@@ -760,15 +531,14 @@ int gte_set_autoreset_injection(gte_env* E, int32_t n, const int32_t* inj_idx,
   Params& p = E->p;
   const size_t count = (size_t)p.N * (size_t)n;
   // the queues of an earlier call are released here (the stream is idle: nothing reads them)
-  auto put = [&](int32_t** slot, const int32_t* src, const int32_t** param) -> int {
+  auto put = [&](DeviceBlock* slot, const int32_t* src, const int32_t** param) -> int {
     *param = nullptr;
-    if (*slot) { (void)hipFree(*slot); *slot = nullptr; }
+    slot->reset();  // (freed BEFORE the new queue is allocated)
     if (!src || n == 0) return GTE_OK;
-    void* dev = nullptr;
-    HIPCHK(hipMalloc(&dev, sizeof(int32_t) * count));
-    *slot = (int32_t*)dev;  // owned by the env from here on (freed above or in gte_destroy)
+    TRY(device_alloc(slot, sizeof(int32_t) * count, "queue of %zu injected draws: %s", count));
+    void* const dev = slot->get();
     HIPCHK(hipMemcpy(dev, src, sizeof(int32_t) * count, hipMemcpyHostToDevice));
-    *param = *slot;
+    *param = (const int32_t*)dev;
     return GTE_OK;
   };
   TRY(put(&E->d_q_idx, inj_idx, &p.q_idx));
@@ -779,22 +549,6 @@ int gte_set_autoreset_injection(gte_env* E, int32_t n, const int32_t* inj_idx,
   HIPCHK(hipStreamSynchronize(E->stream));
   HIPCHK(hipDeviceSynchronize());
   return GTE_OK;
-}
-
-// Stream capture (hipStreamBeginCapture by whoever owns the stream — e.g. torch.cuda.graph around
-// policy + step): everything a step enqueues is capturable — the step kernel and the re-sort's
-// three kernels, no memset — provided nothing comes from pageable host memory, and the host-side bookkeeping a
-// replay cannot repeat stays consistent: the two-slot terminal counter alternates per launch, so
-// a graph must hold an EVEN number of steps and be replayed from the slot it was captured at
-// (gte_get_outputs().term_slot; StepGraph in step_graph.py checks both).  The trajectory log's
-// row index comes from the device cursor (log_cursor above), so logged envs are capturable too;
-// the host's mirror of it (log_rows) advances during a capture as if the steps ran: the owner of
-// the capture restores it and advances it per replay (gte_get_schedule / gte_set_schedule /
-// gte_advance_log).
-static bool stream_capturing(gte_env* E) {
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(E->stream, &capture) != hipSuccess) { (void)hipGetLastError(); capture = hipStreamCaptureStatusNone; }
-  return capture == hipStreamCaptureStatusActive;
 }
 
 // two-slot terminal counter: this launch adds to one slot (cleared by the previous
@@ -1065,15 +819,30 @@ int gte_rollout(gte_env* E, const int32_t* actions, int32_t n_steps, const gte_r
   return rc;
 }
 
+}  // extern "C"
+namespace gte_host {
+
+thread_local std::string g_err = "";
+
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
 // gte_backtest's launches, after its checks: the steps of gte_rollout(actions, n_steps, NULL), each
 // folded into the statistics records
 // With actions == NULL (gte_backtest_signals) each step's actions are looked up in the bound signal tables
 // for `strategy` instead.
 // the lookup of gte_signal_actions, with the exits decided as well while rules are bound
-static hipError_t launch_lookup(gte_env* E, const int32_t* strategy, int32_t* actions) {
-  if (E->exits.rules)
-    return gte::launch_exit_actions(E->p, E->d_sig, E->sig_S, strategy, E->exits, actions, E->stream);
-  return gte::launch_signal_actions(E->p, E->d_sig, E->sig_S, strategy, actions, E->stream);
+hipError_t launch_lookup(gte_env* E, const int32_t* strategy, int32_t* actions) {
+  if (E->signals.exits.rules)
+    return gte::launch_exit_actions(E->p, E->signals.d_tab, E->signals.S, strategy, E->signals.exits, actions, E->stream);
+  return gte::launch_signal_actions(E->p, E->signals.d_tab, E->signals.S, strategy, actions, E->stream);
 }
 
 // With `cv` (gte_backtest_curves) the launches are those of gte_curves.hip, which write the rows as well.
@@ -1086,53 +855,53 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   // step launches below establish it again).  They store the env's own flags densely, so the flag claim
   // stands for those launches; backtest_entry withdraws it afterwards
   ledger().wrote(E, {flag_span(E, E->p.terminated), flag_span(E, E->p.truncated)}, false, WINDOW);
-  if (signals && !E->d_sig_actions) TRY(dev_alloc_late(E, &E->d_sig_actions, N));
+  if (signals && !E->backtest.sig_actions) TRY(dev_alloc_late(E, &E->backtest.sig_actions, N));
   if (cv) {  // the window that is open between two launches of a call (gte_curves.hip), allocated by the first such call
-    if (!E->cv_carry) TRY(dev_alloc_late(E, &E->cv_carry, N));
-    cv->carry = E->cv_carry;
+    if (!E->backtest.carry) TRY(dev_alloc_late(E, &E->backtest.carry, N));
+    cv->carry = E->backtest.carry;
   }
-  if (!E->bt_stats) {
-    if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->bt_final_rec, N));
-    TRY(dev_alloc_late(E, &E->bt_stats, N));  // (its wait covers the fill before it too)
+  if (!E->backtest.stats) {
+    if (E->p.autoreset == GTE_AUTORESET_SAME_STEP && !E->p.final_rec) TRY(dev_alloc(E, &E->backtest.final_rec, N));
+    TRY(dev_alloc_late(E, &E->backtest.stats, N));  // (its wait covers the fill before it too)
     clear = 1;
   }
   // tracking was switched since the last call: both records start afresh, so that they cover the same transitions
-  if (E->tr_changed) clear = 1;
-  E->tr_changed = false;
-  gte_trade_stats* const trades = E->tr_on ? E->tr_stats : nullptr;
+  if (E->trades.changed) clear = 1;
+  E->trades.changed = false;
+  gte_trade_stats* const trades = E->trades.on ? E->trades.stats : nullptr;
   // ... with the trade list on, through the unit that writes it as well (gte_trade_list.hip)
-  const bool listed = trades && E->tl_cap > 0;
-  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
+  const bool listed = trades && E->trades.cap > 0;
+  const gte::TradeList tl = {E->trades.list.as<gte_trade>(), E->trades.open_row.as<int32_t>(), E->trades.cap};
   // the same for period tracking (never on together with trades: gte_track_periods, gte_track_trades)
-  if (E->pd_changed) clear = 1;
-  E->pd_changed = false;
-  const bool periods = E->pd_B > 0;
-  const gte::Periods per = {E->d_prow, E->pd_stats, E->pd_B};
+  if (E->periods.changed) clear = 1;
+  E->periods.changed = false;
+  const bool periods = E->periods.B > 0;
+  const gte::Periods per = {E->periods.d_row, E->periods.stats.as<gte_period_stats>(), E->periods.B};
   // same-step mode: the terminal valuation comes from the terminal records, the env's or our own
-  EnvRec* const terminal = E->p.final_rec ? E->p.final_rec : E->bt_final_rec;
+  EnvRec* const terminal = E->p.final_rec ? E->p.final_rec : E->backtest.final_rec;
   Params ps = E->p;
   ps.perm = nullptr;  // identity order, as in the state-only rollout: per-env loads and stores coalesce
   ps.final_rec = terminal;
-  hipError_t le = listed   ? gte::launch_trade_list_begin(ps, E->bt_stats, trades, tl, clear, E->stream)
-                  : trades ? gte::launch_trade_begin(ps, E->bt_stats, trades, clear, E->stream)
-                           : gte::launch_backtest_begin(ps, E->bt_stats, clear, E->stream);
+  hipError_t le = listed   ? gte::launch_trade_list_begin(ps, E->backtest.stats, trades, tl, clear, E->stream)
+                  : trades ? gte::launch_trade_begin(ps, E->backtest.stats, trades, clear, E->stream)
+                           : gte::launch_backtest_begin(ps, E->backtest.stats, clear, E->stream);
   if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   if (periods && clear)  // a cleared period record is all zero, and a reset row changes none
-    HIPCHK(hipMemsetAsync(E->pd_stats, 0, sizeof(gte_period_stats) * N * (size_t)E->pd_B, E->stream));
+    HIPCHK(hipMemsetAsync(per.records, 0, sizeof(gte_period_stats) * N * (size_t)E->periods.B, E->stream));
   // one step as an ordinary launch (it also produces the observation and the terminal list), then
   // its results into the records
   auto step_and_fold = [&](int32_t k) -> int {
     if (signals) {
-      const hipError_t se = launch_lookup(E, strategy, E->d_sig_actions);
+      const hipError_t se = launch_lookup(E, strategy, E->backtest.sig_actions);
       if (se != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(se));
     }
-    const int32_t* const row = signals ? E->d_sig_actions : actions + (size_t)k * N;
-    TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->bt_final_rec));
-    const hipError_t fe = cv        ? gte::launch_curve_fold(ps, E->bt_stats, *cv, k, n_steps, E->stream)
-                          : listed  ? gte::launch_trade_list_fold(ps, E->bt_stats, trades, tl, E->stream)
-                          : trades  ? gte::launch_trade_fold(ps, E->bt_stats, trades, E->stream)
-                          : periods ? gte::launch_period_fold(ps, E->bt_stats, per, E->stream)
-                                    : gte::launch_backtest_fold(ps, E->bt_stats, E->stream);
+    const int32_t* const row = signals ? E->backtest.sig_actions : actions + (size_t)k * N;
+    TRY(enqueue_step(E, own_targets(E, row), L.store, false, E->backtest.final_rec));
+    const hipError_t fe = cv        ? gte::launch_curve_fold(ps, E->backtest.stats, *cv, k, n_steps, E->stream)
+                          : listed  ? gte::launch_trade_list_fold(ps, E->backtest.stats, trades, tl, E->stream)
+                          : trades  ? gte::launch_trade_fold(ps, E->backtest.stats, trades, E->stream)
+                          : periods ? gte::launch_period_fold(ps, E->backtest.stats, per, E->stream)
+                                    : gte::launch_backtest_fold(ps, E->backtest.stats, E->stream);
     if (fe != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(fe));
     return GTE_OK;
   };
@@ -1148,921 +917,39 @@ static int backtest(gte_env* E, const int32_t* actions, const int32_t* strategy,
   if (n_steps > 1) {
     TRY(age_order(E, n_steps - 1));
     // one launch, its actions from `src`; with a tracker on, the unit that keeps that record in registers as well
-    const gte::SummarySource src = {actions, E->d_sig, E->sig_S, strategy, E->exits.rules ? &E->exits : nullptr};
+    const gte::SummarySource src = {actions, E->signals.d_tab, E->signals.S, strategy, E->signals.exits.rules ? &E->signals.exits : nullptr};
     const int32_t k = n_steps - 1, epw = L.state_epw;
-    le = cv        ? gte::launch_curve_summary(ps, src, E->bt_stats, *cv, k, epw, E->stream)
-         : listed  ? gte::launch_trade_list_summary(ps, src, E->bt_stats, trades, tl, k, epw, E->stream)
-         : trades  ? gte::launch_trade_summary(ps, src, E->bt_stats, trades, k, epw, E->stream)
-         : periods ? gte::launch_period_summary(ps, src, E->bt_stats, per, k, epw, E->stream)
-         : signals ? gte::launch_signal_summary(ps, src, E->bt_stats, k, epw, E->stream)
-                   : gte::launch_backtest_summary(ps, src, E->bt_stats, k, epw, E->stream);
+    le = cv        ? gte::launch_curve_summary(ps, src, E->backtest.stats, *cv, k, epw, E->stream)
+         : listed  ? gte::launch_trade_list_summary(ps, src, E->backtest.stats, trades, tl, k, epw, E->stream)
+         : trades  ? gte::launch_trade_summary(ps, src, E->backtest.stats, trades, k, epw, E->stream)
+         : periods ? gte::launch_period_summary(ps, src, E->backtest.stats, per, k, epw, E->stream)
+         : signals ? gte::launch_signal_summary(ps, src, E->backtest.stats, k, epw, E->stream)
+                   : gte::launch_backtest_summary(ps, src, E->backtest.stats, k, epw, E->stream);
     if (le != hipSuccess) return fail(GTE_ERR_HIP, "backtest launch: %s", hipGetErrorString(le));
   }
   return step_and_fold(n_steps - 1);
 }
 
 // what gte_backtest and gte_backtest_signals (`who`) share once their own arguments are checked
-static int backtest_entry(gte_env* E, const char* who, const int32_t* actions, const int32_t* strategy,
+int backtest_entry(gte_env* E, const char* who, const int32_t* actions, const int32_t* strategy,
                           int32_t n_steps, int32_t clear, gte_backtest_stats** stats_device,
-                          gte::Curves* cv = nullptr) {
+                   gte::Curves* cv) {
   if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
   if (stream_capturing(E))
     return fail(GTE_ERR_STATE, "%s inside a stream capture: a backtest is one launch already, run it eagerly", who);
-  if (E->pd_B > 0)
+  if (E->periods.B > 0)
     for (int d = 0; d < E->p.D; ++d)
-      if (!E->d_prow || !E->h_prow[d].base)
+      if (!E->periods.d_row || !E->periods.h_row[d].base)
         return fail(GTE_ERR_STATE, "%s: period tracking is on and dataset %d has no period row (gte_bind_periods)", who, d);
   HIPCHK(hipSetDevice(E->cfg.device));
   const int rc = backtest(E, actions, strategy, n_steps, clear, cv);
   ledger().withdraw(E, FLAGS);  // (as after a rollout: the next step stores densely)
-  if (stats_device) *stats_device = E->bt_stats;
+  if (stats_device) *stats_device = E->backtest.stats;
   return rc;
 }
 
-int gte_backtest(gte_env* E, const int32_t* actions, int32_t n_steps, int32_t clear,
-                 gte_backtest_stats** stats_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_backtest before gte_reset");
-  if (!actions) return fail(GTE_ERR_INVALID, "actions is NULL");
-  return backtest_entry(E, "gte_backtest", actions, nullptr, n_steps, clear, stats_device);
-}
-
-// ---- a per-dataset table of rows on the device: the checks gte_bind_signals and the builders share ----
-// A row holds T elements and is padded: the stride is a whole number of 16-byte pieces and at least T
-// rounded up to 16 elements, so that an aligned 16-byte access anywhere in a row stays inside it.
-static int64_t round_up_16(int64_t T) { return (T + 15) / 16 * 16; }
-
-// dataset d of a builder call -> its T: a builder runs outside a capture, on a dataset that was uploaded
-static int builder_dataset(gte_env* E, const char* who, int32_t d, int64_t* T) {
-  if (d < 0 || d >= E->p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "%s inside a stream capture", who);
-  *T = E->h_ds[d].T;
-  if (*T <= 0) return fail(GTE_ERR_STATE, "%s: dataset %d was never uploaded", who, d);
-  return GTE_OK;
-}
-
-// `stride`, in elements of `elem` bytes, of a table over the T rows of dataset d
-static int check_stride(const char* name, int64_t stride, size_t elem, int64_t T, int32_t d) {
-  const int64_t k = 16 / (int64_t)elem;
-  if (stride % k == 0 && stride >= round_up_16(T)) return GTE_OK;
-  return fail(GTE_ERR_INVALID, "%s %lld%s: a multiple of %lld and >= %lld (the %lld rows of dataset %d rounded up "
-              "to 16) required", name, (long long)stride, elem == sizeof(float) ? " floats" : "", (long long)k,
-              (long long)round_up_16(T), (long long)T, d);
-}
-
-// what a kernel touches of a table: T16 elements of each of its rows
-struct RowSpan { const void* base; int64_t rows, stride; size_t elem; };
-static bool spans_overlap(const RowSpan& r, const RowSpan& w, int64_t T16) {
-  const uintptr_t r0 = (uintptr_t)r.base, w0 = (uintptr_t)w.base;
-  const uintptr_t r1 = r0 + r.elem * (size_t)((r.rows - 1) * r.stride + T16);
-  const uintptr_t w1 = w0 + w.elem * (size_t)((w.rows - 1) * w.stride + T16);
-  return r0 < w1 && w0 < r1;
-}
-
-// ---- what the reductions, rankings and reads of the per-env record families share: each family's entry
-// points run these in the order they always refused in, `who` being the entry point for the message.  The
-// leaderboard analyses of the [S, B] period records (gte_reality_check, gte_cscv, gte_diversify) take from here
-// as well what they share: the stats and resample checks, the walk over a period mask, the test of a list of
-// output pointers, the scratch each of them keeps and the tail after their launches ----
-// the head of every gte_reduce_* / gte_rank_* call and of the three analyses
-static int check_strategies(const gte_env* E, int32_t n_strategies) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-  return GTE_OK;
-}
-
-static int check_n_periods(int32_t n_periods, int lo) {
-  if (n_periods >= lo && n_periods <= GTE_MAX_PERIODS) return GTE_OK;
-  return fail(GTE_ERR_INVALID, "n_periods %d outside [%d, %d]", n_periods, lo, GTE_MAX_PERIODS);
-}
-
-static int check_period_mask(const uint64_t* period_mask) {
-  return period_mask ? GTE_OK : fail(GTE_ERR_INVALID, "period_mask is NULL");
-}
-
-// n = the periods the two words select; a bit at or above n_periods is refused (how few are too few, and the
-// words for it, is the caller's)
-static int count_periods(const uint64_t* period_mask, int32_t n_periods, int* n) {
-  *n = 0;
-  for (int b = 0; b < 128; ++b) {
-    if (!((period_mask[b >> 6] >> (b & 63)) & 1)) continue;
-    if (b >= n_periods) return fail(GTE_ERR_INVALID, "period_mask selects period %d, at or above n_periods %d", b, n_periods);
-    ++*n;
-  }
-  return GTE_OK;
-}
-
-static int check_stats(const void* stats) {
-  if (stats && !((uintptr_t)stats & 15)) return GTE_OK;
-  return fail(GTE_ERR_INVALID, "stats_device must be a 16-byte aligned device array");
-}
-
-static int check_n_resamples(int32_t n_resamples) {
-  if (n_resamples >= 1 && n_resamples <= GTE_BOOT_MAX_RESAMPLES) return GTE_OK;
-  return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_BOOT_MAX_RESAMPLES);
-}
-
-// the pools of gte_pool_trades and gte_trade_monte_carlo
-static int check_n_pools(int32_t n_pools) {
-  if (n_pools >= 1 && n_pools <= GTE_MC_MAX_POOLS) return GTE_OK;
-  return fail(GTE_ERR_INVALID, "n_pools %d outside [1, %d]", n_pools, GTE_MC_MAX_POOLS);
-}
-
-// every pointer of the list set, and none with a bit of `low_bits` (alignment less one) in its address
-static bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t low_bits) {
-  uintptr_t address_bits = 0;
-  for (const void* p : ptrs) {
-    if (!p) return false;
-    address_bits |= (uintptr_t)p;
-  }
-  return !(address_bits & low_bits);
-}
-
-// at least `need` bytes behind s->base: too small a block gives way to one of max(need, 2 * have) bytes (the old
-// one stays until gte_destroy: launches in flight may use it)
-static int grow(gte_env* E, Scratch* s, size_t need) {
-  if (s->bytes >= need) return GTE_OK;
-  const size_t bytes = need > 2 * s->bytes ? need : 2 * s->bytes;
-  uint8_t* fresh = nullptr;
-  TRY(dev_alloc(E, &fresh, bytes, false));
-  s->base = fresh;
-  s->bytes = bytes;
-  return GTE_OK;
-}
-
-// what an analysis returns once its launches are enqueued, `what` naming it
-static int launched(hipError_t e, const char* what) {
-  return e == hipSuccess ? GTE_OK : fail(GTE_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
-}
-
-static int check_reduce_args(gte_env* E, const char* who, const void* records, const int32_t* group_offsets,
-                             const int32_t* group_envs, const void* out) {
-  if (!out || ((uintptr_t)out & 15)) return fail(GTE_ERR_INVALID, "out_device must be a 16-byte aligned device array");
-  if ((uintptr_t)records & 15) return fail(GTE_ERR_INVALID, "records must be 16-byte aligned");
-  if ((group_offsets == nullptr) != (group_envs == nullptr))
-    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
-  if (((uintptr_t)group_offsets & 3) || ((uintptr_t)group_envs & 3))
-    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "%s inside a stream capture", who);
-  return GTE_OK;
-}
-
-// metric in [lo, hi], the family's first and last
-static int check_rank_args(gte_env* E, const char* who, int32_t k, int32_t metric, int lo, int hi, const void* stats,
-                           const int32_t* top_index, const double* top_score, const double* scores) {
-  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
-  if (metric < lo || metric > hi) return fail(GTE_ERR_INVALID, "metric %d unknown", metric);
-  TRY(check_stats(stats));
-  if (!top_index || ((uintptr_t)top_index & 3) || !top_score || ((uintptr_t)top_score & 7))
-    return fail(GTE_ERR_INVALID, "top_index_device (int32 [k]) and top_score_device (f64 [k]) must be aligned device arrays");
-  if ((uintptr_t)scores & 7) return fail(GTE_ERR_INVALID, "scores_device must be 8-byte aligned");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "%s inside a stream capture", who);
-  return GTE_OK;
-}
-
-// rows first .. first + count - 1 of a per-env record array (`base`: row_bytes per env, or NULL before the call
-// `before` made it) to the host, after everything enqueued on the env's stream
-static int read_records(gte_env* E, const char* who, const char* before, const void* base, size_t row_bytes,
-                        int32_t first, int32_t count, void* out) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (!base) return fail(GTE_ERR_STATE, "%s before %s", who, before);
-  if (first < 0 || count < 0 || (int64_t)first + count > E->p.N)
-    return fail(GTE_ERR_INVALID, "env range [%d, %d) outside [0, %d)", first, first + count, E->p.N);
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  if (count > 0)
-    HIPCHK(hipMemcpy(out, (const char*)base + (size_t)first * row_bytes, (size_t)count * row_bytes, hipMemcpyDeviceToHost));
-  return GTE_OK;
-}
-
-int gte_bind_signals(gte_env* E, int32_t d, const int8_t* signals_device, int32_t n_strategies,
-                     int64_t row_stride) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  const Params& p = E->p;
-  if (d < 0 || d >= p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bind_signals inside a stream capture");
-  if (signals_device) {
-    const int64_t T = E->h_ds[d].T;
-    if (T <= 0) return fail(GTE_ERR_STATE, "gte_bind_signals: dataset %d was never uploaded", d);
-    if ((uintptr_t)signals_device & 15) return fail(GTE_ERR_INVALID, "signals must be 16-byte aligned");
-    TRY(check_stride("row_stride", row_stride, sizeof(int8_t), T, d));
-    if (n_strategies < 1) return fail(GTE_ERR_INVALID, "n_strategies must be >= 1");
-    for (int o = 0; o < (int)E->h_sig.size(); ++o)
-      if (o != d && E->h_sig[o].base && E->sig_S != n_strategies)
-        return fail(GTE_ERR_INVALID, "n_strategies %d: the table of dataset %d has %d", n_strategies, o, E->sig_S);
-  } else if (!E->d_sig) {
-    return GTE_OK;  // nothing was ever bound
-  }
-  HIPCHK(hipSetDevice(E->cfg.device));
-  if (!E->d_sig) {
-    E->h_sig.assign((size_t)p.D, gte::SignalTable{nullptr, 0});
-    TRY(dev_alloc(E, &E->d_sig, (size_t)p.D));
-  }
-  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight read the descriptors
-  TRY(publish_signal_table(E, d, signals_device ? gte::SignalTable{signals_device, row_stride}
-                                                : gte::SignalTable{nullptr, 0}));
-  if (signals_device) E->sig_S = n_strategies;
-  return GTE_OK;
-}
-
-// every resident dataset has a table: the lookups may run
-static int signals_ready(const gte_env* E, const char* who) {
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "%s before gte_reset", who);
-  for (int d = 0; d < E->p.D; ++d)
-    if (!E->d_sig || !E->h_sig[d].base)
-      return fail(GTE_ERR_STATE, "%s: dataset %d has no signal table (gte_bind_signals)", who, d);
-  return GTE_OK;
-}
-
-int gte_signal_actions(gte_env* E, const int32_t* strategy_device, int32_t* actions_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!actions_device) return fail(GTE_ERR_INVALID, "actions is NULL");
-  TRY(signals_ready(E, "gte_signal_actions"));
-  if (!stream_capturing(E)) HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = launch_lookup(E, strategy_device, actions_device);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal lookup launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_backtest_signals(gte_env* E, const int32_t* strategy_device, int32_t n_steps, int32_t clear,
-                         gte_backtest_stats** stats_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  TRY(signals_ready(E, "gte_backtest_signals"));
-  return backtest_entry(E, "gte_backtest_signals", nullptr, strategy_device, n_steps, clear, stats_device);
-}
-
-int gte_backtest_curves(gte_env* E, const int32_t* actions, const int32_t* strategy_device, int32_t n_steps,
-                        int32_t stride, int32_t clear, const gte_curve_bufs* bufs, gte_backtest_stats** stats_device) {
-  const char* const who = "gte_backtest_curves";
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "%s before gte_reset", who);
-  if (!bufs) return fail(GTE_ERR_INVALID, "%s: bufs is NULL", who);
-  if (n_steps < 1) return fail(GTE_ERR_INVALID, "n_steps must be >= 1");
-  if (stride < 1) return fail(GTE_ERR_INVALID, "%s: stride %d must be >= 1", who, stride);
-  if (!bufs->valuation && !bufs->drawdown && !bufs->reward && !bufs->position && !bufs->row && !bufs->flags)
-    return fail(GTE_ERR_INVALID, "%s: all six columns are NULL, nothing to keep", who);
-  if (((uintptr_t)bufs->valuation | (uintptr_t)bufs->drawdown | (uintptr_t)bufs->reward) & 7)
-    return fail(GTE_ERR_INVALID, "%s: valuation, drawdown and reward must be 8-byte aligned", who);
-  if (((uintptr_t)bufs->position | (uintptr_t)bufs->row) & 3)
-    return fail(GTE_ERR_INVALID, "%s: position and row must be 4-byte aligned", who);
-  if (E->tr_on || E->pd_B > 0)
-    return fail(GTE_ERR_STATE, "%s: %s tracking is on, and a launch keeps one tracker (gte_track_%s(env, 0, ...) first)",
-                who, E->tr_on ? "trade" : "period", E->tr_on ? "trades" : "periods");
-  if (!actions) TRY(signals_ready(E, who));
-  // (the carry is the library's: backtest() allocates it, on the env's device, and fills it in)
-  gte::Curves cv = {nullptr, stride, *bufs};
-  return backtest_entry(E, who, actions, actions ? nullptr : strategy_device, n_steps, clear, stats_device, &cv);
-}
-
-int gte_bind_exit_rules(gte_env* E, const gte_exit_rule* rules_device, int32_t n_rules,
-                        const int32_t* rule_of_env_device, gte_exit_state** state_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bind_exit_rules inside a stream capture");
-  if (rules_device) {
-    if ((uintptr_t)rules_device & 3) return fail(GTE_ERR_INVALID, "exit rules must be 4-byte aligned");
-    if ((uintptr_t)rule_of_env_device & 3) return fail(GTE_ERR_INVALID, "rule_of_env must be 4-byte aligned");
-    if (n_rules < 1) return fail(GTE_ERR_INVALID, "n_rules must be >= 1");
-  }
-  HIPCHK(hipSetDevice(E->cfg.device));
-  if (rules_device && !E->exits.state) TRY(dev_alloc_late(E, &E->exits.state, (size_t)E->p.N));
-  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight read the rules and the state
-  if (E->exits.state) {
-    const hipError_t e = gte::launch_exit_init(E->exits.state, E->p.N, E->stream);
-    if (e != hipSuccess) return fail(GTE_ERR_HIP, "exit state launch: %s", hipGetErrorString(e));
-  }
-  E->exits.rules = rules_device;
-  E->exits.rule_of_env = rules_device ? rule_of_env_device : nullptr;
-  E->exits.n_rules = rules_device ? n_rules : 0;
-  if (state_device) *state_device = E->exits.state;
-  return GTE_OK;
-}
-
-int gte_read_exit_state(gte_env* E, int32_t first, int32_t count, gte_exit_state* out) {
-  return read_records(E, "gte_read_exit_state", "gte_bind_exit_rules", E ? E->exits.state : nullptr,
-                      sizeof(gte_exit_state), first, count, out);
-}
-
-int gte_build_signals(gte_env* E, int32_t d, const float* indicators_device, int32_t n_indicators,
-                      int64_t ind_stride, const gte_signal_rule* rules_device, int32_t n_rules,
-                      int8_t* table_device, int64_t row_stride) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  int64_t T;
-  TRY(builder_dataset(E, "gte_build_signals", d, &T));
-  if (!indicators_device || !rules_device || !table_device) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (((uintptr_t)indicators_device & 15) || ((uintptr_t)table_device & 15))
-    return fail(GTE_ERR_INVALID, "the indicator bank and the table must be 16-byte aligned");
-  if ((uintptr_t)rules_device & 3) return fail(GTE_ERR_INVALID, "rules must be 4-byte aligned");
-  TRY(check_stride("row_stride", row_stride, sizeof(int8_t), T, d));
-  TRY(check_stride("ind_stride", ind_stride, sizeof(float), T, d));
-  if (n_indicators < 1) return fail(GTE_ERR_INVALID, "n_indicators must be >= 1");
-  if (n_rules < 1) return fail(GTE_ERR_INVALID, "n_rules must be >= 1");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::launch_build_signals(indicators_device, n_indicators, ind_stride, rules_device, n_rules,
-                                                 T, table_device, row_stride, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal build launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_compose_signals(gte_env* E, int32_t d, const int8_t* clauses_device, int32_t n_clause_rows,
-                        int64_t clause_stride, const gte_signal_compose* specs_device, int32_t n_specs,
-                        int8_t* table_device, int64_t row_stride) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  int64_t T;
-  TRY(builder_dataset(E, "gte_compose_signals", d, &T));
-  if (!clauses_device || !specs_device || !table_device) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (((uintptr_t)clauses_device & 15) || ((uintptr_t)table_device & 15))
-    return fail(GTE_ERR_INVALID, "the clause table and the table must be 16-byte aligned");
-  if ((uintptr_t)specs_device & 3) return fail(GTE_ERR_INVALID, "specs must be 4-byte aligned");
-  TRY(check_stride("row_stride", row_stride, sizeof(int8_t), T, d));
-  TRY(check_stride("clause_stride", clause_stride, sizeof(int8_t), T, d));
-  if (n_clause_rows < 1) return fail(GTE_ERR_INVALID, "n_clause_rows must be >= 1");
-  if (n_specs < 1) return fail(GTE_ERR_INVALID, "n_specs must be >= 1");
-  // what the kernel may read of the clause table and what it writes of the table: disjoint
-  if (spans_overlap({clauses_device, n_clause_rows, clause_stride, sizeof(int8_t)},
-                    {table_device, n_specs, row_stride, sizeof(int8_t)}, round_up_16(T)))
-    return fail(GTE_ERR_INVALID, "the clause table and the table overlap");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::launch_compose_signals(clauses_device, n_clause_rows, clause_stride, specs_device, n_specs,
-                                                   T, table_device, row_stride, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "signal compose launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_build_indicators(gte_env* E, int32_t d, const gte_indicator_spec* specs_device, int32_t n_specs,
-                         const float* input_device, int32_t n_inputs, int64_t input_stride, float* bank_device,
-                         int64_t ind_stride) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  int64_t T;
-  TRY(builder_dataset(E, "gte_build_indicators", d, &T));
-  if (T > INT32_MAX - 2 * GTE_IND_MAX_WINDOW)  // (the kernel indexes rows with 32 bits, like EnvRec.idx)
-    return fail(GTE_ERR_INVALID, "gte_build_indicators: dataset %d has too many rows", d);
-  if (!specs_device || !bank_device) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (n_inputs < 0) return fail(GTE_ERR_INVALID, "n_inputs must be >= 0");
-  if ((input_device != nullptr) != (n_inputs > 0))
-    return fail(GTE_ERR_INVALID, "input_device must be non-NULL exactly when n_inputs > 0");
-  if (((uintptr_t)bank_device & 15) || ((uintptr_t)input_device & 15))
-    return fail(GTE_ERR_INVALID, "the indicator bank and the input bank must be 16-byte aligned");
-  if ((uintptr_t)specs_device & 3) return fail(GTE_ERR_INVALID, "specs must be 4-byte aligned");
-  TRY(check_stride("ind_stride", ind_stride, sizeof(float), T, d));
-  if (n_inputs > 0) TRY(check_stride("input_stride", input_stride, sizeof(float), T, d));
-  if (n_specs < 1) return fail(GTE_ERR_INVALID, "n_specs must be >= 1");
-  // what the kernel reads of the input and what it writes of the bank: disjoint
-  if (n_inputs > 0 && spans_overlap({input_device, n_inputs, input_stride, sizeof(float)},
-                                    {bank_device, n_specs, ind_stride, sizeof(float)}, round_up_16(T)))
-    return fail(GTE_ERR_INVALID, "the input bank and the indicator bank overlap");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::launch_build_indicators(E->h_ds[d], E->p.Fobs, E->p.Fobs - E->p.nd, specs_device, n_specs,
-                                                    input_device, n_inputs, input_stride, bank_device, ind_stride,
-                                                    E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "indicator build launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_reduce_backtest_stats(gte_env* E, const gte_backtest_stats* records_device, int32_t n_strategies,
-                              const int32_t* group_offsets_device, const int32_t* group_envs_device,
-                              gte_strategy_stats* out_device) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_reduce_args(E, "gte_reduce_backtest_stats", records_device, group_offsets_device, group_envs_device,
-                        out_device));
-  const gte_backtest_stats* const records = records_device ? records_device : E->bt_stats;
-  if (!records) return fail(GTE_ERR_STATE, "gte_reduce_backtest_stats before gte_backtest: the env has no records yet");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::launch_reduce_strategies(records, E->p.N, n_strategies, E->cfg.env_id_base,
-                                                     group_offsets_device, group_envs_device, out_device, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "strategy reduction launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-// the two candidate lists of the selection launches, grown to what S strategies need (gte_strategy.hip)
-static int rank_scratch(gte_env* E, int32_t n_strategies) {
-  for (int w = 0; w < 2; ++w) {
-    const int64_t need = gte::rank_scratch_entries(n_strategies, w);
-    if (E->rank_entries[w] >= need) continue;
-    const int64_t entries = need > 2 * E->rank_entries[w] ? need : 2 * E->rank_entries[w];
-    TRY(dev_alloc(E, &E->rank_score[w], (size_t)entries, false));
-    TRY(dev_alloc(E, &E->rank_index[w], (size_t)entries, false));
-    E->rank_entries[w] = entries;
-  }
-  return GTE_OK;
-}
-
-// how gte_rank_trade_stats and gte_rank_period_stats end: their score kernel (e: its launch) has filled
-// candidate list 0, the selection launches of gte_strategy.hip follow
-static int rank_select(gte_env* E, hipError_t e, const char* what, int32_t n_strategies, int32_t k, int32_t* top_index,
-                       double* top_score) {
-  if (e == hipSuccess)
-    e = gte::launch_rank_select(n_strategies, k, top_index, top_score, E->rank_score, E->rank_index, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "%s ranking launch: %s", what, hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_rank_strategies(gte_env* E, const gte_strategy_stats* stats_device, int32_t n_strategies, int32_t metric,
-                        int64_t min_episodes, int32_t k, int32_t* top_index_device, double* top_score_device,
-                        double* scores_device) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_rank_args(E, "gte_rank_strategies", k, metric, GTE_METRIC_MEAN_REWARD, GTE_METRIC_WORST_REWARD_SUM,
-                      stats_device, top_index_device, top_score_device, scores_device));
-  HIPCHK(hipSetDevice(E->cfg.device));
-  TRY(rank_scratch(E, n_strategies));
-  const hipError_t e = gte::launch_rank_strategies(stats_device, n_strategies, metric, min_episodes, k,
-                                                   top_index_device, top_score_device, scores_device, E->rank_score,
-                                                   E->rank_index, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "strategy ranking launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_reduce_trade_stats(gte_env* E, const gte_trade_stats* records_device, int32_t n_strategies,
-                           const int32_t* group_offsets_device, const int32_t* group_envs_device,
-                           gte_strategy_trade_stats* out_device) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_reduce_args(E, "gte_reduce_trade_stats", records_device, group_offsets_device, group_envs_device,
-                        out_device));
-  const gte_trade_stats* const records = records_device ? records_device : E->tr_stats;
-  if (!records) return fail(GTE_ERR_STATE, "gte_reduce_trade_stats before gte_track_trades: the env has no trade records yet");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::launch_reduce_trade_stats(records, E->p.N, n_strategies, E->cfg.env_id_base,
-                                                      group_offsets_device, group_envs_device, out_device, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "trade reduction launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_rank_trade_stats(gte_env* E, const gte_strategy_trade_stats* stats_device, int32_t n_strategies, int32_t metric,
-                         int64_t min_trades, int32_t k, int32_t* top_index_device, double* top_score_device,
-                         double* scores_device) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_rank_args(E, "gte_rank_trade_stats", k, metric, GTE_TRADE_METRIC_WIN_RATE,
-                      GTE_TRADE_METRIC_NEG_MAX_LOSS_STREAK, stats_device, top_index_device, top_score_device,
-                      scores_device));
-  HIPCHK(hipSetDevice(E->cfg.device));
-  TRY(rank_scratch(E, n_strategies));
-  const hipError_t e = gte::launch_trade_scores(stats_device, n_strategies, metric, min_trades, scores_device,
-                                                E->rank_score[0], E->rank_index[0], E->stream);
-  return rank_select(E, e, "trade", n_strategies, k, top_index_device, top_score_device);
-}
-
-int gte_read_backtest_stats(gte_env* E, int32_t first, int32_t count, gte_backtest_stats* out) {
-  return read_records(E, "gte_read_backtest_stats", "gte_backtest", E ? E->bt_stats : nullptr,
-                      sizeof(gte_backtest_stats), first, count, out);
-}
-
-// the list turned off: its memory goes back (N * capacity * 48 bytes; the env's stream is idle), open_row stays
-static void drop_trade_list(gte_env* E) {
-  if (E->tl_list) (void)hipFree(E->tl_list);
-  E->tl_list = nullptr;
-  E->tl_cap = E->tl_alloc_cap = 0;
-}
-
-int gte_track_trades(gte_env* E, int32_t on, gte_trade_stats** records_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_trades before gte_reset");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_trades inside a stream capture");
-  if (on && E->pd_B > 0)
-    return fail(GTE_ERR_STATE, "gte_track_trades: period tracking is on, and trade and period records together are "
-                "not implemented (gte_track_periods(env, 0, ...) first)");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  if (on && !E->tr_stats) TRY(dev_alloc_late(E, &E->tr_stats, (size_t)E->p.N));
-  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the records
-  if ((on != 0) != E->tr_on) E->tr_changed = true;
-  E->tr_on = on != 0;
-  if (!on && E->tl_cap > 0) {  // the list goes with the tracking
-    drop_trade_list(E);
-    E->tr_changed = true;
-  }
-  if (records_device) *records_device = E->tr_stats;
-  return GTE_OK;
-}
-
-int gte_track_trade_list(gte_env* E, int32_t capacity, gte_trade** list_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (capacity < 0 || capacity > GTE_MAX_TRADE_LIST)
-    return fail(GTE_ERR_INVALID, "gte_track_trade_list: capacity %d outside [0, %d]", capacity, GTE_MAX_TRADE_LIST);
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_trade_list before gte_reset");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_trade_list inside a stream capture");
-  if (capacity > 0 && !E->tr_on)
-    return fail(GTE_ERR_STATE, "gte_track_trade_list: trade tracking is off (gte_track_trades(env, 1, ...) first)");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the list
-  if (capacity > 0 && capacity != E->tl_alloc_cap) {
-    void *fresh = nullptr, *rows = E->tl_open_row;
-    hipError_t e = hipMalloc(&fresh, sizeof(gte_trade) * (size_t)E->p.N * (size_t)capacity);
-    if (e == hipSuccess && !rows) {
-      e = hipMalloc(&rows, sizeof(int32_t) * (size_t)E->p.N);
-      if (e != hipSuccess) (void)hipFree(fresh);
-    }
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "trade list (%d envs x %d trades): %s", E->p.N,
-                  capacity, hipGetErrorString(e));
-    }
-    if (E->tl_list) (void)hipFree(E->tl_list);
-    E->tl_list = (gte_trade*)fresh;  // (never zeroed: `closed` says what of it is valid)
-    E->tl_open_row = (int32_t*)rows;  // (written by the next backtest call's clearing: tr_changed)
-    E->tl_alloc_cap = capacity;
-  }
-  if (capacity != E->tl_cap) E->tr_changed = true;
-  E->tl_cap = capacity;
-  if (capacity == 0) drop_trade_list(E);
-  if (list_device) *list_device = E->tl_list;
-  return GTE_OK;
-}
-
-// what both gathers check first
-static int trade_list_on(gte_env* E, const char* who) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (E->tl_cap < 1 || !E->tl_list || !E->tr_stats)
-    return fail(GTE_ERR_STATE, "%s: the trade list is off (gte_track_trade_list)", who);
-  // a switch of tracking, of the list or of its capacity since the last backtest call: `closed` still counts the
-  // trades of before, and the list (fresh memory, never zeroed) holds none of them
-  if (E->tr_changed)
-    return fail(GTE_ERR_STATE, "%s: the trade list was switched and no backtest call has cleared the records since: "
-                "it holds nothing yet", who);
-  return GTE_OK;
-}
-
-static size_t round_up_16z(size_t n) { return (n + 15) & ~(size_t)15; }
-
-int gte_read_trade_list(gte_env* E, const int32_t* env_ids, int32_t n_ids, gte_trade_batch* out) {
-  TRY(trade_list_on(E, "gte_read_trade_list"));
-  if (!out) return fail(GTE_ERR_INVALID, "NULL argument");
-  const int N = E->p.N;
-  if (!env_ids) n_ids = N;
-  if (n_ids < 0) return fail(GTE_ERR_INVALID, "n_ids must be >= 0");
-  for (int32_t i = 0; env_ids && i < n_ids; ++i)
-    if (env_ids[i] < 0 || env_ids[i] >= N) return fail(GTE_ERR_INVALID, "env_ids[%d] = %d out of range", i, env_ids[i]);
-  HIPCHK(hipSetDevice(E->cfg.device));
-  // the device block: [ids i32 n -> 16] [first i64 n+1 | closed i32 n -> 16] [trades]; the host copy: from `first` on
-  const size_t n = (size_t)n_ids;
-  const size_t ids_bytes = round_up_16z(4 * n), head = round_up_16z(8 * (n + 1) + 4 * n);
-  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
-  int64_t total = 0;
-  char* b = nullptr;
-  int64_t* first = nullptr;
-  // count and scan; one read of the total; if the block cannot hold that many records it grows and is counted
-  // into again; then the pack
-  for (int pass = 0; pass < 2; ++pass) {
-    const size_t need = ids_bytes + head + sizeof(gte_trade) * (size_t)total;
-    if (pass == 1 && need <= E->tl_dev_bytes) break;
-    if (need > E->tl_dev_bytes) {
-      void* fresh = nullptr;
-      const size_t bytes = need + need / 2;
-      const hipError_t e = hipMalloc(&fresh, bytes);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "trade list block (%zu bytes): %s", bytes,
-                    hipGetErrorString(e));
-      }
-      HIPCHK(hipStreamSynchronize(E->stream));  // (a gather in flight writes the old block)
-      if (E->tl_dev) (void)hipFree(E->tl_dev);
-      E->tl_dev = fresh;
-      E->tl_dev_bytes = bytes;
-    }
-    b = (char*)E->tl_dev;
-    first = (int64_t*)(b + ids_bytes);
-    if (env_ids && n) HIPCHK(hipMemcpyAsync(b, env_ids, 4 * n, hipMemcpyHostToDevice, E->stream));
-    const hipError_t le = gte::launch_trade_list_scan(E->tr_stats, tl, N, env_ids ? (const int32_t*)b : nullptr, n_ids,
-                                                      first, (int32_t*)(first + n + 1), E->stream);
-    if (le != hipSuccess) return fail(GTE_ERR_HIP, "trade list scan launch: %s", hipGetErrorString(le));
-    if (pass == 0) {
-      HIPCHK(hipMemcpyAsync(&total, first + n, 8, hipMemcpyDeviceToHost, E->stream));
-      HIPCHK(hipStreamSynchronize(E->stream));
-    }
-  }
-  if (total > 0) {
-    const hipError_t le = gte::launch_trade_list_pack(tl, N, env_ids ? (const int32_t*)b : nullptr, n_ids, first,
-                                                      (gte_trade*)(b + ids_bytes + head), total, E->stream);
-    if (le != hipSuccess) return fail(GTE_ERR_HIP, "trade list pack launch: %s", hipGetErrorString(le));
-  }
-  const size_t bytes = head + sizeof(gte_trade) * (size_t)total;
-  if (bytes > E->tl_host_bytes) {
-    if (E->tl_host) HIPCHK(hipHostFree(E->tl_host));
-    E->tl_host = nullptr; E->tl_host_bytes = 0;
-    HIPCHK(hipHostMalloc(&E->tl_host, bytes + bytes / 2, hipHostMallocDefault));
-    E->tl_host_bytes = bytes + bytes / 2;
-  }
-  HIPCHK(hipMemcpyAsync(E->tl_host, (char*)E->tl_dev + ids_bytes, bytes, hipMemcpyDeviceToHost, E->stream));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  out->n_ids = n_ids;
-  out->capacity = E->tl_cap;
-  out->n_trades = total;
-  out->first = (const int64_t*)E->tl_host;
-  out->closed = (const int32_t*)(out->first + n + 1);
-  out->trades = (const gte_trade*)((const char*)E->tl_host + head);
-  return GTE_OK;
-}
-
-int gte_pack_trade_list(gte_env* E, const int32_t* env_ids_device, int32_t n_ids, int64_t* first_device,
-                        int32_t* closed_device, gte_trade* trades_device, int64_t max_trades) {
-  TRY(trade_list_on(E, "gte_pack_trade_list"));
-  if (!env_ids_device) n_ids = E->p.N;
-  if (n_ids < 0) return fail(GTE_ERR_INVALID, "n_ids must be >= 0");
-  if (max_trades < 0 || (max_trades > 0 && !trades_device))
-    return fail(GTE_ERR_INVALID, "trades_device (gte_trade [max_trades]) is NULL or max_trades < 0");
-  if (!first_device || ((uintptr_t)first_device & 7) || (n_ids > 0 && !closed_device) ||
-      ((uintptr_t)closed_device & 3) || ((uintptr_t)env_ids_device & 3))
-    return fail(GTE_ERR_INVALID, "first_device (int64 [n_ids + 1]), closed_device and env_ids_device (int32 [n_ids]) "
-                "must be aligned device pointers");
-  if ((uintptr_t)trades_device & 15) return fail(GTE_ERR_INVALID, "trades_device must be 16-byte aligned");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
-  hipError_t le = gte::launch_trade_list_scan(E->tr_stats, tl, E->p.N, env_ids_device, n_ids, first_device,
-                                              closed_device, E->stream);
-  if (le == hipSuccess && max_trades > 0 && n_ids > 0)
-    le = gte::launch_trade_list_pack(tl, E->p.N, env_ids_device, n_ids, first_device, trades_device, max_trades,
-                                     E->stream);
-  if (le != hipSuccess) return fail(GTE_ERR_HIP, "trade list gather launch: %s", hipGetErrorString(le));
-  return GTE_OK;
-}
-
-int gte_read_trade_stats(gte_env* E, int32_t first, int32_t count, gte_trade_stats* out) {
-  return read_records(E, "gte_read_trade_stats", "gte_track_trades", E ? E->tr_stats : nullptr,
-                      sizeof(gte_trade_stats), first, count, out);
-}
-
-int gte_bind_periods(gte_env* E, int32_t d, const int8_t* period_of_row) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  const Params& p = E->p;
-  if (d < 0 || d >= p.D) return fail(GTE_ERR_INVALID, "dataset index %d out of range", d);
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bind_periods inside a stream capture");
-  const int64_t T = E->h_ds[d].T;
-  if (period_of_row && T <= 0) return fail(GTE_ERR_STATE, "gte_bind_periods: dataset %d was never uploaded", d);
-  if (!period_of_row && !E->d_prow) return GTE_OK;  // nothing was ever bound
-  HIPCHK(hipSetDevice(E->cfg.device));
-  if (!E->d_prow) {
-    E->h_prow.assign((size_t)p.D, gte::PeriodRow{nullptr, 0});
-    TRY(dev_alloc(E, &E->d_prow, (size_t)p.D));
-  }
-  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight read the rows
-  if (!period_of_row) {
-    if (E->h_prow[d].base) TRY(publish_period_row(E, d, gte::PeriodRow{nullptr, 0}));
-    return GTE_OK;
-  }
-  const size_t T16 = (size_t)round_up_16(T);
-  void* row = nullptr;
-  hipError_t e = hipMalloc(&row, T16);
-  if (e == hipSuccess) e = hipMemset(row, 0xFF, T16);  // the padding: -1, a row of no period
-  if (e == hipSuccess) e = hipMemcpy(row, period_of_row, (size_t)T, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    if (row) (void)hipFree(row);
-    return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "period row of dataset %d: %s", d,
-                hipGetErrorString(e));
-  }
-  const int rc = publish_period_row(E, d, gte::PeriodRow{(const int8_t*)row, (int32_t)T16});
-  if (rc != GTE_OK) (void)hipFree(row);
-  return rc;
-}
-
-int gte_track_periods(gte_env* E, int32_t n_periods, gte_period_stats** records_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  TRY(check_n_periods(n_periods, 0));
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_track_periods before gte_reset");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_track_periods inside a stream capture");
-  if (n_periods > 0 && E->tr_on)
-    return fail(GTE_ERR_STATE, "gte_track_periods: trade tracking is on, and trade and period records together are "
-                "not implemented (gte_track_trades(env, 0, ...) first)");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(hipStreamSynchronize(E->stream));  // launches in flight write the records
-  if (n_periods > 0 && n_periods != E->pd_alloc_B) {
-    void* fresh = nullptr;
-    const hipError_t e = hipMalloc(&fresh, sizeof(gte_period_stats) * (size_t)E->p.N * (size_t)n_periods);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e == hipErrorOutOfMemory ? GTE_ERR_OOM : GTE_ERR_HIP, "period records (%d envs x %d periods): %s",
-                  E->p.N, n_periods, hipGetErrorString(e));
-    }
-    if (E->pd_stats) (void)hipFree(E->pd_stats);
-    E->pd_stats = (gte_period_stats*)fresh;  // (cleared by the next backtest call: pd_changed)
-    E->pd_alloc_B = n_periods;
-  }
-  if (n_periods != E->pd_B) E->pd_changed = true;
-  E->pd_B = n_periods;
-  if (records_device) *records_device = E->pd_stats;
-  return GTE_OK;
-}
-
-int gte_read_period_stats(gte_env* E, int32_t first, int32_t count, gte_period_stats* out) {
-  return read_records(E, "gte_read_period_stats", "gte_track_periods", E ? E->pd_stats : nullptr,
-                      E ? sizeof(gte_period_stats) * (size_t)E->pd_alloc_B : 0, first, count, out);
-}
-
-int gte_reduce_period_stats(gte_env* E, const gte_period_stats* records_device, int32_t n_periods, int32_t n_strategies,
-                            const int32_t* group_offsets_device, const int32_t* group_envs_device,
-                            gte_strategy_period_stats* out_device) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_n_periods(n_periods, 1));
-  TRY(check_reduce_args(E, "gte_reduce_period_stats", records_device, group_offsets_device, group_envs_device,
-                        out_device));
-  if (!records_device && !E->pd_stats)
-    return fail(GTE_ERR_STATE, "gte_reduce_period_stats before gte_track_periods: the env has no period records yet");
-  if (!records_device && n_periods != E->pd_alloc_B)
-    return fail(GTE_ERR_INVALID, "n_periods %d: the env's records have %d", n_periods, E->pd_alloc_B);
-  const gte_period_stats* const records = records_device ? records_device : E->pd_stats;
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const hipError_t e = gte::launch_reduce_period_stats(records, E->p.N, n_periods, n_strategies, E->cfg.env_id_base,
-                                                       group_offsets_device, group_envs_device, out_device, E->stream);
-  if (e != hipSuccess) return fail(GTE_ERR_HIP, "period reduction launch: %s", hipGetErrorString(e));
-  return GTE_OK;
-}
-
-int gte_rank_period_stats(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
-                          int32_t n_periods, const uint64_t period_mask[2], int32_t metric, int64_t min_steps, int32_t k,
-                          int32_t* top_index_device, double* top_score_device, double* scores_device) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_n_periods(n_periods, 1));
-  TRY(check_period_mask(period_mask));
-  TRY(check_rank_args(E, "gte_rank_period_stats", k, metric, GTE_PERIOD_METRIC_MEAN_REWARD,
-                      GTE_PERIOD_METRIC_POSITIVE_SHARE, stats_device, top_index_device, top_score_device,
-                      scores_device));
-  HIPCHK(hipSetDevice(E->cfg.device));
-  TRY(rank_scratch(E, n_strategies));
-  const hipError_t e = gte::launch_period_scores(stats_device, n_strategies, n_periods, period_mask, metric, min_steps,
-                                                 scores_device, E->rank_score[0], E->rank_index[0], E->stream);
-  return rank_select(E, e, "period", n_strategies, k, top_index_device, top_score_device);
-}
-
-int gte_bootstrap_weights(gte_env* E, int32_t n, int32_t n_resamples, double block, uint64_t seed,
-                          double* weights_device) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (n < 2 || n > GTE_MAX_PERIODS) return fail(GTE_ERR_INVALID, "n %d outside [2, %d]", n, GTE_MAX_PERIODS);
-  TRY(check_n_resamples(n_resamples));
-  if (!(block >= 1.0)) return fail(GTE_ERR_INVALID, "block must be >= 1.0");
-  if (!weights_device || ((uintptr_t)weights_device & 7))
-    return fail(GTE_ERR_INVALID, "weights_device must be an 8-byte aligned device array");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_bootstrap_weights inside a stream capture");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  double t = floor(4294967296.0 / block);
-  if (t > 4294967295.0) t = 4294967295.0;
-  return launched(gte::launch_bootstrap_weights(n, n_resamples, (uint32_t)t, block == 1.0 ? 1 : 0, seed,
-                                                weights_device, E->stream),
-                  "bootstrap weights");
-}
-
-int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
-                      int32_t n_periods, const uint64_t period_mask[2], const double* benchmark_device,
-                      const double* weights_device, int32_t n_resamples, const gte_reality_check_out* out) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_n_periods(n_periods, 1));
-  TRY(check_n_resamples(n_resamples));
-  TRY(check_period_mask(period_mask));
-  int n;
-  TRY(count_periods(period_mask, n_periods, &n));
-  if (n < 2) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: at least two are needed", n);
-  TRY(check_stats(stats_device));
-  if (!weights_device || ((uintptr_t)weights_device & 7) || ((uintptr_t)benchmark_device & 7))
-    return fail(GTE_ERR_INVALID, "weights_device (required) and benchmark_device must be 8-byte aligned device arrays");
-  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
-  if (!all_aligned({out->mean, out->boot_sum, out->boot_sq_sum, out->max_stat, out->summary}, 7))
-    return fail(GTE_ERR_INVALID, "out: mean, boot_sum, boot_sq_sum, max_stat and summary must be 8-byte aligned device pointers");
-  if (!all_aligned({out->count_ge, out->count_adj, out->max_index}, 3))
-    return fail(GTE_ERR_INVALID, "out: count_ge, count_adj and max_index must be 4-byte aligned device pointers");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reality_check inside a stream capture");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  TRY(grow(E, &E->boot_scratch, gte::reality_check_scratch_bytes(n_strategies, n, n_resamples)));
-  return launched(gte::launch_reality_check(stats_device, n_strategies, n_periods, period_mask, n, benchmark_device,
-                                            weights_device, n_resamples, *out, E->boot_scratch.base, E->stream),
-                  "reality check");
-}
-
-int gte_cscv(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
-             const uint64_t* group_masks, int32_t n_groups, const uint32_t* is_groups, const uint32_t* oos_groups,
-             int32_t n_splits, int32_t metric, const gte_cscv_out* out) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_n_periods(n_periods, 1));
-  if (n_groups < 2 || n_groups > GTE_CSCV_MAX_GROUPS)
-    return fail(GTE_ERR_INVALID, "n_groups %d outside [2, %d]", n_groups, GTE_CSCV_MAX_GROUPS);
-  if (n_splits < 1 || n_splits > GTE_CSCV_MAX_SPLITS)
-    return fail(GTE_ERR_INVALID, "n_splits %d outside [1, %d]", n_splits, GTE_CSCV_MAX_SPLITS);
-  if (metric != GTE_PERIOD_METRIC_MEAN_REWARD && metric != GTE_PERIOD_METRIC_SHARPE &&
-      metric != GTE_PERIOD_METRIC_REWARD_SUM)
-    return fail(GTE_ERR_INVALID, "metric %d: gte_cscv scores by MEAN_REWARD, SHARPE or REWARD_SUM", metric);
-  TRY(check_stats(stats_device));
-  if (!all_aligned({group_masks}, 7)) return fail(GTE_ERR_INVALID, "group_masks must be an 8-byte aligned host array");
-  if (!all_aligned({is_groups, oos_groups}, 3))
-    return fail(GTE_ERR_INVALID, "is_groups and oos_groups must be 4-byte aligned host arrays");
-  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
-  if (!all_aligned({out->is_score, out->oos_score}, 7) || !all_aligned({out->summary}, 3))
-    return fail(GTE_ERR_INVALID, "out: is_score and oos_score must be 8-byte, summary 4-byte aligned device pointers");
-  if (!all_aligned({out->best, out->below, out->equal, out->ranked}, 3))
-    return fail(GTE_ERR_INVALID, "out: best, below, equal and ranked must be 4-byte aligned device pointers");
-  uint64_t seen[2] = {0, 0};
-  for (int g = 0; g < n_groups; ++g) {
-    const uint64_t w0 = group_masks[2 * g], w1 = group_masks[2 * g + 1];
-    if (!(w0 | w1)) return fail(GTE_ERR_INVALID, "group %d is empty", g);
-    for (int b = n_periods; b < 128; ++b)
-      if (((b < 64 ? w0 : w1) >> (b & 63)) & 1)
-        return fail(GTE_ERR_INVALID, "group %d selects period %d, at or above n_periods %d", g, b, n_periods);
-    if ((w0 & seen[0]) | (w1 & seen[1])) return fail(GTE_ERR_INVALID, "group %d shares a period with an earlier group", g);
-    seen[0] |= w0;
-    seen[1] |= w1;
-  }
-  const uint32_t all = n_groups == 32 ? 0xFFFFFFFFu : (1u << n_groups) - 1u;
-  for (int c = 0; c < n_splits; ++c) {
-    const uint32_t a = is_groups[c], b = oos_groups[c];
-    if (!a || !b) return fail(GTE_ERR_INVALID, "split %d has an empty %s side", c, !a ? "in-sample" : "out-of-sample");
-    if ((a | b) & ~all) return fail(GTE_ERR_INVALID, "split %d uses a group at or above n_groups %d", c, n_groups);
-    if (a & b) return fail(GTE_ERR_INVALID, "split %d has a group on both sides", c);
-  }
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_cscv inside a stream capture");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  TRY(grow(E, &E->cscv_scratch, gte::cscv_scratch_bytes(n_strategies, n_groups, n_splits)));
-  // the three tables packed as gte_launch.h lays them out, so that one copy stages them
-  std::vector<uint8_t> tables(gte::cscv_table_bytes(n_groups, n_splits));
-  memcpy(tables.data(), group_masks, 16 * (size_t)n_groups);
-  memcpy(tables.data() + 16 * (size_t)n_groups, is_groups, 4 * (size_t)n_splits);
-  memcpy(tables.data() + 16 * (size_t)n_groups + 4 * (size_t)n_splits, oos_groups, 4 * (size_t)n_splits);
-  return launched(gte::launch_cscv(stats_device, n_strategies, n_periods, tables.data(), n_groups, n_splits, metric,
-                                   *out, E->cscv_scratch.base, E->stream),
-                  "cscv");
-}
-
-int gte_diversify(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
-                  const uint64_t period_mask[2], const double* scores_device, double max_corr, int32_t k,
-                  const gte_diversify_out* out) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_n_periods(n_periods, 1));
-  if (k < 1 || k > GTE_RANK_MAX) return fail(GTE_ERR_INVALID, "k must lie in [1, %d]", GTE_RANK_MAX);
-  TRY(check_period_mask(period_mask));
-  int n;
-  TRY(count_periods(period_mask, n_periods, &n));
-  if (n < 3) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: a correlation needs at least three", n);
-  if (max_corr != max_corr) return fail(GTE_ERR_INVALID, "max_corr is NaN");
-  TRY(check_stats(stats_device));
-  if (!all_aligned({scores_device}, 7)) return fail(GTE_ERR_INVALID, "scores_device must be an 8-byte aligned device array");
-  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
-  if (!all_aligned({out->pick_score, out->owner_corr, out->pick_corr}, 7))
-    return fail(GTE_ERR_INVALID, "out: pick_score, owner_corr and pick_corr must be 8-byte aligned device pointers");
-  if (!all_aligned({out->pick, out->cluster_size, out->owner, out->summary}, 3))
-    return fail(GTE_ERR_INVALID, "out: pick, cluster_size, owner and summary must be 4-byte aligned device pointers");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_diversify inside a stream capture");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  TRY(grow(E, &E->div_scratch, gte::diversify_scratch_bytes(n_strategies, n, k)));
-  return launched(gte::launch_diversify(stats_device, n_strategies, n_periods, period_mask, n, scores_device, max_corr,
-                                        k, *out, E->div_scratch.base, E->stream),
-                  "diversify");
-}
-
-int gte_pool_trades(gte_env* E, int32_t n_strategies, const int32_t* group_offsets_device,
-                    const int32_t* group_envs_device, const int32_t* strategies_device, int32_t n_pools,
-                    int64_t* first_device, int32_t* truncated_device, double* factors_device, int64_t max_factors) {
-  TRY(check_strategies(E, n_strategies));
-  TRY(check_n_pools(n_pools));
-  if ((group_offsets_device == nullptr) != (group_envs_device == nullptr))
-    return fail(GTE_ERR_INVALID, "group_offsets and group_envs: both or neither");
-  if (((uintptr_t)group_offsets_device & 3) || ((uintptr_t)group_envs_device & 3))
-    return fail(GTE_ERR_INVALID, "the group lists must be 4-byte aligned");
-  if (!all_aligned({strategies_device, truncated_device}, 3))
-    return fail(GTE_ERR_INVALID, "strategies_device and truncated_device (int32 [n_pools]) must be 4-byte aligned device pointers");
-  if (!all_aligned({first_device}, 7))
-    return fail(GTE_ERR_INVALID, "first_device (int64 [n_pools + 1]) must be an 8-byte aligned device pointer");
-  if (max_factors < 0 || (max_factors > 0 && !factors_device) || ((uintptr_t)factors_device & 7))
-    return fail(GTE_ERR_INVALID, "factors_device (f64 [max_factors]) is NULL or not 8-byte aligned, or max_factors < 0");
-  TRY(trade_list_on(E, "gte_pool_trades"));
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_pool_trades inside a stream capture");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const gte::TradeList tl = {E->tl_list, E->tl_open_row, E->tl_cap};
-  hipError_t le = gte::launch_pool_count(E->tr_stats, tl, E->p.N, n_strategies, E->cfg.env_id_base,
-                                         group_offsets_device, group_envs_device, strategies_device, n_pools,
-                                         first_device, truncated_device, E->stream);
-  if (le == hipSuccess && max_factors > 0)
-    le = gte::launch_pool_pack(E->tr_stats, tl, E->p.N, n_strategies, E->cfg.env_id_base, group_offsets_device,
-                               group_envs_device, strategies_device, n_pools, first_device, factors_device,
-                               max_factors, E->stream);
-  return launched(le, "trade pool");
-}
-
-int gte_trade_monte_carlo(gte_env* E, const double* factors_device, const int64_t* first_device,
-                          const uint32_t* stream_device, int32_t n_pools, int32_t n_resamples, int32_t path_len,
-                          uint64_t seed, double ruin_level, const double* dd_levels, int32_t n_levels,
-                          const gte_mc_out* out) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  TRY(check_n_pools(n_pools));
-  if (n_resamples < 1 || n_resamples > GTE_MC_MAX_RESAMPLES)
-    return fail(GTE_ERR_INVALID, "n_resamples %d outside [1, %d]", n_resamples, GTE_MC_MAX_RESAMPLES);
-  if (path_len < 0 || path_len > GTE_MC_MAX_PATH)
-    return fail(GTE_ERR_INVALID, "path_len %d outside [0, %d]", path_len, GTE_MC_MAX_PATH);
-  if (n_levels < 0 || n_levels > GTE_MC_MAX_LEVELS)
-    return fail(GTE_ERR_INVALID, "n_levels %d outside [0, %d]", n_levels, GTE_MC_MAX_LEVELS);
-  if (ruin_level != ruin_level) return fail(GTE_ERR_INVALID, "ruin_level is NaN");
-  if (!all_aligned({factors_device, first_device}, 7))
-    return fail(GTE_ERR_INVALID, "factors_device (f64) and first_device (int64 [n_pools + 1]) must be 8-byte aligned device pointers");
-  if ((uintptr_t)stream_device & 3) return fail(GTE_ERR_INVALID, "stream_device must be 4-byte aligned");
-  if (n_levels > 0 && !all_aligned({dd_levels}, 7))
-    return fail(GTE_ERR_INVALID, "dd_levels must be an 8-byte aligned host array of n_levels doubles");
-  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
-  if (!all_aligned({out->pool}, 15)) return fail(GTE_ERR_INVALID, "out: pool must be a 16-byte aligned device pointer");
-  if (((uintptr_t)out->final & 7) || ((uintptr_t)out->max_drawdown & 7) || ((uintptr_t)out->low & 7) ||
-      ((uintptr_t)out->max_loss_streak & 3))
-    return fail(GTE_ERR_INVALID, "out: final, max_drawdown and low must be 8-byte, max_loss_streak 4-byte aligned device pointers");
-  if (((uintptr_t)out->dd_count & 3) || (n_levels > 0 && !out->dd_count))
-    return fail(GTE_ERR_INVALID, "out: dd_count (int32 [n_pools * n_levels]) must be a 4-byte aligned device pointer");
-  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_trade_monte_carlo inside a stream capture");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  TRY(grow(E, &E->mc_scratch, gte::monte_carlo_scratch_bytes(n_pools, n_resamples, n_levels)));
-  return launched(gte::launch_trade_monte_carlo(factors_device, first_device, stream_device, n_pools, n_resamples,
-                                                path_len, seed, ruin_level, dd_levels, n_levels, *out,
-                                                E->mc_scratch.base, E->stream),
-                  "trade Monte Carlo");
-}
+}  // namespace gte_host
+extern "C" {
 
 int gte_add_limit_orders(gte_env* E, const int32_t* pos_index, const double* limit,
                          const uint8_t* persistent) {
@@ -2092,152 +979,6 @@ int gte_add_limit_orders(gte_env* E, const int32_t* pos_index, const double* lim
   HIPCHK(gte::launch_add_orders(p, E->d_inj_pos, E->d_lo_limit_in,
                                 persistent ? E->d_lo_persist_in : nullptr, E->stream));
   HIPCHK(hipStreamSynchronize(E->stream));  // host arrays and staging buffers are free again
-  return GTE_OK;
-}
-
-int gte_get_log(gte_env* E, gte_log_view* out) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
-  gte::LogRow* r = E->log.rows;  // the columns as strided views of the [L, N] rows
-  out->idx = &r->idx; out->step = &r->step; out->position_index = &r->pos;
-  out->dataset_index = &r->dsi; out->portfolio_valuation = &r->pv;
-  out->real_position = &r->realpos; out->reward = &r->reward; out->flags = &r->flags;
-  out->rows = E->log_rows; out->L = E->cfg.log_steps; out->N = E->p.N;
-  out->asset = &r->asset; out->fiat = &r->fiat;
-  out->interest_asset = &r->ia; out->interest_fiat = &r->ifi;
-  out->env_stride = (int64_t)sizeof(gte::LogRow);
-  out->row_stride = (int64_t)sizeof(gte::LogRow) * E->p.N;
-  out->cursor = E->log_cursor; out->cursor_slot = E->term_slot; out->reserved0 = 0;
-  return GTE_OK;
-}
-
-// rows first .. first+n-1 (mod L) of ONE env, oldest first: at most two strided 2-D copies per array
-static int pull_log_column(gte_env* E, int32_t env_id, int64_t first, int32_t n, void* host,
-                           size_t offset, size_t elem) {
-  if (!host) return GTE_OK;
-  const int N = E->p.N, L = E->cfg.log_steps;
-  const size_t pitch = sizeof(gte::LogRow) * (size_t)N;  // the same env, one row later
-  const char* col = (const char*)E->log.rows + offset + sizeof(gte::LogRow) * (size_t)env_id;
-  const int64_t run1 = (first + n <= L) ? n : (L - first);
-  HIPCHK(hipMemcpy2D(host, elem, col + (size_t)first * pitch, pitch, elem, (size_t)run1,
-                     hipMemcpyDeviceToHost));
-  if (run1 < n)
-    HIPCHK(hipMemcpy2D((char*)host + run1 * elem, elem, col, pitch, elem, (size_t)(n - run1),
-                       hipMemcpyDeviceToHost));
-  return GTE_OK;
-}
-
-static int log_window(gte_env* E, int32_t env_id, int32_t* n, int32_t* n_out, int64_t* first) {
-  if (!E || !n_out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
-  const int N = E->p.N, L = E->cfg.log_steps;
-  if (env_id < 0 || env_id >= N) return fail(GTE_ERR_INVALID, "env_id out of range");
-  const int64_t have = E->log_rows < L ? E->log_rows : L;
-  if (*n > have) *n = (int32_t)have;
-  if (*n < 0) *n = 0;
-  *n_out = *n;
-  *first = *n ? (E->log_rows - *n) % L : 0;
-  if (*n) {
-    HIPCHK(hipSetDevice(E->cfg.device));
-    HIPCHK(hipStreamSynchronize(E->stream));
-  }
-  return GTE_OK;
-}
-
-int gte_read_log(gte_env* E, int32_t env_id, int32_t n, int32_t* idx, int32_t* step,
-                 int32_t* position_index, int32_t* dataset_index, double* portfolio_valuation,
-                 double* real_position, double* reward, uint8_t* flags, int32_t* n_out) {
-  int64_t first = 0;
-  TRY(log_window(E, env_id, &n, n_out, &first));
-  if (n == 0) return GTE_OK;
-  TRY(pull_log_column(E, env_id, first, n, idx, offsetof(gte::LogRow, idx), 4));
-  TRY(pull_log_column(E, env_id, first, n, step, offsetof(gte::LogRow, step), 4));
-  TRY(pull_log_column(E, env_id, first, n, position_index, offsetof(gte::LogRow, pos), 4));
-  TRY(pull_log_column(E, env_id, first, n, dataset_index, offsetof(gte::LogRow, dsi), 4));
-  TRY(pull_log_column(E, env_id, first, n, portfolio_valuation, offsetof(gte::LogRow, pv), 8));
-  TRY(pull_log_column(E, env_id, first, n, real_position, offsetof(gte::LogRow, realpos), 8));
-  TRY(pull_log_column(E, env_id, first, n, reward, offsetof(gte::LogRow, reward), 8));
-  TRY(pull_log_column(E, env_id, first, n, flags, offsetof(gte::LogRow, flags), 1));
-  return GTE_OK;
-}
-
-int gte_read_log_portfolio(gte_env* E, int32_t env_id, int32_t n, double* asset, double* fiat,
-                           double* interest_asset, double* interest_fiat, int32_t* n_out) {
-  int64_t first = 0;
-  TRY(log_window(E, env_id, &n, n_out, &first));
-  if (n == 0) return GTE_OK;
-  TRY(pull_log_column(E, env_id, first, n, asset, offsetof(gte::LogRow, asset), 8));
-  TRY(pull_log_column(E, env_id, first, n, fiat, offsetof(gte::LogRow, fiat), 8));
-  TRY(pull_log_column(E, env_id, first, n, interest_asset, offsetof(gte::LogRow, ia), 8));
-  TRY(pull_log_column(E, env_id, first, n, interest_fiat, offsetof(gte::LogRow, ifi), 8));
-  return GTE_OK;
-}
-
-int gte_read_log_envs(gte_env* E, const int32_t* env_ids, int32_t n_ids, int32_t max_rows,
-                      int32_t finished, gte_log_batch* out) {
-  if (!E || !env_ids || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
-  if (n_ids < 0) return fail(GTE_ERR_INVALID, "n_ids must be >= 0");
-  if (finished && !E->p.final_rec)
-    return fail(GTE_ERR_STATE, "finished episodes need autoreset = same-step with final_obs");
-  const int N = E->p.N, L = E->cfg.log_steps;
-  if (max_rows <= 0 || max_rows > L) max_rows = L;
-  for (int32_t i = 0; i < n_ids; ++i)
-    if (env_ids[i] < 0 || env_ids[i] >= N) return fail(GTE_ERR_INVALID, "env_ids[%d] = %d out of range", i, env_ids[i]);
-  memset(out, 0, sizeof *out);
-  out->n_ids = n_ids; out->max_rows = max_rows;
-  if (n_ids == 0) return GTE_OK;
-  HIPCHK(hipSetDevice(E->cfg.device));
-  // [ids i32 n | n_rows i32 n | pad -> 16] [7 f64 columns] [4 i32 columns] [u8 column]
-  const size_t cells = (size_t)n_ids * (size_t)max_rows;
-  const size_t head = (((size_t)n_ids * 8) + 15) & ~(size_t)15;
-  const size_t need = head + cells * (7 * 8 + 4 * 4 + 1);
-  if (need > E->h_logpack_bytes) {  // pinned and mapped: the kernel writes host memory directly
-    if (E->h_logpack) HIPCHK(hipHostFree(E->h_logpack));
-    E->h_logpack = nullptr; E->h_logpack_bytes = 0;
-    HIPCHK(hipHostMalloc(&E->h_logpack, need + need / 2, hipHostMallocMapped));
-    E->h_logpack_bytes = need + need / 2;
-  }
-  char* b = (char*)E->h_logpack;
-  int32_t* ids = (int32_t*)b;
-  memcpy(ids, env_ids, sizeof(int32_t) * (size_t)n_ids);
-  gte::LogPack o;
-  o.n_rows = ids + n_ids;
-  double* f = (double*)(b + head);
-  o.pv = f; o.realpos = f + cells; o.reward = f + 2 * cells; o.asset = f + 3 * cells;
-  o.fiat = f + 4 * cells; o.ia = f + 5 * cells; o.ifi = f + 6 * cells;
-  int32_t* w = (int32_t*)(f + 7 * cells);
-  o.idx = w; o.step = w + cells; o.pos = w + 2 * cells; o.dsi = w + 3 * cells;
-  o.flags = (uint8_t*)(w + 4 * cells);
-  HIPCHK(gte::launch_pack_log(E->log, N, L, (long long)E->log_rows, ids, n_ids, max_rows, finished ? 1 : 0,
-                              E->cfg.autoreset == GTE_AUTORESET_DISABLED ? 1 : 0,
-                              E->p.final_rec, E->p.reward64, o, E->stream));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  out->n_rows = o.n_rows;
-  out->idx = o.idx; out->step = o.step; out->position_index = o.pos; out->dataset_index = o.dsi;
-  out->portfolio_valuation = o.pv; out->real_position = o.realpos; out->reward = o.reward;
-  out->asset = o.asset; out->fiat = o.fiat; out->interest_asset = o.ia; out->interest_fiat = o.ifi;
-  out->flags = o.flags;
-  return GTE_OK;
-}
-
-int gte_set_log_reward(gte_env* E, const double* reward_device) {
-  if (!E || !reward_device) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
-  if (E->log_rows <= 0) return fail(GTE_ERR_STATE, "the log is empty");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(gte::launch_set_log_reward(E->log.rows, E->log_cursor + E->term_slot, E->cfg.log_steps, E->p.N,
-                                    reward_device, E->stream));
-  return GTE_OK;
-}
-
-int gte_apply_reward(gte_env* E, const double* reward_device, int32_t terminal_view) {
-  if (!E || !reward_device) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (E->cfg.log_steps <= 0) return fail(GTE_ERR_STATE, "created with log_steps = 0");
-  if (E->log_rows <= 0) return fail(GTE_ERR_STATE, "the log is empty");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  HIPCHK(gte::launch_apply_reward(E->p, reward_device, E->log.rows, E->log_cursor + E->term_slot,
-                                  terminal_view ? 1 : 0, E->stream));
   return GTE_OK;
 }
 
@@ -2311,59 +1052,6 @@ int gte_bind_sliding_obs(gte_env* E, float* base, int32_t rows_per_env) {
   return GTE_OK;
 }
 
-static_assert(sizeof(gte_env_snapshot) == 96, "gte_env_snapshot layout");
-
-static int read_envs_impl(gte_env* E, int32_t first, int32_t count, int32_t want_obs,
-                          const gte_env_snapshot** out, const float** obs, bool hands_out_views) {
-  if (!E || !out) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (!E->was_reset) return fail(GTE_ERR_STATE, "gte_read_envs before gte_reset");
-  if (first < 0 || count < 1 || (int64_t)first + count > E->p.N)
-    return fail(GTE_ERR_INVALID, "envs %d..%lld out of range", first, (long long)first + count - 1);
-  if (want_obs && !obs) return fail(GTE_ERR_INVALID, "obs is NULL");
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const size_t elems = (size_t)E->p.W * (size_t)E->p.Fobs;
-  const size_t head = sizeof(gte_env_snapshot) * (size_t)count;  // 96 B each: 16-byte aligned
-  const size_t need = head + (want_obs ? sizeof(float) * elems * (size_t)count : 0);
-  // Callers may hold views into the staging buffer: once it exists at full size it is never
-  // reallocated, so size it for the whole batch the first time a buffer is made.
-  const size_t full = (sizeof(gte_env_snapshot) + sizeof(float) * elems) * (size_t)E->p.N;
-  if (hands_out_views) E->view_reads = true;
-  const size_t want = E->view_reads ? full : need;
-  if (want > E->h_snap_bytes) {  // pinned and mapped: the kernel writes host memory directly
-    if (E->h_snap) HIPCHK(hipHostFree(E->h_snap));
-    E->h_snap = nullptr; E->h_snap_bytes = 0;
-    HIPCHK(hipHostMalloc(&E->h_snap, want, hipHostMallocMapped));
-    E->h_snap_bytes = want;
-  }
-  float* h_obs = (float*)((char*)E->h_snap + head);
-  HIPCHK(gte::launch_snapshot(E->p.rec, E->p.reward64, E->p.terminated, E->p.truncated, obs_window0(E->p),
-                              (int64_t)elems, obs_env_stride(E->p), first, count, E->h_snap,
-                              want_obs ? h_obs : nullptr, E->stream));
-  HIPCHK(hipStreamSynchronize(E->stream));
-  *out = (const gte_env_snapshot*)E->h_snap;
-  if (obs) *obs = want_obs ? h_obs : nullptr;
-  return GTE_OK;
-}
-
-int gte_read_envs_view(gte_env* E, int32_t first, int32_t count, int32_t want_obs,
-                       const gte_env_snapshot** out, const float** obs) {
-  return read_envs_impl(E, first, count, want_obs, out, obs, true);
-}
-
-int gte_read_envs(gte_env* E, int32_t first, int32_t count, gte_env_snapshot* out, float* obs) {
-  if (!out) return fail(GTE_ERR_INVALID, "NULL argument");
-  const gte_env_snapshot* snaps = nullptr;
-  const float* h_obs = nullptr;
-  TRY(read_envs_impl(E, first, count, obs ? 1 : 0, &snaps, &h_obs, false));
-  memcpy(out, snaps, sizeof(gte_env_snapshot) * (size_t)count);
-  if (obs) memcpy(obs, h_obs, sizeof(float) * (size_t)E->p.W * (size_t)E->p.Fobs * (size_t)count);
-  return GTE_OK;
-}
-
-int gte_read_env(gte_env* E, int32_t e, gte_env_snapshot* out, float* obs) {
-  return gte_read_envs(E, e, 1, out, obs);
-}
-
 int gte_bind_returns(gte_env* E, float* reward, uint8_t* terminated, uint8_t* truncated) {
   if (!E || !reward || !terminated || !truncated) return fail(GTE_ERR_INVALID, "NULL argument");
   // Params travel by value with every launch: later launches see the new pointers,
@@ -2418,127 +1106,6 @@ int gte_get_final_state(gte_env* E, gte_state_view* out) {
   return state_view(E, E->p.final_rec, E->fsoa, out);
 }
 
-// ---------------------------------------------------------------------------
-// multi-GPU: the return all-gather over RCCL (gte_comm.hip)
-
-int gte_comm_unique_id(uint8_t* id_out) {
-  if (!id_out) return fail(GTE_ERR_INVALID, "id_out is NULL");
-  if (const char* why = gte::rccl_load()) return fail(GTE_ERR_STATE, "RCCL unavailable: %s", why);
-  const int r = gte::rccl_unique_id(id_out);
-  if (r != 0) return fail(GTE_ERR_HIP, "ncclGetUniqueId: %s", gte::rccl_error(r));
-  return GTE_OK;
-}
-
-int gte_comm_init(gte_env* E, const uint8_t* id, int32_t rank, int32_t world) {
-  if (!E || !id) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (world < 1 || rank < 0 || rank >= world) return fail(GTE_ERR_INVALID, "rank %d of %d", rank, world);
-  if (E->comm) return fail(GTE_ERR_STATE, "the env already has a communicator");
-  if (const char* why = gte::rccl_load()) return fail(GTE_ERR_STATE, "RCCL unavailable: %s", why);
-  HIPCHK(hipSetDevice(E->cfg.device));
-  const int r = gte::rccl_comm_init(&E->comm, id, rank, world);
-  if (r != 0) { E->comm = nullptr; return fail(GTE_ERR_HIP, "ncclCommInitRank: %s", gte::rccl_error(r)); }
-  E->comm_rank = rank;
-  E->comm_world = world;
-  // anything failing from here on must not leave a half-made communicator behind (a retry would
-  // be refused with "already has a communicator"): undo everything, keep the error message
-  auto finish = [&]() -> int {
-    HIPCHK(hipStreamCreateWithFlags(&E->comm_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&E->comm_ready, hipEventDisableTiming));
-    for (auto& ev : E->comm_done) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    if (E->gathered_returns) {  // a communicator of another size was here before
-      for (void*& q : E->allocs) if (q == (void*)E->gathered_returns) q = nullptr;
-      (void)hipFree(E->gathered_returns);
-      E->gathered_returns = nullptr;
-    }
-    TRY(dev_alloc(E, &E->gathered_returns, (size_t)world * 6 * (size_t)E->p.N));
-    HIPCHK(hipDeviceSynchronize());
-    return GTE_OK;
-  };
-  const int rc = finish();
-  if (rc != GTE_OK) {
-    const std::string keep = g_err;
-    (void)gte_comm_destroy(E);
-    g_err = keep;
-  }
-  return rc;
-}
-
-int gte_allgather(gte_env* E, const void* src_device, void* dst_device, uint64_t bytes_per_rank,
-                  int32_t mode) {
-  if (!E || !src_device || !dst_device) return fail(GTE_ERR_INVALID, "NULL argument");
-  if (!E->comm) return fail(GTE_ERR_STATE, "gte_allgather before gte_comm_init");
-  if (mode != 0 && mode != 1) return fail(GTE_ERR_INVALID, "mode must be 0 (env stream) or 1 (overlapped)");
-  hipStream_t s = E->stream;
-  if (mode == 1) {  // behind everything enqueued so far, beside everything enqueued later
-    HIPCHK(hipEventRecord(E->comm_ready, E->stream));
-    HIPCHK(hipStreamWaitEvent(E->comm_stream, E->comm_ready, 0));
-    s = E->comm_stream;
-  }
-  const int r = gte::rccl_allgather_bytes(E->comm, src_device, dst_device, (size_t)bytes_per_rank, s);
-  if (r != 0) return fail(GTE_ERR_HIP, "ncclAllGather: %s", gte::rccl_error(r));
-  if (mode == 1) {
-    HIPCHK(hipEventRecord(E->comm_done[E->comm_seq & 3], E->comm_stream));
-    E->comm_seq += 1;
-  }
-  return GTE_OK;
-}
-
-int gte_allgather_returns(gte_env* E, void* dst_device, int32_t mode, const void** gathered) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!E->comm) return fail(GTE_ERR_STATE, "gte_allgather_returns before gte_comm_init");
-  const Params& p = E->p;
-  const size_t N = (size_t)p.N;
-  if ((const uint8_t*)p.terminated != (const uint8_t*)p.reward + 4 * N || p.truncated != p.terminated + N)
-    return fail(GTE_ERR_STATE, "the bound return buffers are not one packed [reward f32 | terminated u8 "
-                               "| truncated u8] block of 6N bytes");
-  void* dst = dst_device ? dst_device : (void*)E->gathered_returns;
-  TRY(gte_allgather(E, p.reward, dst, 6 * N, mode));
-  if (gathered) *gathered = dst;
-  return GTE_OK;
-}
-
-int gte_allgather_obs(gte_env* E, float* dst_device, int32_t mode) {
-  if (!E || !dst_device) return fail(GTE_ERR_INVALID, "NULL argument");
-  const Params& p = E->p;
-  if (!p.obs) return fail(GTE_ERR_STATE, "gte_allgather_obs before gte_reset (no observation exists yet)");
-  if (E->sliding)
-    return fail(GTE_ERR_STATE, "gte_allgather_obs on a sliding observation buffer: the windows are not contiguous "
-                               "(bind a classic buffer with gte_bind_outputs first)");
-  return gte_allgather(E, p.obs, dst_device, sizeof(float) * (size_t)p.N * p.W * p.Fobs, mode);
-}
-
-int gte_comm_wait(gte_env* E, int32_t back) {
-  if (!E || !E->comm) return fail(GTE_ERR_STATE, "no communicator");
-  if (back < 0 || back > 3) return fail(GTE_ERR_INVALID, "back must be 0..3");
-  const int64_t k = E->comm_seq - 1 - back;  // the overlapped gather to wait for
-  if (k < 0) return GTE_OK;                  // not issued yet: nothing to wait for
-  HIPCHK(hipStreamWaitEvent(E->stream, E->comm_done[k & 3], 0));
-  return GTE_OK;
-}
-
-int gte_comm_synchronize(gte_env* E) {
-  if (!E || !E->comm) return fail(GTE_ERR_STATE, "no communicator");
-  HIPCHK(hipStreamSynchronize(E->comm_stream));
-  return GTE_OK;
-}
-
-int gte_comm_destroy(gte_env* E) {
-  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
-  if (!E->comm) return GTE_OK;
-  (void)hipStreamSynchronize(E->stream);
-  if (E->comm_stream) (void)hipStreamSynchronize(E->comm_stream);
-  const int r = gte::rccl_comm_destroy(E->comm);
-  E->comm = nullptr;
-  if (E->comm_ready) (void)hipEventDestroy(E->comm_ready);
-  for (auto& ev : E->comm_done) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
-  if (E->comm_stream) (void)hipStreamDestroy(E->comm_stream);
-  E->comm_ready = nullptr;
-  E->comm_seq = 0;
-  E->comm_stream = nullptr;
-  if (r != 0) return fail(GTE_ERR_HIP, "ncclCommDestroy: %s", gte::rccl_error(r));
-  return GTE_OK;
-}
-
 int gte_set_stream(gte_env* E, void* hip_stream) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
   HIPCHK(hipStreamSynchronize(E->stream));
@@ -2579,31 +1146,6 @@ int gte_timer_stop(gte_env* E, float* elapsed_ms) {
   return GTE_OK;
 }
 
-int gte_read_obs(gte_env* E, int32_t first_env, int32_t n, float* host_dst) {
-  if (!E || !host_dst) return fail(GTE_ERR_INVALID, "NULL argument");
-  const Params& p = E->p;
-  if (first_env < 0 || n < 0 || (int64_t)first_env + n > p.N)
-    return fail(GTE_ERR_INVALID, "env range [%d, %d) out of [0, %d)", first_env, first_env + n, p.N);
-  const size_t per = (size_t)p.W * p.Fobs;
-  if (!p.obs) return fail(GTE_ERR_STATE, "gte_read_obs before gte_reset (no observation exists yet)");
-  HIPCHK(hipStreamSynchronize(E->stream));
-  const size_t stride = (size_t)obs_env_stride(p);
-  const float* src = obs_window0(p) + stride * first_env;
-  if (stride == per || n == 0)  // classic buffer: one contiguous copy
-    HIPCHK(hipMemcpy(host_dst, src, sizeof(float) * per * n, hipMemcpyDeviceToHost));
-  else
-    HIPCHK(hipMemcpy2D(host_dst, sizeof(float) * per, src, sizeof(float) * stride, sizeof(float) * per, (size_t)n,
-                       hipMemcpyDeviceToHost));
-  return GTE_OK;
-}
-
-int gte_copy_to_host(gte_env* E, const void* device_src, void* host_dst, uint64_t bytes) {
-  if (!E || !device_src || !host_dst) return fail(GTE_ERR_INVALID, "NULL argument");
-  HIPCHK(hipStreamSynchronize(E->stream));
-  HIPCHK(hipMemcpy(host_dst, device_src, (size_t)bytes, hipMemcpyDeviceToHost));
-  return GTE_OK;
-}
-
 int gte_get_launch_info(gte_env* E, int32_t* envs_per_wave, int32_t* threads_per_block,
                         int32_t* n_blocks, int32_t* vector_bytes) {
   if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
@@ -2632,25 +1174,12 @@ void gte_destroy(gte_env* E) {
   (void)gte_comm_destroy(E);
   (void)hipStreamSynchronize(E->stream);
   if (E->own_stream) (void)hipStreamSynchronize(E->own_stream);
-  for (void* ptr : E->allocs) if (ptr) (void)hipFree(ptr);
-  for (auto& v : E->ds_allocs)
-    for (void* ptr : v)
-      if (ptr) (void)hipFree(ptr);
-  for (int32_t* q : {E->d_q_idx, E->d_q_pos, E->d_q_ds})
-    if (q) (void)hipFree(q);
-  if (E->pd_stats) (void)hipFree(E->pd_stats);
-  for (void* q : {(void*)E->tl_list, (void*)E->tl_open_row, E->tl_dev})
-    if (q) (void)hipFree(q);
-  if (E->tl_host) (void)hipHostFree(E->tl_host);
-  for (const gte::PeriodRow& r : E->h_prow)
-    if (r.base) (void)hipFree(const_cast<int8_t*>(r.base));
-  if (E->h_snap) (void)hipHostFree(E->h_snap);
-  if (E->h_logpack) (void)hipHostFree(E->h_logpack);
+  for (void* ptr : E->allocs) if (ptr) device_free(ptr);
   if (E->ev0) (void)hipEventDestroy(E->ev0);
   if (E->ev1) (void)hipEventDestroy(E->ev1);
   if (E->own_stream) (void)hipStreamDestroy(E->own_stream);
   ledger().forget(E);
-  delete E;
+  delete E;  // (with every block the env may replace: the owners of gte_host.h)
 }
 
 }  // extern "C"

@@ -24,11 +24,7 @@
 
 #include <dlfcn.h>
 
-#include <cstdio>
-#include <cstring>
-#include <string>
-
-#include "gte_launch.h"
+#include "gte_host.h"  // (with <cstdio>, <cstring>, <string>)
 
 namespace gte {
 
@@ -103,3 +99,123 @@ int rccl_allgather_bytes(void* comm, const void* src, void* dst, size_t bytes, h
 int rccl_comm_destroy(void* comm) { return (int)rccl().CommDestroy((ncclComm_t)comm); }
 
 }  // namespace gte
+
+extern "C" {  // the entry points of include/gte.h that use the wrappers above
+
+int gte_comm_unique_id(uint8_t* id_out) {
+  if (!id_out) return fail(GTE_ERR_INVALID, "id_out is NULL");
+  if (const char* why = gte::rccl_load()) return fail(GTE_ERR_STATE, "RCCL unavailable: %s", why);
+  const int r = gte::rccl_unique_id(id_out);
+  if (r != 0) return fail(GTE_ERR_HIP, "ncclGetUniqueId: %s", gte::rccl_error(r));
+  return GTE_OK;
+}
+
+int gte_comm_init(gte_env* E, const uint8_t* id, int32_t rank, int32_t world) {
+  if (!E || !id) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (world < 1 || rank < 0 || rank >= world) return fail(GTE_ERR_INVALID, "rank %d of %d", rank, world);
+  if (E->comm.handle) return fail(GTE_ERR_STATE, "the env already has a communicator");
+  if (const char* why = gte::rccl_load()) return fail(GTE_ERR_STATE, "RCCL unavailable: %s", why);
+  HIPCHK(hipSetDevice(E->cfg.device));
+  const int r = gte::rccl_comm_init(&E->comm.handle, id, rank, world);
+  if (r != 0) { E->comm.handle = nullptr; return fail(GTE_ERR_HIP, "ncclCommInitRank: %s", gte::rccl_error(r)); }
+  E->comm.rank = rank;
+  E->comm.world = world;
+  // anything failing from here on must not leave a half-made communicator behind (a retry would
+  // be refused with "already has a communicator"): undo everything, keep the error message
+  auto finish = [&]() -> int {
+    HIPCHK(hipStreamCreateWithFlags(&E->comm.stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&E->comm.ready, hipEventDisableTiming));
+    for (auto& ev : E->comm.done) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    E->comm.gathered_returns.reset();  // a communicator of another size was here before
+    const size_t bytes = (size_t)world * 6 * (size_t)E->p.N;
+    TRY(device_alloc(&E->comm.gathered_returns, bytes, "gathered returns (%d ranks x %d envs): %s", world, E->p.N));
+    HIPCHK(hipMemset(E->comm.gathered_returns.get(), 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+    return GTE_OK;
+  };
+  const int rc = finish();
+  if (rc != GTE_OK) {
+    const std::string keep = g_err;
+    (void)gte_comm_destroy(E);
+    g_err = keep;
+  }
+  return rc;
+}
+
+int gte_allgather(gte_env* E, const void* src_device, void* dst_device, uint64_t bytes_per_rank,
+                  int32_t mode) {
+  if (!E || !src_device || !dst_device) return fail(GTE_ERR_INVALID, "NULL argument");
+  if (!E->comm.handle) return fail(GTE_ERR_STATE, "gte_allgather before gte_comm_init");
+  if (mode != 0 && mode != 1) return fail(GTE_ERR_INVALID, "mode must be 0 (env stream) or 1 (overlapped)");
+  hipStream_t s = E->stream;
+  if (mode == 1) {  // behind everything enqueued so far, beside everything enqueued later
+    HIPCHK(hipEventRecord(E->comm.ready, E->stream));
+    HIPCHK(hipStreamWaitEvent(E->comm.stream, E->comm.ready, 0));
+    s = E->comm.stream;
+  }
+  const int r = gte::rccl_allgather_bytes(E->comm.handle, src_device, dst_device, (size_t)bytes_per_rank, s);
+  if (r != 0) return fail(GTE_ERR_HIP, "ncclAllGather: %s", gte::rccl_error(r));
+  if (mode == 1) {
+    HIPCHK(hipEventRecord(E->comm.done[E->comm.seq & 3], E->comm.stream));
+    E->comm.seq += 1;
+  }
+  return GTE_OK;
+}
+
+int gte_allgather_returns(gte_env* E, void* dst_device, int32_t mode, const void** gathered) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!E->comm.handle) return fail(GTE_ERR_STATE, "gte_allgather_returns before gte_comm_init");
+  const Params& p = E->p;
+  const size_t N = (size_t)p.N;
+  if ((const uint8_t*)p.terminated != (const uint8_t*)p.reward + 4 * N || p.truncated != p.terminated + N)
+    return fail(GTE_ERR_STATE, "the bound return buffers are not one packed [reward f32 | terminated u8 "
+                               "| truncated u8] block of 6N bytes");
+  void* dst = dst_device ? dst_device : E->comm.gathered_returns.get();
+  TRY(gte_allgather(E, p.reward, dst, 6 * N, mode));
+  if (gathered) *gathered = dst;
+  return GTE_OK;
+}
+
+int gte_allgather_obs(gte_env* E, float* dst_device, int32_t mode) {
+  if (!E || !dst_device) return fail(GTE_ERR_INVALID, "NULL argument");
+  const Params& p = E->p;
+  if (!p.obs) return fail(GTE_ERR_STATE, "gte_allgather_obs before gte_reset (no observation exists yet)");
+  if (E->sliding)
+    return fail(GTE_ERR_STATE, "gte_allgather_obs on a sliding observation buffer: the windows are not contiguous "
+                               "(bind a classic buffer with gte_bind_outputs first)");
+  return gte_allgather(E, p.obs, dst_device, sizeof(float) * (size_t)p.N * p.W * p.Fobs, mode);
+}
+
+int gte_comm_wait(gte_env* E, int32_t back) {
+  if (!E || !E->comm.handle) return fail(GTE_ERR_STATE, "no communicator");
+  if (back < 0 || back > 3) return fail(GTE_ERR_INVALID, "back must be 0..3");
+  const int64_t k = E->comm.seq - 1 - back;  // the overlapped gather to wait for
+  if (k < 0) return GTE_OK;                  // not issued yet: nothing to wait for
+  HIPCHK(hipStreamWaitEvent(E->stream, E->comm.done[k & 3], 0));
+  return GTE_OK;
+}
+
+int gte_comm_synchronize(gte_env* E) {
+  if (!E || !E->comm.handle) return fail(GTE_ERR_STATE, "no communicator");
+  HIPCHK(hipStreamSynchronize(E->comm.stream));
+  return GTE_OK;
+}
+
+int gte_comm_destroy(gte_env* E) {
+  if (!E) return fail(GTE_ERR_INVALID, "env is NULL");
+  if (!E->comm.handle) return GTE_OK;
+  (void)hipStreamSynchronize(E->stream);
+  if (E->comm.stream) (void)hipStreamSynchronize(E->comm.stream);
+  const int r = gte::rccl_comm_destroy(E->comm.handle);
+  E->comm.handle = nullptr;
+  if (E->comm.ready) (void)hipEventDestroy(E->comm.ready);
+  for (auto& ev : E->comm.done) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+  if (E->comm.stream) (void)hipStreamDestroy(E->comm.stream);
+  E->comm.ready = nullptr;
+  E->comm.seq = 0;
+  E->comm.stream = nullptr;
+  if (r != 0) return fail(GTE_ERR_HIP, "ncclCommDestroy: %s", gte::rccl_error(r));
+  return GTE_OK;
+}
+
+}  // extern "C"

@@ -278,8 +278,27 @@ def _csrc_sources():
             if n.endswith((".hip", ".h"))}
 
 
-def _signatures(text):
-    """`ret name(params)` of every function declared or defined at column 0 inside `namespace gte`
+def _namespace_spans(text, namespace):
+    """(start, end) of the text between the braces of every `namespace <namespace> {` block that opens at column 0"""
+    spans = []
+    for m in re.finditer(rf"^namespace {namespace} \{{", text, re.M):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"{": 1, "}": -1}.get(text[i], 0)
+            i += 1
+        spans.append((m.end(), i - 1))
+    return spans
+
+
+def _outside_namespace(text, namespace):
+    for a, b in reversed(_namespace_spans(text, namespace)):
+        text = text[:a] + text[b:]
+    return text
+
+
+def _signatures(text, namespace="gte"):
+    """`ret name(params)` of every function declared or defined at column 0 inside `namespace <namespace>`
+    (every block of it the text has, each to its closing brace)
     that is not static / inline / a template / device code -> {name: (signature, is_definition)},
     white space normalised.  GTE_HOT_NAME(x) stands for x and x_nt (gte_hot.hip is compiled twice).
 
@@ -291,7 +310,7 @@ def _signatures(text):
     either: then it cannot be called across files).  Parameter NAMES are compared as well as types:
     stricter than the compiler, on purpose — the header is the one place a reader looks them up."""
     out = {}
-    inside = text.split("namespace gte {", 1)[1] if "namespace gte {" in text else ""
+    inside = "\n".join(text[a:b] for a, b in _namespace_spans(text, namespace))
     skip = r"static\b|template\b|inline\b|__global__|__device__|struct\b|typedef\b|enum\b|constexpr\b|using\b|return\b"
     for m in re.finditer(rf"^(?!{skip})([A-Za-z_][\w \*&:<>]*?[\s\*&])(GTE_HOT_NAME\(\w+\)|\w+)\(", inside, re.M):
         if re.search(r"^template\b[^\n]*\n\Z", inside[:m.start()], re.M):
@@ -329,30 +348,174 @@ def test_every_struct_under_csrc_is_defined_in_exactly_one_file():
         assert seen[s] == ["gte_plan.h"]
 
 
+def _host_units():
+    """the host side's translation units: the gte_api*.hip of the Makefile's SRCS (gte_comm.hip, which holds the
+    RCCL wrappers of `namespace gte` as well as its entry points, is added where a test says so)"""
+    units = [u for u in _makefile_srcs() if re.fullmatch(r"gte_api\w*\.hip", u)]
+    assert units == ["gte_api.hip", "gte_api_backtest.hip", "gte_api_leaderboard.hip", "gte_api_read.hip"], units
+    return units
+
+
+def _host_files():
+    return _host_units() + ["gte_host.h"]
+
+
+_DEFINITION = re.compile(r"^(?![ \t#}/])(?!(?:struct|namespace|extern|using|typedef|enum|static_assert|template)\b)"
+                         r"[^\n;{}()=]*?\b(\w+)\(", re.M)
+
+
+def _defined_functions(text):
+    """names of the functions defined at column 0 (static or not, in a namespace block or an extern "C" block or
+    outside): `... name(params) {`, the head on one line as everywhere in csrc/"""
+    out = []
+    for m in _DEFINITION.finditer(text):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"(": 1, ")": -1}.get(text[i], 0)
+            i += 1
+        if text[i:].lstrip()[:1] == "{":
+            out.append(m.group(1))
+    return out
+
+
 def test_gte_api_declares_no_gte_function_itself():
-    """The host file takes every prototype from gte_launch.h: it opens no `namespace gte` and has no
-    function declaration at file scope (the hand-copied block it had was checked against nothing)."""
-    api = _csrc_sources()["gte_api.hip"]
-    assert '#include "gte_launch.h"' in api and "namespace gte" not in api
-    protos = re.findall(r"^(?!static_assert)[A-Za-z_][^\n;{}]*\([^;{}]*\)\s*;", api, re.M)
-    assert protos == [], protos
-    assert _signatures(api) == {}
+    """The host side takes every kernel-side prototype from gte_launch.h, through gte_host.h: no host unit opens a
+    `namespace gte` or has a function declaration at file scope (the hand-copied block gte_api.hip had was checked
+    against nothing).  The only prototypes of the host side are those of `namespace gte_host` in gte_host.h."""
+    src = _csrc_sources()
+    assert '#include "gte_launch.h"' in src["gte_host.h"]
+    assert '#include "gte_host.h"' in src["gte_comm.hip"]
+    for name in _host_files():
+        text = src[name]
+        assert name == "gte_host.h" or '#include "gte_host.h"' in text, name
+        assert not re.search(r"namespace gte\b", text), name  # (`namespace gte_host` is another word)
+        protos = re.findall(r"^(?!static_assert)[A-Za-z_][^\n;{}]*\([^;{}]*\)\s*;",
+                            _outside_namespace(text, "gte_host"), re.M)
+        assert protos == [], (name, protos)
+        assert _signatures(text) == {}, name
+        if name != "gte_host.h":  # a unit defines gte_host functions, it declares none
+            assert all(is_def for _, is_def in _signatures(text, "gte_host").values()), name
+
+
+def test_host_functions_that_cross_units_are_declared_once_in_gte_host_h():
+    """Every function of `namespace gte_host` is declared in gte_host.h and defined in exactly one unit with the
+    same signature, parameter names included (the reader of the gte_launch.h test, told the namespace)."""
+    src = _csrc_sources()
+    declared = _signatures(src["gte_host.h"], "gte_host")
+    assert not any(is_def for _, is_def in declared.values())
+    assert sorted(declared) == ["backtest_entry", "fail", "launch_lookup", "publish_period_row", "publish_signal_table",
+                                "trade_list_on"]
+    defined = {}
+    for name in _host_units() + ["gte_comm.hip"]:
+        for fn, (sig, is_def) in _signatures(src[name], "gte_host").items():
+            assert is_def, f"{name} declares {fn} itself"
+            assert fn not in defined, f"{fn} is defined in {name} and in {defined[fn]}"
+            defined[fn] = name
+            assert fn in declared, f"{name}: {fn} is not declared in gte_host.h"
+            assert declared[fn][0] == sig, f"{name}: {sig}  !=  {declared[fn][0]}"
+    assert sorted(declared) == sorted(defined), "gte_host.h declares a function no unit defines"
+    # the step path stays within one unit, backtest()'s per-step loop with it: nothing that launches a step per
+    # call crosses a unit boundary (enqueue_step and what it needs are static there, as they always were)
+    assert defined["fail"] == defined["backtest_entry"] == "gte_api.hip"
+    for fn in ("enqueue_step", "own_targets", "age_order", "report_rollout_path", "backtest"):
+        assert re.search(rf"^static [^\n]*\b{fn}\(", src["gte_api.hip"], re.M), fn
+    assert src["gte_api.hip"].count("thread_local") == 1 and "extern thread_local std::string g_err;" in src["gte_host.h"]
+    for name in _host_units()[1:] + ["gte_comm.hip"]:  # ONE error string: no unit has a thread-local of its own
+        assert "thread_local" not in src[name], name
+
+
+def test_no_host_function_is_defined_twice_and_every_entry_point_once():
+    """Copying a helper into a second unit is how the copies come back: no function name is defined, static or
+    not, in two files of the host side.  Every gte_* function of include/gte.h and include/gte_mc.h is defined at
+    column 0 in exactly one unit; struct gte_env has one body, in gte_host.h."""
+    src = _csrc_sources()
+    where = {}
+    for name in _host_files() + ["gte_comm.hip"]:
+        for fn in set(_defined_functions(src[name])):
+            where.setdefault(fn, []).append(name)
+    assert len(where) >= 150 and where["dev_alloc"] == ["gte_host.h"] and where["backtest"] == ["gte_api.hip"]
+    assert {fn: files for fn, files in where.items() if len(files) != 1} == {}
+    entry_points = _declared_functions()
+    assert len(entry_points) >= 70
+    for fn in entry_points:
+        units = [u for u in _makefile_srcs() if re.search(rf"^[A-Za-z_][\w \*]*[ \*]{fn}\(", src[u], re.M)
+                 and fn in _defined_functions(src[u])]
+        assert len(units) == 1, (fn, units)
+        assert units[0] in _host_units() + ["gte_comm.hip"], (fn, units)
+    assert [n for n, t in src.items() if re.search(r"^\s*struct\s+gte_env\s*\{", t, re.M)] == ["gte_host.h"]
+
+
+def test_replaceable_memory_has_one_owner_type_and_gte_destroy_names_no_feature():
+    """hipMalloc, hipFree, hipHostMalloc and hipHostFree are called in gte_host.h only (dev_alloc, the
+    allocate-and-report step and the HIP bindings of gte_own.h's owner), and gte_destroy names no member of a
+    feature struct: a buffer the env may replace is an owner inside its feature's struct, released by `delete E`,
+    so a feature cannot forget its line there."""
+    src = _csrc_sources()
+    for name in _host_units() + ["gte_comm.hip"]:
+        for call in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree("):
+            assert call not in src[name], (name, call)
+    for call in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree("):
+        assert call in src["gte_host.h"], call
+    env = re.search(r"^struct gte_env \{\n(.*?)^\};", src["gte_host.h"], re.M | re.S).group(1)
+    features = re.findall(r"^  (\w+State) (\w+);", env, re.M)
+    assert [m for _, m in features] == ["backtest", "trades", "periods", "signals", "rank", "comm", "readback"]
+    for struct, _ in features:
+        assert re.search(rf"^struct {struct} \{{", src["gte_host.h"], re.M), struct
+    body = re.search(r"^void gte_destroy\(gte_env\* E\) \{\n(.*?)^\}", src["gte_api.hip"], re.M | re.S).group(1)
+    for _, member in features:
+        assert not re.search(rf"E->{member}\b", body), member
+    for owner in re.findall(r"\b(?:DeviceBlock|PinnedBlock)>? ([^;]+);", env):  # the owners gte_env holds flat
+        for member in re.findall(r"\w+", re.sub(r"\[\d+\]", "", owner)):
+            assert member not in body, member
+    for kept in ("hipSetDevice(", "gte_comm_destroy(E)", "E->allocs", "hipEventDestroy(", "hipStreamDestroy(",
+                 "ledger().forget(E)", "delete E;"):
+        assert kept in body, kept
+    assert body.count("hipStreamSynchronize(") == 2
+
+
+def test_error_channel_is_one_string_for_every_host_unit():
+    """fail() is defined in gte_api.hip and called from five units: the message of a refusal in any of them is what
+    gte_last_error() returns.  One entry point per unit whose first check is the NULL env; none touches a device."""
+    lib = _abi.load_library()
+    calls = (  # unit, call, message
+        ("gte_api.hip", lambda: lib.gte_step(None, None, 0), "env is NULL"),
+        ("gte_api_backtest.hip", lambda: lib.gte_backtest(None, None, 1, 0, None), "env is NULL"),
+        ("gte_api_leaderboard.hip", lambda: lib.gte_cscv(None, None, 1, 1, None, 2, None, None, 1, 0, None), "env is NULL"),
+        ("gte_api_read.hip", lambda: lib.gte_get_log(None, None), "NULL argument"),
+        ("gte_comm.hip", lambda: lib.gte_comm_init(None, None, 0, 1), "NULL argument"),
+    )
+    src = _csrc_sources()
+    for (unit, call, message), fn in zip(calls, ("gte_step", "gte_backtest", "gte_cscv", "gte_get_log", "gte_comm_init")):
+        assert fn in _defined_functions(src[unit]), (unit, fn)
+    for unit, call, message in calls:
+        # first the OTHER message, through gte_api.hip (whose unit gte_last_error reads): a unit that wrote to a
+        # string of its own would leave this one in place
+        if message == "env is NULL":
+            assert lib.gte_get_schedule(None, None) == _abi.GTE_ERR_INVALID
+        else:
+            assert lib.gte_synchronize(None) == _abi.GTE_ERR_INVALID
+        assert lib.gte_last_error().decode() in ("env is NULL", "NULL argument")
+        assert lib.gte_last_error().decode() != message
+        assert call() == _abi.GTE_ERR_INVALID, unit
+        assert lib.gte_last_error().decode() == message, (unit, lib.gte_last_error())
 
 
 def test_gte_api_keeps_no_ledger_of_its_own():
     """What a sparse flag store and a slide step rely on is proved in gte_ledger.h, behind its mutex: the
-    host file keeps no lock and no validity bit of its own."""
-    api = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "gte_api.hip")).read()
-    assert '#include "gte_ledger.h"' in api
-    for gone in ("std::mutex", "lock_guard", "flags_sparse_ok", "slide_valid"):
-        assert gone not in api, gone
+    host side keeps no lock and no validity bit of its own."""
+    read = lambda f: open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", f)).read()
+    assert '#include "gte_ledger.h"' in read("gte_host.h")
+    for name in _host_files() + ["gte_comm.hip"]:
+        for gone in ("std::mutex", "lock_guard", "flags_sparse_ok", "slide_valid"):
+            assert gone not in read(name), (name, gone)
 
 
 def test_gte_api_plans_nothing_itself():
-    """The launch rules are in gte_plan.h, fed with values: the host file asks the device for its properties once,
+    """The launch rules are in gte_plan.h, fed with values: the host side asks the device for its properties once,
     in require_device (whose CU count the planner's Chip hands on), reads the planner's environment switches only
-    where it fills Knobs (debug_geometry / read_knobs), and stands no placeholder pointer in for a Shape bool."""
-    api = _csrc_sources()["gte_api.hip"]
+    where it fills Knobs (debug_geometry / read_knobs), and stands no placeholder pointer in for a Shape bool.
+    Counted over all host units and gte_host.h together."""
+    api = "\n".join(_csrc_sources()[name] for name in _host_files())
     once = api.split("static int require_device(")[1].split("\n}\n")[0]
     assert once.count("hipGetDeviceProperties") == 1 and api.count("hipGetDeviceProperties") == 1
     assert "multiProcessorCount <= 0" in once  # gte_create refuses a device without compute units
@@ -407,18 +570,18 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
     src = _csrc_sources()
     declared = _signatures(src["gte_launch.h"])
     assert len(declared) >= 30 and not any(is_def for _, is_def in declared.values())
-    units = [u for u in _makefile_srcs() if u != "gte_api.hip"]
+    units = [u for u in _makefile_srcs() if u not in _host_units()]  # (the host units: the gte_host.h tests)
     assert "gte_backtest.hip" in units and "gte_hot_nt.hip" in units and len(units) >= 7
     # gte_hot.hip and gte_hot_nt.hip compile one body under two names: GTE_HOT_NAME(x) = x and x_nt
     assert [u for u in units if "gte_hot_body.h" in _included(src, u)] == ["gte_hot.hip", "gte_hot_nt.hip"]
     assert "#define GTE_HOT_NAME(x) x\n" in src["gte_hot.hip"] and "#define GTE_HOT_NAME(x) x##_nt\n" in src["gte_hot_nt.hip"]
     assert not any(d.endswith(".hip") for d in src if d not in _makefile_srcs())
     defined = {}
-    for name in units + sorted(h for h in src if h.endswith(".h") and h != "gte_launch.h"):
+    for name in units + sorted(h for h in src if h.endswith(".h") and h not in ("gte_launch.h", "gte_host.h")):
         text = src[name]
-        # (gte_ledger.h: host bookkeeping only, no device code and no cross-file gte:: function; gte_members.h:
-        # forceinline and inline rules only, compiled for the host by tests/test_strategy_records_cpu.py)
-        no_launch_h = ("gte_device.h", "gte_ledger.h", "gte_plan.h", "gte_members.h")
+        # (gte_ledger.h and gte_own.h: host bookkeeping only, no device code and no cross-file gte:: function;
+        # gte_members.h: forceinline and inline rules only, compiled for the host by tests/test_strategy_records_cpu.py)
+        no_launch_h = ("gte_device.h", "gte_ledger.h", "gte_plan.h", "gte_members.h", "gte_own.h")
         assert name in no_launch_h or "gte_launch.h" in _included(src, name), name
         for fn, (sig, is_def) in _signatures(text).items():
             assert is_def, f"{name} declares {fn} itself"
@@ -431,16 +594,17 @@ def test_cross_file_functions_are_declared_once_in_gte_launch_h():
     for fn in ("launch_backtest_begin", "launch_backtest_summary", "launch_backtest_fold",
                "launch_signal_actions", "launch_signal_summary"):
         assert defined.get(fn) == "gte_backtest.hip", fn
-        assert f"gte::{fn}(" in src["gte_api.hip"], fn
+        assert f"gte::{fn}(" in src["gte_api.hip"], fn  # (backtest() and launch_lookup: the unit of enqueue_step)
     assert sorted(declared) == sorted(defined), "gte_launch.h declares a function no file defines"
     # gte_backtest.hip runs phase A with the terminal-record store compiled in
     assert "#define GTE_HOT_ONLY" not in src["gte_backtest.hip"]
     makefile = open(os.path.join(ROOT, "gym-trading-env_amd", "csrc", "Makefile")).read()
     hdrs = re.search(r"^HDRS = (.*)$", makefile, re.M).group(1).split()
     assert sorted(h for h in src if h.endswith(".h")) == sorted(h for h in hdrs if "/" not in h)
-    # the ledger and the planner stand alone (tests/ledger_check.cpp, tests/plan_check.cpp compile them with g++):
-    # nothing of csrc/, nothing of HIP; the planner takes include/gte.h for the GTE_KV_* names
-    for alone, own in (("gte_ledger.h", ()), ("gte_plan.h", ('"../../include/gte.h"',))):
+    # the ledger, the planner and the owner type stand alone (tests/ledger_check.cpp, tests/plan_check.cpp and
+    # tests/own_check.cpp compile them with g++): nothing of csrc/, nothing of HIP; the planner takes include/gte.h
+    # for the GTE_KV_* names
+    for alone, own in (("gte_ledger.h", ()), ("gte_plan.h", ('"../../include/gte.h"',)), ("gte_own.h", ())):
         includes = re.findall(r'#\s*include\s*([<"][^>"]+[>"])', src[alone])
         assert includes and not any((i.startswith('"') and i not in own) or "hip" in i.lower() for i in includes), includes
         assert "__global__" not in src[alone] and "__device__" not in src[alone]

@@ -257,4 +257,4 @@ def test_the_new_unit_is_built_like_the_others_and_uses_no_scratch():
     src = th._csrc_sources()
     assert "launch_compose_signals" in th._signatures(src["gte_launch.h"])
     assert th._signatures(src["gte_compose.hip"])["launch_compose_signals"][1]
-    assert "gte::launch_compose_signals(" in src["gte_api.hip"]
+    assert "gte::launch_compose_signals(" in src["gte_api_backtest.hip"]
