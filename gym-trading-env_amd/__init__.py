@@ -11,7 +11,8 @@ from ._abi import GteError  # noqa: F401
 
 __all__ = ["TradingEnv", "MultiDatasetTradingEnv", "BatchedTradingEnv", "SB3TradingVecEnv", "GteError",
            "BacktestStats", "StrategyStats", "ExitState", "TradeStats", "StrategyTradeStats", "TradeList",
-           "PeriodStats", "StrategyPeriodStats", "RealityCheck", "OverfitCheck", "Diversified", "Curves", "TradeMonteCarlo",
+           "PeriodStats", "StrategyPeriodStats", "RealityCheck", "SpaTest", "OverfitCheck", "Diversified", "Curves",
+           "TradeMonteCarlo",
            "monte_carlo", "periods",
            "basic_reward_function", "dynamic_feature_last_position_taken",
            "dynamic_feature_real_position"]
@@ -25,7 +26,7 @@ _LAZY = {
     "BacktestStats": "backtest_stats", "StrategyStats": "backtest_stats", "ExitState": "exit_state",
     "TradeStats": "trade_stats", "StrategyTradeStats": "trade_stats", "TradeList": "trade_list",
     "PeriodStats": "period_stats", "StrategyPeriodStats": "period_stats",
-    "RealityCheck": "reality_check", "OverfitCheck": "overfit", "Diversified": "diversify",
+    "RealityCheck": "reality_check", "SpaTest": "spa", "OverfitCheck": "overfit", "Diversified": "diversify",
     "Curves": "curves", "TradeMonteCarlo": "monte_carlo",
 }
 

@@ -81,6 +81,7 @@ GTE_MAX_PERIODS = 128
 # gte_reality_check: resamples per slab of the moment sums, and the most resamples of one call
 GTE_BOOT_SLAB = 256
 GTE_BOOT_MAX_RESAMPLES = 65536
+GTE_SPA_MAX_ROUNDS = 64
 # gte_cscv: the most groups and splits of one call, and the splits a workgroup takes
 GTE_CSCV_MAX_GROUPS = 32
 GTE_CSCV_MAX_SPLITS = 65536
@@ -287,6 +288,22 @@ class GteRealityCheckOut(C.Structure):
     """struct gte_reality_check_out (include/gte.h): device pointers, kept as integers."""
     _fields_ = [(n, C.c_void_p) for n in ("mean", "boot_sum", "boot_sq_sum", "count_ge", "count_adj", "max_stat",
                                           "max_index", "summary")]
+
+
+#: struct gte_spa_summary (include/gte.h), in declaration order: one 40-byte record
+SPA_SUMMARY_DTYPE = [("statistic", "<f8")] + [(n, "<i4") for n in (
+    "best", "count_lower", "count_consistent", "count_upper", "rounds_run", "num_rejected", "studentised", "reserved")]
+
+
+class GteSpaSummary(C.Structure):
+    """struct gte_spa_summary (include/gte.h)."""
+    _fields_ = [(n, {"<f8": C.c_double, "<i4": C.c_int32}[t]) for n, t in SPA_SUMMARY_DTYPE]
+
+
+class GteSpaOut(C.Structure):
+    """struct gte_spa_out (include/gte.h): device pointers, kept as integers."""
+    _fields_ = [(n, C.c_void_p) for n in ("t_stat", "std_error", "recentred", "count_adj", "rejected_round", "max_stat",
+                                          "max_index", "crit", "round_rejected", "summary")]
 
 
 #: struct gte_cscv_summary (include/gte.h), in declaration order: one 24-byte record
@@ -548,6 +565,8 @@ SYMBOLS = {
     "gte_bootstrap_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p]),
     "gte_reality_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_void_p,
                                     C.c_void_p, C.c_int32, _P(GteRealityCheckOut)]),
+    "gte_spa_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_void_p, C.c_void_p,
+                               C.c_int32, C.c_double, C.c_int32, C.c_int32, _P(GteRealityCheckOut), _P(GteSpaOut)]),
     "gte_cscv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                            C.c_int32, C.c_int32, _P(GteCscvOut)]),
     "gte_diversify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint64), C.c_void_p, C.c_double,

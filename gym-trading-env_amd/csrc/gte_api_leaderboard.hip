@@ -1,5 +1,6 @@
 // gte_api_leaderboard.hip — the leaderboard entry points of include/gte.h: the reduce / rank pair of each record
-// family, the bootstrap weights, the analyses (reality check, CSCV, diversify, trade pools and their Monte Carlo).
+// family, the bootstrap weights, the analyses (reality check, SPA test, CSCV, diversify, trade pools and their Monte
+// Carlo).
 #include "gte_host.h"
 
 extern "C" {
@@ -163,30 +164,71 @@ int gte_bootstrap_weights(gte_env* E, int32_t n, int32_t n_resamples, double blo
                   "bootstrap weights");
 }
 
-int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
-                      int32_t n_periods, const uint64_t period_mask[2], const double* benchmark_device,
-                      const double* weights_device, int32_t n_resamples, const gte_reality_check_out* out) {
+// what gte_reality_check and gte_spa_test check of the arguments they share, in this order; `out`: the reality
+// check's outputs under the name `what` they have in the call; n: the selected periods
+static int check_reality_check_args(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                                    int32_t n_periods, const uint64_t period_mask[2], const double* benchmark_device,
+                                    const double* weights_device, int32_t n_resamples,
+                                    const gte_reality_check_out* out, const char* what, int* n) {
   TRY(check_strategies(E, n_strategies));
   TRY(check_n_periods(n_periods, 1));
   TRY(check_n_resamples(n_resamples));
   TRY(check_period_mask(period_mask));
-  int n;
-  TRY(count_periods(period_mask, n_periods, &n));
-  if (n < 2) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: at least two are needed", n);
+  TRY(count_periods(period_mask, n_periods, n));
+  if (*n < 2) return fail(GTE_ERR_INVALID, "period_mask selects %d periods: at least two are needed", *n);
   TRY(check_stats(stats_device));
   if (!weights_device || ((uintptr_t)weights_device & 7) || ((uintptr_t)benchmark_device & 7))
     return fail(GTE_ERR_INVALID, "weights_device (required) and benchmark_device must be 8-byte aligned device arrays");
-  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
+  if (!out) return fail(GTE_ERR_INVALID, "%s is NULL", what);
   if (!all_aligned({out->mean, out->boot_sum, out->boot_sq_sum, out->max_stat, out->summary}, 7))
-    return fail(GTE_ERR_INVALID, "out: mean, boot_sum, boot_sq_sum, max_stat and summary must be 8-byte aligned device pointers");
+    return fail(GTE_ERR_INVALID, "%s: mean, boot_sum, boot_sq_sum, max_stat and summary must be 8-byte aligned device pointers", what);
   if (!all_aligned({out->count_ge, out->count_adj, out->max_index}, 3))
-    return fail(GTE_ERR_INVALID, "out: count_ge, count_adj and max_index must be 4-byte aligned device pointers");
+    return fail(GTE_ERR_INVALID, "%s: count_ge, count_adj and max_index must be 4-byte aligned device pointers", what);
+  return GTE_OK;
+}
+
+int gte_reality_check(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                      int32_t n_periods, const uint64_t period_mask[2], const double* benchmark_device,
+                      const double* weights_device, int32_t n_resamples, const gte_reality_check_out* out) {
+  int n;
+  TRY(check_reality_check_args(E, stats_device, n_strategies, n_periods, period_mask, benchmark_device, weights_device,
+                               n_resamples, out, "out", &n));
   if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_reality_check inside a stream capture");
   HIPCHK(hipSetDevice(E->cfg.device));
   TRY(grow(E, &E->rank.boot_scratch, gte::reality_check_scratch_bytes(n_strategies, n, n_resamples)));
   return launched(gte::launch_reality_check(stats_device, n_strategies, n_periods, period_mask, n, benchmark_device,
                                             weights_device, n_resamples, *out, E->rank.boot_scratch.base, E->stream),
                   "reality check");
+}
+
+int gte_spa_test(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,
+                 const uint64_t period_mask[2], const double* benchmark_device, const double* weights_device,
+                 int32_t n_resamples, double threshold, int32_t crit_rank, int32_t max_rounds,
+                 const gte_reality_check_out* rc, const gte_spa_out* out) {
+  int n;
+  TRY(check_reality_check_args(E, stats_device, n_strategies, n_periods, period_mask, benchmark_device, weights_device,
+                               n_resamples, rc, "rc", &n));
+  if (!(threshold >= 0.0)) return fail(GTE_ERR_INVALID, "threshold must be >= 0.0 (+inf allowed), not NaN");
+  if (crit_rank < 0 || crit_rank >= n_resamples)
+    return fail(GTE_ERR_INVALID, "crit_rank %d outside [0, %d]", crit_rank, n_resamples - 1);
+  if (max_rounds < 1 || max_rounds > GTE_SPA_MAX_ROUNDS)
+    return fail(GTE_ERR_INVALID, "max_rounds %d outside [1, %d]", max_rounds, GTE_SPA_MAX_ROUNDS);
+  if (!out) return fail(GTE_ERR_INVALID, "out is NULL");
+  if (!all_aligned({out->t_stat, out->std_error, out->max_stat, out->crit, out->summary}, 7))
+    return fail(GTE_ERR_INVALID, "out: t_stat, std_error, max_stat, crit and summary must be 8-byte aligned device pointers");
+  if (!all_aligned({out->count_adj, out->rejected_round, out->max_index, out->round_rejected}, 3))
+    return fail(GTE_ERR_INVALID, "out: count_adj, rejected_round, max_index and round_rejected must be 4-byte aligned device pointers");
+  if (!out->recentred) return fail(GTE_ERR_INVALID, "out: recentred is NULL");
+  if (stream_capturing(E)) return fail(GTE_ERR_STATE, "gte_spa_test inside a stream capture");
+  HIPCHK(hipSetDevice(E->cfg.device));
+  TRY(grow(E, &E->rank.boot_scratch, gte::reality_check_scratch_bytes(n_strategies, n, n_resamples)));
+  TRY(grow(E, &E->rank.spa_scratch, gte::spa_scratch_bytes(n_strategies, n, n_resamples)));
+  hipError_t e = gte::launch_reality_check(stats_device, n_strategies, n_periods, period_mask, n, benchmark_device,
+                                           weights_device, n_resamples, *rc, E->rank.boot_scratch.base, E->stream);
+  if (e == hipSuccess)
+    e = gte::launch_spa(stats_device, n_strategies, n_periods, period_mask, n, benchmark_device, weights_device,
+                        n_resamples, threshold, crit_rank, max_rounds, *rc, *out, E->rank.spa_scratch.base, E->stream);
+  return launched(e, "SPA test");
 }
 
 int gte_cscv(gte_env* E, const gte_strategy_period_stats* stats_device, int32_t n_strategies, int32_t n_periods,

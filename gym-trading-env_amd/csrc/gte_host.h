@@ -124,9 +124,10 @@ struct RankState {
   double* score[2] = {nullptr, nullptr};
   int32_t* index[2] = {nullptr, nullptr};
   int64_t entries[2] = {0, 0};
-  // gte_reality_check, gte_cscv, gte_diversify, gte_trade_monte_carlo: the scratch of each (gte_bootstrap.hip,
-  // gte_cscv.hip, gte_diversify.hip, gte_montecarlo.hip), a block of its own that grow() keeps the same way
-  Scratch boot_scratch, cscv_scratch, div_scratch, mc_scratch;
+  // gte_reality_check, gte_cscv, gte_diversify, gte_trade_monte_carlo, gte_spa_test: the scratch of each
+  // (gte_bootstrap.hip, gte_cscv.hip, gte_diversify.hip, gte_montecarlo.hip, gte_spa.hip), a block of its own that
+  // grow() keeps the same way (gte_spa_test also runs a reality check: in boot_scratch, as gte_reality_check does)
+  Scratch boot_scratch, cscv_scratch, div_scratch, mc_scratch, spa_scratch;
 };
 
 struct CommState {

@@ -290,6 +290,17 @@ hipError_t launch_reality_check(const gte_strategy_period_stats* stats, int n_st
                                 int n_resamples, const gte_reality_check_out& out, void* scratch,
                                 hipStream_t stream);
 
+// --- gte_spa.hip: the test for superior predictive ability and its step-down (gte_spa_test, include/gte.h); the
+// caller has checked alignments, and launch_reality_check has been enqueued into `rc` on the same stream
+// bytes of library-owned scratch one test of S strategies, n selected periods and R resamples needs
+size_t spa_scratch_bytes(int n_strategies, int n, int n_resamples);
+// prepare, round 0 with its three recentrings and max_rounds - 1 further rounds that return at once when the
+// step-down has stopped (period_mask: host, two words, n bits set, none at or above n_periods)
+hipError_t launch_spa(const gte_strategy_period_stats* stats, int n_strategies, int n_periods,
+                      const uint64_t period_mask[2], int n, const double* benchmark, const double* weights,
+                      int n_resamples, double threshold, int crit_rank, int max_rounds,
+                      const gte_reality_check_out& rc, const gte_spa_out& out, void* scratch, hipStream_t stream);
+
 // --- gte_cscv.hip: the probability of backtest overfitting (gte_cscv, include/gte.h); the caller has checked
 // alignments and the three tables
 // bytes of library-owned scratch one call with S strategies, G groups and C splits needs

@@ -187,6 +187,18 @@ class StrategyPeriodStats(StrategyRecords):
         from . import reality_check
         return reality_check.run(self, periods, n_resamples, block, seed, benchmark, weights)
 
+    def spa(self, periods=None, n_resamples=1000, block=1.0, seed=0, benchmark=None, weights=None, alpha=0.05,
+            max_rounds=8, threshold=None):
+        """Hansen's test for Superior Predictive Ability of this leaderboard over `periods` and its step-down, on the
+        device (`gte_spa_test`): the Reality Check studentised, so that poor but noisy strategies do not blind it,
+        and WHICH strategies beat the benchmark at family-wise level `alpha`.  A `SpaTest`, which carries the
+        `RealityCheck` of the same weights.  `periods`, `n_resamples`, `block`, `seed`, `benchmark` and `weights` as
+        in `reality_check`; at most `max_rounds` rounds of step-down; `threshold`: a strategy whose t-statistic is
+        below -threshold does not contribute to the null (None: Hansen's sqrt(2 log log n), which needs at least
+        three periods).  Enqueued on the env's stream; nothing waits."""
+        from . import spa
+        return spa.run(self, periods, n_resamples, block, seed, benchmark, weights, alpha, max_rounds, threshold)
+
 
     def cscv(self, periods=None, groups=None, metric="sharpe", splits=None):
         """The probability of backtest overfitting of this leaderboard by combinatorially symmetric

@@ -1358,6 +1358,78 @@ int gte_reality_check(gte_env* env, const gte_strategy_period_stats* stats_devic
                       const double* benchmark_device /* [n_periods] or NULL */, const double* weights_device,
                       int32_t n_resamples, const gte_reality_check_out* out);
 
+/* ---- TEST FOR SUPERIOR PREDICTIVE ABILITY (Hansen 2005) AND ITS STEP-DOWN (Hsu, Hsu, Kuan 2010, after Romano and
+ * Wolf 2005): the Reality Check above, studentised — every strategy measured in its own bootstrap deviation, so that
+ * a poor but noisy strategy no longer widens the null distribution — with the null recentred so that clearly poor
+ * strategies do not contribute, and a step-down that says WHICH strategies beat the benchmark, not only whether the
+ * best one does.  From the same [S, B] records, mask, benchmark and weights as gte_reality_check; the [R, S] matrix is
+ * never written.  One fixed order of IEEE f64 operations, every one of them ONE operation as written.
+ *
+ * PASS 1 is gte_reality_check itself, unchanged, into `rc` (all of whose arrays are written as that call writes
+ * them).  With eligible, d_i, mean_s, boot_sum, boot_sq_sum as defined there, R = n_resamples, dR = (double)R, per
+ * eligible strategy:
+ *     m1 = boot_sum[s] / dR;    v = boot_sq_sum[s] / dR - m1 * m1;    se_s = sqrt(v > 0 ? v : 0.0);    rse_s = 1.0 / se_s
+ * Strategy s is STUDENTISED iff it is eligible, mean_s and se_s are finite and se_s > 0.  For a studentised strategy
+ *     t_s = mean_s * rse_s
+ *     g0_s = mean_s > 0 ? mean_s : 0.0          (lower: Hansen's SPA_l)
+ *     g1_s = t_s >= -threshold ? mean_s : 0.0   (consistent: SPA_c; recentred[s] = 1 iff the first branch is taken)
+ *     g2_s = mean_s                             (upper: SPA_u, the studentised Reality Check)
+ * THE STATISTIC.  m = -inf, best = -1; over studentised s ascending: if (t_s > m) { m = t_s; best = s; }
+ * statistic = m > 0.0 ? m : 0.0.
+ * A PASS over a set `live` of strategies with recentring j, per resample r:
+ *     q_rs = a / (double)n, a the chain of gte_reality_check (a = 0.0; over i ascending: a = a + weights[r][i] * d_i)
+ *     z = (q_rs - gj_s) * rse_s          (a multiplication by the reciprocal, not a division by se_s)
+ *     m = -inf, index = -1; over live s ascending: if (z > m) { m = z; index = s; }        (a NaN never wins)
+ *     M_j[r] = m > 0.0 ? m : 0.0         (never NaN, never -0.0);   I_j[r] = index
+ * ROUND 0 passes over live_0, the studentised strategies, with j = 0, 1, 2:  max_stat[j * R + r] = M_j[r],
+ * max_index[j * R + r] = I_j[r] (all 0.0 and -1 when nothing is studentised).  When at least one strategy is
+ * studentised:   count_lower, count_consistent, count_upper = #{r : M_j[r] >= statistic} for j = 0, 1, 2 (else 0);
+ * the SPA p-values are count / R.   count_adj[s] = #{r : M_1[r] >= t_s} for a studentised s (else 0): its
+ * single-step adjusted p-value is count_adj[s] / R.
+ * THE STEP-DOWN, on the consistent recentring.  Round k = 0, 1, ... runs while live_k is not empty and
+ * k < max_rounds:  M = M_1 of a pass over live_k (round 0: the one above);  crit[k] = the element of rank crit_rank
+ * (0-based) of M[0 .. R-1] sorted ascending;  every s of live_k with t_s > crit[k] is rejected:
+ * rejected_round[s] = k, and live_{k+1} is live_k without them;  round_rejected[k] = their number.  A round that
+ * rejects nothing is the last.  rounds_run = the rounds that ran (0 when nothing is studentised), num_rejected the sum
+ * of round_rejected.  With crit_rank = ceil((1 - alpha) * R) - 1 the rejected strategies are those whose mean is
+ * above the benchmark's at family-wise level alpha.
+ * WRITTEN (all of every array): t_stat[s] (t_s; NaN unless studentised), std_error[s] (se_s; NaN for an ineligible
+ * strategy), recentred[s] (u8; 0 unless studentised), count_adj[s], rejected_round[s] (-1: not rejected),
+ * max_stat, max_index [3 * R], crit [max_rounds] (NaN from rounds_run on), round_rejected [max_rounds] (0 from
+ * rounds_run on), summary.
+ * The launches of gte_reality_check, then 6 + 3 * (max_rounds - 1) on the env's stream: every later round is enqueued
+ * unconditionally and returns at once when the step-down has stopped (a flag on the device); nothing visits the
+ * host, no atomics.  Library-owned scratch of its own, grown as gte_reality_check's.  The inputs are only read; the
+ * outputs must not overlap them or each other.
+ * GTE_ERR_INVALID, with nothing launched and nothing written, for everything gte_reality_check refuses (`rc` and its
+ * members as `out` there), a threshold that is NaN or negative (+inf is allowed: g1 = g2), crit_rank outside
+ * [0, n_resamples - 1], max_rounds outside [1, GTE_SPA_MAX_ROUNDS], a NULL `out` or member of it, or one not aligned
+ * for its type.  GTE_ERR_STATE inside a stream capture. */
+#define GTE_SPA_MAX_ROUNDS 64
+typedef struct gte_spa_summary {             /* 40 bytes */
+  double  statistic;
+  int32_t best;            /* -1 when no t_s compared greater than -inf */
+  int32_t count_lower, count_consistent, count_upper;
+  int32_t rounds_run, num_rejected;
+  int32_t studentised;     /* the number of studentised strategies */
+  int32_t reserved;        /* written as zero */
+} gte_spa_summary;
+typedef struct gte_spa_out {                 /* DEVICE pointers, all required */
+  double  *t_stat, *std_error;               /* f64 [n_strategies] */
+  uint8_t *recentred;                        /* u8  [n_strategies] */
+  int32_t *count_adj, *rejected_round;       /* i32 [n_strategies] */
+  double  *max_stat;                         /* f64 [3 * n_resamples] */
+  int32_t *max_index;                        /* i32 [3 * n_resamples] */
+  double  *crit;                             /* f64 [max_rounds] */
+  int32_t *round_rejected;                   /* i32 [max_rounds] */
+  gte_spa_summary* summary;                  /* one record */
+} gte_spa_out;
+int gte_spa_test(gte_env* env, const gte_strategy_period_stats* stats_device, int32_t n_strategies,
+                 int32_t n_periods, const uint64_t period_mask[2],
+                 const double* benchmark_device /* [n_periods] or NULL */, const double* weights_device,
+                 int32_t n_resamples, double threshold, int32_t crit_rank, int32_t max_rounds,
+                 const gte_reality_check_out* rc, const gte_spa_out* out);
+
 /* ---- PROBABILITY OF BACKTEST OVERFITTING by combinatorially symmetric cross-validation, CSCV (Bailey, Borwein,
  * Lopez de Prado, Zhu 2017): how much does picking the best of S strategies overfit?  The periods are cut into G
  * groups; every split takes some groups as in-sample (IS) and others as out-of-sample (OOS), picks the IS winner
